@@ -545,6 +545,43 @@ def test_bench_clock_sampler_degrades_without_a_gpu():
         assert 50 <= out["sclk_mhz_avg"] <= 3000
 
 
+def test_bench_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
+    """bench.py --dump-outputs: loss, logits and the same seeded sample of the parameters, their gradients and Adam's moments, float32,
+    the sample identical from call to call (two builds are compared output for output)."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("din_bench_module", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    g = torch.Generator().manual_seed(7)
+    params = [torch.nn.Parameter(torch.randn(s, generator=g)) for s in ((64, 32), (32,), (300,))]
+    for p in params:
+        p.grad = 2.0 * p.detach()
+    ret = {"activities": torch.randn(4, 8, generator=g, dtype=torch.float64)}
+    adam = {p: (3.0 * p.detach(), 4.0 * p.detach()) for p in params}
+    for d in ("a", "b"):
+        mod.dump_outputs(str(tmp_path / d), torch.tensor(1.5), ret, params, adam, sample=256)
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(a) == ["activities.npy", "adam_exp_avg_sample.npy", "adam_exp_avg_sq_sample.npy", "grads_sample.npy", "loss.npy",
+                         "params_sample.npy"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["activities.npy"].shape == (4, 8) and float(a["loss.npy"][0]) == 1.5
+    ps = a["params_sample.npy"]
+    assert ps.shape == (256,) and np.array_equal(a["grads_sample.npy"], 2.0 * ps)
+    assert np.array_equal(a["adam_exp_avg_sample.npy"], 3.0 * ps) and np.array_equal(a["adam_exp_avg_sq_sample.npy"], 4.0 * ps)
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f)) for f, v in a.items())
+    mod.dump_outputs(str(tmp_path / "c"), torch.tensor(0.0), {}, params[1:])           # below the sample size: everything, in order
+    assert np.array_equal(np.load(tmp_path / "c" / "params_sample.npy"), torch.cat([params[1], params[2]]).detach().numpy())
+
+
+def test_bench_plain_run_options():
+    """--per-layer comes from the warm-up survey that only --full runs; --steps sets the timed steps and must be positive."""
+    for extra in (["--per-layer", "x.txt"], ["--steps", "0"]):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                             text=True, timeout=120)
+        assert res.returncode == 2 and "error" in res.stdout, res.stdout
+
+
 def test_dropout_seeds_distinct_over_ranks_and_replays():
     """Every (rank, step) pair draws its own dropout mask, eager and under graph replay (the replay stride used to equal the
     per-rank stride mod 2^63, so rank r at replay k repeated rank 0's masks of replay k + r).  A captured step's device-side seed is

@@ -8,7 +8,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-run() { name=$1; shift; timeout 600 python bench.py "$@" > $OUT/bench_$name.log 2>&1; tail -1 $OUT/bench_$name.log > $OUT/bench_$name.json; cut -c1-160 $OUT/bench_$name.json; }
+run() { name=$1; shift; timeout 600 python bench.py --full "$@" > $OUT/bench_$name.log 2>&1; tail -1 $OUT/bench_$name.log > $OUT/bench_$name.json; cut -c1-160 $OUT/bench_$name.json; }
 run inv3_bf16_b32 --per-layer $OUT/inv3_bf16_per_layer.txt
 run inv3_bf16_b4 --global-batch 4 --no-cpu-baseline --no-extras --per-layer $OUT/inv3_bf16_b4_per_layer.txt
 run inv3_bf16_b32_host_images --host-images --no-cpu-baseline
@@ -26,8 +26,8 @@ run vgg16_bf16_t10_b8 --workload vgg16_bf16 --frames 10 --global-batch 8 --no-cp
 # gradient-bucket path in one process (world size 1, RCCL): hook + flat buckets + async all_reduce + views, no wire
 for c in 4 32; do
   MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 python bench.py --global-batch $c --steps 20 --warmup 5 \
-      --no-cpu-baseline --force-buckets 2>&1 | grep '"metric"' > $OUT/bench_inv3_bf16_b${c}_forced_buckets.json
-  timeout 600 python bench.py --global-batch $c --steps 20 --warmup 5 --no-cpu-baseline 2>&1 | tail -1 > $OUT/bench_inv3_bf16_b${c}_20steps.json
+      --full --no-cpu-baseline --force-buckets 2>&1 | grep '"metric"' > $OUT/bench_inv3_bf16_b${c}_forced_buckets.json
+  timeout 600 python bench.py --global-batch $c --steps 20 --warmup 5 --full --no-cpu-baseline 2>&1 | tail -1 > $OUT/bench_inv3_bf16_b${c}_20steps.json
   cut -c75-170 $OUT/bench_inv3_bf16_b${c}_20steps.json $OUT/bench_inv3_bf16_b${c}_forced_buckets.json
 done
 # rocprofv3 kernel-trace summaries (same command as the default bench line, 5 timed + 2 warm-up steps)
@@ -43,6 +43,6 @@ python tools/pmc_traffic.py "$F" "$W" $OUT/pmc_traffic.json
 rm -rf $OUT/prof_b32 $OUT/prof_b4 $OUT/pmc_fetch $OUT/pmc_write
 # multi-GPU path, dry: two ranks share this one device (gloo), every rank checks that all ranks hold identical averaged gradients
 # (round 5: launched PLAINLY, the way the driver calls it -- bench.py starts its own two ranks)
-DIN_SINGLE_DEVICE=1 DIN_DIST_BACKEND=gloo DIN_CHECK_ALLREDUCE=1 timeout 600 python bench.py --gpus 2 --steps 3 --warmup 2 --global-batch 8 --no-cpu-baseline > $OUT/two_ranks_one_device.log 2>&1
+DIN_SINGLE_DEVICE=1 DIN_DIST_BACKEND=gloo DIN_CHECK_ALLREDUCE=1 timeout 600 python bench.py --gpus 2 --steps 3 --warmup 2 --global-batch 8 --full --no-cpu-baseline > $OUT/two_ranks_one_device.log 2>&1
 tail -4 $OUT/two_ranks_one_device.log | cut -c1-300
 ls -la $OUT | head -50
