@@ -3232,9 +3232,9 @@ int run_gather(ConvK& k, GatherPlan g, int dtype, void* workspace, int64_t ws_by
     return DIN_OK;
 }
 
-// column sums of a pixel-major tensor view -> out[c] (zeroed here, fp32 atomics across row slabs)
-static int launch_colsum(int dtype, const void* g, float* out, int64_t M, int c, int ld, int coff, hipStream_t st) {
-    hipMemsetAsync(out, 0, sizeof(float) * c, st);
+// column sums of a pixel-major tensor view -> out[c] (fp32 atomics across row slabs): zeroed here first, or added into when `zero` is false
+static int launch_colsum(int dtype, const void* g, float* out, int64_t M, int c, int ld, int coff, hipStream_t st, bool zero = true) {
+    if (zero && hipMemsetAsync(out, 0, sizeof(float) * c, st) != hipSuccess) DIN_FAIL(DIN_E_LAUNCH, "colsum: memset");
     const int epc = dtype == DIN_F32 ? 4 : 8;
     if (c % epc == 0 && c / epc <= 256 && ld % epc == 0 && coff % epc == 0) {
         // 256 workgroups (one per CU), eight 16-byte loads in flight per thread, each streaming a contiguous slab of rows (XCD-contiguous order).
@@ -3824,7 +3824,8 @@ int din_conv_wgrad(const din_conv_desc* d, const void* in, const void* dout, flo
         DIN_CHECK_LAUNCH("conv_wgrad_reduce");
     }
     if (dbias && !bias_fused) {
-        if (int e = launch_colsum(d->dtype, dout, dbias, k.M, d->cout, d->ldo, d->cooff, st)) return e;
+        // (fp32 / bf16 tail kernels: no fused bias sum.  accumulate bit 1 adds into the caller-zeroed dbias, as the fused paths do)
+        if (int e = launch_colsum(d->dtype, dout, dbias, k.M, d->cout, d->ldo, d->cooff, st, !prezeroed)) return e;
     }
     return DIN_OK;
 }

@@ -163,8 +163,8 @@ int din_conv_dgrad_x(const din_conv_desc* d, const void* dout, const void* wpk_t
                      const din_conv_src* x, void* workspace, int64_t workspace_bytes, void* stream);
 /* 1 when din_conv_dgrad_x serves this descriptor with the fused kernel, 0 when it runs the two-launch form.  Host-only planning call. */
 int din_conv_dgrad_x_fused(const din_conv_desc* d);
-/* dw: [cout][cin][kh][kw] fp32, overwritten (or += when accumulate!=0), multiplied by scale[cout] when scale
- * is given.  dbias (nullable) [cout] fp32 = column sums of dout.  wdot (nullable) [cout] fp32 =
+/* dw: [cout][cin][kh][kw] fp32, overwritten (or += when accumulate bit 0 (value 1) is set; bit 1 alone leaves dw overwritten),
+ * multiplied by scale[cout] when scale is given.  dbias (nullable) [cout] fp32 = column sums of dout.  wdot (nullable) [cout] fp32 =
  * <w[co,:], dw_raw[co,:]> (needs w) -- the BatchNorm-eval scale gradient.  accumulate bit 1 (value 2): dbias / wdot were zeroed by
  * the caller (they are accumulated into with atomics; a backbone zeroes one flat buffer for all its layers instead of 2 memsets per
  * layer).                                                                                                   */

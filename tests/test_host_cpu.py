@@ -117,6 +117,44 @@ def test_register_resident_kernel_keeps_its_hand_counted_lds_reads_hazard_free(t
     assert checked == 10
 
 
+def _function_body(text, signature):
+    """the text of the C function whose definition starts with `signature`, braces matched"""
+    i = text.index(signature)
+    i = text.index("{", i)
+    depth = 0
+    for j in range(i, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[j], 0)
+        if depth == 0:
+            return text[i:j + 1]
+    raise AssertionError(f"unbalanced braces after {signature}")
+
+
+def test_every_wgrad_kernel_instantiation_has_a_row_in_the_fp64_table():
+    """the conv_wgrad_*_kernel<...> instantiations din_conv_wgrad launches (directly, through launch_wgrad_halo, and the filter banks of
+    launch_wgrad_pipe) equal the kernels named by the rows of tests/test_gpu_wgrad.py: a kernel added without a row fails here, on the CPU"""
+    import re
+    from tests.test_gpu_wgrad import WGRAD_CASES
+    csrc = os.path.join(ROOT, "din-group-activity-recognition-benchmark_amd", "csrc")
+
+    def src(name):
+        with open(os.path.join(csrc, name)) as fh:
+            return re.sub(r"//[^\n]*", "", fh.read())
+
+    def norm(name):
+        return re.sub(r"\s+", "", name)
+
+    pat = re.compile(r"\bconv_wgrad_\w+?_kernel\b(?:\s*<[^<>;()]*>)?")
+    bodies = [_function_body(src("conv_igemm.hip"), "int din_conv_wgrad(const din_conv_desc* d"),
+              _function_body(src("conv_wgrad_halo.hip"), "int launch_wgrad_halo(")]
+    launched = {norm(m) for b in bodies for m in pat.findall(b)} - {"conv_wgrad_reduce_kernel"}
+    assert "din_wgrad::launch_wgrad_pipe(" in bodies[0]
+    banks = set(re.findall(r"conv_wgrad_pipe_kernel<(\d+),\s*256\b", _function_body(src("conv_wgrad_pipe.hip"), "int launch_wgrad_pipe(")))
+    launched |= {f"conv_wgrad_pipe_kernel<{b},256>" for b in banks}
+    assert len(launched) >= 24, sorted(launched)
+    named = {norm(r["kernel"]) for r in WGRAD_CASES}
+    assert launched == named, f"launched without a row: {sorted(launched - named)}; rows naming no launch: {sorted(named - launched)}"
+
+
 def test_conv_planning_is_callable_without_gpu():
     from din_amd import _lib
     lib = _lib.load()
