@@ -36,17 +36,53 @@ def _as_kernel_list(k):
     return [tuple(k)]
 
 
+def make_backbone(cfg, name=None):
+    """the backbone of cfg.backbone (or `name`), in cfg.backbone_dtype; shared by the stage-2 models and the stage-1 Basenets"""
+    name = cfg.backbone if name is None else name
+    dt = getattr(cfg, "backbone_dtype", "fp32")
+    if name == "inv3":
+        return MyInception_v3(transform_input=False, pretrained=True, compute_dtype=dt)
+    if name == "vgg16":
+        return MyVGG16(pretrained=True, compute_dtype=dt)
+    raise NotImplementedError(f"backbone {name!r}: the MI355X hot path covers 'vgg16' and 'inv3' "
+                              f"(BASELINE.json configs); vgg19/res18/alex are out of scope")
+
+
+def embed_boxes(model, images_in, boxes_in, N, fc):
+    """images [B,T,3,H,W] (uint8 | fp32), boxes [B,T,N,4] -> fc(RoIAlign(backbone(images))) [B,T,N,fc.out_features] (reference
+    infer_model.py:152-184, base_model.py:77-114), plus (bufs, views, graph) of the backbone run.  `model` holds .cfg, .backbone and
+    .roi_align.  No activation: the callers apply their own (LayerNorm + ReLU in stage 2, ReLU + dropout in the stage-1 head)."""
+    cfg = model.cfg
+    B, T = images_in.shape[0], images_in.shape[1]
+    H, W = cfg.image_size
+    OH, OW = cfg.out_size
+    D, K = cfg.emb_features, cfg.crop_size[0]
+    images_flat = images_in.reshape(B * T, 3, H, W)
+    boxes_flat = boxes_in.reshape(B * T * N, 4)
+    boxes_idx = ops.boxes_frame_index(B * T, N, boxes_in.device)                  # infer_model.py:155-157
+    bufs, graph = model.backbone.forward_nhwc(images_flat)                       # prep fused (:161-162)
+    fm = bufs[0]
+    assert tuple(fm.shape[1:3]) == (OH, OW), f"backbone output {tuple(fm.shape[1:3])} != cfg.out_size {(OH, OW)}"   # (:164)
+    views = model.backbone.output_views(graph)
+    if fm.shape[3] >= D:                                                         # one map holds all D channels (VGG; materialised fuse)
+        tid = graph.output_tids[0]
+        crops = model.roi_align(fm, boxes_flat, boxes_idx, nhwc=True, channels=D,
+                                relu_masked=graph.tensors[tid].relu_masked)      # [BTN, D, K, K]  (:178-180)
+    else:
+        # multi-scale fuse + RoIAlign in one step (:165-180): every backbone output is sampled through its virtual align_corners
+        # resize to (OH, OW); the resized / concatenated map is never built, forward or backward
+        assert sum(c for _, _, c in views) == D, f"backbone outputs hold {sum(c for _, _, c in views)} channels, cfg.emb_features = {D}"
+        maps = [(b, c, graph.tensors[tid].relu_masked) for b, (tid, _coff, c) in zip(bufs, views)]
+        crops = model.roi_align.forward_multiscale(maps, boxes_flat, boxes_idx, (OH, OW))
+    feats = crops.reshape(B, T, N, D * K * K)
+    y = ops.linear(feats, fc.weight, fc.bias, lowp=getattr(cfg, "backbone_dtype", "fp32") == "bf16")              # :184
+    return y, bufs, views, graph
+
+
 class _DynamicBase(nn.Module):
     def _build_trunk(self, cfg):
         D, K, NFB = cfg.emb_features, cfg.crop_size[0], cfg.num_features_boxes
-        dt = getattr(cfg, "backbone_dtype", "fp32")
-        if cfg.backbone == "inv3":
-            self.backbone = MyInception_v3(transform_input=False, pretrained=True, compute_dtype=dt)
-        elif cfg.backbone == "vgg16":
-            self.backbone = MyVGG16(pretrained=True, compute_dtype=dt)
-        else:
-            raise NotImplementedError(f"backbone {cfg.backbone!r}: the MI355X hot path covers 'vgg16' and 'inv3' "
-                                      f"(BASELINE.json configs); vgg19/res18/alex are out of scope")
+        self.backbone = make_backbone(cfg)
         if not cfg.train_backbone:
             for p in self.backbone.parameters():
                 p.requires_grad = False
@@ -84,31 +120,7 @@ class _DynamicBase(nn.Module):
 
     # ---- shared front: images -> per-box embeddings [B,T,N,NFB] ------------------------------------------
     def _embed(self, images_in, boxes_in, N, return_context: bool = False):
-        cfg = self.cfg
-        B, T = images_in.shape[0], images_in.shape[1]
-        H, W = cfg.image_size
-        OH, OW = cfg.out_size
-        D, K = cfg.emb_features, cfg.crop_size[0]
-        images_flat = images_in.reshape(B * T, 3, H, W)
-        boxes_flat = boxes_in.reshape(B * T * N, 4)
-        boxes_idx = ops.boxes_frame_index(B * T, N, boxes_in.device)                  # infer_model.py:155-157
-        bufs, graph = self.backbone.forward_nhwc(images_flat)                        # prep fused (:161-162)
-        fm = bufs[0]
-        assert tuple(fm.shape[1:3]) == (OH, OW), f"backbone output {tuple(fm.shape[1:3])} != cfg.out_size {(OH, OW)}"   # (:164)
-        views = self.backbone.output_views(graph)
-        if fm.shape[3] >= D:                                                         # one map holds all D channels (VGG; materialised fuse)
-            tid = graph.output_tids[0]
-            crops = self.roi_align(fm, boxes_flat, boxes_idx, nhwc=True, channels=D,
-                                   relu_masked=graph.tensors[tid].relu_masked)      # [BTN, D, K, K]  (:178-180)
-        else:
-            # multi-scale fuse + RoIAlign in one step (:165-180): every backbone output is sampled through its virtual align_corners
-            # resize to (OH, OW); the resized / concatenated map is never built, forward or backward
-            assert sum(c for _, _, c in views) == D, f"backbone outputs hold {sum(c for _, _, c in views)} channels, cfg.emb_features = {D}"
-            maps = [(b, c, graph.tensors[tid].relu_masked) for b, (tid, _coff, c) in zip(bufs, views)]
-            crops = self.roi_align.forward_multiscale(maps, boxes_flat, boxes_idx, (OH, OW))
-        feats = crops.reshape(B, T, N, D * K * K)
-        x = ops.linear(feats, self.fc_emb_1.weight, self.fc_emb_1.bias,
-                       lowp=getattr(self.cfg, "backbone_dtype", "fp32") == "bf16")              # :184
+        x, bufs, views, graph = embed_boxes(self, images_in, boxes_in, N, self.fc_emb_1)
         x = ops.layer_norm(x, self.nl_emb_1.weight, self.nl_emb_1.bias, relu=True)   # :185-186
         if return_context:                                                           # the LAST backbone output, pixel-major (:404)
             tid_last, coff, c = views[-1]

@@ -536,6 +536,62 @@ class HeadFunction(torch.autograd.Function):
         return ds, dw, db, None
 
 
+class BasenetHeadFunction(torch.autograd.Function):
+    """Stage-1 head (reference base_model.py:117-139 / :243-268): y [BT, N, C] (the fc_emb output) -> (actions, activities) with
+    s = dropout(relu(y)) formed on the fly (bitwise ActDropoutFunction.apply(y, True, drop_p, seed)).
+
+    n_per_frame None: actions [BT/T*N, A_act], activities [BT/T, A_grp] when mean_over_t (volleyball, T != 1), else [BT*N] / [BT].
+    n_per_frame int32 [BT] (collective): actions compacted to [ALL_N, A_act] in (frame, box) order, activities [BT, A_grp].  ALL_N sizes the
+    output, so this path does exactly ONE 4-byte device-to-host read per forward (the sum of the counts, or -1 when a count is outside
+    1..N, which the library refuses); the reference does B*T such reads.  Forward one launch, backward one launch, deterministic."""
+
+    @staticmethod
+    def forward(ctx, y, w_act, b_act, w_grp, b_grp, n_per_frame, T: int, mean_over_t: bool, drop_p: float, seed: int):
+        lib = L.load()
+        y = y.contiguous()
+        w_act, b_act, w_grp, b_grp = w_act.contiguous(), b_act.contiguous(), w_grp.contiguous(), b_grp.contiguous()
+        if n_per_frame is not None:
+            n_per_frame = n_per_frame.reshape(-1).to(torch.int32).contiguous()
+        require_gpu(y, w_act, b_act, w_grp, b_grp, n_per_frame)
+        n, c = y.shape[-2], y.shape[-1]
+        bt = y.numel() // (n * c)
+        aa, ag = w_act.shape[0], w_grp.shape[0]
+        mean = bool(mean_over_t)
+        if n_per_frame is not None:
+            ok = ((n_per_frame >= 1) & (n_per_frame <= n)).all()
+            all_n = int(torch.where(ok, n_per_frame.sum(), -1).to(torch.int32).item())     # the one 4-byte read
+        else:
+            all_n = (bt // T if mean else bt) * n
+        groups = bt // T if mean else bt
+        actions = torch.empty((max(all_n, 1), aa), dtype=torch.float32, device=y.device)     # (all_n < 1: refused by the library)
+        activities = torch.empty((groups, ag), dtype=torch.float32, device=y.device)
+        argmax = torch.empty((bt, c), dtype=torch.int32, device=y.device)
+        L.check(lib.din_basenet_head_fwd(_ptr(y), _ptr(w_act), _ptr(b_act), _ptr(w_grp), _ptr(b_grp), _ptr(n_per_frame), all_n, bt, int(T),
+                                         int(mean), n, c, aa, ag, float(drop_p), int(seed), _ptr(SEED_OFFSET), _ptr(actions),
+                                         _ptr(activities), _ptr(argmax), _stream()), "basenet_head_fwd")
+        ctx.save_for_backward(y, w_act, w_grp, argmax)
+        ctx.n_per_frame, ctx.seed_offset = n_per_frame, SEED_OFFSET
+        ctx.args = (all_n, bt, int(T), int(mean), n, c, aa, ag, float(drop_p), int(seed))
+        return actions, activities
+
+    @staticmethod
+    def backward(ctx, g_actions, g_activities):
+        lib = L.load()
+        y, w_act, w_grp, argmax = ctx.saved_tensors
+        all_n, bt, T, mean, n, c, aa, ag, drop_p, seed = ctx.args
+        g_actions = (g_actions if g_actions is not None else torch.zeros((all_n, aa), device=y.device)).contiguous().float()
+        g_activities = (g_activities if g_activities is not None else
+                        torch.zeros((bt // T if mean else bt, ag), device=y.device)).contiguous().float()
+        g_y = torch.empty_like(y)
+        dw_act, dw_grp = torch.empty_like(w_act), torch.empty_like(w_grp)
+        db_act = torch.empty(aa, dtype=torch.float32, device=y.device)
+        db_grp = torch.empty(ag, dtype=torch.float32, device=y.device)
+        L.check(lib.din_basenet_head_bwd(_ptr(g_actions), _ptr(g_activities), _ptr(y), _ptr(w_act), _ptr(w_grp), _ptr(argmax),
+                                         _ptr(ctx.n_per_frame), all_n, bt, T, mean, n, c, aa, ag, drop_p, seed, _ptr(ctx.seed_offset),
+                                         _ptr(g_y), _ptr(dw_act), _ptr(db_act), _ptr(dw_grp), _ptr(db_grp), _stream()), "basenet_head_bwd")
+        return g_y, dw_act, db_act, dw_grp, db_grp, None, None, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------
 # layout views for API parity (NOT on the training path)
 # ------------------------------------------------------------------------------------------------

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DIN_ABI_VERSION 9   /* 9: din_conv_wgrad_group (the weight gradients of several layers in one launch).   8: din_set_option / din_get_option replace every getenv() of the library (tests select kernels through the ABI; a stray environment variable can no longer change a launch).   7: din_conv_dgrad_x (a strided dgrad that carries the 1x1 / stride-1 dgrad of a sibling conv reading the same view).   6: batch-statistics BatchNorm is deterministic: din_bn_stats / din_bn_bwd_stats write per-workgroup fp64 slabs into a workspace (din_bn_workspace), din_bn_finalize / din_bn_reduce add them in slab order -- no atomics, nothing for the caller to zero.   5: dropout seeds take an optional device-side offset (din_layernorm_*, din_act_dropout_*), din_counter_add, din_conv1x1_wgrad_multi.   2: din_walk_* take plain / clamp / n_per_clip; + bn, mask_actors.  3: din_roi_align_* take the box grid and a crop channel range.  4: din_conv_desc.in_u8, context-encoding entry points */
+#define DIN_ABI_VERSION 9   /* 9: din_conv_wgrad_group (the weight gradients of several layers in one launch); din_basenet_head_fwd / _bwd were added later as a purely additive change (no existing signature changed), so the version stays 9.   8: din_set_option / din_get_option replace every getenv() of the library (tests select kernels through the ABI; a stray environment variable can no longer change a launch).   7: din_conv_dgrad_x (a strided dgrad that carries the 1x1 / stride-1 dgrad of a sibling conv reading the same view).   6: batch-statistics BatchNorm is deterministic: din_bn_stats / din_bn_bwd_stats write per-workgroup fp64 slabs into a workspace (din_bn_workspace), din_bn_finalize / din_bn_reduce add them in slab order -- no atomics, nothing for the caller to zero.   5: dropout seeds take an optional device-side offset (din_layernorm_*, din_act_dropout_*), din_counter_add, din_conv1x1_wgrad_multi.   2: din_walk_* take plain / clamp / n_per_clip; + bn, mask_actors.  3: din_roi_align_* take the box grid and a crop channel range.  4: din_conv_desc.in_u8, context-encoding entry points */
 
 enum { DIN_F32 = 0, DIN_BF16 = 1 };
 
@@ -419,6 +419,31 @@ int din_head_fwd(const float* s, const float* w, const float* bias, const int32_
 /* ds overwritten; dw, dbias ACCUMULATED atomically (caller zeroes) */
 int din_head_bwd(const float* dscores, const float* s, const float* w, const int32_t* argmax,
                  int b, int t, int n, int c, int a, float* ds, float* dw, float* dbias, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-1 base-model head (reference base_model.py:117-139 Basenet_volleyball, :243-268 Basenet_collective):
+ *   s = dropout(relu(y)),  actions = s W_act^T + b_act (one row per valid box),  activities = max_boxes(s) W_grp^T + b_grp (per frame)
+ * y fp32 [bt][n][c] (the fc_emb output; c <= 4096, n <= 256); w_act [a_act][c], w_grp [a_grp][c] (a_act, a_grp <= 16).  s is never
+ * materialised: ReLU and the keep mask of din_act_dropout_fwd (same seed, same flat element index of y, optional seed_offset) are applied
+ * on the fly, so s is bitwise din_act_dropout_fwd(y, relu=1).
+ * mean_over_t != 0 (volleyball with T != 1, :135-137): t frames per clip, actions [bt/t*n][a_act] and activities [bt/t][a_grp] are the
+ *   means over the clip's frames.  Otherwise actions [all_n][a_act], activities [bt][a_grp].
+ * n_per_frame (nullable, device int32 [bt]): frame k holds n_per_frame[k] valid boxes (stage-1 collective counts per frame,
+ *   train_net.py:284-290); action rows are compacted in (frame, box) order, offsets formed on the device.  all_n = number of action rows:
+ *   bt/t*n (mean), bt*n (no n_per_frame) or the sum of n_per_frame, which the caller reads once from the device to size `actions`; a
+ *   caller that finds a count outside 1..n passes all_n < 1 and gets DIN_E_ARG.
+ * argmax int32 [bt][c]: the box of each channel's maximum (first maximum wins), saved for the backward.
+ * Forward: ONE kernel launch.  Backward: ONE kernel launch, deterministic (fixed-order sums, no atomics): g_y [bt][n][c] overwritten
+ *   (zero for padding boxes), dw_act / db_act / dw_grp / db_grp overwritten.  g_actions / g_activities have the forward's output shapes.
+ * ---------------------------------------------------------------------------------------------- */
+int din_basenet_head_fwd(const float* y, const float* w_act, const float* b_act, const float* w_grp, const float* b_grp,
+                         const int32_t* n_per_frame, int all_n, int bt, int t, int mean_over_t, int n, int c, int a_act, int a_grp,
+                         float drop_p, uint64_t seed, const uint64_t* seed_offset, float* actions, float* activities, int32_t* argmax,
+                         void* stream);
+int din_basenet_head_bwd(const float* g_actions, const float* g_activities, const float* y, const float* w_act, const float* w_grp,
+                         const int32_t* argmax, const int32_t* n_per_frame, int all_n, int bt, int t, int mean_over_t, int n, int c,
+                         int a_act, int a_grp, float drop_p, uint64_t seed, const uint64_t* seed_offset, float* g_y, float* dw_act,
+                         float* db_act, float* dw_grp, float* db_grp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Small helpers used by the host mirror
