@@ -107,6 +107,7 @@ SIGNATURES: Dict[str, tuple] = {
     "din_avgpool_bwd": (_I, [_PD, _P, _P, _P, _I, _P]),
     "din_bilinear_fwd": (_I, [_PD, _P, _P, _P]),
     "din_bilinear_bwd": (_I, [_PD, _P, _P, _P, _I, _P]),
+    "din_pool_kernel_name": (_I, [_PD, _I, _I, _I, _I, C.c_char_p, _I]),
     "din_roi_align_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P]),
     "din_roi_align_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "din_roi_crop_grad_transpose": (_I, [_P, _I, _I, _I, _P, _P]),

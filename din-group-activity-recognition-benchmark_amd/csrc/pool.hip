@@ -952,6 +952,92 @@ inline bool is_box3(const din_pool_desc* d) { return d->k == 3 && d->stride == 1
 inline int pool_grid_cap() { const char* e = DIN_OPT("DIN_POOL_GRID_CAP"); return e ? atoi(e) : 32768; }
 inline bool maxpool_rows() { const char* e = DIN_OPT("DIN_MAXPOOL_ROWS"); return e ? atoi(e) != 0 : true; }
 
+// ---- which kernel a launch resolves to ------------------------------------------------------------------------------------------------
+// One decision per entry point (plan_*), taken from the descriptor and the options alone.  The launchers below switch on it and
+// din_pool_kernel_name prints it, so what a test or a profiler is told is what runs.  Names are spelled as at the launch sites
+// (tests/test_host_cpu.py compares the two lists).
+#define POOL_KERNELS(X) \
+    X(MAXPOOL_FWD_8_3, "maxpool_fwd_kernel<8, 3>") X(MAXPOOL_FWD_8_2, "maxpool_fwd_kernel<8, 2>") X(MAXPOOL_FWD_8_0, "maxpool_fwd_kernel<8, 0>") \
+    X(MAXPOOL_FWD_4_3, "maxpool_fwd_kernel<4, 3>") X(MAXPOOL_FWD_4_2, "maxpool_fwd_kernel<4, 2>") X(MAXPOOL_FWD_4_0, "maxpool_fwd_kernel<4, 0>") \
+    X(MAXPOOL_STRIP, "maxpool3s2_strip_kernel<4>") X(MAXPOOL_ROW_FWD, "maxpool3s2_row_fwd_kernel<256>") \
+    X(MAXPOOL_BWD_AMAX_8_2, "maxpool_bwd_amax_kernel<8, 2>") X(MAXPOOL_BWD_AMAX_8_1, "maxpool_bwd_amax_kernel<8, 1>") \
+    X(MAXPOOL_BWD_AMAX_8_0, "maxpool_bwd_amax_kernel<8, 0>") X(MAXPOOL_BWD_AMAX_4_2, "maxpool_bwd_amax_kernel<4, 2>") \
+    X(MAXPOOL_BWD_AMAX_4_1, "maxpool_bwd_amax_kernel<4, 1>") X(MAXPOOL_BWD_AMAX_4_0, "maxpool_bwd_amax_kernel<4, 0>") \
+    X(MAXPOOL_BWD_K3S2_8, "maxpool_bwd_amax_k3s2_kernel<8>") X(MAXPOOL_BWD_K3S2_4, "maxpool_bwd_amax_k3s2_kernel<4>") \
+    X(MAXPOOL_ROW_BWD, "maxpool3s2_row_bwd_kernel<256, false>") X(MAXPOOL_ROW_BWD_ACC, "maxpool3s2_row_bwd_kernel<256, true>") \
+    X(MAXPOOL_BWD_SCAN, "maxpool_bwd_kernel") \
+    X(AVGPOOL_FWD_8_BOX, "avgpool_fwd_kernel<8, true>") X(AVGPOOL_FWD_8, "avgpool_fwd_kernel<8, false>") \
+    X(AVGPOOL_FWD_4_BOX, "avgpool_fwd_kernel<4, true>") X(AVGPOOL_FWD_4, "avgpool_fwd_kernel<4, false>") \
+    X(AVGPOOL_BWD_8_BOX, "avgpool_bwd_kernel<8, true>") X(AVGPOOL_BWD_8, "avgpool_bwd_kernel<8, false>") \
+    X(AVGPOOL_BWD_4_BOX, "avgpool_bwd_kernel<4, true>") X(AVGPOOL_BWD_4, "avgpool_bwd_kernel<4, false>") \
+    X(AVGPOOL_STRIP_FWD_8, "avgpool3_strip_kernel<8, 8, false>") X(AVGPOOL_STRIP_FWD_4, "avgpool3_strip_kernel<4, 8, false>") \
+    X(AVGPOOL_STRIP_BWD_8, "avgpool3_strip_kernel<8, 8, true>") X(AVGPOOL_STRIP_BWD_4, "avgpool3_strip_kernel<4, 8, true>") \
+    X(BILINEAR_FWD_8, "bilinear_fwd_kernel<8>") X(BILINEAR_FWD_4, "bilinear_fwd_kernel<4>") \
+    X(BILINEAR_CELLS_8, "bilinear_fwd_cells_kernel<8>") X(BILINEAR_CELLS_4, "bilinear_fwd_cells_kernel<4>") \
+    X(BILINEAR_BWD_8, "bilinear_bwd_kernel<8>") X(BILINEAR_BWD_4, "bilinear_bwd_kernel<4>") \
+    X(BILINEAR_HOISTED_8, "bilinear_bwd_hoisted_kernel<8, 8>") X(BILINEAR_HOISTED_4, "bilinear_bwd_hoisted_kernel<4, 8>")
+enum PoolKernel {
+#define X(id, name) PK_##id,
+    POOL_KERNELS(X)
+#undef X
+    PK_COUNT
+};
+const char* const pool_kernel_names[PK_COUNT] = {
+#define X(id, name) name,
+    POOL_KERNELS(X)
+#undef X
+};
+
+PoolKernel plan_maxpool_fwd(const din_pool_desc* d) {
+    const bool v8 = wide8(d);
+    // column strips for the wide maps (measured, tools/pool_bench.py: 192 ch 570 -> 537 us, 288 ch 285 -> 201 us; 64 ch 864 -> 1027 us: not there);
+    // DIN_MAXPOOL_STRIP=0 / 2: never / always
+    const char* ms = DIN_OPT("DIN_MAXPOOL_STRIP");
+    const int strip_mode = ms ? atoi(ms) : 1;
+    // row kernels (scalar row bases, max3 with the tap in the low mantissa bits): tools/pool_bench.py; DIN_MAXPOOL_ROWS=0: the kernels below
+    // measured (same box, us): 64 ch 851 -> 653, 192 ch 539 (strip) -> 502, 288 ch 207 (strip) -> 182
+    if (v8 && d->k == 3 && d->stride == 2 && d->pad == 0 && 2 * d->oh + 1 <= d->h && 2 * d->ow + 1 <= d->w && maxpool_rows()) return PK_MAXPOOL_ROW_FWD;
+    if (v8 && d->k == 3 && d->stride == 2 && strip_mode != 0 && (d->c >= 128 || strip_mode == 2)) return PK_MAXPOOL_STRIP;
+    if (v8) return d->k == 3 ? PK_MAXPOOL_FWD_8_3 : d->k == 2 ? PK_MAXPOOL_FWD_8_2 : PK_MAXPOOL_FWD_8_0;
+    return d->k == 3 ? PK_MAXPOOL_FWD_4_3 : d->k == 2 ? PK_MAXPOOL_FWD_4_2 : PK_MAXPOOL_FWD_4_0;
+}
+PoolKernel plan_maxpool_bwd(const din_pool_desc* d, bool has_argmax, bool accumulate) {
+    if (!has_argmax) return PK_MAXPOOL_BWD_SCAN;
+    const bool v8 = wide8(d);
+    if (d->k == 3 && d->stride == 2 && d->pad == 0) {
+        if (v8 && maxpool_rows()) return accumulate ? PK_MAXPOOL_ROW_BWD_ACC : PK_MAXPOOL_ROW_BWD;
+        return v8 ? PK_MAXPOOL_BWD_K3S2_8 : PK_MAXPOOL_BWD_K3S2_4;
+    }
+    const int nw = (d->k + d->stride - 1) / d->stride;       // windows per axis that can contain one input element
+    if (v8) return nw == 2 ? PK_MAXPOOL_BWD_AMAX_8_2 : nw == 1 ? PK_MAXPOOL_BWD_AMAX_8_1 : PK_MAXPOOL_BWD_AMAX_8_0;
+    return nw == 2 ? PK_MAXPOOL_BWD_AMAX_4_2 : nw == 1 ? PK_MAXPOOL_BWD_AMAX_4_1 : PK_MAXPOOL_BWD_AMAX_4_0;
+}
+PoolKernel plan_avgpool(const din_pool_desc* d, bool backward) {
+    const bool v8 = wide8(d), b3 = is_box3(d);
+    if (b3 && avgpool_strip_rows() > 0) {
+        if (backward) return v8 ? PK_AVGPOOL_STRIP_BWD_8 : PK_AVGPOOL_STRIP_BWD_4;
+        return v8 ? PK_AVGPOOL_STRIP_FWD_8 : PK_AVGPOOL_STRIP_FWD_4;
+    }
+    if (backward) return v8 ? (b3 ? PK_AVGPOOL_BWD_8_BOX : PK_AVGPOOL_BWD_8) : (b3 ? PK_AVGPOOL_BWD_4_BOX : PK_AVGPOOL_BWD_4);
+    return v8 ? (b3 ? PK_AVGPOOL_FWD_8_BOX : PK_AVGPOOL_FWD_8) : (b3 ? PK_AVGPOOL_FWD_4_BOX : PK_AVGPOOL_FWD_4);
+}
+PoolKernel plan_bilinear_fwd(const din_pool_desc* d) {
+    const bool v8 = wide8(d);
+    const char* ce = DIN_OPT("DIN_BILINEAR_CELLS");
+    const int cells_env = ce ? atoi(ce) : 1;
+    if (cells_env && d->oh >= d->h && d->ow >= d->w && d->h > 1 && d->w > 1) return v8 ? PK_BILINEAR_CELLS_8 : PK_BILINEAR_CELLS_4;   // up-sampling
+    return v8 ? PK_BILINEAR_FWD_8 : PK_BILINEAR_FWD_4;
+}
+PoolKernel plan_bilinear_bwd(const din_pool_desc* d) {
+    const bool v8 = wide8(d);
+    // candidate window per axis: outputs with source coordinate in (i - 1, i + 1) -> at most 2 / scale + 3 of them
+    const float scy = d->oh > 1 ? (float)(d->h - 1) / (float)(d->oh - 1) : 0.f, scx = d->ow > 1 ? (float)(d->w - 1) / (float)(d->ow - 1) : 0.f;
+    const char* he = DIN_OPT("DIN_BILINEAR_HOIST");
+    const bool hoist = (he ? atoi(he) != 0 : true) && scy > 0.f && scx > 0.f && 2.f / scy + 3.f <= 8.f && 2.f / scx + 3.f <= 8.f;
+    if (hoist) return v8 ? PK_BILINEAR_HOISTED_8 : PK_BILINEAR_HOISTED_4;
+    return v8 ? PK_BILINEAR_BWD_8 : PK_BILINEAR_BWD_4;
+}
+
 }  // namespace
 
 #define POOL_LAUNCH(kern, total, ...) hipLaunchKernelGGL(kern, dim3(grid_1d(total, 256, pool_grid_cap())), dim3(256), 0, as_stream(stream), __VA_ARGS__)
@@ -962,40 +1048,33 @@ int din_maxpool_fwd(const din_pool_desc* d, const void* in, void* out, uint8_t* 
     if (int e = check_pool(d, "maxpool_fwd")) return e;
     DIN_REQUIRE(in && out, "maxpool_fwd: null pointer");
     DIN_REQUIRE(d->k * d->k < 254, "maxpool_fwd: window too large for the byte arg-max map");
+    const PoolKernel pk = plan_maxpool_fwd(d);
     const int v = wide8(d) ? 8 : 4;
     const int64_t total = (int64_t)d->nb * d->oh * d->ow * (d->c / v);
     const Dec3 dd = make_dec(d->c / v, d->ow, d->oh, total);
-    // column strips for the wide maps (measured, tools/pool_bench.py: 192 ch 570 -> 537 us, 288 ch 285 -> 201 us; 64 ch 864 -> 1027 us: not there);
-    // DIN_MAXPOOL_STRIP=0 / 2: never / always
-    const char* ms = DIN_OPT("DIN_MAXPOOL_STRIP");
-    const int strip_mode = ms ? atoi(ms) : 1;
-    // row kernels (scalar row bases, max3 with the tap in the low mantissa bits): tools/pool_bench.py; DIN_MAXPOOL_ROWS=0: the kernels below
-    const bool strip = v == 8 && d->k == 3 && d->stride == 2 && strip_mode != 0 && (d->c >= 128 || strip_mode == 2);
-    // measured (same box, us): 64 ch 851 -> 653, 192 ch 539 (strip) -> 502, 288 ch 207 (strip) -> 182
-    if (v == 8 && d->k == 3 && d->stride == 2 && d->pad == 0 && 2 * d->oh + 1 <= d->h && 2 * d->ow + 1 <= d->w && maxpool_rows()) {
+    switch (pk) {
+    case PK_MAXPOOL_ROW_FWD: {
         const int items = d->ow * (d->c / 8);
         hipLaunchKernelGGL(maxpool3s2_row_fwd_kernel<256>, dim3(d->nb * d->oh * ((items + 255) / 256)), dim3(256), 0, as_stream(stream), *d, make_fastdiv(d->c / 8),
                                (const bf16_t*)in, (bf16_t*)out, argmax);
-        DIN_CHECK_LAUNCH("maxpool_fwd");
-        return DIN_OK;
+        break;
     }
-    if (strip) {
-        constexpr int R = 4;
+    case PK_MAXPOOL_STRIP: {
+        constexpr int R = 4;                                            // output rows per strip
+        static_assert(R == 4, "the launch below and its name in POOL_KERNELS spell maxpool3s2_strip_kernel<4>");
         const int strips = (d->oh + R - 1) / R;
         const int64_t tot = (int64_t)d->nb * strips * d->ow * (d->c / v);
         const Dec3 ds = make_dec(d->c / v, d->ow, strips, tot);
-        POOL_LAUNCH((maxpool3s2_strip_kernel<R>), tot, *d, ds, in, out, argmax);
-        DIN_CHECK_LAUNCH("maxpool_fwd");
-        return DIN_OK;
+        POOL_LAUNCH((maxpool3s2_strip_kernel<4>), tot, *d, ds, in, out, argmax);
+        break;
     }
-    if (v == 8) {
-        if (d->k == 3) POOL_LAUNCH((maxpool_fwd_kernel<8, 3>), total, *d, dd, in, out, argmax);
-        else if (d->k == 2) POOL_LAUNCH((maxpool_fwd_kernel<8, 2>), total, *d, dd, in, out, argmax);
-        else POOL_LAUNCH((maxpool_fwd_kernel<8, 0>), total, *d, dd, in, out, argmax);
-    } else {
-        if (d->k == 3) POOL_LAUNCH((maxpool_fwd_kernel<4, 3>), total, *d, dd, in, out, argmax);
-        else if (d->k == 2) POOL_LAUNCH((maxpool_fwd_kernel<4, 2>), total, *d, dd, in, out, argmax);
-        else POOL_LAUNCH((maxpool_fwd_kernel<4, 0>), total, *d, dd, in, out, argmax);
+    case PK_MAXPOOL_FWD_8_3: POOL_LAUNCH((maxpool_fwd_kernel<8, 3>), total, *d, dd, in, out, argmax); break;
+    case PK_MAXPOOL_FWD_8_2: POOL_LAUNCH((maxpool_fwd_kernel<8, 2>), total, *d, dd, in, out, argmax); break;
+    case PK_MAXPOOL_FWD_8_0: POOL_LAUNCH((maxpool_fwd_kernel<8, 0>), total, *d, dd, in, out, argmax); break;
+    case PK_MAXPOOL_FWD_4_3: POOL_LAUNCH((maxpool_fwd_kernel<4, 3>), total, *d, dd, in, out, argmax); break;
+    case PK_MAXPOOL_FWD_4_2: POOL_LAUNCH((maxpool_fwd_kernel<4, 2>), total, *d, dd, in, out, argmax); break;
+    case PK_MAXPOOL_FWD_4_0: POOL_LAUNCH((maxpool_fwd_kernel<4, 0>), total, *d, dd, in, out, argmax); break;
+    default: DIN_FAIL(DIN_E_ARG, "maxpool_fwd: no kernel for plan %d", (int)pk);
     }
     DIN_CHECK_LAUNCH("maxpool_fwd");
     return DIN_OK;
@@ -1005,44 +1084,35 @@ int din_maxpool_bwd(const din_pool_desc* d, const void* in, const uint8_t* argma
     if (int e = check_pool(d, "maxpool_bwd")) return e;
     DIN_REQUIRE((in || argmax) && dout && din_, "maxpool_bwd: null pointer");
     DIN_REQUIRE(d->stride >= 1 && d->k >= 1, "maxpool_bwd: bad window");
-    if (argmax) {
-        DIN_REQUIRE(relu_mask, "maxpool_bwd: the arg-max map encodes the fused ReLU mask; relu_mask must be set");
-        const int v = wide8(d) ? 8 : 4;
-        if (d->k == 3 && d->stride == 2 && d->pad == 0) {
-            const int hb = (d->h + 1) / 2, wb = (d->w + 1) / 2;
-            if (v == 8 && maxpool_rows()) {
-                        const int items = wb * (d->c / 8);
-                const FastDiv cgd = make_fastdiv(d->c / 8);
-                const bf16_t* go = (const bf16_t*)dout; bf16_t* gi = (bf16_t*)din_;
-                const dim3 grid(d->nb * hb * ((items + 255) / 256));
-                if (accumulate) hipLaunchKernelGGL((maxpool3s2_row_bwd_kernel<256, true>), grid, dim3(256), 0, as_stream(stream), *d, cgd, argmax, go, gi);
-                else hipLaunchKernelGGL((maxpool3s2_row_bwd_kernel<256, false>), grid, dim3(256), 0, as_stream(stream), *d, cgd, argmax, go, gi);
-                DIN_CHECK_LAUNCH("maxpool_bwd");
-                return DIN_OK;
-            }
-            const int64_t totalb = (int64_t)d->nb * hb * wb * (d->c / v);
-            const Dec3 ddb = make_dec(d->c / v, wb, hb, totalb);
-            if (v == 8) POOL_LAUNCH((maxpool_bwd_amax_k3s2_kernel<8>), totalb, *d, ddb, argmax, dout, din_, accumulate);
-            else POOL_LAUNCH((maxpool_bwd_amax_k3s2_kernel<4>), totalb, *d, ddb, argmax, dout, din_, accumulate);
-            DIN_CHECK_LAUNCH("maxpool_bwd");
-            return DIN_OK;
-        }
-        const int64_t total = (int64_t)d->nb * d->h * d->w * (d->c / v);
-        const Dec3 dd = make_dec(d->c / v, d->w, d->h, total);
-        const int nw = (d->k + d->stride - 1) / d->stride;       // windows per axis that can contain one input element
-        if (v == 8) {
-            if (nw == 2) POOL_LAUNCH((maxpool_bwd_amax_kernel<8, 2>), total, *d, dd, argmax, dout, din_, accumulate);
-            else if (nw == 1) POOL_LAUNCH((maxpool_bwd_amax_kernel<8, 1>), total, *d, dd, argmax, dout, din_, accumulate);
-            else POOL_LAUNCH((maxpool_bwd_amax_kernel<8, 0>), total, *d, dd, argmax, dout, din_, accumulate);
-        } else {
-            if (nw == 2) POOL_LAUNCH((maxpool_bwd_amax_kernel<4, 2>), total, *d, dd, argmax, dout, din_, accumulate);
-            else if (nw == 1) POOL_LAUNCH((maxpool_bwd_amax_kernel<4, 1>), total, *d, dd, argmax, dout, din_, accumulate);
-            else POOL_LAUNCH((maxpool_bwd_amax_kernel<4, 0>), total, *d, dd, argmax, dout, din_, accumulate);
-        }
-    } else {
-        const int64_t total = (int64_t)d->nb * d->h * d->w * (d->c / 4);
-        const Dec3 dd = make_dec(d->c / 4, d->w, d->h, total);
-        POOL_LAUNCH(maxpool_bwd_kernel, total, *d, dd, in, dout, din_, relu_mask, accumulate);
+    DIN_REQUIRE(!argmax || relu_mask, "maxpool_bwd: the arg-max map encodes the fused ReLU mask; relu_mask must be set");
+    const PoolKernel pk = plan_maxpool_bwd(d, argmax != nullptr, accumulate != 0);
+    const int v = pk == PK_MAXPOOL_BWD_SCAN ? 4 : wide8(d) ? 8 : 4;
+    const int64_t total = (int64_t)d->nb * d->h * d->w * (d->c / v);
+    const Dec3 dd = make_dec(d->c / v, d->w, d->h, total);
+    const int hb = (d->h + 1) / 2, wb = (d->w + 1) / 2;      // 3/2/0 kernels: 2x2 pixel blocks
+    const int64_t totalb = (int64_t)d->nb * hb * wb * (d->c / v);
+    const Dec3 ddb = make_dec(d->c / v, wb, hb, totalb);
+    switch (pk) {
+    case PK_MAXPOOL_ROW_BWD:
+    case PK_MAXPOOL_ROW_BWD_ACC: {
+        const int items = wb * (d->c / 8);
+        const FastDiv cgd = make_fastdiv(d->c / 8);
+        const bf16_t* go = (const bf16_t*)dout; bf16_t* gi = (bf16_t*)din_;
+        const dim3 grid(d->nb * hb * ((items + 255) / 256));
+        if (pk == PK_MAXPOOL_ROW_BWD_ACC) hipLaunchKernelGGL((maxpool3s2_row_bwd_kernel<256, true>), grid, dim3(256), 0, as_stream(stream), *d, cgd, argmax, go, gi);
+        else hipLaunchKernelGGL((maxpool3s2_row_bwd_kernel<256, false>), grid, dim3(256), 0, as_stream(stream), *d, cgd, argmax, go, gi);
+        break;
+    }
+    case PK_MAXPOOL_BWD_K3S2_8: POOL_LAUNCH((maxpool_bwd_amax_k3s2_kernel<8>), totalb, *d, ddb, argmax, dout, din_, accumulate); break;
+    case PK_MAXPOOL_BWD_K3S2_4: POOL_LAUNCH((maxpool_bwd_amax_k3s2_kernel<4>), totalb, *d, ddb, argmax, dout, din_, accumulate); break;
+    case PK_MAXPOOL_BWD_AMAX_8_2: POOL_LAUNCH((maxpool_bwd_amax_kernel<8, 2>), total, *d, dd, argmax, dout, din_, accumulate); break;
+    case PK_MAXPOOL_BWD_AMAX_8_1: POOL_LAUNCH((maxpool_bwd_amax_kernel<8, 1>), total, *d, dd, argmax, dout, din_, accumulate); break;
+    case PK_MAXPOOL_BWD_AMAX_8_0: POOL_LAUNCH((maxpool_bwd_amax_kernel<8, 0>), total, *d, dd, argmax, dout, din_, accumulate); break;
+    case PK_MAXPOOL_BWD_AMAX_4_2: POOL_LAUNCH((maxpool_bwd_amax_kernel<4, 2>), total, *d, dd, argmax, dout, din_, accumulate); break;
+    case PK_MAXPOOL_BWD_AMAX_4_1: POOL_LAUNCH((maxpool_bwd_amax_kernel<4, 1>), total, *d, dd, argmax, dout, din_, accumulate); break;
+    case PK_MAXPOOL_BWD_AMAX_4_0: POOL_LAUNCH((maxpool_bwd_amax_kernel<4, 0>), total, *d, dd, argmax, dout, din_, accumulate); break;
+    case PK_MAXPOOL_BWD_SCAN: POOL_LAUNCH(maxpool_bwd_kernel, total, *d, dd, in, dout, din_, relu_mask, accumulate); break;
+    default: DIN_FAIL(DIN_E_ARG, "maxpool_bwd: no kernel for plan %d", (int)pk);
     }
     DIN_CHECK_LAUNCH("maxpool_bwd");
     return DIN_OK;
@@ -1055,19 +1125,21 @@ int din_avgpool_fwd(const din_pool_desc* d, const void* in, void* out, const flo
     const int v = wide8(d) ? 8 : 4;
     const int64_t total = (int64_t)d->nb * d->oh * d->ow * (d->c / v);
     const Dec3 dd = make_dec(d->c / v, d->ow, d->oh, total);
-    const bool b3 = is_box3(d);
-    if (b3 && avgpool_strip_rows() > 0) {
-        constexpr int R = 8;
-        const int strips = (d->h + R - 1) / R;
-        const int64_t tot = (int64_t)d->nb * strips * d->w * (d->c / v);
-        const Dec3 ds = make_dec(d->c / v, d->w, strips, tot);
-        if (v == 8) POOL_LAUNCH((avgpool3_strip_kernel<8, R, false>), tot, d->nb, d->h, d->w, d->c / v, ds, d->dtype, in, d->ldi, d->cioff, out, d->ldo, d->cooff, bias, flags, (const void*)nullptr, 0);
-        else POOL_LAUNCH((avgpool3_strip_kernel<4, R, false>), tot, d->nb, d->h, d->w, d->c / v, ds, d->dtype, in, d->ldi, d->cioff, out, d->ldo, d->cooff, bias, flags, (const void*)nullptr, 0);
-        DIN_CHECK_LAUNCH("avgpool_fwd");
-        return DIN_OK;
+    constexpr int R = 8;                                                // rows per strip
+    static_assert(R == 8, "the launches below and their names in POOL_KERNELS spell avgpool3_strip_kernel<V, 8, ...>");
+    const int strips = (d->h + R - 1) / R;
+    const int64_t tot = (int64_t)d->nb * strips * d->w * (d->c / v);
+    const Dec3 ds = make_dec(d->c / v, d->w, strips, tot);
+    const PoolKernel pk = plan_avgpool(d, false);
+    switch (pk) {
+    case PK_AVGPOOL_STRIP_FWD_8: POOL_LAUNCH((avgpool3_strip_kernel<8, 8, false>), tot, d->nb, d->h, d->w, d->c / v, ds, d->dtype, in, d->ldi, d->cioff, out, d->ldo, d->cooff, bias, flags, (const void*)nullptr, 0); break;
+    case PK_AVGPOOL_STRIP_FWD_4: POOL_LAUNCH((avgpool3_strip_kernel<4, 8, false>), tot, d->nb, d->h, d->w, d->c / v, ds, d->dtype, in, d->ldi, d->cioff, out, d->ldo, d->cooff, bias, flags, (const void*)nullptr, 0); break;
+    case PK_AVGPOOL_FWD_8_BOX: POOL_LAUNCH((avgpool_fwd_kernel<8, true>), total, *d, dd, in, out, bias, flags); break;
+    case PK_AVGPOOL_FWD_8: POOL_LAUNCH((avgpool_fwd_kernel<8, false>), total, *d, dd, in, out, bias, flags); break;
+    case PK_AVGPOOL_FWD_4_BOX: POOL_LAUNCH((avgpool_fwd_kernel<4, true>), total, *d, dd, in, out, bias, flags); break;
+    case PK_AVGPOOL_FWD_4: POOL_LAUNCH((avgpool_fwd_kernel<4, false>), total, *d, dd, in, out, bias, flags); break;
+    default: DIN_FAIL(DIN_E_ARG, "avgpool_fwd: no kernel for plan %d", (int)pk);
     }
-    if (v == 8) { if (b3) POOL_LAUNCH((avgpool_fwd_kernel<8, true>), total, *d, dd, in, out, bias, flags); else POOL_LAUNCH((avgpool_fwd_kernel<8, false>), total, *d, dd, in, out, bias, flags); }
-    else { if (b3) POOL_LAUNCH((avgpool_fwd_kernel<4, true>), total, *d, dd, in, out, bias, flags); else POOL_LAUNCH((avgpool_fwd_kernel<4, false>), total, *d, dd, in, out, bias, flags); }
     DIN_CHECK_LAUNCH("avgpool_fwd");
     return DIN_OK;
 }
@@ -1078,19 +1150,21 @@ int din_avgpool_bwd(const din_pool_desc* d, const void* dout, void* din_, const 
     const int v = wide8(d) ? 8 : 4;
     const int64_t total = (int64_t)d->nb * d->h * d->w * (d->c / v);
     const Dec3 dd = make_dec(d->c / v, d->w, d->h, total);
-    const bool b3 = is_box3(d);
-    if (b3 && avgpool_strip_rows() > 0) {                               // the box filter is symmetric: same strip, source = dout view, destination = din view
-        constexpr int R = 8;
-        const int strips = (d->h + R - 1) / R;
-        const int64_t tot = (int64_t)d->nb * strips * d->w * (d->c / v);
-        const Dec3 ds = make_dec(d->c / v, d->w, strips, tot);
-        if (v == 8) POOL_LAUNCH((avgpool3_strip_kernel<8, R, true>), tot, d->nb, d->h, d->w, d->c / v, ds, d->dtype, dout, d->ldo, d->cooff, din_, d->ldi, d->cioff, (const float*)nullptr, 0, mask, accumulate);
-        else POOL_LAUNCH((avgpool3_strip_kernel<4, R, true>), tot, d->nb, d->h, d->w, d->c / v, ds, d->dtype, dout, d->ldo, d->cooff, din_, d->ldi, d->cioff, (const float*)nullptr, 0, mask, accumulate);
-        DIN_CHECK_LAUNCH("avgpool_bwd");
-        return DIN_OK;
+    constexpr int R = 8;                                                // rows per strip
+    static_assert(R == 8, "the launches below and their names in POOL_KERNELS spell avgpool3_strip_kernel<V, 8, ...>");
+    const int strips = (d->h + R - 1) / R;
+    const int64_t tot = (int64_t)d->nb * strips * d->w * (d->c / v);
+    const Dec3 ds = make_dec(d->c / v, d->w, strips, tot);
+    const PoolKernel pk = plan_avgpool(d, true);
+    switch (pk) {                                                       // the box filter is symmetric: same strip, source = dout view, destination = din view
+    case PK_AVGPOOL_STRIP_BWD_8: POOL_LAUNCH((avgpool3_strip_kernel<8, 8, true>), tot, d->nb, d->h, d->w, d->c / v, ds, d->dtype, dout, d->ldo, d->cooff, din_, d->ldi, d->cioff, (const float*)nullptr, 0, mask, accumulate); break;
+    case PK_AVGPOOL_STRIP_BWD_4: POOL_LAUNCH((avgpool3_strip_kernel<4, 8, true>), tot, d->nb, d->h, d->w, d->c / v, ds, d->dtype, dout, d->ldo, d->cooff, din_, d->ldi, d->cioff, (const float*)nullptr, 0, mask, accumulate); break;
+    case PK_AVGPOOL_BWD_8_BOX: POOL_LAUNCH((avgpool_bwd_kernel<8, true>), total, *d, dd, dout, din_, mask, accumulate); break;
+    case PK_AVGPOOL_BWD_8: POOL_LAUNCH((avgpool_bwd_kernel<8, false>), total, *d, dd, dout, din_, mask, accumulate); break;
+    case PK_AVGPOOL_BWD_4_BOX: POOL_LAUNCH((avgpool_bwd_kernel<4, true>), total, *d, dd, dout, din_, mask, accumulate); break;
+    case PK_AVGPOOL_BWD_4: POOL_LAUNCH((avgpool_bwd_kernel<4, false>), total, *d, dd, dout, din_, mask, accumulate); break;
+    default: DIN_FAIL(DIN_E_ARG, "avgpool_bwd: no kernel for plan %d", (int)pk);
     }
-    if (v == 8) { if (b3) POOL_LAUNCH((avgpool_bwd_kernel<8, true>), total, *d, dd, dout, din_, mask, accumulate); else POOL_LAUNCH((avgpool_bwd_kernel<8, false>), total, *d, dd, dout, din_, mask, accumulate); }
-    else { if (b3) POOL_LAUNCH((avgpool_bwd_kernel<4, true>), total, *d, dd, dout, din_, mask, accumulate); else POOL_LAUNCH((avgpool_bwd_kernel<4, false>), total, *d, dd, dout, din_, mask, accumulate); }
     DIN_CHECK_LAUNCH("avgpool_bwd");
     return DIN_OK;
 }
@@ -1098,20 +1172,18 @@ int din_bilinear_fwd(const din_pool_desc* d, const void* in, void* out, void* st
     if (int e = check_pool(d, "bilinear_fwd")) return e;
     DIN_REQUIRE(in && out, "bilinear_fwd: null pointer");
     const int v = wide8(d) ? 8 : 4;
-    const char* ce = DIN_OPT("DIN_BILINEAR_CELLS");
-    const int cells_env = ce ? atoi(ce) : 1;
-    if (cells_env && d->oh >= d->h && d->ow >= d->w && d->h > 1 && d->w > 1) {          // up-sampling: one thread per source cell
-        const int64_t total = (int64_t)d->nb * d->h * d->w * (d->c / v);
-        const Dec3 dd = make_dec(d->c / v, d->w, d->h, total);
-        if (v == 8) POOL_LAUNCH(bilinear_fwd_cells_kernel<8>, total, *d, dd, in, out);
-        else POOL_LAUNCH(bilinear_fwd_cells_kernel<4>, total, *d, dd, in, out);
-        DIN_CHECK_LAUNCH("bilinear_fwd");
-        return DIN_OK;
-    }
+    const int64_t cells = (int64_t)d->nb * d->h * d->w * (d->c / v);                    // up-sampling: one thread per source cell
+    const Dec3 dc = make_dec(d->c / v, d->w, d->h, cells);
     const int64_t total = (int64_t)d->nb * d->oh * d->ow * (d->c / v);
     const Dec3 dd = make_dec(d->c / v, d->ow, d->oh, total);
-    if (v == 8) POOL_LAUNCH(bilinear_fwd_kernel<8>, total, *d, dd, in, out);
-    else POOL_LAUNCH(bilinear_fwd_kernel<4>, total, *d, dd, in, out);
+    const PoolKernel pk = plan_bilinear_fwd(d);
+    switch (pk) {
+    case PK_BILINEAR_CELLS_8: POOL_LAUNCH(bilinear_fwd_cells_kernel<8>, cells, *d, dc, in, out); break;
+    case PK_BILINEAR_CELLS_4: POOL_LAUNCH(bilinear_fwd_cells_kernel<4>, cells, *d, dc, in, out); break;
+    case PK_BILINEAR_FWD_8: POOL_LAUNCH(bilinear_fwd_kernel<8>, total, *d, dd, in, out); break;
+    case PK_BILINEAR_FWD_4: POOL_LAUNCH(bilinear_fwd_kernel<4>, total, *d, dd, in, out); break;
+    default: DIN_FAIL(DIN_E_ARG, "bilinear_fwd: no kernel for plan %d", (int)pk);
+    }
     DIN_CHECK_LAUNCH("bilinear_fwd");
     return DIN_OK;
 }
@@ -1121,17 +1193,26 @@ int din_bilinear_bwd(const din_pool_desc* d, const void* dout, void* din_, const
     const int v = wide8(d) ? 8 : 4;
     const int64_t total = (int64_t)d->nb * d->h * d->w * (d->c / v);
     const Dec3 dd = make_dec(d->c / v, d->w, d->h, total);
-    // candidate window per axis: outputs with source coordinate in (i - 1, i + 1) -> at most 2 / scale + 3 of them
-    const float scy = d->oh > 1 ? (float)(d->h - 1) / (float)(d->oh - 1) : 0.f, scx = d->ow > 1 ? (float)(d->w - 1) / (float)(d->ow - 1) : 0.f;
-    const char* he = DIN_OPT("DIN_BILINEAR_HOIST");
-    const bool hoist = (he ? atoi(he) != 0 : true) && scy > 0.f && scx > 0.f && 2.f / scy + 3.f <= 8.f && 2.f / scx + 3.f <= 8.f;
-    if (hoist) {
-        if (v == 8) POOL_LAUNCH((bilinear_bwd_hoisted_kernel<8, 8>), total, *d, dd, dout, din_, mask, accumulate);
-        else POOL_LAUNCH((bilinear_bwd_hoisted_kernel<4, 8>), total, *d, dd, dout, din_, mask, accumulate);
+    const PoolKernel pk = plan_bilinear_bwd(d);
+    switch (pk) {
+    case PK_BILINEAR_HOISTED_8: POOL_LAUNCH((bilinear_bwd_hoisted_kernel<8, 8>), total, *d, dd, dout, din_, mask, accumulate); break;
+    case PK_BILINEAR_HOISTED_4: POOL_LAUNCH((bilinear_bwd_hoisted_kernel<4, 8>), total, *d, dd, dout, din_, mask, accumulate); break;
+    case PK_BILINEAR_BWD_8: POOL_LAUNCH(bilinear_bwd_kernel<8>, total, *d, dd, dout, din_, mask, accumulate); break;
+    case PK_BILINEAR_BWD_4: POOL_LAUNCH(bilinear_bwd_kernel<4>, total, *d, dd, dout, din_, mask, accumulate); break;
+    default: DIN_FAIL(DIN_E_ARG, "bilinear_bwd: no kernel for plan %d", (int)pk);
     }
-    else if (v == 8) POOL_LAUNCH(bilinear_bwd_kernel<8>, total, *d, dd, dout, din_, mask, accumulate);
-    else POOL_LAUNCH(bilinear_bwd_kernel<4>, total, *d, dd, dout, din_, mask, accumulate);
     DIN_CHECK_LAUNCH("bilinear_bwd");
+    return DIN_OK;
+}
+int din_pool_kernel_name(const din_pool_desc* d, int op, int backward, int has_argmax, int accumulate, char* buf, int buf_bytes) {
+    if (int e = check_pool(d, "pool_kernel_name")) return e;
+    DIN_REQUIRE(op >= 0 && op <= 2, "pool_kernel_name: op must be 0 (maxpool), 1 (avgpool) or 2 (bilinear)");
+    DIN_REQUIRE(buf != nullptr, "pool_kernel_name: null buffer");
+    const PoolKernel pk = op == 0 ? (backward ? plan_maxpool_bwd(d, has_argmax != 0, accumulate != 0) : plan_maxpool_fwd(d))
+                        : op == 1 ? plan_avgpool(d, backward != 0)
+                                  : (backward ? plan_bilinear_bwd(d) : plan_bilinear_fwd(d));
+    const int n = snprintf(buf, buf_bytes > 0 ? (size_t)buf_bytes : 0, "%s", pool_kernel_names[pk]);
+    DIN_REQUIRE(n < buf_bytes, "pool_kernel_name: the name needs %d bytes", n + 1);
     return DIN_OK;
 }
 

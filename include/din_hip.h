@@ -293,6 +293,11 @@ int din_avgpool_bwd(const din_pool_desc* d, const void* dout, void* din_, const 
 int din_bilinear_fwd(const din_pool_desc* d, const void* in, void* out, void* stream); /* align_corners=True */
 int din_bilinear_bwd(const din_pool_desc* d, const void* dout, void* din_, const void* mask, int accumulate,
                      void* stream);
+/* host-only: writes the name of the kernel instantiation the launch resolves to, exactly as it is spelled at the launch site
+ * ("maxpool3s2_row_bwd_kernel<256, true>"), from the decision function the launchers themselves switch on -- for tests and for a
+ * profiler-side caller that wants to spell the name rocprofv3 prints.  has_argmax / accumulate matter to din_maxpool_bwd only. */
+int din_pool_kernel_name(const din_pool_desc* d, int op /*0 maxpool,1 avgpool,2 bilinear*/, int backward, int has_argmax,
+                         int accumulate, char* buf, int buf_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Row R  RoIAlign(K,K) = TF crop_and_resize, transform_fpcoor=True (third-party longcw/RoIAlign.pytorch;

@@ -493,7 +493,9 @@ def test_pools(env, kind, k, s, p, dtype, ldi, cioff):
         L.check(lib.din_maxpool_fwd(C.byref(d), xin.data_ptr(), out.data_ptr(), amax.data_ptr(), None))
     else:
         L.check(lib.din_avgpool_fwd(C.byref(d), xin.data_ptr(), out.data_ptr(), None, 0, None))
-    tol = 1e-6 if dtype == "fp32" else 8e-3
+    # bf16: one rounding of the fp32 result on store, <= 2^-8 of the element (tests/test_gpu_pool.py holds every element to that; max-rel
+    # over the tensor cannot exceed it), plus the fp32 sums' few 1e-7
+    tol = 1e-6 if dtype == "fp32" else 4e-3
     assert rel(from_nhwc(out, 16), y) <= tol
     if kind == "avgpool":                                                 # fused bias + ReLU epilogue (commuted 1x1 conv) and colsum
         bias = torch.randn(16, generator=g).cuda()
@@ -508,14 +510,14 @@ def test_pools(env, kind, k, s, p, dtype, ldi, cioff):
         L.check(lib.din_maxpool_bwd(C.byref(d), xin.data_ptr(), None, gout.data_ptr(), dx.data_ptr(), 1, 0, None))
         torch.cuda.synchronize()
         want = xr.grad * (x > 0).float()
-        assert rel(from_nhwc(dx, 16, cioff), want) <= (1e-6 if dtype == "fp32" else 1.5e-2)
+        assert rel(from_nhwc(dx, 16, cioff), want) <= tol
         dx.zero_()                                                        # same answer from the saved arg-max map
         L.check(lib.din_maxpool_bwd(C.byref(d), None, amax.data_ptr(), gout.data_ptr(), dx.data_ptr(), 1, 0, None))
     else:
         L.check(lib.din_avgpool_bwd(C.byref(d), gout.data_ptr(), dx.data_ptr(), xin.data_ptr(), 0, None))
     torch.cuda.synchronize()
     want = xr.grad * (x > 0).float()
-    assert rel(from_nhwc(dx, 16, cioff), want) <= (1e-6 if dtype == "fp32" else 1.5e-2)
+    assert rel(from_nhwc(dx, 16, cioff), want) <= tol
 
 
 def test_bilinear_align_corners(env):

@@ -155,6 +155,27 @@ def test_every_wgrad_kernel_instantiation_has_a_row_in_the_fp64_table():
     assert launched == named, f"launched without a row: {sorted(launched - named)}; rows naming no launch: {sorted(named - launched)}"
 
 
+def test_every_pool_kernel_instantiation_has_a_row_in_the_fp64_table():
+    """the kernel instantiations csrc/pool.hip launches (hipLaunchKernelGGL / POOL_LAUNCH sites, comments stripped) equal the kernels named by
+    the rows of tests/test_gpu_pool.py and the names din_pool_kernel_name can answer: a kernel added without a row, a row naming no launch
+    or a name the query spells differently from its launch site fails here, on the CPU"""
+    import re
+    from tests.test_gpu_pool import POOL_CASES
+    with open(os.path.join(ROOT, "din-group-activity-recognition-benchmark_amd", "csrc", "pool.hip")) as fh:
+        text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S))
+
+    def norm(name):
+        return re.sub(r"\s+", "", name)
+
+    sites = re.findall(r"(?:hipLaunchKernelGGL|POOL_LAUNCH)\(\s*\(?\s*(\w+_kernel\b(?:\s*<[^<>;()]*>)?)", text)
+    launched = {norm(s) for s in sites}
+    assert len(launched) >= 39, sorted(launched)
+    named = {norm(r["kernel"]) for r in POOL_CASES}
+    assert launched == named, f"launched without a row: {sorted(launched - named)}; rows naming no launch: {sorted(named - launched)}"
+    answers = {norm(n) for n in re.findall(r'X\(\w+,\s*"([^"]+)"\)', text)}     # the POOL_KERNELS list: enum and name table come from it
+    assert answers == launched, f"din_pool_kernel_name and the launch sites disagree: {sorted(answers ^ launched)}"
+
+
 def test_conv_planning_is_callable_without_gpu():
     from din_amd import _lib
     lib = _lib.load()
