@@ -13,7 +13,7 @@ _DEFAULTS = dict(
     backbone="res18", crop_size=(5, 5), train_backbone=False, out_size=(87, 157), emb_features=1056,
     num_actions=9, num_activities=8, actions_loss_weight=1.0, actions_weights=None,
     num_frames=3, num_before=5, num_after=4,
-    num_features_boxes=1024, num_features_relation=256, num_graph=16, num_features_gcn=1024, gcn_layers=1,
+    num_features_boxes=1024, num_features_relation=256, num_graph=16, num_features_gcn=1024, gcn_layers=1, pos_threshold=0.2,
     train_random_seed=0, train_learning_rate=1e-4, lr_plan={11: 3e-5, 21: 1e-5}, train_dropout_prob=0.3, weight_decay=0,
     max_epoch=30, test_interval_epoch=1,
     training_stage=1, stage1_model_path="", test_before_train=False, exp_note="Group-Activity-Recognition", exp_name=None,

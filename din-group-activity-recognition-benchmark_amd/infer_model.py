@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import ops
 from .backbone.backbone import MyInception_v3, MyVGG16
+from .infer_module.ARG_infer_module import GCN_Module
 from .infer_module.dynamic_infer_module import (Dynamic_Person_Inference, Hierarchical_Dynamic_Inference,
                                                 Multi_Dynamic_Inference)
 from .infer_module.positional_encoding import Context_PositionEmbeddingSine
@@ -303,4 +304,57 @@ class Dynamic_collective(_DynamicBase):
         s = s.permute(0, 2, 1, 3).contiguous()                                        # [B, T, N, C]
         # max over the clip's n_b actors, fc, mean over T (:1306-1309)
         scores = ops.HeadFunction.apply(s, self.fc_activities.weight, self.fc_activities.bias, n_per_clip)
+        return {"activities": scores}
+
+
+class ARG_volleyball(_DynamicBase):
+    """the Actor Relation Graph baseline for the volleyball dataset (reference infer_model.py:870-1023): the shared trunk, `gcn_layers`
+    GCN_Module blocks over the T*N actors of a clip, `graph + x`, dropout, max over N, fc_activities, mean over T.  Same constructor,
+    `forward((images, boxes)) -> {'activities': [B, A]}`, `loadmodel` and state_dict keys (backbone.*, fc_emb_1, nl_emb_1, gcn_list.*,
+    fc_activities), so the reference's checkpoints load unchanged.
+
+    In eval() a clip of 3*T frames is folded into three T-frame sub-clips -- flat frame order, consecutive thirds, as :939-947 -- whose
+    scores are averaged (:1016-1019).
+
+    Deliberate differences from the reference: the caller's `boxes` are left untouched (GCN_Module's docstring); the dropout mask is
+    the counter hash of the other models here, not the host RNG stream; 'res18' / 'vgg19' / 'alex' are out of scope (make_backbone)."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        NFB, NFG = cfg.num_features_boxes, cfg.num_features_gcn
+        assert NFG == NFB, (f"ARG_volleyball adds the graph features to the box embeddings (infer_model.py:995): num_features_gcn ({NFG}) "
+                            f"must equal num_features_boxes ({NFB})")
+        self._build_trunk(cfg)
+        self.gcn_list = nn.ModuleList([GCN_Module(cfg) for _ in range(cfg.gcn_layers)])            # :909
+        for i, m in enumerate(self.gcn_list):
+            m.centre_rounds = i + 1
+        self.dropout_global = nn.Dropout(p=cfg.train_dropout_prob)      # holder of p; the mask is formed by ops.ActDropoutFunction
+        self.fc_activities = nn.Linear(NFG, cfg.num_activities)
+        self._init_linears()
+
+    def forward(self, batch_data):
+        images_in, boxes_in = batch_data
+        cfg = self.cfg
+        B, T, N = images_in.shape[0], images_in.shape[1], cfg.num_boxes
+        if not self.training:                                                             # :939-943
+            if T % 3 != 0:
+                raise ValueError(f"ARG_volleyball in eval() folds a clip into three sub-clips (reference infer_model.py:939-943): the clip "
+                                 f"has {T} frames, not a multiple of 3")
+            B, T = B * 3, T // 3
+            images_in = images_in.reshape((B, T) + tuple(images_in.shape[2:]))
+            boxes_in = boxes_in.reshape((B, T) + tuple(boxes_in.shape[2:]))
+        x = self._embed(images_in, boxes_in, N)                                           # [B,T,N,NFB]  (:946-980)
+        graph = x.reshape(B, T * N, -1)
+        boxes_flat = boxes_in.reshape(B * T * N, 4)
+        for gcn in self.gcn_list:                                                         # :986-987
+            graph, _relation_graph = gcn(graph, boxes_flat)
+        s = ops.AxpbyFunction.apply(graph.reshape(B, T, N, -1), x, 1.0, 1.0)              # :995
+        p = cfg.train_dropout_prob if self.training else 0.0
+        s = ops.ActDropoutFunction.apply(s, False, p, self._dropout_seed())               # :997
+        scores = ops.HeadFunction.apply(s, self.fc_activities.weight, self.fc_activities.bias, None)   # :1006-1014
+        if not self.training:                                                             # :1016-1019
+            B = B // 3
+            scores = ops.AxpbyFunction.apply(ops.AxpbyFunction.apply(scores.reshape(B, 3, -1)[:, 0], scores.reshape(B, 3, -1)[:, 1], 1.0, 1.0),
+                                             scores.reshape(B, 3, -1)[:, 2], 1.0 / 3.0, 1.0 / 3.0)
         return {"activities": scores}

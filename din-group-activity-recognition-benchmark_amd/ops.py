@@ -593,6 +593,67 @@ class BasenetHeadFunction(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# Actor Relation Graph block (ARG baseline)
+# ------------------------------------------------------------------------------------------------
+def arg_graph_workspace_floats(b: int, tn: int, ng: int, nfg: int, backward: bool) -> int:
+    """scratch the two entry points ask for (include/din_hip.h)"""
+    nchunk = (nfg + 63) // 64
+    if not backward:
+        return b * ng * nchunk * 3
+    return b * ng * tn * nfg + (b * ng * nchunk * 2 + 3) // 4 * 4 + b * ng * tn * tn
+
+
+class ArgGraphFunction(torch.autograd.Function):
+    """proj [B, TN, NG*(2*NFR+NFG)] = X [W_theta,0.. | W_phi,0.. | W_gcn,0..]^T (+ biases), boxes [B, TN, 4], gamma / beta [NG, TN, NFG]
+    -> (out [B, TN, NFG], rel [B, NG, TN, TN], mask bool [B, TN, TN]) -- reference ARG_infer_module.py:46-89 after its Linear layers.
+    centre_rounds: the GCN layer's index + 1 (how often the reference has averaged the box corners in place by then)."""
+
+    @staticmethod
+    def forward(ctx, proj, boxes, gamma, beta, ng: int, nfr: int, nfg: int, thr: float, centre_rounds: int):
+        lib = L.load()
+        proj, gamma, beta = proj.contiguous(), gamma.contiguous(), beta.contiguous()
+        boxes = boxes.detach().float().contiguous()
+        require_gpu(proj, boxes, gamma, beta)
+        b, tn, ld = proj.shape
+        assert ld == ng * (2 * nfr + nfg), (proj.shape, ng, nfr, nfg)
+        assert tuple(boxes.shape) == (b, tn, 4) and tuple(gamma.shape) == (ng, tn, nfg) == tuple(beta.shape), (boxes.shape, gamma.shape)
+        dev = proj.device
+        out = torch.empty((b, tn, nfg), dtype=torch.float32, device=dev)
+        rel = torch.empty((b, ng, tn, tn), dtype=torch.float32, device=dev)
+        mask = torch.empty((b, tn, tn), dtype=torch.uint8, device=dev)
+        z = torch.empty((b, ng, tn, nfg), dtype=torch.float32, device=dev)
+        stats = torch.empty((b, ng, 2), dtype=torch.float32, device=dev)
+        nws = arg_graph_workspace_floats(b, tn, ng, nfg, False)
+        ws = torch.empty(nws, dtype=torch.float32, device=dev)
+        base, esz = proj.data_ptr(), 4
+        L.check(lib.din_arg_graph_fwd(base, base + ng * nfr * esz, base + 2 * ng * nfr * esz, ld, _ptr(boxes), int(centre_rounds), float(thr),
+                                      _ptr(gamma), _ptr(beta), 1e-5, b, tn, ng, nfr, nfg, _ptr(out), _ptr(rel), _ptr(mask), _ptr(z),
+                                      _ptr(stats), _ptr(ws), nws, _stream()), "arg_graph_fwd")
+        ctx.save_for_backward(proj, gamma, beta, rel, z, stats)
+        ctx.dims = (b, tn, ng, nfr, nfg)
+        mask = mask.view(torch.bool)
+        ctx.mark_non_differentiable(rel, mask)
+        return out, rel, mask
+
+    @staticmethod
+    def backward(ctx, gout, _grel, _gmask):
+        lib = L.load()
+        proj, gamma, beta, rel, z, stats = ctx.saved_tensors
+        b, tn, ng, nfr, nfg = ctx.dims
+        ld = proj.shape[2]
+        gout = gout.contiguous()
+        dproj = torch.empty_like(proj)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+        nws = arg_graph_workspace_floats(b, tn, ng, nfg, True)
+        ws = torch.empty(nws, dtype=torch.float32, device=proj.device)
+        base, gbase, esz = proj.data_ptr(), dproj.data_ptr(), 4
+        L.check(lib.din_arg_graph_bwd(_ptr(gout), base, base + ng * nfr * esz, base + 2 * ng * nfr * esz, ld, _ptr(gamma), _ptr(beta),
+                                      _ptr(rel), _ptr(z), _ptr(stats), b, tn, ng, nfr, nfg, gbase, gbase + ng * nfr * esz,
+                                      gbase + 2 * ng * nfr * esz, ld, _ptr(dgamma), _ptr(dbeta), _ptr(ws), nws, _stream()), "arg_graph_bwd")
+        return dproj, None, dgamma, dbeta, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
 # layout views for API parity (NOT on the training path)
 # ------------------------------------------------------------------------------------------------
 class NHWCToNCHWFunction(torch.autograd.Function):

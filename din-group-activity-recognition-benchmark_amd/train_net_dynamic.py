@@ -15,6 +15,7 @@ with MAX_N boxes plus bboxes_num [T]); with none given it trains on a synthetic 
 """
 from __future__ import annotations
 
+import copy
 import os
 
 import random
@@ -27,7 +28,7 @@ import torch.utils.data as data
 
 from . import parallel
 from .input_feed import DeviceFeed
-from .infer_model import Dynamic_collective, Dynamic_TCE_volleyball, Dynamic_volleyball
+from .infer_model import ARG_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, Dynamic_volleyball
 from .optim import FusedAdam
 from .utils import AverageMeter, Timer, print_log
 
@@ -87,9 +88,9 @@ class SyntheticCollective(SyntheticVolleyball):
 
 def build_model(cfg):
     registry = {"dynamic_volleyball": Dynamic_volleyball, "dynamic_tce_volleyball": Dynamic_TCE_volleyball,
-                "dynamic_collective": Dynamic_collective}                            # reference train_net_dynamic.py:66-73
+                "dynamic_collective": Dynamic_collective, "arg_volleyball": ARG_volleyball}   # reference train_net_dynamic.py:66-73
     if cfg.inference_module_name not in registry:
-        raise NotImplementedError(f"{cfg.inference_module_name}: only the DIN models are on the MI355X hot path")
+        raise NotImplementedError(f"{cfg.inference_module_name}: only the DIN models and the ARG baseline are on the MI355X hot path")
     return registry[cfg.inference_module_name](cfg)
 
 
@@ -205,6 +206,11 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
         from .dataset import return_dataset
         training_set, validation_set = return_dataset(cfg)
     training_set = training_set or synth(cfg, length=max(cfg.batch_size * 2, 4))
+    if validation_set is None and cfg.inference_module_name == "arg_volleyball":
+        # ARG test clips hold three sub-clips of num_frames frames each (volleyball.py:212-214, infer_model.py:939-943)
+        vcfg = copy.copy(cfg)
+        vcfg.num_frames = 3 * cfg.num_frames
+        validation_set = synth(vcfg, length=max(cfg.test_batch_size, 2), seed=1)
     validation_set = validation_set or synth(cfg, length=max(cfg.test_batch_size, 2), seed=1)
     if cfg.batch_size % world != 0:
         raise ValueError(f"batch_size {cfg.batch_size} must be divisible by the number of ranks {world}: the gradient all-reduce averages "

@@ -102,10 +102,6 @@ class VolleyballDataset(data.Dataset):
                  num_before=4, num_after=4, is_training=True, is_finetune=False, uint8_images=True):
         self.anns, self.tracks, self.frames = anns, tracks, frames
         self.images_path, self.image_size, self.feature_size = images_path, tuple(image_size), tuple(feature_size)
-        if inference_module_name == "arg_volleyball":
-            # (reference volleyball.py:207-212: ARG samples 3 random frames in training and a fixed 9-frame order in test -- a stage-2 baseline
-            #  outside the DIN path; refusing is better than silently feeding it full windows)
-            raise NotImplementedError("VolleyballDataset: the 'arg_volleyball' frame sampling is not ported (DIN stage-2 path only)")
         self.inference_module_name = inference_module_name
         self.num_boxes, self.num_before, self.num_after = num_boxes, num_before, num_after
         self.is_training, self.is_finetune, self.uint8_images = is_training, is_finetune, uint8_images
@@ -118,10 +114,15 @@ class VolleyballDataset(data.Dataset):
 
     def volley_frames_sample(self, frame):
         """stage 2 (DIN): the whole window src-num_before .. src+num_after, training and test alike (volleyball.py:214-219); stage 1
-        (is_finetune): one random frame of the window in training (:187-193)"""
+        (is_finetune): one random frame of the window in training (:187-193); stage 2 of 'arg_volleyball' (:207-214): 3 frames drawn from
+        the window without replacement in training, the fixed nine src + (-3, 0, 3, -4, -1, 2, -2, 1, 4) in test (three sub-clips of 3)"""
         sid, src = frame
         if self.is_finetune and self.is_training:
             return [(sid, src, random.randint(src - self.num_before, src + self.num_after))]
+        if not self.is_finetune and self.inference_module_name == "arg_volleyball":
+            if self.is_training:
+                return [(sid, src, fid) for fid in random.sample(range(src - self.num_before, src + self.num_after + 1), 3)]
+            return [(sid, src, src + d) for d in (-3, 0, 3, -4, -1, 2, -2, 1, 4)]
         return volley_frames_around(frame, self.num_before, self.num_after)
 
     def load_samples_sequence(self, select_frames):

@@ -451,6 +451,32 @@ int din_basenet_head_bwd(const float* g_actions, const float* g_activities, cons
                          float* db_act, float* dw_grp, float* db_grp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Actor Relation Graph block (reference infer_module/ARG_infer_module.py:46-89 GCN_Module), everything after the projections.
+ *   theta, phi fp32 [b][tn][ng][nfr] and y fp32 [b][tn][ng][nfg] with ROW STRIDE ld floats between consecutive (b, tn) rows: column slices
+ *   of one projection output X [W_theta | W_phi | W_gcn]^T (y_g = X W_gcn,g^T; the graph is applied after it: R (X W^T) == (R X) W^T).
+ *   boxes fp32 [b][tn][4] (x1, y1, x2, y2) in feature px; centre_rounds = how often the reference's in-place update
+ *   col0 = (col0 + col2) / 2, col1 = (col1 + col3) / 2 (:48-49, once per GCN layer on the caller's tensor) has run when this layer reads
+ *   the centres: layer l passes l + 1; the caller's boxes are not written.  thr = pos_threshold * OW (>= 0).
+ *   gamma, beta fp32 [ng][tn][nfg] (nl_gcn_list), eps of the LayerNorm.
+ * Per (clip, graph): S = theta phi^T / sqrt(nfr); S[i][j] = -inf where i != j and dist(centre_i, centre_j) > thr (strict; a NaN distance
+ *   is kept); R = softmax over j; Z = R y_g; V = relu(LayerNorm over the whole [tn][nfg] slab (Z) * gamma_g + beta_g).
+ * Outputs: out [b][tn][nfg] = sum of V over the graphs in order; rel [b][ng][tn][tn] = R of every graph (rel[:, ng-1] is the module's
+ *   second return value); mask uint8 [b][tn][tn] (1 = masked); z [b][ng][tn][nfg] and stats [b][ng][2] = (mean, rstd), kept for the backward.
+ * ws: ws_floats >= b * ng * ceil(nfg / 64) * 3 floats of scratch.
+ * Limits: 1 <= tn <= 120; 1 <= ng <= 1024; nfr, nfg, ld multiples of 4; theta / phi / y 16-byte aligned; b * ng <= 65535; else DIN_E_ARG, nothing is read.
+ * Forward 4 launches, backward 5; deterministic (fixed-order sums, no atomics), fp32 throughout.
+ * Backward: g_out [b][tn][nfg] -> d_theta, d_phi, d_y (same column layout, row stride ld_grad, every element of the three slices written),
+ *   d_gamma, d_beta [ng][tn][nfg] overwritten.  ws: ws_floats >= b*ng*tn*nfg + roundup4(b*ng*ceil(nfg/64)*2) + b*ng*tn*tn, 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int din_arg_graph_fwd(const float* theta, const float* phi, const float* y, int64_t ld, const float* boxes, int centre_rounds, float thr,
+                      const float* gamma, const float* beta, float eps, int b, int tn, int ng, int nfr, int nfg, float* out, float* rel,
+                      uint8_t* mask, float* z, float* stats, float* ws, int64_t ws_floats, void* stream);
+int din_arg_graph_bwd(const float* g_out, const float* theta, const float* phi, const float* y, int64_t ld, const float* gamma,
+                      const float* beta, const float* rel, const float* z, const float* stats, int b, int tn, int ng, int nfr, int nfg,
+                      float* d_theta, float* d_phi, float* d_y, int64_t ld_grad, float* d_gamma, float* d_beta, float* ws, int64_t ws_floats,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Small helpers used by the host mirror
  * ---------------------------------------------------------------------------------------------- */
 /* out = alpha*x + beta*y (fp32, elementwise) -- ratio mean / beta-weighted sum (:144-147), residual sums */
