@@ -2611,6 +2611,9 @@ __global__ void bn_fold_bwd_multi_kernel(const uint64_t* __restrict__ ptrs, cons
 // ---- host-side planning ----------------------------------------------------------------------------
 inline int epc_of(int dtype) { return dtype == DIN_F32 ? 4 : 8; }
 inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
+inline int opt_int(const char* v, int dflt) { return v ? atoi(v) : dflt; }
+// stem layers on conv_small_kernel / conv_wgrad_small_kernel (DIN_CONV_SMALL=0: off); din_conv_accepts_u8 answers from the same switch
+static bool conv_small_wanted() { return opt_int(DIN_OPT("DIN_CONV_SMALL"), 1) != 0; }
 
 struct GatherPlan { int bm, bn, n_co_tiles, n_px_tiles, cpt, Q, nk, splitk, ks_per_split, cout_pad; int64_t ws_bytes; };
 
@@ -2705,8 +2708,7 @@ WgradPlan plan_wgrad(const din_conv_desc* d) {
     // stem layers (conv_wgrad_small_kernel): small = 1: 32 -> <=32, 2: 32 -> <=64 (stride 1), 3: image layer (<= 8 channels, stride 2)
     w.small = 0;
     {
-        const char* sv = DIN_OPT("DIN_CONV_SMALL");
-        const bool want = sv ? atoi(sv) != 0 : true;
+        const bool want = conv_small_wanted();
         const int64_t M = (int64_t)d->nb * d->oh * d->ow;
         const bool common = want && d->dtype == DIN_BF16 && d->kh == 3 && d->kw == 3 && d->dh == 1 && d->dw == 1 && d->cout % 8 == 0 &&
                             d->ldi % 8 == 0 && d->cioff % 8 == 0 && d->ldo % 8 == 0 && d->cooff % 8 == 0 && M >= 256 * 1024 &&
@@ -2850,12 +2852,11 @@ int check_desc(const din_conv_desc* d) {
     return DIN_OK;
 }
 
-
-// halo kernel eligibility / shape (shared by run_gather and din_conv_kernel_tile).  Returns the filter-tile width (0: not eligible).
 // hipFuncSetAttribute is a slow host call: raise a kernel's dynamic-LDS limit once per (thread, kernel), not per launch
 template <typename K>
 static void raise_lds_limit(K kern, size_t lds) { din_raise_lds(reinterpret_cast<const void*>(kern), lds); }
 
+// halo kernel eligibility / shape.  hp.bn is the filter-tile width.
 struct HaloPlan { int bn, th, tw, nsw, nwv, n_co_tiles; size_t lds; };
 static bool plan_halo(int dtype, int kh, int kw, int cred, int cprod, int oh, int ow, int64_t M, HaloPlan& hp) {
     const char* hv = DIN_OPT("DIN_CONV_HALO");
@@ -2893,175 +2894,111 @@ static bool plan_halo(int dtype, int kh, int kw, int cred, int cprod, int oh, in
     return hp.lds <= 160 * 1024;
 }
 
-template <typename T, int BMT, int BN, int WM, int WN, int KCS, int NS, bool FASTK = false, bool XSRC = false, bool LANEK = false>
+template <typename T, int BMT, int BN, int WM, int WN, int KCS, int NS, bool MULTI, bool FASTK, bool XSRC, bool LANEK>
 void launch_fast(const ConvK& k, dim3 grid, hipStream_t st) {
     constexpr int LR_ = 64 * WM * WN / KCS, BNP_ = (BN + LR_ - 1) / LR_ * LR_;       // filter rows padded to whole loader passes
     size_t stage = (size_t)NS * (BMT + BNP_) * KCS * 16 + (k.remap ? 128 : 0);   // stage ring (+ remap table)
     // a single k-step (1x1 layers with <= 64 input channels: Conv2d_3b, the 64-channel dgrads) only ever touches ring stage 0: ask for one
     // stage, so that more of these memory-bound workgroups are resident per CU and their loads / stores overlap (DIN_CONV_ONESTAGE=0: off)
-    const bool one_stage_ok = !(DIN_OPT("DIN_CONV_ONESTAGE") && atoi(DIN_OPT("DIN_CONV_ONESTAGE")) == 0);
+    const bool one_stage_ok = !MULTI && !(DIN_OPT("DIN_CONV_ONESTAGE") && atoi(DIN_OPT("DIN_CONV_ONESTAGE")) == 0);
     if (one_stage_ok && !k.remap && k.xsteps == 0 && k.ks_per_split * (8 / KCS) <= 1) stage = (size_t)(BMT + BNP_) * KCS * 16;
     size_t epi = (size_t)BMT * (BN * sizeof(T) + 16);
     size_t lds = stage > epi ? stage : epi;
-    auto kern = conv_gather_fast_kernel<T, BMT, BN, WM, WN, KCS, NS, false, FASTK, XSRC, LANEK>;
+    auto kern = conv_gather_fast_kernel<T, BMT, BN, WM, WN, KCS, NS, MULTI, FASTK, XSRC, LANEK>;
     if (lds > 65536) raise_lds_limit(kern, lds);
     hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, st, k);
 }
 
-// the per-lane k-walk (LANEK) serves: bf16 8-wave 128-pixel tiles, single source, no tap remap, tap-major k-order, reduction channels that
-// are NOT whole k-steps per tap but at least one k-step wide (so a k-step crosses at most one tap boundary)
-static bool gather_lanek(const ConvK& k) {
-    const char* lv = DIN_OPT("DIN_CONV_LANEK");
-    const char* fv = DIN_OPT("DIN_CONV_FASTK");
+// ---- kernel selection of a forward / data-gradient launch: decided ONCE, in choose_gather ------------
+// run_gather and din_conv1x1_dgrad_multi launch what it returns; din_conv_kernel_tile / din_conv_kernel_variant report what it returns.
+enum GatherFamily { GATHER_REGW, GATHER_STREAM, GATHER_HALO, GATHER_SMALL, GATHER_PIPE, GATHER_GENERIC, GATHER_TILE };
+// conv_gather_fast_kernel<T, BM, BN, WM, WN, KCS, NS, MULTI, FASTK, XSRC, LANEK>
+struct TileInst { int bm, bn, wm, wn, kcs, ns; bool multi, fastk, xsrc, lanek; };
+// conv_small_kernel<cpt, bn, nbuf, 3, 3, image ? 2 : 1, u8, waves, epi> with its dynamic LDS and persistent grid
+struct SmallVariant { int cpt, bn, nbuf, waves; bool epi, image, u8; size_t lds; int grid; };
+struct GatherChoice {
+    GatherFamily family;
+    GatherPlan g;               // the plan after the 256 -> 128 pixel fallbacks (bm, bn, n_px_tiles, n_co_tiles)
+    int korder;                 // ConvK::korder of the launch
+    int n_co_tiles;             // ConvK::n_co_tiles of the launch (the halo kernel counts its own filter tiles)
+    int bn;                     // filter tile of the chosen kernel (regw: filters per class)
+    TileInst tile;              // GATHER_TILE (GATHER_GENERIC: bm, bn only)
+    HaloPlan halo;              // GATHER_HALO
+    SmallVariant small;         // GATHER_SMALL
+};
+
+// the plan fields of a chosen launch, written into its argument block
+static void set_plan_fields(ConvK& k, const GatherChoice& c) {
+    if (k.nsrc == 0) { k.cpt = c.g.cpt; k.Q = c.g.Q; k.nk = c.g.nk; if (!k.remap) k.wld = c.g.nk * KC; }    // (a multi-source launch lays its reduction out itself)
+    k.korder = c.korder; k.splitk = c.g.splitk; k.ks_per_split = c.g.ks_per_split; k.n_co_tiles = c.n_co_tiles;
+}
+
+// the instantiation of the 128- / 256-pixel tile kernel for a launch whose plan fields are set
+static TileInst choose_tile(const ConvK& k, int bm, int bn, int dtype) {
+    const bool bf16 = dtype == DIN_BF16;
+    const int taps = k.kh * k.kw;
+    // ring geometry per tile, from A/B runs of tools/conv_bench.py (DIN_CONV_PIPE=0/1 switches the alternatives; 4 / 8: four / eight waves):
+    //   256x64  : 4 stages x 4 chunks (80 KiB)  -- short-K, latency-bound launches gain 9 % from the deeper ring
+    //   others  : 2 stages x 8 chunks           -- MFMA-dense tiles lose 8-10 % when the stage (and the barrier interval) is halved
+    const int pipe = opt_int(DIN_OPT("DIN_CONV_PIPE"), -1);
+    TileInst t{bm, bn, 2, 2, 8, 2, k.nsrc > 0, false, false, false};
+    auto shape = [&](int wm, int wn, int kcs, int ns) { t.wm = wm; t.wn = wn; t.kcs = kcs; t.ns = ns; };
+    if (t.multi) {      // 8 waves (bf16) where the filter tile is whole 64-row loader passes
+        if (bn != 64 && bn != 96 && bn != 160 && bn != 192) t.bn = 128;
+        if (bf16 && (t.bn % 64 == 0 || pipe == 8) && pipe != 4) shape(4, 2, 8, 2);
+        return t;
+    }
+    // the scalar-walk specialisation (FASTK) whenever the launch qualifies: bf16 8- / 16-wave tiles, whole k-steps per tap, no tap remap,
+    // taps-inside-chunks k-order or a single tap; DIN_CONV_FASTK=0 keeps the general loop
+    const bool fastk_on = opt_int(DIN_OPT("DIN_CONV_FASTK"), 1) != 0;
+    const bool fastk = fastk_on && !k.remap && k.nsrc == 0 && (k.cpt % 8) == 0 && (k.korder || taps == 1);
+    // the per-lane k-walk (LANEK) serves: bf16 8-wave 128-pixel tiles, single source, no tap remap, tap-major k-order, reduction channels that
+    // are NOT whole k-steps per tap but at least one k-step wide (so a k-step crosses at most one tap boundary).
     // measured (tools/ab_lanek.sh, profiles/r06_lanek.txt): forward launches +4..7 % (Conv2d_4a 1929 -> 1858 us, the 160-channel 7-tap layers
     // 165 -> 155 us); data gradients (ReLU mask / accumulate operands in the epilogue, the register file full) 1-2 % SLOWER: forward only
     // unless DIN_CONV_LANEK=2
-    const int mode = lv ? atoi(lv) : 1;
-    if (mode == 1 && (k.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM))) return false;
-    return mode != 0 && (fv ? atoi(fv) != 0 : true) && !k.remap && k.nsrc == 0 && !k.korder && k.xsteps == 0 &&
-           (k.cpt % 8) != 0 && k.cpt >= 8 && k.kh * k.kw > 1 && k.kh * k.kw <= 31;
-}
-
-// 8-wave 128 x BN tile: the scalar-walk specialisation (FASTK) whenever the launch qualifies (bf16, whole k-steps per tap, no tap remap,
-// taps-inside-chunks k-order or a single tap); DIN_CONV_FASTK=0 keeps the general loop
-template <typename T, int BN>
-void launch_wave8(const ConvK& k, dim3 grid, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {
-        const char* fv = DIN_OPT("DIN_CONV_FASTK");
-        const bool want = fv ? atoi(fv) != 0 : true;
-        const bool fastk = want && !k.remap && k.nsrc == 0 && (k.cpt % 8) == 0 && (k.korder || k.kh * k.kw == 1);
-        if constexpr (BN == 192) {
-            // wave grid 2 x 4 (64 pixels x 48 filters per wave: 4 + 3 fragments per 12 MFMAs) instead of 4 x 2 (32 x 96: 2 + 6): an eighth
-            // fewer LDS fragment reads for the same tile (experiment switch DIN_CONV_WAVEGRID=24)
-            const bool grid24 = DIN_OPT("DIN_CONV_WAVEGRID") && atoi(DIN_OPT("DIN_CONV_WAVEGRID")) == 24;
-            if (grid24) {
-                if (fastk) launch_fast<T, 128, BN, 2, 4, 8, 2, true>(k, grid, st);
-                else launch_fast<T, 128, BN, 2, 4, 8, 2>(k, grid, st);
-                return;
-            }
-        }
+    const int lmode = opt_int(DIN_OPT("DIN_CONV_LANEK"), 1);
+    const bool lanek = lmode != 0 && !(lmode == 1 && (k.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM))) && fastk_on && !k.remap && k.nsrc == 0 &&
+                       !k.korder && k.xsteps == 0 && (k.cpt % 8) != 0 && k.cpt >= 8 && taps > 1 && taps <= 31;
 #ifdef DIN_EXPERIMENTS
-        if constexpr (BN >= 128) {
-            const bool wg3 = DIN_OPT("DIN_CONV_WG3") && atoi(DIN_OPT("DIN_CONV_WG3")) == 1;
-            if (fastk && wg3) { launch_fast<T, 128, BN, 2, 2, 4, 2, true>(k, grid, st); return; }
-        }
-#endif
-        if (fastk) {
-            launch_fast<T, 128, BN, 4, 2, 8, 2, true>(k, grid, st);
-            return;
-        }
-        if (gather_lanek(k)) {
-            launch_fast<T, 128, BN, 4, 2, 8, 2, true, false, true>(k, grid, st);
-            return;
-        }
-    }
-    if constexpr (sizeof(T) == 2 && (BN == 192 || BN == 160)) {
-        // experiment switch DIN_CONV_RING=3: three 32-deep stages (two in flight, one counted vmcnt per barrier) instead of two 64-deep ones
-        // (one in flight, vmcnt(0)) for the general loop's 8-wave tiles -- same LDS budget (72 vs 80 KiB per workgroup), half the MFMAs per barrier
-        #ifdef DIN_EXPERIMENTS
-        const bool ring3 = DIN_OPT("DIN_CONV_RING") && atoi(DIN_OPT("DIN_CONV_RING")) == 3;
+    // DIN_CONV_WG3=1: four waves on a 4-chunk stage at three workgroups per CU; DIN_CONV_RING=3: three 32-deep stages (two in flight, one counted
+    // vmcnt per barrier) instead of two 64-deep ones for the general loop's 8-wave tiles -- same LDS budget (72 vs 80 KiB per workgroup), half
+    // the MFMAs per barrier; DIN_CONV_W16=1 with DIN_CONV_TILE=256: the 256-pixel sixteen-wave tile for the 128- / 160- / 192-filter layers
+    // (Mixed_6b-6d: 98 / 85 instead of 71 / 64 FLOP per staged byte; ONE filter stage per 256 pixels)
+    const bool wg3 = opt_int(DIN_OPT("DIN_CONV_WG3"), 0) == 1, ring3 = opt_int(DIN_OPT("DIN_CONV_RING"), 0) == 3, w16 = opt_int(DIN_OPT("DIN_CONV_W16"), 0) == 1;
 #else
-        constexpr bool ring3 = false;
+    constexpr bool wg3 = false, ring3 = false, w16 = false;
 #endif
-        if (ring3 && !k.remap) { launch_fast<T, 128, BN, 4, 2, 4, 3>(k, grid, st); return; }
+    // 8-wave 128 x BN tile (4 x 2, four waves per SIMD at two workgroups per CU) -- same LDS ring, more waves to hide the stage waits:
+    // +8..12 % on the 7-tap layers, +24 % on thin-K dgrads (bf16 only; DIN_CONV_PIPE=4 restores the 4-wave form)
+    auto wave8 = [&]() {
+        // 128 x 192: wave grid 2 x 4 (64 pixels x 48 filters per wave: 4 + 3 fragments per 12 MFMAs) instead of 4 x 2 (32 x 96: 2 + 6): an eighth
+        // fewer LDS fragment reads for the same tile (experiment switch DIN_CONV_WAVEGRID=24)
+        if (bn == 192 && opt_int(DIN_OPT("DIN_CONV_WAVEGRID"), 0) == 24) { shape(2, 4, 8, 2); t.fastk = fastk; }
+        else if (bn >= 128 && fastk && wg3) { shape(2, 2, 4, 2); t.fastk = true; }
+        else if (fastk) { shape(4, 2, 8, 2); t.fastk = true; }
+        else if (lanek) { shape(4, 2, 8, 2); t.fastk = t.lanek = true; }
+        else if ((bn == 192 || bn == 160) && ring3 && !k.remap) shape(4, 2, 4, 3);
+        else shape(4, 2, 8, 2);
+    };
+    if (bm == 256 && bn == 64) { if (pipe != 0) shape(4, 1, 4, 4); else shape(4, 1, 8, 2); }
+    else if (bm == 256 && bn == 256) { if (pipe == 1) shape(4, 2, 4, 4); else shape(4, 2, 8, 2); }
+    else if (bm == 256) {                                                   // (bf16 only: plan_gather)
+        if (bn == 96 || (bn == 160 && !w16)) shape(2, 2, 8, 2);
+        else if (w16) { shape(8, 2, 8, 2); t.fastk = fastk; }
+        else if (bn == 192) shape(4, 2, 8, 2);
+        else { t.bn = 128; if (pipe == 1) shape(4, 2, 4, 4); else shape(4, 2, 8, 2); }
     }
-    launch_fast<T, 128, BN, 4, 2, 8, 2>(k, grid, st);
-}
-
-template <typename T, int BN>
-void launch_fast_multi(const ConvK& k, dim3 grid, hipStream_t st) {
-    size_t epi = (size_t)128 * (BN * sizeof(T) + 16);
-    const char* pv = DIN_OPT("DIN_CONV_PIPE");
-    if (sizeof(T) == 2 && (BN % 64 == 0 || (pv && atoi(pv) == 8)) && !(pv && atoi(pv) == 4)) {   // 8 waves (bf16) where the filter tile is whole 64-row loader passes
-        size_t stage8 = (size_t)2 * (128 + (BN + 63) / 64 * 64) * 8 * 16;
-        size_t lds8 = stage8 > epi ? stage8 : epi;
-        auto kern = conv_gather_fast_kernel<T, 128, BN, 4, 2, 8, 2, true>;
-        if (lds8 > 65536) raise_lds_limit(kern, lds8);
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds8, st, k);
-        return;
-    }
-    size_t stage = (size_t)2 * (128 + BN) * 8 * 16;
-    size_t lds = stage > epi ? stage : epi;
-    auto kern = conv_gather_fast_kernel<T, 128, BN, 2, 2, 8, 2, true>;
-    if (lds > 65536) raise_lds_limit(kern, lds);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k);
-}
-
-template <typename T>
-void launch_gather(const ConvK& k, int n_px_tiles, int bm, int bn, hipStream_t st) {
-    if (k.nsrc > 0) {
-        dim3 mgrid(n_px_tiles * k.n_co_tiles, 1);
-        if (bn == 64) launch_fast_multi<T, 64>(k, mgrid, st);
-        else if (bn == 96) launch_fast_multi<T, 96>(k, mgrid, st);
-        else if (bn == 160) launch_fast_multi<T, 160>(k, mgrid, st);
-        else if (bn == 192) launch_fast_multi<T, 192>(k, mgrid, st);
-        else launch_fast_multi<T, 128>(k, mgrid, st);
-        return;
-    }
-    const bool fast = k.divy == 1 && k.divx == 1 && k.kh * k.kw <= 32;
-    dim3 grid(n_px_tiles * k.n_co_tiles, k.splitk);
-    if (!fast) {
-        size_t lds = 2 * (BM + 128) * KC * 16;
-        if (bn == 64) hipLaunchKernelGGL((conv_gather_generic_kernel<T, 64>), grid, dim3(NTHREADS), lds, st, k);
-        else hipLaunchKernelGGL((conv_gather_generic_kernel<T, 128>), grid, dim3(NTHREADS), lds, st, k);
-        return;
-    }
-    // ring geometry per tile, from A/B runs of tools/conv_bench.py (DIN_CONV_PIPE=0/1 switches the alternatives):
-    //   256x64  : 4 stages x 4 chunks (80 KiB)  -- short-K, latency-bound launches gain 9 % from the deeper ring
-    //   others  : 2 stages x 8 chunks           -- MFMA-dense tiles lose 8-10 % when the stage (and the barrier interval) is halved
-    const char* pv = DIN_OPT("DIN_CONV_PIPE");
-    const int pipe = pv ? atoi(pv) : -1;
-    if (bm == 256 && bn == 64) { if (pipe != 0) launch_fast<T, 256, 64, 4, 1, 4, 4>(k, grid, st); else launch_fast<T, 256, 64, 4, 1, 8, 2>(k, grid, st); }
-    else if (bm == 256 && bn == 256) {
-        if constexpr (sizeof(T) == 2) { if (pipe == 1) launch_fast<T, 256, 256, 4, 2, 4, 4>(k, grid, st); else launch_fast<T, 256, 256, 4, 2, 8, 2>(k, grid, st); }
-    }
-    else if (bm == 256) {
-        if constexpr (sizeof(T) == 2) {
-            if (bn == 96) launch_fast<T, 256, 96, 2, 2, 8, 2>(k, grid, st);
-#ifdef DIN_EXPERIMENTS
-            // experiment (round 4, DIN_CONV_W16=1 with DIN_CONV_TILE=256): the 256-pixel sixteen-wave tile for the 160- / 128-filter 7-tap layers
-            // (Mixed_6b-6d: 98 / 85 instead of 71 / 64 FLOP per staged byte)
-            else if ((bn == 160 || bn == 128) && DIN_OPT("DIN_CONV_W16") && atoi(DIN_OPT("DIN_CONV_W16")) == 1) {
-                const char* fv = DIN_OPT("DIN_CONV_FASTK");
-                const bool fastk = (fv ? atoi(fv) != 0 : true) && !k.remap && k.nsrc == 0 && (k.cpt % 8) == 0 && (k.korder || k.kh * k.kw == 1);
-                if (bn == 160) { if (fastk) launch_fast<T, 256, 160, 8, 2, 8, 2, true>(k, grid, st); else launch_fast<T, 256, 160, 8, 2, 8, 2>(k, grid, st); }
-                else { if (fastk) launch_fast<T, 256, 128, 8, 2, 8, 2, true>(k, grid, st); else launch_fast<T, 256, 128, 8, 2, 8, 2>(k, grid, st); }
-            }
-#endif
-            else if (bn == 160) launch_fast<T, 256, 160, 2, 2, 8, 2>(k, grid, st);
-            else if (bn == 192) {
-                // experiment (DIN_CONV_W16=1 with DIN_CONV_TILE=256): sixteen waves as 8 x 2 on the 256 x 192 tile -- the 128 x 192 kernel's wave
-                // tile and four waves per SIMD, but ONE filter stage per 256 pixels: 64 instead of 80 LDS-DMA transfers per 256-pixel k-step
-                #ifdef DIN_EXPERIMENTS
-                const bool w16 = DIN_OPT("DIN_CONV_W16") && atoi(DIN_OPT("DIN_CONV_W16")) == 1;
-#else
-                constexpr bool w16 = false;
-#endif
-                const char* fv = DIN_OPT("DIN_CONV_FASTK");
-                const bool fastk = (fv ? atoi(fv) != 0 : true) && !k.remap && k.nsrc == 0 && (k.cpt % 8) == 0 && (k.korder || k.kh * k.kw == 1);
-                if (w16 && fastk) launch_fast<T, 256, 192, 8, 2, 8, 2, true>(k, grid, st);
-                else if (w16) launch_fast<T, 256, 192, 8, 2, 8, 2>(k, grid, st);
-                else launch_fast<T, 256, 192, 4, 2, 8, 2>(k, grid, st);
-            }
-            else { if (pipe == 1) launch_fast<T, 256, 128, 4, 2, 4, 4>(k, grid, st); else launch_fast<T, 256, 128, 4, 2, 8, 2>(k, grid, st); }
-        }
-    }
-    else if (bn == 64) {
-        if (pipe == 1) launch_fast<T, 128, 64, 2, 2, 8, 3>(k, grid, st);
-        else if (pipe != 4 && sizeof(T) == 2) launch_wave8<T, 64>(k, grid, st);
-        else launch_fast<T, 128, 64, 2, 2, 8, 2>(k, grid, st);
-    }
+    else if (bn == 64) { if (pipe == 1) shape(2, 2, 8, 3); else if (pipe != 4 && bf16) wave8(); }
     // 128 x 96: four waves (eight measured 5-14 % slower on Conv2d_3b) -- except the parity classes of a strided dgrad, whose scattered,
     // epilogue-bound tiles gain 5 % from eight waves (Mixed_6a.branch3x3 dgrad 1379 -> 1312 us)
     else if (bn == 96) {
-        if constexpr (sizeof(T) == 2) { if (k.xsteps > 0) { launch_fast<T, 128, 96, 4, 2, 8, 2, false, true>(k, grid, st); return; } }
-        if ((pipe == 8 || (k.remap && pipe != 4)) && sizeof(T) == 2) launch_fast<T, 128, 96, 4, 2, 8, 2>(k, grid, st); else launch_fast<T, 128, 96, 2, 2, 8, 2>(k, grid, st);
+        if (bf16 && k.xsteps > 0) { shape(4, 2, 8, 2); t.xsrc = true; }
+        else if ((pipe == 8 || (k.remap && pipe != 4)) && bf16) shape(4, 2, 8, 2);
     }
-    else if (bn == 160) { if (pipe != 4 && sizeof(T) == 2) launch_wave8<T, 160>(k, grid, st); else launch_fast<T, 128, 160, 2, 2, 8, 2>(k, grid, st); }
-    // 128 x {128,160,192}: 8 waves (4 x 2, four per SIMD at two workgroups per CU) -- same LDS ring, more waves to hide the stage waits:
-    // +8..12 % on the 7-tap layers, +24 % on thin-K dgrads (bf16 only; DIN_CONV_PIPE=4 restores the 4-wave form)
-    else if (bn == 192) { if (pipe != 4 && sizeof(T) == 2) launch_wave8<T, 192>(k, grid, st); else launch_fast<T, 128, 192, 2, 2, 8, 2>(k, grid, st); }
-    else { if (pipe == 1) launch_fast<T, 128, 128, 2, 2, 4, 4>(k, grid, st); else if (pipe != 4 && sizeof(T) == 2) launch_wave8<T, 128>(k, grid, st); else launch_fast<T, 128, 128, 2, 2, 8, 2>(k, grid, st); }
+    else if (bn == 160 || bn == 192) { if (pipe != 4 && bf16) wave8(); }
+    else { t.bn = 128; if (pipe == 1) shape(2, 2, 4, 4); else if (pipe != 4 && bf16) wave8(); }
+    return t;
 }
 
 // 256-pixel software-pipelined tiles (conv_gather_pipe.hip): bf16 launches with whole 32-channel blocks per tap whose filter tile the
@@ -3077,21 +3014,209 @@ bool want_gather_pipe(int dtype, int64_t M, int cred, int taps, int bn, int spli
     return tiles >= (mode == 2 ? 1 : 512);
 }
 
-int run_gather(ConvK& k, GatherPlan g, int dtype, void* workspace, int64_t ws_bytes, hipStream_t st, const char* what) {
-    const bool fast = k.divy == 1 && k.divx == 1 && k.kh * k.kw <= 32;
-    if (!fast && g.bn != 64 && g.bn != 128) { g.bn = 128; g.n_co_tiles = (k.Cout + 127) / 128; }
-    if (g.bm == 256 && (!fast || k.remap || g.splitk > 1)) {
-        g.bm = 128; if (g.bn == 256) g.bn = 128;
-        g.n_px_tiles = (k.M + 127) / 128; g.n_co_tiles = (k.Cout + g.bn - 1) / g.bn;
+// Which kernel a launch runs on: geometry, flags and options only -- no pointer is read (ConvK::u8 only as "raw uint8 frames"), nothing is
+// launched.  `k0` carries the geometry and flags of the launch, `g` its plan.  Precedence: regw, stream, halo (unless a stem shape), small,
+// gather-pipe, then the tile kernels.
+GatherChoice choose_gather(const ConvK& k0, GatherPlan g, int dtype) {
+    GatherChoice c{};
+    const bool fast = k0.divy == 1 && k0.divx == 1 && k0.kh * k0.kw <= 32;
+    if (!fast && g.bn != 64 && g.bn != 128) { g.bn = 128; g.n_co_tiles = (k0.Cout + 127) / 128; }
+    if (k0.nsrc > 0 && g.bn == 256) g.bn = 128;
+    if (g.bm == 256 && (!fast || k0.remap || g.splitk > 1 || k0.nsrc > 0)) { g.bm = 128; if (g.bn == 256) g.bn = 128; }
+    g.n_px_tiles = (k0.M + g.bm - 1) / g.bm; g.n_co_tiles = (k0.Cout + g.bn - 1) / g.bn;
+    c.g = g; c.bn = g.bn; c.n_co_tiles = g.n_co_tiles;
+    c.korder = (opt_int(DIN_OPT("DIN_CONV_KORDER"), 1) != 0 && fast && !k0.remap && g.splitk == 1 && (g.cpt % KC) == 0 && k0.kh * k0.kw > 1) ? 1 : 0;
+    ConvK k = k0;                                          // (the eligibility rules below read the plan fields from the argument block)
+    set_plan_fields(k, c);
+    const bool single = !k.remap && k.nsrc == 0 && k.csplit == 0;
+    const bool mask8 = !(k.flags & DIN_CONV_MASK) || (k.ldm % 8 == 0 && k.moff % 8 == 0);
+    const bool views_2g = (long long)k.H * k.W * k.ldi * 2 < 0x7fffffffll && (long long)k.OH * k.OW * k.ldo * 2 < 0x7fffffffll &&
+                          (long long)k.OH * k.OW * (k.ldm > 0 ? k.ldm : 1) * 2 < 0x7fffffffll;
+    if (fast && g.splitk == 1 && k.xsteps == 0) {
+        // 1x1 layers with a 640..768-channel reduction over a large map (the Mixed_6 block entries): filters resident in registers (conv_regw.hip)
+        if (din_gather::conv1x1_regw_eligible(k, dtype)) {
+            int nks = 0;                                   // 32-channel k-steps as launch_conv1x1_regw counts them: <= 10 -> classes of 128 filters
+            for (int s = 0; s < (k.nsrc > 0 ? k.nsrc : 1); ++s) nks += ((k.nsrc > 0 ? k.src[s].cpt : k.cpt) + 7) / 8 * 2;
+            c.family = GATHER_REGW; c.bn = nks <= 10 ? 128 : 192;
+            return c;
+        }
+        // 1x1 layers with a short reduction over a large map: persistent streaming kernel (conv_stream.hip)
+        if (din_gather::conv1x1_stream_eligible(k, dtype)) { c.family = GATHER_STREAM; c.bn = din_gather::conv1x1_stream_tile(k.Cout); return c; }
     }
-    k.cpt = g.cpt; k.Q = g.Q; k.nk = g.nk;
-    if (!k.remap) k.wld = g.nk * KC;
-    {
-        const char* ko = DIN_OPT("DIN_CONV_KORDER");
-        const bool want = ko ? atoi(ko) != 0 : true;
-        k.korder = (want && fast && !k.remap && g.splitk == 1 && (g.cpt % KC) == 0 && k.kh * k.kw > 1) ? 1 : 0;
+    // mid-network multi-tap layers: halo tiles + filter-slab ring (conv_halo_kernel); the stem shapes keep their own kernel below
+    const bool stem_shape = k.kh == 3 && k.kw == 3 && (k.Cin == 32 || k.Cin == 64) && k.Cout <= 64 && !(k.Cin == 64 && k.Cout > 32) && (int64_t)k.M >= 256 * 1024;
+    if (fast && single && g.splitk == 1 && !stem_shape && k.ay == 1 && k.ax == 1 && (k.cy == 1 || k.cy == -1) && (k.cx == 1 || k.cx == -1) && k.cy == k.cx &&
+        k.out_sy == 0 && k.ldi % 8 == 0 && k.cioff % 8 == 0 && k.ldo % 4 == 0 && k.cooff % 4 == 0 &&
+        (!(k.flags & DIN_CONV_MASK) || (k.ldm % 4 == 0 && k.moff % 4 == 0)) && views_2g &&
+        plan_halo(dtype, k.kh, k.kw, k.Cin, k.Cout, k.OH, k.OW, k.M, c.halo)) {
+        c.family = GATHER_HALO; c.bn = c.halo.bn; c.n_co_tiles = c.halo.n_co_tiles;
+        return c;
     }
-    k.splitk = g.splitk; k.ks_per_split = g.ks_per_split; k.n_co_tiles = g.n_co_tiles;
+    {   // stem layers: stationary filters + halo tiles (conv_small_kernel)
+        const bool common = conv_small_wanted() && dtype == DIN_BF16 && fast && single && g.splitk == 1 && k.kh == 3 && k.kw == 3 &&
+                            k.Cout <= 64 && k.Cout % 8 == 0 && k.cooff % 8 == 0 && k.ldo % 8 == 0 && k.ldi % 8 == 0 && k.cioff % 8 == 0 &&
+                            mask8 && views_2g && k.out_sy == 0 && (int64_t)k.M >= 256 * 1024;
+        // 32/64-channel 3x3 stride-1 layers (fwd and dgrad) ...
+        const bool stem = common && (g.cpt == 4 || g.cpt == 8) && g.cpt * 8 == k.Cin && k.ay == 1 && k.ax == 1 &&
+                          (k.cy == 1 || k.cy == -1) && (k.cx == 1 || k.cx == -1) && !(g.cpt == 8 && k.Cout > 32);
+        // ... and the image layer: <= 8 (zero-padded) channels per pixel, stride 2, forward only
+        const bool image = common && g.cpt == 1 && k.Cin <= 8 && k.ldi >= 8 && k.Cout <= 32 && k.ay == 2 && k.ax == 2 && k.cy == 1 && k.cx == 1 &&
+                           k.wld >= 12;
+        if (stem || image) {
+            SmallVariant& s = c.small;
+            s.cpt = g.cpt; s.bn = k.Cout <= 32 ? 32 : 64; s.image = image; s.u8 = k.u8 != nullptr;
+            const int st_ = image ? 2 : 1;
+            const int hpx = (7 * st_ + 3) * (31 * st_ + 3);
+            const int hbytes = (hpx * g.cpt * 16 + 1023) / 1024 * 1024;
+            // 128-byte pixels (the 64-channel dgrad of Conv2d_2b): one halo buffer (80 KiB) or -- DIN_CONV_SMALL_NBUF8=2 -- two (124 KiB, the next
+            // halo in flight under this tile's MFMAs like the 64-byte-pixel variants); one workgroup per CU either way
+            const bool two8 = g.cpt == 8 && opt_int(DIN_OPT("DIN_CONV_SMALL_NBUF8"), 0) == 2;
+            s.lds = (size_t)(image ? 3 * s.bn * 64 : 9 * s.bn * g.cpt * 16) + (size_t)((g.cpt == 8 && !two8) ? 1 : 2) * hbytes + (s.u8 ? 512 : 0);   // (+ the uint8 -> bf16 table)
+            // the image layer's 42 KiB workgroups fit three to a CU: 768 persistent workgroups measured 690 -> 618 us on the 96 frames
+            // (1024: no better, four do not fit); DIN_CONV_IMAGE_GRID overrides
+            const int gv = opt_int(DIN_OPT("DIN_CONV_IMAGE_GRID"), 0);
+            s.grid = image ? (gv > 0 ? gv : 768) : 512;
+            // dgrad launches with a mask / accumulate operand: the variant that requests them a tile phase early (DIN_CONV_SMALL_EPI=0: in the store loop)
+            const bool epi = (k.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM)) && opt_int(DIN_OPT("DIN_CONV_SMALL_EPI"), 1) != 0;
+            // the two 80 KiB variants (one workgroup per CU) run on eight waves; DIN_CONV_SMALL_WAVES=4 restores four
+            // (64-byte pixels x 32 filters: eight waves measured slower, 706 -> 765 us)
+            const bool w8 = !image && !(g.cpt == 4 && s.bn == 32) && opt_int(DIN_OPT("DIN_CONV_SMALL_WAVES"), 8) != 4;
+            s.waves = w8 ? 8 : 4;
+            s.nbuf = (g.cpt == 8 && !(two8 && w8)) ? 1 : 2;
+            s.epi = epi && !image && ((g.cpt == 4 && s.bn == 32) || (g.cpt == 8 && w8));     // (the instantiations that exist)
+            c.family = GATHER_SMALL; c.bn = s.bn;
+            return c;
+        }
+    }
+    if (fast && !k.remap && k.nsrc == 0 && want_gather_pipe(dtype, k.M, k.Cin, k.kh * k.kw, g.bn, g.splitk, g.n_co_tiles) &&
+        g.cpt % 4 == 0 && k.Cout % 8 == 0 && k.cooff % 8 == 0 && k.ldo % 8 == 0 && mask8 &&
+        (k.csplit == 0 || (k.csplit % 8 == 0 && k.ldo2 % 8 == 0 && k.cooff2 % 8 == 0))) {
+        c.family = GATHER_PIPE;
+        return c;
+    }
+    c.family = fast ? GATHER_TILE : GATHER_GENERIC;
+    c.tile = fast ? choose_tile(k, g.bm, g.bn, dtype) : TileInst{128, g.bn == 64 ? 64 : 128, 2, 2, 8, 2, false, false, false, false};
+    c.bn = c.tile.bn;
+    return c;
+}
+
+// The one table from a chosen TileInst to its template instantiation: every conv_gather_fast_kernel the library holds is a row here (some
+// are reached only through an experiment switch of a -DDIN_EXPERIMENTS build).  false: no such instantiation.
+template <typename T>
+bool launch_tile(const ConvK& k, const TileInst& t, dim3 grid, hipStream_t st) {
+#define DIN_TILE(BM_, BN_, WM_, WN_, KCS_, NS_, MULTI_, FASTK_, XSRC_, LANEK_)                                                           \
+    if (t.bm == BM_ && t.bn == BN_ && t.wm == WM_ && t.wn == WN_ && t.kcs == KCS_ && t.ns == NS_ && t.multi == MULTI_ && t.fastk == FASTK_ && \
+        t.xsrc == XSRC_ && t.lanek == LANEK_) {                                                                                         \
+        launch_fast<T, BM_, BN_, WM_, WN_, KCS_, NS_, MULTI_, FASTK_, XSRC_, LANEK_>(k, grid, st);                                         \
+        return true;                                                                                                                    \
+    }
+#define DIN_TILE_PLAIN(BM_, BN_, WM_, WN_, KCS_, NS_) DIN_TILE(BM_, BN_, WM_, WN_, KCS_, NS_, false, false, false, false)
+#define DIN_TILE_WALKS(BM_, BN_, WM_, WN_, KCS_, NS_) DIN_TILE_PLAIN(BM_, BN_, WM_, WN_, KCS_, NS_) DIN_TILE(BM_, BN_, WM_, WN_, KCS_, NS_, false, true, false, false)
+#define DIN_TILE_MULTI(BN_) DIN_TILE(128, BN_, 4, 2, 8, 2, true, false, false, false) DIN_TILE(128, BN_, 2, 2, 8, 2, true, false, false, false)
+    // fp32 and bf16: four waves, and the general loop on eight
+    DIN_TILE_PLAIN(256, 64, 4, 1, 4, 4) DIN_TILE_PLAIN(256, 64, 4, 1, 8, 2)
+    DIN_TILE_PLAIN(128, 64, 2, 2, 8, 3) DIN_TILE_PLAIN(128, 64, 2, 2, 8, 2) DIN_TILE_PLAIN(128, 96, 2, 2, 8, 2) DIN_TILE_PLAIN(128, 128, 2, 2, 4, 4)
+    DIN_TILE_PLAIN(128, 128, 2, 2, 8, 2) DIN_TILE_PLAIN(128, 160, 2, 2, 8, 2) DIN_TILE_PLAIN(128, 192, 2, 2, 8, 2)
+    DIN_TILE_PLAIN(128, 64, 4, 2, 8, 2) DIN_TILE_PLAIN(128, 96, 4, 2, 8, 2) DIN_TILE_PLAIN(128, 128, 4, 2, 8, 2) DIN_TILE_PLAIN(128, 160, 4, 2, 8, 2)
+    DIN_TILE_PLAIN(128, 192, 4, 2, 8, 2)
+    DIN_TILE_MULTI(64) DIN_TILE_MULTI(96) DIN_TILE_MULTI(128) DIN_TILE_MULTI(160) DIN_TILE_MULTI(192)
+    if constexpr (sizeof(T) == 2) {
+        DIN_TILE_PLAIN(256, 256, 4, 2, 4, 4) DIN_TILE_PLAIN(256, 256, 4, 2, 8, 2) DIN_TILE_PLAIN(256, 128, 4, 2, 4, 4) DIN_TILE_PLAIN(256, 128, 4, 2, 8, 2)
+        DIN_TILE_PLAIN(256, 96, 2, 2, 8, 2) DIN_TILE_PLAIN(256, 160, 2, 2, 8, 2) DIN_TILE_PLAIN(256, 192, 4, 2, 8, 2) DIN_TILE_WALKS(256, 192, 8, 2, 8, 2)
+        DIN_TILE(128, 96, 4, 2, 8, 2, false, false, true, false)                                      // + the extra 1x1 source of din_conv_dgrad_x
+        DIN_TILE_WALKS(128, 192, 2, 4, 8, 2)
+        DIN_TILE(128, 64, 4, 2, 8, 2, false, true, false, false) DIN_TILE(128, 128, 4, 2, 8, 2, false, true, false, false)
+        DIN_TILE(128, 160, 4, 2, 8, 2, false, true, false, false) DIN_TILE(128, 192, 4, 2, 8, 2, false, true, false, false)
+        DIN_TILE(128, 64, 4, 2, 8, 2, false, true, false, true) DIN_TILE(128, 128, 4, 2, 8, 2, false, true, false, true)
+        DIN_TILE(128, 160, 4, 2, 8, 2, false, true, false, true) DIN_TILE(128, 192, 4, 2, 8, 2, false, true, false, true)
+        DIN_TILE_PLAIN(128, 160, 4, 2, 4, 3) DIN_TILE_PLAIN(128, 192, 4, 2, 4, 3)
+#ifdef DIN_EXPERIMENTS
+        DIN_TILE_WALKS(256, 160, 8, 2, 8, 2) DIN_TILE_WALKS(256, 128, 8, 2, 8, 2)
+        DIN_TILE(128, 128, 2, 2, 4, 2, false, true, false, false) DIN_TILE(128, 160, 2, 2, 4, 2, false, true, false, false)
+        DIN_TILE(128, 192, 2, 2, 4, 2, false, true, false, false)
+#endif
+    }
+#undef DIN_TILE_MULTI
+#undef DIN_TILE_WALKS
+#undef DIN_TILE_PLAIN
+#undef DIN_TILE
+    return false;
+}
+
+// launches the chosen kernel on an argument block whose plan fields are set (set_plan_fields)
+int launch_choice(ConvK& k, const GatherChoice& c, int dtype, hipStream_t st, const char* what) {
+    switch (c.family) {
+    case GATHER_REGW:
+        if (din_gather::launch_conv1x1_regw(k, st)) DIN_FAIL(DIN_E_LAUNCH, "%s: conv1x1_regw launch failed", what);
+        return DIN_OK;
+    case GATHER_STREAM:
+        if (din_gather::launch_conv1x1_stream(k, st)) DIN_FAIL(DIN_E_LAUNCH, "%s: conv1x1_stream launch failed", what);
+        return DIN_OK;
+    case GATHER_HALO: {
+        const HaloPlan& hp = c.halo;
+        const int tiles = ((k.OH + hp.th - 1) / hp.th) * ((k.OW + hp.tw - 1) / hp.tw) * k.NB * hp.n_co_tiles;
+        auto launch = [&](auto kern) {
+            raise_lds_limit(kern, hp.lds);
+            hipLaunchKernelGGL(kern, dim3(tiles < 256 ? tiles : 256), dim3(64 * hp.nwv), hp.lds, st, k);
+        };
+        if (k.kh == 3 && k.kw == 3 && hp.nwv == 16) {
+            if (hp.bn == 64) launch(conv_halo_kernel<64, 3, 3, 8, 32, 2, 16>);
+            else if (hp.bn == 80) launch(conv_halo_kernel<80, 3, 3, 8, 32, 2, 16>);
+            else launch(conv_halo_kernel<96, 3, 3, 8, 32, 2, 16>);
+        }
+        else if (k.kh == 3 && k.kw == 3) { if (hp.bn == 64) launch(conv_halo_kernel<64, 3, 3, 8, 32, 3>); else launch(conv_halo_kernel<96, 3, 3, 8, 32, 3>); }
+        else if (k.kh == 1 && k.kw == 7) { if (hp.bn == 64) launch(conv_halo_kernel<64, 1, 7, 16, 16, 3>); else launch(conv_halo_kernel<96, 1, 7, 16, 16, 3>); }
+        else { if (hp.bn == 64) launch(conv_halo_kernel<64, 7, 1, 16, 16, 3>); else launch(conv_halo_kernel<96, 7, 1, 16, 16, 3>); }
+        break;
+    }
+    case GATHER_SMALL: {
+        const SmallVariant& s = c.small;
+        auto launch = [&](auto kern) {
+            if (s.lds > 65536) raise_lds_limit(kern, s.lds);
+            hipLaunchKernelGGL(kern, dim3(s.grid), dim3(64 * s.waves), s.lds, st, k);
+        };
+        if (s.image && s.u8) launch(conv_small_kernel<1, 32, 2, 3, 3, 2, true>);
+        else if (s.image) launch(conv_small_kernel<1, 32, 2, 3, 3, 2>);
+        else if (s.cpt == 4 && s.bn == 32) { if (s.epi) launch(conv_small_kernel<4, 32, 2, 3, 3, 1, false, 4, true>); else launch(conv_small_kernel<4, 32, 2, 3, 3, 1>); }
+        else if (s.cpt == 4) { if (s.waves == 8) launch(conv_small_kernel<4, 64, 2, 3, 3, 1, false, 8>); else launch(conv_small_kernel<4, 64, 2, 3, 3, 1>); }
+        else if (s.waves == 4) launch(conv_small_kernel<8, 32, 1, 3, 3, 1>);
+        else if (s.nbuf == 2) { if (s.epi) launch(conv_small_kernel<8, 32, 2, 3, 3, 1, false, 8, true>); else launch(conv_small_kernel<8, 32, 2, 3, 3, 1, false, 8>); }
+        else { if (s.epi) launch(conv_small_kernel<8, 32, 1, 3, 3, 1, false, 8, true>); else launch(conv_small_kernel<8, 32, 1, 3, 3, 1, false, 8>); }
+        break;
+    }
+    case GATHER_PIPE:
+        if (int e = din_gather::launch_gather_pipe(k, c.g.bn, (k.M + 255) / 256, st)) return e;
+        break;
+    case GATHER_GENERIC: {
+        const dim3 grid(c.g.n_px_tiles * k.n_co_tiles, k.splitk);
+        const size_t lds = 2 * (BM + 128) * KC * 16;
+        if (dtype == DIN_F32) {
+            if (c.tile.bn == 64) hipLaunchKernelGGL((conv_gather_generic_kernel<float, 64>), grid, dim3(NTHREADS), lds, st, k);
+            else hipLaunchKernelGGL((conv_gather_generic_kernel<float, 128>), grid, dim3(NTHREADS), lds, st, k);
+        } else {
+            if (c.tile.bn == 64) hipLaunchKernelGGL((conv_gather_generic_kernel<bf16_t, 64>), grid, dim3(NTHREADS), lds, st, k);
+            else hipLaunchKernelGGL((conv_gather_generic_kernel<bf16_t, 128>), grid, dim3(NTHREADS), lds, st, k);
+        }
+        break;
+    }
+    case GATHER_TILE: {
+        const dim3 grid(c.g.n_px_tiles * k.n_co_tiles, k.splitk);
+        const TileInst& t = c.tile;
+        if (!(dtype == DIN_F32 ? launch_tile<float>(k, t, grid, st) : launch_tile<bf16_t>(k, t, grid, st)))
+            DIN_FAIL(DIN_E_LAUNCH, "%s: no conv_gather_fast_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d> for dtype %d", what, t.bm, t.bn, t.wm, t.wn, t.kcs,
+                     t.ns, (int)t.multi, (int)t.fastk, (int)t.xsrc, (int)t.lanek, dtype);
+        break;
+    }
+    }
+    DIN_CHECK_LAUNCH(what);
+    return DIN_OK;
+}
+
+// choose, check the workspace, launch the chosen kernel, finish a split reduction
+int run_gather(ConvK& k, GatherPlan g0, int dtype, void* workspace, int64_t ws_bytes, hipStream_t st, const char* what) {
+    const GatherChoice c = choose_gather(k, g0, dtype);
+    const GatherPlan& g = c.g;
+    set_plan_fields(k, c);
     if (const char* eb = DIN_OPT("DIN_CONV_EPI_BATCH")) { if (atoi(eb) == 0) k.flags |= 0x100; }
     // timing experiments only (results are WRONG): DIN_GATHER_KNOCK bit 0 = the pixel-tile transfers of the scalar-walk loop fetch nothing
     // (all lanes out of range: issued, landed as zeros, no cache / HBM access), bit 1 = the same for the filter tile, bit 2 = no MFMA
@@ -3100,128 +3225,16 @@ int run_gather(ConvK& k, GatherPlan g, int dtype, void* workspace, int64_t ws_by
     if (const char* kn = DIN_OPT("DIN_GATHER_KNOCK")) k.flags |= (atoi(kn) & 7) << 9;
 #endif
     if (DIN_OPT("DIN_DEBUG_PLAN"))
-        fprintf(stderr, "[din] %s M=%d NB=%d HxW=%dx%d Cin=%d Cout=%d k=%dx%d ay=%d cy=%d tile=%dx%d splitk=%d korder=%d remap=%d flags=%d dtype=%d\n", what,
-                k.M, k.NB, k.H, k.W, k.Cin, k.Cout, k.kh, k.kw, k.ay, k.cy, g.bm, g.bn, g.splitk, k.korder, k.remap, k.flags, dtype);
-    if (k.csplit > 0 && (!fast || g.splitk > 1)) DIN_FAIL(DIN_E_ARG, "%s: two destinations need the staged epilogue of the buffer-addressed kernel", what);
+        fprintf(stderr, "[din] %s M=%d NB=%d HxW=%dx%d Cin=%d Cout=%d k=%dx%d ay=%d cy=%d tile=%dx%d splitk=%d korder=%d remap=%d flags=%d dtype=%d family=%d\n", what,
+                k.M, k.NB, k.H, k.W, k.Cin, k.Cout, k.kh, k.kw, k.ay, k.cy, g.bm, g.bn, g.splitk, k.korder, k.remap, k.flags, dtype, (int)c.family);
+    if (k.csplit > 0 && (c.family == GATHER_GENERIC || g.splitk > 1)) DIN_FAIL(DIN_E_ARG, "%s: two destinations need the staged epilogue of the buffer-addressed kernel", what);
     if (g.splitk > 1) {
         if (ws_bytes < g.ws_bytes || workspace == nullptr)
             DIN_FAIL(DIN_E_WORKSPACE, "%s: workspace %lld < %lld bytes", what, (long long)ws_bytes, (long long)g.ws_bytes);
         k.partial = reinterpret_cast<float*>(workspace);
     }
-    if (fast && g.splitk == 1 && k.nsrc == 0 && k.xsteps == 0 && din_gather::conv1x1_regw_eligible(k, dtype)) {
-        // 1x1 layers with a 640..768-channel reduction over a large map (the Mixed_6 block entries): filters resident in registers (conv_regw.hip)
-        if (din_gather::launch_conv1x1_regw(k, st)) DIN_FAIL(DIN_E_LAUNCH, "%s: conv1x1_regw launch failed", what);
-        return DIN_OK;
-    }
-    if (fast && g.splitk == 1 && k.nsrc == 0 && k.xsteps == 0 && din_gather::conv1x1_stream_eligible(k, dtype)) {
-        // 1x1 layers with a short reduction over a large map: persistent streaming kernel (conv_stream.hip)
-        if (din_gather::launch_conv1x1_stream(k, st)) DIN_FAIL(DIN_E_LAUNCH, "%s: conv1x1_stream launch failed", what);
-        return DIN_OK;
-    }
-    {
-        // mid-network multi-tap layers: halo tiles + filter-slab ring (conv_halo_kernel); the stem shapes keep their own kernel below
-        HaloPlan hp;
-        const bool stem_shape = k.kh == 3 && k.kw == 3 && (k.Cin == 32 || k.Cin == 64) && k.Cout <= 64 && !(k.Cin == 64 && k.Cout > 32) &&
-                                (int64_t)k.M >= 256 * 1024;
-        if (fast && !k.remap && k.nsrc == 0 && k.csplit == 0 && g.splitk == 1 && !stem_shape && k.ay == 1 && k.ax == 1 && (k.cy == 1 || k.cy == -1) &&
-            (k.cx == 1 || k.cx == -1) && k.cy == k.cx && k.out_sy == 0 && k.ldi % 8 == 0 && k.cioff % 8 == 0 && k.ldo % 4 == 0 && k.cooff % 4 == 0 &&
-            (!(k.flags & DIN_CONV_MASK) || (k.ldm % 4 == 0 && k.moff % 4 == 0)) &&
-            (long long)k.H * k.W * k.ldi * 2 < 0x7fffffffll && (long long)k.OH * k.OW * k.ldo * 2 < 0x7fffffffll &&
-            (long long)k.OH * k.OW * (k.ldm > 0 ? k.ldm : 1) * 2 < 0x7fffffffll &&
-            plan_halo(dtype, k.kh, k.kw, k.Cin, k.Cout, k.OH, k.OW, k.M, hp)) {
-            k.n_co_tiles = hp.n_co_tiles;
-            const int tiles = ((k.OH + hp.th - 1) / hp.th) * ((k.OW + hp.tw - 1) / hp.tw) * k.NB * hp.n_co_tiles;
-            dim3 grid(tiles < 256 ? tiles : 256);
-            auto launch = [&](auto kern) {
-                raise_lds_limit(kern, hp.lds);
-                hipLaunchKernelGGL(kern, grid, dim3(512), hp.lds, st, k);
-            };
-            bool done = true;
-            if (k.kh == 3 && k.kw == 3 && hp.nwv == 16) {
-                auto launch16 = [&](auto kern) {
-                    raise_lds_limit(kern, hp.lds);
-                    hipLaunchKernelGGL(kern, grid, dim3(1024), hp.lds, st, k);
-                };
-                if (hp.bn == 64) launch16(conv_halo_kernel<64, 3, 3, 8, 32, 2, 16>);
-                else if (hp.bn == 80) launch16(conv_halo_kernel<80, 3, 3, 8, 32, 2, 16>);
-                else launch16(conv_halo_kernel<96, 3, 3, 8, 32, 2, 16>);
-            }
-            else if (k.kh == 3 && k.kw == 3) { if (hp.bn == 64) launch(conv_halo_kernel<64, 3, 3, 8, 32, 3>); else launch(conv_halo_kernel<96, 3, 3, 8, 32, 3>); }
-            else if (k.kh == 1 && k.kw == 7) { if (hp.bn == 64) launch(conv_halo_kernel<64, 1, 7, 16, 16, 3>); else launch(conv_halo_kernel<96, 1, 7, 16, 16, 3>); }
-            else if (k.kh == 7 && k.kw == 1) { if (hp.bn == 64) launch(conv_halo_kernel<64, 7, 1, 16, 16, 3>); else launch(conv_halo_kernel<96, 7, 1, 16, 16, 3>); }
-            else done = false;
-            if (done) { DIN_CHECK_LAUNCH(what); return DIN_OK; }
-        }
-    }
-    {
-        // stem layers: stationary filters + halo tiles (conv_small_kernel)
-        const char* sv = DIN_OPT("DIN_CONV_SMALL");
-        const bool want = sv ? atoi(sv) != 0 : true;
-        const bool common = want && dtype == DIN_BF16 && fast && !k.remap && k.nsrc == 0 && k.csplit == 0 && g.splitk == 1 && k.kh == 3 && k.kw == 3 &&
-                            k.Cout <= 64 && k.Cout % 8 == 0 && k.cooff % 8 == 0 && k.ldo % 8 == 0 && k.ldi % 8 == 0 && k.cioff % 8 == 0 &&
-                            (!(k.flags & DIN_CONV_MASK) || (k.ldm % 8 == 0 && k.moff % 8 == 0)) &&
-                            (long long)k.H * k.W * k.ldi * 2 < 0x7fffffffll && (long long)k.OH * k.OW * k.ldo * 2 < 0x7fffffffll &&
-                            (long long)k.OH * k.OW * (k.ldm > 0 ? k.ldm : 1) * 2 < 0x7fffffffll && k.out_sy == 0 && (int64_t)k.M >= 256 * 1024;
-        // 32/64-channel 3x3 stride-1 layers (fwd and dgrad) ...
-        const bool stem = common && (g.cpt == 4 || g.cpt == 8) && g.cpt * 8 == k.Cin && k.ay == 1 && k.ax == 1 &&
-                          (k.cy == 1 || k.cy == -1) && (k.cx == 1 || k.cx == -1) && !(g.cpt == 8 && k.Cout > 32);
-        // ... and the image layer: <= 8 (zero-padded) channels per pixel, stride 2, forward only
-        const bool image = common && g.cpt == 1 && k.Cin <= 8 && k.ldi >= 8 && k.Cout <= 32 && k.ay == 2 && k.ax == 2 && k.cy == 1 && k.cx == 1 &&
-                           k.wld >= 12;
-        if (stem || image) {
-            const int bnS = k.Cout <= 32 ? 32 : 64;
-            const int st_ = image ? 2 : 1;
-            const int hpx = (7 * st_ + 3) * (31 * st_ + 3);
-            const int hbytes = (hpx * g.cpt * 16 + 1023) / 1024 * 1024;
-            // 128-byte pixels (the 64-channel dgrad of Conv2d_2b): one halo buffer (80 KiB) or -- DIN_CONV_SMALL_NBUF8=2 -- two (124 KiB, the next
-            // halo in flight under this tile's MFMAs like the 64-byte-pixel variants); one workgroup per CU either way
-            const char* nb8 = DIN_OPT("DIN_CONV_SMALL_NBUF8");
-            const bool two8 = g.cpt == 8 && (nb8 ? atoi(nb8) == 2 : false);
-            const int nbuf = (g.cpt == 8 && !two8) ? 1 : 2;
-            const size_t lds = (size_t)(image ? 3 * bnS * 64 : 9 * bnS * g.cpt * 16) + (size_t)nbuf * hbytes + (k.u8 ? 512 : 0);   // (+ the uint8 -> bf16 table)
-            dim3 grid(512);
-            // dgrad launches with a mask / accumulate operand: the variant that requests them a tile phase early (DIN_CONV_SMALL_EPI=0: in the store loop)
-            const bool epi = (k.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM)) && !(DIN_OPT("DIN_CONV_SMALL_EPI") && atoi(DIN_OPT("DIN_CONV_SMALL_EPI")) == 0);
-            // the image layer's 42 KiB workgroups fit three to a CU: 768 persistent workgroups measured 690 -> 618 us on the 96 frames
-            // (1024: no better, four do not fit); DIN_CONV_IMAGE_GRID overrides
-            if (image) { const char* gv = DIN_OPT("DIN_CONV_IMAGE_GRID"); grid.x = gv && atoi(gv) > 0 ? atoi(gv) : 768; }
-            auto launch = [&](auto kern) {
-                if (lds > 65536) raise_lds_limit(kern, lds);
-                hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), lds, st, k);
-            };
-            if (image && k.u8) launch(conv_small_kernel<1, 32, 2, 3, 3, 2, true>);
-            else if (image) launch(conv_small_kernel<1, 32, 2, 3, 3, 2>);
-            else if (g.cpt == 4 && bnS == 32) {                                                // (eight waves measured slower here: 706 -> 765 us)
-                if (epi) launch(conv_small_kernel<4, 32, 2, 3, 3, 1, false, 4, true>); else launch(conv_small_kernel<4, 32, 2, 3, 3, 1>);
-            }
-            else {
-                // the two 80 KiB variants (one workgroup per CU) run on eight waves; DIN_CONV_SMALL_WAVES=4 restores four
-                const bool w8 = !(DIN_OPT("DIN_CONV_SMALL_WAVES") && atoi(DIN_OPT("DIN_CONV_SMALL_WAVES")) == 4);
-                auto launch8 = [&](auto kern) {
-                    if (lds > 65536) raise_lds_limit(kern, lds);
-                    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, k);
-                };
-                if (g.cpt == 4) { if (w8) launch8(conv_small_kernel<4, 64, 2, 3, 3, 1, false, 8>); else launch(conv_small_kernel<4, 64, 2, 3, 3, 1>); }
-                else if (two8 && w8) { if (epi) launch8(conv_small_kernel<8, 32, 2, 3, 3, 1, false, 8, true>); else launch8(conv_small_kernel<8, 32, 2, 3, 3, 1, false, 8>); }
-                else if (epi && w8) launch8(conv_small_kernel<8, 32, 1, 3, 3, 1, false, 8, true>);
-                else { if (w8) launch8(conv_small_kernel<8, 32, 1, 3, 3, 1, false, 8>); else launch(conv_small_kernel<8, 32, 1, 3, 3, 1>); }
-            }
-            DIN_CHECK_LAUNCH(what);
-            return DIN_OK;
-        }
-    }
-    DIN_REQUIRE(!k.u8, "%s: in_u8 is only served by the image-layer kernel (see din_conv_accepts_u8)", what);
-    if (fast && !k.remap && k.nsrc == 0 && want_gather_pipe(dtype, k.M, k.Cin, k.kh * k.kw, g.bn, g.splitk, (k.Cout + g.bn - 1) / g.bn) &&
-        g.cpt % 4 == 0 && k.Cout % 8 == 0 && k.cooff % 8 == 0 && k.ldo % 8 == 0 &&
-        (!(k.flags & DIN_CONV_MASK) || (k.ldm % 8 == 0 && k.moff % 8 == 0)) && (k.csplit == 0 || (k.csplit % 8 == 0 && k.ldo2 % 8 == 0 && k.cooff2 % 8 == 0))) {
-        k.n_co_tiles = (k.Cout + g.bn - 1) / g.bn;
-        if (int e = din_gather::launch_gather_pipe(k, g.bn, (k.M + 255) / 256, st)) return e;
-        DIN_CHECK_LAUNCH(what);
-        return DIN_OK;
-    }
-    if (dtype == DIN_F32) launch_gather<float>(k, g.n_px_tiles, g.bm, g.bn, st);
-    else launch_gather<bf16_t>(k, g.n_px_tiles, g.bm, g.bn, st);
-    DIN_CHECK_LAUNCH(what);
+    DIN_REQUIRE(!k.u8 || c.family == GATHER_SMALL, "%s: in_u8 is only served by the image-layer kernel (see din_conv_accepts_u8)", what);
+    if (int e = launch_choice(k, c, dtype, st, what)) return e;
     if (g.splitk > 1) {
         int64_t total = (int64_t)k.M * k.Cout;
         int cpad = g.n_co_tiles * g.bn;
@@ -3231,6 +3244,87 @@ int run_gather(ConvK& k, GatherPlan g, int dtype, void* workspace, int64_t ws_by
     }
     return DIN_OK;
 }
+
+// ---- descriptor -> launch ------------------------------------------------------------------------------
+// A strided data gradient is decomposed by output parity (py, px).  Class (py, px) only sees the taps r = r0 + sh*r', s = s0 + sw*s' with
+// r0 = (py+ph) % sh: a stride-1 gather oy = a + (py+ph-r0)/sh - r' over the sub-grid y = sh*a + py -- no structurally zero taps are
+// multiplied, and it runs on the fast (buffer-addressed) kernel.
+struct ParityClass { int py, px, Ha, Wa, r0c, s0c, khs, kws; };
+static bool dgrad_by_parity(const din_conv_desc* d) { return (d->sh > 1 || d->sw > 1) && d->dh == 1 && d->dw == 1 && d->kh * d->kw <= 32; }
+// f(class) for every non-empty parity class; stops at the first non-zero return and hands it back
+template <typename F>
+static int for_each_parity_class(const din_conv_desc* d, F f) {
+    for (int py = 0; py < d->sh; ++py)
+        for (int px = 0; px < d->sw; ++px) {
+            ParityClass pc{py, px, (d->h - py + d->sh - 1) / d->sh, (d->w - px + d->sw - 1) / d->sw, (py + d->ph) % d->sh, (px + d->pw) % d->sw, 0, 0};
+            if (pc.Ha <= 0 || pc.Wa <= 0) continue;
+            pc.khs = pc.r0c < d->kh ? (d->kh - pc.r0c + d->sh - 1) / d->sh : 0;
+            pc.kws = pc.s0c < d->kw ? (d->kw - pc.s0c + d->sw - 1) / d->sw : 0;
+            if (int e = f(pc)) return e;
+        }
+    return 0;
+}
+
+// plan of the launch `which` (0 forward, 1 data gradient; pc: one parity class of a strided data gradient)
+static GatherPlan plan_launch(const din_conv_desc* d, int which, const ParityClass* pc = nullptr) {
+    if (which == 0) return plan_gather(d->nb * d->oh * d->ow, d->cin, d->cout, d->kh * d->kw, d->dtype);
+    if (!pc) return plan_gather(d->nb * d->h * d->w, d->cout, d->cin, d->kh * d->kw, d->dtype);
+    return plan_gather(d->nb * pc->Ha * pc->Wa, d->cout, d->cin, pc->khs * pc->kws, d->dtype, true);
+}
+
+// Geometry of that launch as the kernels' argument block; the caller adds pointers, flags and the mask view.
+// The CANONICAL LAUNCH of a descriptor -- the one din_conv_kernel_tile / din_conv_kernel_variant report -- is:
+//   forward        single destination, no dgrad flags;
+//   data gradient  DIN_CONV_MASK without DIN_CONV_ACCUM, the mask view equal to the layer's input view (ldm = ldi, moff = cioff);
+//   strided dgrad  parity class (0, 0) of the above.
+static ConvK conv_k_of(const din_conv_desc* d, int which, const ParityClass* pc = nullptr) {
+    const int esz = d->dtype == DIN_F32 ? 4 : 2;
+    ConvK k{};
+    k.NB = d->nb; k.kh = d->kh; k.kw = d->kw;
+    k.w_bytes = din_conv_packed_elems(d, which) * esz;
+    if (which == 0) {
+        k.H = d->h; k.W = d->w; k.Cin = d->cin; k.ldi = d->ldi; k.cioff = d->cioff;
+        k.OH = d->oh; k.OW = d->ow; k.Cout = d->cout; k.ldo = d->ldo; k.cooff = d->cooff;
+        k.ay = d->sh; k.by = -d->ph; k.cy = d->dh; k.divy = 1;
+        k.ax = d->sw; k.bx = -d->pw; k.cx = d->dw; k.divx = 1;
+        k.M = d->nb * d->oh * d->ow;
+        k.in_bytes = (long long)d->nb * d->h * d->w * d->ldi * esz;
+        if (d->in_u8) { k.ldi = 8; k.cioff = 0; k.in_bytes = (long long)d->nb * d->h * d->w * 16; }   // raw uint8 frames: plan as the 8-channel prepared tensor the image layer would read
+        return k;
+    }
+    // the "input" of the gather is dout (geometry oh x ow x cout), the "output" is din (h x w x cin)
+    k.H = d->oh; k.W = d->ow; k.Cin = d->cout; k.ldi = d->ldo; k.cioff = d->cooff;
+    k.OH = d->h; k.OW = d->w; k.Cout = d->cin; k.ldo = d->ldi; k.cooff = d->cioff;
+    k.in_bytes = (long long)d->nb * d->oh * d->ow * d->ldo * esz;
+    if (!pc) {
+        // y_in = oy*sh - ph + r*dh  =>  oy = (y_in + ph - r*dh) / sh
+        k.ay = 1; k.by = d->ph; k.cy = -d->dh; k.divy = d->sh;
+        k.ax = 1; k.bx = d->pw; k.cx = -d->dw; k.divx = d->sw;
+        k.M = d->nb * d->h * d->w;
+        return k;
+    }
+    const int epc = epc_of(d->dtype);
+    const bool taps = pc->khs > 0 && pc->kws > 0;
+    k.kh = taps ? pc->khs : 0; k.kw = taps ? pc->kws : 1;
+    k.ay = 1; k.by = (pc->py + d->ph - pc->r0c) / d->sh; k.cy = -1; k.divy = 1;
+    k.ax = 1; k.bx = (pc->px + d->pw - pc->s0c) / d->sw; k.cx = -1; k.divx = 1;
+    k.OH = pc->Ha; k.OW = pc->Wa; k.M = d->nb * pc->Ha * pc->Wa;
+    k.out_sy = d->sh; k.out_sx = d->sw; k.out_y0 = pc->py; k.out_x0 = pc->px; k.out_H = d->h; k.out_W = d->w;
+    k.remap = 1; k.wld = (d->kh * d->kw * (pad_to(d->cout, epc) / epc) + KC - 1) / KC * KC;           // rows of the full packed bank
+    for (int rr = 0; rr < pc->khs; ++rr)
+        for (int ss = 0; ss < pc->kws; ++ss) k.wtap[rr * pc->kws + ss] = (unsigned char)((pc->r0c + d->sh * rr) * d->kw + (pc->s0c + d->sw * ss));
+    return k;
+}
+
+// what the canonical launch of a descriptor (conv_k_of) resolves to
+static GatherChoice canonical_choice(const din_conv_desc* d, int which) {
+    ParityClass first{};
+    const bool parity = which == 1 && dgrad_by_parity(d) && for_each_parity_class(d, [&](const ParityClass& pc) { first = pc; return 1; });
+    ConvK k = conv_k_of(d, which, parity ? &first : nullptr);
+    if (which == 1) { k.flags = DIN_CONV_MASK; k.ldm = d->ldi; k.moff = d->cioff; }
+    return choose_gather(k, plan_launch(d, which, parity ? &first : nullptr), d->dtype);
+}
+
 
 // column sums of a pixel-major tensor view -> out[c] (fp32 atomics across row slabs): zeroed here first, or added into when `zero` is false
 static int launch_colsum(int dtype, const void* g, float* out, int64_t M, int c, int ld, int coff, hipStream_t st, bool zero = true) {
@@ -3333,118 +3427,36 @@ int din_conv_pack_multi(const din_pack_desc* table, const int32_t* layer_of, con
 int din_conv_kernel_tile(const din_conv_desc* d, int which, int32_t* bm, int32_t* bn) {
     DIN_REQUIRE(d && bm && bn && which >= 0 && which <= 2, "conv_kernel_tile: bad argument");
     if (which == 2) { WgradPlan wp = plan_wgrad(d); if (wp.small == 4) { *bm = 3; *bn = wp.bco; return DIN_OK; } *bm = wp.small ? 0 : wp.bco; *bn = wp.small ? wp.bco : (wp.pipe ? 2000 + wp.bk : wp.ring ? 1000 + wp.bk : WG_TILE); return DIN_OK; }
-    const bool strided = which == 1 && (d->sh > 1 || d->sw > 1);
-    GatherPlan g = which == 0 ? plan_gather(d->nb * d->oh * d->ow, d->cin, d->cout, d->kh * d->kw, d->dtype)
-                              : plan_gather(d->nb * (strided ? (d->h + d->sh - 1) / d->sh * ((d->w + d->sw - 1) / d->sw) : d->h * d->w),
-                                            d->cout, d->cin, d->kh * d->kw, d->dtype, strided);
-    if (g.bm == 256 && (strided || g.splitk > 1)) { g.bm = 128; if (g.bn == 256) g.bn = 128; }
-    *bm = g.bm; *bn = g.bn;
-    {   // conv_gather_pipe_kernel<BN>: bm = 2 (the halo / stem kernels below still take precedence, as in run_gather)
-        const int cred = which == 0 ? d->cin : d->cout, cprod = which == 0 ? d->cout : d->cin;
-        const int64_t M = which == 0 ? (int64_t)d->nb * d->oh * d->ow : (int64_t)d->nb * d->h * d->w;
-        if (!strided && d->dh == 1 && d->dw == 1 && want_gather_pipe(d->dtype, M, cred, d->kh * d->kw, g.bn, g.splitk, (cprod + g.bn - 1) / g.bn) &&
-            cprod % 8 == 0 && (which == 0 ? d->cooff % 8 == 0 && d->ldo % 8 == 0 : d->cioff % 8 == 0 && d->ldi % 8 == 0)) *bm = 2;
+    // the canonical launch of the descriptor (conv_k_of), as choose_gather resolves it
+    const GatherChoice c = canonical_choice(d, which);
+    switch (c.family) {
+    case GATHER_SMALL: *bm = 0; break;
+    case GATHER_HALO: *bm = 1; break;
+    case GATHER_PIPE: *bm = 2; break;
+    case GATHER_STREAM: *bm = 4; break;
+    case GATHER_REGW: *bm = 5; break;
+    default: *bm = c.tile.bm; break;
     }
-    {   // mid-network multi-tap layers run conv_halo_kernel: bm = 1
-        HaloPlan hp;
-        const int cred = which == 0 ? d->cin : d->cout, cprod = which == 0 ? d->cout : d->cin;
-        const int64_t M = which == 0 ? (int64_t)d->nb * d->oh * d->ow : (int64_t)d->nb * d->h * d->w;
-        const int oh_ = which == 0 ? d->oh : d->h, ow_ = which == 0 ? d->ow : d->w;
-        if (d->sh == 1 && d->sw == 1 && d->dh == 1 && d->dw == 1 && g.splitk == 1 && plan_halo(d->dtype, d->kh, d->kw, cred, cprod, oh_, ow_, M, hp)) { *bm = 1; *bn = hp.bn; }
-    }
-    {   // 1x1 layers with a short reduction over a large map run conv1x1_stream_kernel (conv_stream.hip): bm = 4
-        // (same conditions as din_gather::conv1x1_stream_eligible, evaluated on the descriptor)
-        const char* sv = DIN_OPT("DIN_CONV_STREAM");
-        const int mode = sv ? atoi(sv) : 1;
-        const int cred = which == 0 ? d->cin : d->cout, cprod = which == 0 ? d->cout : d->cin;
-        const int64_t M = which == 0 ? (int64_t)d->nb * d->oh * d->ow : (int64_t)d->nb * d->h * d->w;
-        const int ldr = which == 0 ? d->ldi : d->ldo, offr = which == 0 ? d->cioff : d->cooff;
-        const int ldp = which == 0 ? d->ldo : d->ldi, offp = which == 0 ? d->cooff : d->cioff;
-        const int blocks = (pad_to(cred, 8) / 8 + 7) / 8;
-        if (mode && d->dtype == DIN_BF16 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && d->ph == 0 && d->pw == 0 && !d->in_u8 &&
-            g.splitk == 1 && cprod % 8 == 0 && ldp % 8 == 0 && offp % 8 == 0 && ldr % 8 == 0 && offr % 8 == 0 &&
-            M * ldr * 2 < 0x7fffffffll && M * ldp * 2 < 0x7fffffffll && pad_to(cprod, din_gather::conv1x1_stream_tile(cprod)) * 4 <= 2048 &&
-            (mode == 2 || (blocks <= 6 && M >= (DIN_OPT("DIN_CONV_STREAM_MINPIX") ? atoll(DIN_OPT("DIN_CONV_STREAM_MINPIX")) : 256 * 1024) && (cprod <= 96 || (cprod <= 192 && which == 0))))) { *bm = 4; *bn = din_gather::conv1x1_stream_tile(cprod); }
-    }
-    {   // 1x1 layers with a 640..768-channel reduction over a large map run conv1x1_regw_kernel (conv_regw.hip, filters resident in registers):
-        // bm = 5, bn = 192 | 128 filters per class (same conditions as din_gather::conv1x1_regw_eligible, evaluated on the descriptor; single destination, no accumulate)
-        const char* rv = DIN_OPT("DIN_CONV_REGW");
-        const int mode = rv ? atoi(rv) : 1;
-        const int cred = which == 0 ? d->cin : d->cout, cprod = which == 0 ? d->cout : d->cin;
-        const int64_t M = which == 0 ? (int64_t)d->nb * d->oh * d->ow : (int64_t)d->nb * d->h * d->w;
-        const int ldr = which == 0 ? d->ldi : d->ldo, offr = which == 0 ? d->cioff : d->cooff;
-        const int ldp = which == 0 ? d->ldo : d->ldi, offp = which == 0 ? d->cooff : d->cioff;
-        const int nks = cred % 8 == 0 ? (cred + 63) / 64 * 2 : 0;      // (a multi-source launch pads EACH source to whole stages: din_conv1x1_dgrad_multi decides itself)
-        const bool shortk = nks == 6 || nks == 8 || nks == 10;          // Mixed_5: classes of 128 filters, two workgroups per CU
-        const char* sk = DIN_OPT("DIN_CONV_REGW_SHORT");
-        const char* mp = DIN_OPT("DIN_CONV_REGW_MINPIX");
-        if (mode && d->dtype == DIN_BF16 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && d->ph == 0 && d->pw == 0 && !d->in_u8 &&
-            g.splitk == 1 && (shortk || nks == 20 || nks == 24) && cprod <= (shortk ? 512 : 768) && cprod % 8 == 0 && ldp % 8 == 0 && offp % 8 == 0 &&
-            ldr % 8 == 0 && offr % 8 == 0 && M * ldr * 2 < 0x7fffffffll &&
-            (mode == 2 || (shortk ? (sk ? atoi(sk) != 0 : true) && M >= (mp ? atoll(mp) : 128 * 1024) && cprod > 96 : M >= (mp ? atoll(mp) : 64 * 1024)))) { *bm = 5; *bn = shortk ? 128 : 192; }
-    }
-    {   // stem layers run conv_small_kernel (same conditions as run_gather, for tensors with 16-byte aligned channel offsets): bm = 0
-        const int cred = which == 0 ? d->cin : d->cout, cprod = which == 0 ? d->cout : d->cin;
-        const int64_t M = which == 0 ? (int64_t)d->nb * d->oh * d->ow : (int64_t)d->nb * d->h * d->w;
-        const char* sv = DIN_OPT("DIN_CONV_SMALL");
-        if ((sv ? atoi(sv) != 0 : true) && d->dtype == DIN_BF16 && d->kh == 3 && d->kw == 3 && d->sh == 1 && d->sw == 1 && d->dh == 1 &&
-            d->dw == 1 && (cred == 32 || cred == 64) && cprod <= 64 && cprod % 8 == 0 && !(cred == 64 && cprod > 32) && g.splitk == 1 &&
-            M >= 256 * 1024) { *bm = 0; *bn = cprod <= 32 ? 32 : 64; }
-        if ((sv ? atoi(sv) != 0 : true) && which == 0 && d->dtype == DIN_BF16 && d->kh == 3 && d->kw == 3 && d->sh == 2 && d->sw == 2 &&
-            d->dh == 1 && d->dw == 1 && d->cin <= 8 && d->cout <= 32 && d->cout % 8 == 0 && g.splitk == 1 && M >= 256 * 1024) { *bm = 0; *bn = 32; }
-    }
+    *bn = c.bn;
     return DIN_OK;
 }
 
 int din_conv_kernel_variant(const din_conv_desc* d, int which, int32_t* flags) {
     DIN_REQUIRE(d && flags && which >= 0 && which <= 1, "conv_kernel_variant: bad argument");
-    int32_t bm = 0, bn = 0;
-    if (int e = din_conv_kernel_tile(d, which, &bm, &bn)) return e;
+    const GatherChoice c = canonical_choice(d, which);
     *flags = 0;
-    if (bm != 128 || d->dtype != DIN_BF16) return DIN_OK;          // the 8-wave / FASTK instantiations exist for bf16 128 x BN tiles only
-    const char* pv = DIN_OPT("DIN_CONV_PIPE");
-    const int pipe = pv ? atoi(pv) : -1;
-    const bool strided = which == 1 && (d->sh > 1 || d->sw > 1);
-    const bool wave8 = ((bn == 64 || bn == 128 || bn == 160 || bn == 192) && pipe != 4 && pipe != 1) ||
-                       (bn == 96 && (pipe == 8 || (strided && pipe != 4)));       // (the parity classes of a strided dgrad: launch_gather)
-    if (wave8) *flags |= 2;
-    const int ntaps = d->kh * d->kw, cred = which == 0 ? d->cin : d->cout;
-    const int cpt = pad_to(cred, 8) / 8;
-    GatherPlan g = which == 0 ? plan_gather(d->nb * d->oh * d->ow, d->cin, d->cout, ntaps, d->dtype)
-                              : plan_gather(d->nb * (strided ? (d->h + d->sh - 1) / d->sh * ((d->w + d->sw - 1) / d->sw) : d->h * d->w), d->cout, d->cin, ntaps, d->dtype, strided);
-    const char* ko = DIN_OPT("DIN_CONV_KORDER");
-    const char* fv = DIN_OPT("DIN_CONV_FASTK");
-    const bool fast = ntaps <= 32 && (which == 0 || (d->sh == 1 && d->sw == 1));      // stride-1 gather: divy == divx == 1, no tap remap
-    const bool korder = (ko ? atoi(ko) != 0 : true) && fast && g.splitk == 1 && cpt % KC == 0 && ntaps > 1;
-    if (wave8 && fast && cpt % KC == 0 && (korder || ntaps == 1) && (fv ? atoi(fv) != 0 : true)) *flags |= 1;
-    const char* lv = DIN_OPT("DIN_CONV_LANEK");                  // bit 2: the per-lane k-walk instantiation (gather_lanek; bit 0 is set with it: FASTK = true)
-    const int lmode = lv ? atoi(lv) : 1;                          // (1: forward launches only -- a data gradient carries the mask / accumulate flags)
-    if (wave8 && bn != 96 && fast && !strided && cpt % KC != 0 && cpt >= 8 && ntaps > 1 && ntaps <= 31 && (fv ? atoi(fv) != 0 : true) &&
-        (lmode == 2 || (lmode == 1 && which == 0))) *flags |= 1 | 4;
+    if (c.family != GATHER_TILE || c.tile.bm != 128) return DIN_OK;     // (the 256-pixel tiles have one wave grid per filter tile)
+    *flags = (c.tile.fastk ? 1 : 0) | (c.tile.wm * c.tile.wn == 8 ? 2 : 0) | (c.tile.lanek ? 4 : 0);
     return DIN_OK;
 }
 
 int64_t din_conv_workspace_bytes(const din_conv_desc* d, int which) {
     if (!d) return 0;
-    if (which == 0) return plan_gather(d->nb * d->oh * d->ow, d->cin, d->cout, d->kh * d->kw, d->dtype).ws_bytes;
-    if (which == 1) {
-        if ((d->sh > 1 || d->sw > 1) && d->dh == 1 && d->dw == 1 && d->kh * d->kw <= 32) {
-            int64_t mx = 0;
-            for (int py = 0; py < d->sh; ++py)
-                for (int px = 0; px < d->sw; ++px) {
-                    const int Ha = (d->h - py + d->sh - 1) / d->sh, Wa = (d->w - px + d->sw - 1) / d->sw;
-                    if (Ha <= 0 || Wa <= 0) continue;
-                    const int r0c = (py + d->ph) % d->sh, s0c = (px + d->pw) % d->sw;
-                    const int khs = r0c < d->kh ? (d->kh - r0c + d->sh - 1) / d->sh : 0;
-                    const int kws = s0c < d->kw ? (d->kw - s0c + d->sw - 1) / d->sw : 0;
-                    int64_t b = plan_gather(d->nb * Ha * Wa, d->cout, d->cin, khs * kws, d->dtype, true).ws_bytes;
-                    if (b > mx) mx = b;
-                }
-            return mx;
-        }
-        return plan_gather(d->nb * d->h * d->w, d->cout, d->cin, d->kh * d->kw, d->dtype).ws_bytes;
-    }
-    return plan_wgrad(d).ws_bytes;
+    if (which != 0 && which != 1) return plan_wgrad(d).ws_bytes;
+    if (which == 0 || !dgrad_by_parity(d)) return plan_launch(d, which).ws_bytes;
+    int64_t mx = 0;
+    for_each_parity_class(d, [&](const ParityClass& pc) { const int64_t b = plan_launch(d, 1, &pc).ws_bytes; if (b > mx) mx = b; return 0; });
+    return mx;
 }
 
 int din_conv_fwd(const din_conv_desc* d, const void* in, const void* wpk, const float* bias, void* out, int flags,
@@ -3453,23 +3465,13 @@ int din_conv_fwd(const din_conv_desc* d, const void* in, const void* wpk, const 
     DIN_REQUIRE(in && wpk && out, "conv_fwd: null pointer");
     DIN_REQUIRE(!(flags & DIN_CONV_BIAS) || bias, "conv_fwd: BIAS flag without bias");
     DIN_REQUIRE(!(flags & (DIN_CONV_ACCUM | DIN_CONV_MASK)), "conv_fwd: ACCUM/MASK are dgrad-only flags");
-    ConvK k{};
-    k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.mask = nullptr; k.partial = nullptr;
-    k.NB = d->nb; k.H = d->h; k.W = d->w; k.Cin = d->cin; k.ldi = d->ldi; k.cioff = d->cioff;
-    k.OH = d->oh; k.OW = d->ow; k.Cout = d->cout; k.ldo = d->ldo; k.cooff = d->cooff;
-    k.kh = d->kh; k.kw = d->kw;
-    k.ay = d->sh; k.by = -d->ph; k.cy = d->dh; k.divy = 1;
-    k.ax = d->sw; k.bx = -d->pw; k.cx = d->dw; k.divx = 1;
-    k.M = d->nb * d->oh * d->ow; k.flags = flags; k.ldm = 0; k.moff = 0;
-    k.in_bytes = (long long)d->nb * d->h * d->w * d->ldi * (d->dtype == DIN_F32 ? 4 : 2);
-    k.w_bytes = din_conv_packed_elems(d, 0) * (d->dtype == DIN_F32 ? 4 : 2);
-    if (d->in_u8) {                                   // raw uint8 frames: plan as the 8-channel prepared tensor the image layer would read
+    ConvK k = conv_k_of(d, 0);
+    k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.flags = flags;
+    if (d->in_u8) {
         DIN_REQUIRE(din_conv_accepts_u8(d), "conv_fwd: in_u8 on a layer din_conv_accepts_u8() rejects");
         k.u8 = reinterpret_cast<const unsigned char*>(in);
-        k.ldi = 8; k.cioff = 0; k.in_bytes = (long long)d->nb * d->h * d->w * 16;
     }
-    GatherPlan g = plan_gather(k.M, d->cin, d->cout, d->kh * d->kw, d->dtype);
-    return run_gather(k, g, d->dtype, workspace, workspace_bytes, as_stream(stream), "conv_fwd");
+    return run_gather(k, plan_launch(d, 0), d->dtype, workspace, workspace_bytes, as_stream(stream), "conv_fwd");
 }
 
 int din_conv_accepts_u8(const din_conv_desc* d) {
@@ -3477,8 +3479,7 @@ int din_conv_accepts_u8(const din_conv_desc* d) {
     if (d->cin != 3 || d->cout > 32 || d->cout % 8 != 0 || d->ldo % 8 != 0 || d->cooff % 8 != 0) return 0;
     if ((int64_t)d->nb * d->oh * d->ow < 256 * 1024) return 0;
     if ((long long)d->h * d->w * 16 >= 0x7fffffffll || (long long)d->oh * d->ow * d->ldo * 2 >= 0x7fffffffll) return 0;
-    const char* sv = DIN_OPT("DIN_CONV_SMALL");
-    if (sv && atoi(sv) == 0) return 0;
+    if (!conv_small_wanted()) return 0;
     const char* uv = DIN_OPT("DIN_CONV_U8");
     if (uv && atoi(uv) == 0) return 0;
     din_conv_desc t = *d;
@@ -3498,19 +3499,11 @@ int din_conv_fwd2(const din_conv_desc* d, const void* in, const void* wpk, const
     DIN_REQUIRE(csplit > 0 && csplit < d->cout && csplit % epc == 0 && d->cout % epc == 0 && d->ldo % epc == 0 && d->cooff % epc == 0 &&
                 ldo2 % epc == 0 && cooff2 % epc == 0 && ldo2 >= cooff2 + (d->cout - csplit) && d->ldo >= d->cooff + csplit,
                 "conv_fwd2: split / strides / offsets must be multiples of %d and the destinations must hold their channel ranges", epc);
-    ConvK k{};
-    k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.mask = nullptr; k.partial = nullptr;
     DIN_REQUIRE(craw == 0 || (craw >= csplit && craw < d->cout && craw % epc == 0), "conv_fwd2: craw must be 0 or a multiple of %d in [csplit, cout)", epc);
+    ConvK k = conv_k_of(d, 0);
+    k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.flags = flags;
     k.out2 = out2; k.ldo2 = ldo2; k.cooff2 = cooff2; k.csplit = csplit; k.craw = craw;
-    k.NB = d->nb; k.H = d->h; k.W = d->w; k.Cin = d->cin; k.ldi = d->ldi; k.cioff = d->cioff;
-    k.OH = d->oh; k.OW = d->ow; k.Cout = d->cout; k.ldo = d->ldo; k.cooff = d->cooff;
-    k.kh = d->kh; k.kw = d->kw;
-    k.ay = d->sh; k.by = -d->ph; k.cy = d->dh; k.divy = 1;
-    k.ax = d->sw; k.bx = -d->pw; k.cx = d->dw; k.divx = 1;
-    k.M = d->nb * d->oh * d->ow; k.flags = flags; k.ldm = 0; k.moff = 0;
-    k.in_bytes = (long long)d->nb * d->h * d->w * d->ldi * (d->dtype == DIN_F32 ? 4 : 2);
-    k.w_bytes = din_conv_packed_elems(d, 0) * (d->dtype == DIN_F32 ? 4 : 2);
-    GatherPlan g = plan_gather(k.M, d->cin, d->cout, d->kh * d->kw, d->dtype);
+    const GatherPlan g = plan_launch(d, 0);
     if (g.splitk > 1) DIN_FAIL(DIN_E_ARG, "conv_fwd2: this shape runs split-K (%d pixels): launch the sibling convs separately", k.M);
     return run_gather(k, g, d->dtype, workspace, workspace_bytes, as_stream(stream), "conv_fwd2");
 }
@@ -3527,18 +3520,8 @@ int din_conv_dgrad(const din_conv_desc* d, const void* dout, const void* wpk_t, 
 // tiles, no split-K)
 static bool dgrad_x_fused(const din_conv_desc* d) {
     if (DIN_OPT("DIN_DGRAD_X") && atoi(DIN_OPT("DIN_DGRAD_X")) == 0) return false;
-    if (d->dtype != DIN_BF16 || !(d->sh > 1 || d->sw > 1) || d->dh != 1 || d->dw != 1 || d->kh * d->kw > 32) return false;
-    for (int py = 0; py < d->sh; ++py)
-        for (int px = 0; px < d->sw; ++px) {
-            const int Ha = (d->h - py + d->sh - 1) / d->sh, Wa = (d->w - px + d->sw - 1) / d->sw;
-            if (Ha <= 0 || Wa <= 0) continue;
-            const int r0c = (py + d->ph) % d->sh, s0c = (px + d->pw) % d->sw;
-            const int khs = r0c < d->kh ? (d->kh - r0c + d->sh - 1) / d->sh : 0;
-            const int kws = s0c < d->kw ? (d->kw - s0c + d->sw - 1) / d->sw : 0;
-            const GatherPlan g = plan_gather(d->nb * Ha * Wa, d->cout, d->cin, khs * kws, d->dtype, true);
-            if (g.bn != 96 || g.splitk != 1) return false;
-        }
-    return true;
+    if (d->dtype != DIN_BF16 || !dgrad_by_parity(d)) return false;
+    return !for_each_parity_class(d, [&](const ParityClass& pc) { const GatherPlan g = plan_launch(d, 1, &pc); return (g.bn != 96 || g.splitk != 1) ? 1 : 0; });
 }
 
 int din_conv_dgrad_x_fused(const din_conv_desc* d) { return (d && check_desc(d) == DIN_OK && dgrad_x_fused(d)) ? 1 : 0; }
@@ -3567,59 +3550,27 @@ static int conv_dgrad_impl(const din_conv_desc* d, const void* dout, const void*
     DIN_REQUIRE(d->ldo % epc == 0 && d->cooff % epc == 0 && d->ldo >= d->cooff + pad_to(d->cout, epc),
                 "conv_dgrad: dout stride/offset must be multiples of %d and cover cout (+zero pad)", epc);
     DIN_REQUIRE(d->ldi % 4 == 0 && d->cioff % 4 == 0, "conv_dgrad: din stride/offset must be multiples of 4");
-    // the "input" of the gather is dout (geometry oh x ow x cout), the "output" is din (h x w x cin)
-    ConvK k{};
-    k.in = dout; k.w = wpk_t; k.out = din_; k.bias = nullptr; k.mask = mask; k.partial = nullptr;
-    k.NB = d->nb; k.H = d->oh; k.W = d->ow; k.Cin = d->cout; k.ldi = d->ldo; k.cioff = d->cooff;
-    k.OH = d->h; k.OW = d->w; k.Cout = d->cin; k.ldo = d->ldi; k.cooff = d->cioff;
-    k.kh = d->kh; k.kw = d->kw;
-    k.flags = flags; k.ldm = ldm; k.moff = moff;
-    k.in_bytes = (long long)d->nb * d->oh * d->ow * d->ldo * (d->dtype == DIN_F32 ? 4 : 2);
-    k.w_bytes = din_conv_packed_elems(d, 1) * (d->dtype == DIN_F32 ? 4 : 2);
-    const bool strided = d->sh > 1 || d->sw > 1;
-    if (!strided || d->dh != 1 || d->dw != 1 || d->kh * d->kw > 32) {
-        // y_in = oy*sh - ph + r*dh  =>  oy = (y_in + ph - r*dh) / sh
-        k.ay = 1; k.by = d->ph; k.cy = -d->dh; k.divy = d->sh;
-        k.ax = 1; k.bx = d->pw; k.cx = -d->dw; k.divx = d->sw;
-        k.M = d->nb * d->h * d->w;
-        GatherPlan g = plan_gather(k.M, d->cout, d->cin, d->kh * d->kw, d->dtype);
-        return run_gather(k, g, d->dtype, workspace, workspace_bytes, as_stream(stream), "conv_dgrad");
+    hipStream_t st = as_stream(stream);
+    auto bind = [&](ConvK& k) { k.in = dout; k.w = wpk_t; k.out = din_; k.mask = mask; k.flags = flags; k.ldm = ldm; k.moff = moff; };
+    if (!dgrad_by_parity(d)) {
+        ConvK k = conv_k_of(d, 1);
+        bind(k);
+        return run_gather(k, plan_launch(d, 1), d->dtype, workspace, workspace_bytes, st, "conv_dgrad");
     }
-    // Strided dgrad: decompose by output parity (py,px).  Class (py,px) only sees the taps r = r0 + sh*r', s = s0 + sw*s'
-    // with r0 = (py+ph) % sh: a stride-1 gather oy = a + (py+ph-r0)/sh - r' over the sub-grid y = sh*a + py -- no structurally
-    // zero taps are multiplied, and it runs on the fast (buffer-addressed) kernel.
-    const int epc2 = epc_of(d->dtype);
-    const int cpt_full = pad_to(d->cout, epc2) / epc2;
-    const int wld_full = (d->kh * d->kw * cpt_full + KC - 1) / KC * KC;
-    for (int py = 0; py < d->sh; ++py)
-        for (int px = 0; px < d->sw; ++px) {
-            const int Ha = (d->h - py + d->sh - 1) / d->sh, Wa = (d->w - px + d->sw - 1) / d->sw;
-            if (Ha <= 0 || Wa <= 0) continue;
-            const int r0c = (py + d->ph) % d->sh, s0c = (px + d->pw) % d->sw;
-            const int khs = r0c < d->kh ? (d->kh - r0c + d->sh - 1) / d->sh : 0;
-            const int kws = s0c < d->kw ? (d->kw - s0c + d->sw - 1) / d->sw : 0;
-            ConvK c = k;
-            c.kh = khs > 0 && kws > 0 ? khs : 0; c.kw = khs > 0 && kws > 0 ? kws : 1;
-            c.ay = 1; c.by = (py + d->ph - r0c) / d->sh; c.cy = -1; c.divy = 1;
-            c.ax = 1; c.bx = (px + d->pw - s0c) / d->sw; c.cx = -1; c.divx = 1;
-            c.OH = Ha; c.OW = Wa; c.M = d->nb * Ha * Wa;
-            c.out_sy = d->sh; c.out_sx = d->sw; c.out_y0 = py; c.out_x0 = px; c.out_H = d->h; c.out_W = d->w;
-            c.remap = 1; c.wld = wld_full;
-            for (int rr = 0; rr < khs; ++rr)
-                for (int ss = 0; ss < kws; ++ss) c.wtap[rr * kws + ss] = (unsigned char)((r0c + d->sh * rr) * d->kw + (s0c + d->sw * ss));
-            if (x) {                                   // extra 1x1 source at the output pixel (din_conv_dgrad_x)
-                ConvK::Src& o = c.src[0];
-                o.in = x->dout; o.w = x->wpk_t; o.ld = x->ldo; o.coff = x->cooff;
-                o.cpt = pad_to(x->cout, epc2) / epc2;
-                o.wld = (o.cpt + KC - 1) / KC * KC;
-                o.in_bytes = (long long)d->nb * d->h * d->w * x->ldo * 2;
-                o.w_bytes = (long long)pad_to(d->cin, 256) * o.wld * 16;
-                c.xsteps = (o.cpt + KC - 1) / KC;
-            }
-            GatherPlan g = plan_gather(c.M, d->cout, d->cin, c.kh * c.kw, d->dtype, true);
-            if (int e = run_gather(c, g, d->dtype, workspace, workspace_bytes, as_stream(stream), "conv_dgrad(strided)")) return e;
+    return for_each_parity_class(d, [&](const ParityClass& pc) {
+        ConvK c = conv_k_of(d, 1, &pc);
+        bind(c);
+        if (x) {                                   // extra 1x1 source at the output pixel (din_conv_dgrad_x)
+            ConvK::Src& o = c.src[0];
+            o.in = x->dout; o.w = x->wpk_t; o.ld = x->ldo; o.coff = x->cooff;
+            o.cpt = pad_to(x->cout, epc) / epc;
+            o.wld = (o.cpt + KC - 1) / KC * KC;
+            o.in_bytes = (long long)d->nb * d->h * d->w * x->ldo * 2;
+            o.w_bytes = (long long)pad_to(d->cin, 256) * o.wld * 16;
+            c.xsteps = (o.cpt + KC - 1) / KC;
         }
-    return DIN_OK;
+        return run_gather(c, plan_launch(d, 1, &pc), d->dtype, workspace, workspace_bytes, st, "conv_dgrad(strided)");
+    });
 }
 
 int din_conv1x1_dgrad_multi(int nsrc, const din_conv_src* srcs, int dtype, int nb, int h, int w, int cin, int ldi, int cioff,
@@ -3653,28 +3604,18 @@ int din_conv1x1_dgrad_multi(int nsrc, const din_conv_src* srcs, int dtype, int n
     k.nsrc = nsrc;
     k.in = srcs[0].dout; k.w = srcs[0].wpk_t; k.in_bytes = k.src[0].in_bytes; k.w_bytes = k.src[0].w_bytes;
     k.Cin = srcs[0].cout; k.ldi = srcs[0].ldo; k.cioff = srcs[0].cooff;
-    GatherPlan g = plan_gather(k.M, 64, cin, 1, dtype);
-    if (g.bn == 256) g.bn = 128;
-    g.bm = 128; g.n_px_tiles = (k.M + 127) / 128; g.n_co_tiles = (cin + g.bn - 1) / g.bn;
+    // the reduction runs over the sources' k-steps, every source padded to whole k-steps; no tap remap, no split
     k.cpt = KC; k.Q = steps * KC; k.nk = steps; k.wld = k.src[0].wld;
-    k.splitk = 1; k.ks_per_split = steps; k.n_co_tiles = g.n_co_tiles; k.remap = 0; k.korder = 0;
+    GatherPlan g = plan_gather(k.M, 64, cin, 1, dtype);
+    g.ks_per_split = steps;
+    const GatherChoice c = choose_gather(k, g, dtype);
+    set_plan_fields(k, c);
     if (DIN_OPT("DIN_DEBUG_PLAN"))
         fprintf(stderr, "[din] conv1x1_dgrad_multi M=%d nsrc=%d couts=%d,%d,%d,%d ld=%d,%d,%d,%d coff=%d,%d,%d,%d cin=%d flags=%d regw=%d\n", k.M, nsrc, srcs[0].cout,
                 nsrc > 1 ? srcs[1].cout : 0, nsrc > 2 ? srcs[2].cout : 0, nsrc > 3 ? srcs[3].cout : 0, srcs[0].ldo, nsrc > 1 ? srcs[1].ldo : 0,
                 nsrc > 2 ? srcs[2].ldo : 0, nsrc > 3 ? srcs[3].ldo : 0, srcs[0].cooff, nsrc > 1 ? srcs[1].cooff : 0, nsrc > 2 ? srcs[2].cooff : 0,
-                nsrc > 3 ? srcs[3].cooff : 0, cin, flags, (int)din_gather::conv1x1_regw_eligible(k, dtype));
-    if (din_gather::conv1x1_regw_eligible(k, dtype)) {
-        if (din_gather::launch_conv1x1_regw(k, as_stream(stream))) DIN_FAIL(DIN_E_LAUNCH, "conv1x1_dgrad_multi: conv1x1_regw launch failed");
-        return DIN_OK;
-    }
-    if (din_gather::conv1x1_stream_eligible(k, dtype)) {
-        if (din_gather::launch_conv1x1_stream(k, as_stream(stream))) DIN_FAIL(DIN_E_LAUNCH, "conv1x1_dgrad_multi: conv1x1_stream launch failed");
-        return DIN_OK;
-    }
-    if (dtype == DIN_F32) launch_gather<float>(k, g.n_px_tiles, 128, g.bn, as_stream(stream));
-    else launch_gather<bf16_t>(k, g.n_px_tiles, 128, g.bn, as_stream(stream));
-    DIN_CHECK_LAUNCH("conv1x1_dgrad_multi");
-    return DIN_OK;
+                nsrc > 3 ? srcs[3].cooff : 0, cin, flags, (int)(c.family == GATHER_REGW));
+    return launch_choice(k, c, dtype, as_stream(stream), "conv1x1_dgrad_multi");
 }
 
 int din_conv_wgrad(const din_conv_desc* d, const void* in, const void* dout, float* dw, float* dbias, const float* scale,

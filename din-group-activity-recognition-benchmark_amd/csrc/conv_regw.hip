@@ -346,8 +346,8 @@ bool conv1x1_regw_eligible(const ConvK& k, int dtype) {
         return false;
     if (k.flags & DIN_CONV_ACCUM) return false;
     if (k.Cout <= 0 || k.Cout > 4 * 64 * (regw_ksteps(k) <= 10 ? 2 : 3) || k.Cout % 8 != 0 || k.ldo % 8 != 0 || k.cooff % 8 != 0) return false;
-    if ((k.flags & DIN_CONV_MASK) && (!k.mask || k.ldm % 8 != 0 || k.moff % 8 != 0 || (long long)k.M * k.ldm * 2 >= 0x7fffffffll || k.csplit > 0)) return false;
-    if (k.csplit > 0 && (k.csplit % 8 != 0 || k.ldo2 % 8 != 0 || k.cooff2 % 8 != 0 || !k.out2)) return false;
+    if ((k.flags & DIN_CONV_MASK) && (k.ldm % 8 != 0 || k.moff % 8 != 0 || (long long)k.M * k.ldm * 2 >= 0x7fffffffll || k.csplit > 0)) return false;
+    if (k.csplit > 0 && (k.csplit % 8 != 0 || k.ldo2 % 8 != 0 || k.cooff2 % 8 != 0)) return false;
     if (!regw_ksteps(k)) return false;
     const int ns = k.nsrc > 0 ? k.nsrc : 1;
     for (int s = 0; s < ns; ++s) {

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Which kernel every forward / data-gradient convolution of the two backbones resolves to, as din_conv_kernel_tile /
+din_conv_kernel_variant report it (no GPU needed): one line per case,
+
+    <backbone> <dtype> nb<frames> <h>x<w> c<cin>><cout> k<kh>x<kw> s<stride> p<ph>,<pw> ld<ldi>+<cioff>><ldo>+<cooff> [u8] which=<0|1> <option>
+        ->  bm bn flags workspace_bytes(0) workspace_bytes(1)
+
+Cases: every distinct conv descriptor of the Inception-v3 trunk (up to Mixed_6e, with the channel-offset views and the fused sibling
+groups nhwc.py lays out) and of VGG16, at 12 / 24 / 96 frames of 720x1280 and at the small test geometry, both dtypes, plus one view
+per kernel family whose channel offsets are not multiples of 8; each with no option set and with every selection option of
+csrc/conv_igemm.hip set alone to each value its comment documents.
+
+The reporter answers from the launcher's own selection function, so two builds that print the same table launch the same kernels:
+
+    python tools/conv_dispatch_table.py > new.txt;  DIN_LIB_PATH=<other build>/libdin_hip.so python tools/conv_dispatch_table.py > old.txt
+
+The full table has ~47 000 lines.  --summary prints what profiles/conv_dispatch_table.txt holds: the no-option decision only, at 96 frames of
+720x1280 and at the small test geometry, forward and data gradient on one line (bm bn flags / bm bn flags  workspace bytes)."""
+import argparse
+import ctypes as C
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+OPTIONS = [
+    ("DIN_CONV_BN", ("96", "128", "160", "192", "256")), ("DIN_CONV_TILE", ("128", "256")), ("DIN_CONV_PIPE", ("0", "1", "4", "8")),
+    ("DIN_CONV_FASTK", ("0",)), ("DIN_CONV_LANEK", ("0", "2")), ("DIN_CONV_KORDER", ("0",)), ("DIN_CONV_SMALL", ("0",)),
+    ("DIN_CONV_HALO", ("0", "2")), ("DIN_CONV_STREAM", ("0", "2")), ("DIN_CONV_STREAM_WIDE", ("0",)),
+    ("DIN_CONV_STREAM_MINPIX", ("32768",)), ("DIN_CONV_STREAM_BN", ("64", "96", "192")), ("DIN_CONV_REGW", ("0", "2")),
+    ("DIN_CONV_REGW_SHORT", ("0", "2")), ("DIN_CONV_REGW_MINPIX", ("32768",)), ("DIN_CONV_WAVEGRID", ("24",)),
+    ("DIN_CONV_ONESTAGE", ("0",)), ("DIN_CONV_SMALL_WAVES", ("4",)), ("DIN_CONV_SMALL_NBUF8", ("2",)), ("DIN_CONV_SMALL_EPI", ("0",)),
+    ("DIN_GATHER_PIPE", ("1", "2")), ("DIN_HALO_WAVES", ("8",)),
+]
+GEOMETRIES = [(12, 720, 1280), (24, 720, 1280), (96, 720, 1280), (6, 139, 203)]
+FIELDS = ("cin", "h", "w", "cout", "oh", "ow", "kh", "kw", "sh", "sw", "ph", "pw", "ldi", "cioff", "ldo", "cooff", "in_u8")
+
+
+def descriptors(L, nhwc, backbone, nb, h, w, dt):
+    """the distinct conv descriptors of one backbone graph, in graph order"""
+    from din_amd.backbone import backbone as B
+    net = (B.MyInception_v3 if backbone == "inv3" else B.MyVGG16)(compute_dtype="bf16" if dt == L.DIN_BF16 else "fp32")
+    g = net.build_graph(h, w, dt)
+    out = []
+    for i, op in enumerate(g.ops):
+        if op.kind != "conv":
+            continue
+        first = op.src.tid == g.input_tid
+        d = nhwc._pooled_descs(g, op, nb, dt)[0] if op.pooled is not None else nhwc._conv_desc(g, op, nb, dt, g.cin_image if first else None)
+        out.append(d)
+        if first and dt == L.DIN_BF16:                     # the image layer on raw uint8 frames
+            u = nhwc._copy_desc(d)
+            u.in_u8, u.ldi, u.cioff = 1, 8, 0
+            out.append(u)
+    for idx in g.fwd_groups:                               # fused siblings: one launch over the concatenated filter bank
+        d = nhwc._copy_desc(out_of(g, nhwc, idx[0], nb, dt))
+        d.cout = sum(g.ops[j].dst.c for j in idx)
+        d.ldo, d.cooff = d.cout, 0
+        out.append(d)
+    return out
+
+
+def out_of(g, nhwc, i, nb, dt):
+    return nhwc._conv_desc(g, g.ops[i], nb, dt)
+
+
+def misaligned(L, nhwc, descs):
+    """one view per kernel family (by the shapes each family serves) moved to channel offsets that are multiples of 4 only"""
+    def family(d):
+        if d.in_u8 or d.sh != 1:
+            return None
+        if d.kh == 1 and d.kw == 1:
+            return "regw" if d.cin >= 640 else ("stream" if d.cin <= 288 else "tile1x1")
+        if d.kh == 3 and d.kw == 3:
+            return "small" if d.cin in (32, 64) and d.cout <= 64 else "halo"
+        return "tile"
+    seen, out = set(), []
+    for d in descs:
+        fam = family(d)
+        if fam is None or fam in seen:
+            continue
+        seen.add(fam)
+        m = nhwc._copy_desc(d)
+        m.ldi, m.cioff, m.ldo, m.cooff = d.ldi + 8, d.cioff + (4 if d.dtype == L.DIN_F32 else 8), d.ldo + 8, d.cooff + 4
+        out.append(m)
+    return out
+
+
+def report(lib, d, which):
+    bm, bn, fl = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    assert lib.din_conv_kernel_tile(C.byref(d), which, C.byref(bm), C.byref(bn)) == 0
+    assert lib.din_conv_kernel_variant(C.byref(d), which, C.byref(fl)) == 0
+    return f"{bm.value} {bn.value} {fl.value} {lib.din_conv_workspace_bytes(C.byref(d), 0)} {lib.din_conv_workspace_bytes(C.byref(d), 1)}"
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--summary", action="store_true", help="no-option decisions at 96 frames and at the small geometry, one line per descriptor")
+    args = ap.parse_args()
+    from din_amd import _lib as L, nhwc
+    lib = L.load()
+    for name, _ in OPTIONS:
+        L.set_option(name, None)
+    cases = []
+    for backbone in ("inv3", "vgg16"):
+        for dt, dtn in ((L.DIN_BF16, "bf16"), (L.DIN_F32, "fp32")):
+            for nb, h, w in GEOMETRIES:
+                descs = descriptors(L, nhwc, backbone, nb, h, w, dt)
+                seen = set()
+                for d in descs + misaligned(L, nhwc, descs):
+                    key = tuple(getattr(d, f) for f in FIELDS)
+                    if key not in seen:
+                        seen.add(key)
+                        cases.append((f"{backbone} {dtn} nb{nb} {d.h}x{d.w} c{d.cin}>{d.cout} k{d.kh}x{d.kw} s{d.sh} p{d.ph},{d.pw} "
+                                      f"ld{d.ldi}+{d.cioff}>{d.ldo}+{d.cooff}{' u8' if d.in_u8 else ''}", d))
+    if args.summary:
+        for label, d in cases:
+            if d.nb in (96, 6):
+                f, g = report(lib, d, 0).split(), report(lib, d, 1).split()
+                print(f"{label}  ->  {' '.join(f[:3])} / {' '.join(g[:3])}  {f[3]} {f[4]}")
+        return
+    for opt, val in [(None, None)] + [(o, v) for o, vals in OPTIONS for v in vals]:
+        if opt:
+            L.set_option(opt, val)
+        try:
+            for label, d in cases:
+                for which in (0, 1):
+                    print(f"{label} which={which} {opt + '=' + val if opt else '-'}  ->  {report(lib, d, which)}")
+        finally:
+            if opt:
+                L.set_option(opt, None)
+
+
+if __name__ == "__main__":
+    main()
