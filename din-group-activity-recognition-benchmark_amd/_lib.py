@@ -125,6 +125,10 @@ SIGNATURES: Dict[str, tuple] = {
     "din_basenet_head_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "din_arg_graph_fwd": (_I, [_P, _P, _P, _L, _P, _I, _F, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
     "din_arg_graph_bwd": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _L, _P]),
+    "din_actor_position_fwd": (_I, [_P, _P, _P, _F, _F, _F, _F, _I, _I, _I, _I, _I, _P, _P]),
+    "din_actor_position_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "din_actor_attn_fwd": (_I, [_P, _P, _P, _L, _P, _P, _P, _F, _F, _U64, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "din_actor_attn_bwd": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P, _F, _U64, _P, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P]),
     "din_axpby": (_I, [_P, _P, _P, _F, _F, _L, _P]),
     "din_mask_actors": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "din_scale_by_param": (_I, [_P, _P, _I, _P, _I, _L, _P]),

@@ -20,7 +20,7 @@ _DEFAULTS = dict(
     set_bn_eval=False, inference_module_name="dynamic_volleyball",
     stride=1, ST_kernel_size=3, dynamic_sampling=True, sampling_ratio=[1, 3], group=1, scale_factor=True, beta_factor=True,
     load_backbone_stage2=False, parallel_inference=False, hierarchical_inference=False, lite_dim=None, num_DIM=1,
-    load_stage2model=False, stage2model=None,
+    load_stage2model=False, stage2model=None, temporal_pooled_first=False,
     backbone_dtype="fp32", hier_dropout_p=0.5,
 )
 

@@ -21,6 +21,7 @@ import torch.nn as nn
 from . import ops
 from .backbone.backbone import MyInception_v3, MyVGG16
 from .infer_module.ARG_infer_module import GCN_Module
+from .infer_module.AT_infer_module import Actor_Transformer, Embfeature_PositionEmbedding
 from .infer_module.dynamic_infer_module import (Dynamic_Person_Inference, Hierarchical_Dynamic_Inference,
                                                 Multi_Dynamic_Inference)
 from .infer_module.positional_encoding import Context_PositionEmbeddingSine
@@ -357,4 +358,41 @@ class ARG_volleyball(_DynamicBase):
             B = B // 3
             scores = ops.AxpbyFunction.apply(ops.AxpbyFunction.apply(scores.reshape(B, 3, -1)[:, 0], scores.reshape(B, 3, -1)[:, 1], 1.0, 1.0),
                                              scores.reshape(B, 3, -1)[:, 2], 1.0 / 3.0, 1.0 / 3.0)
+        return {"activities": scores}
+
+
+class AT_volleyball(_DynamicBase):
+    """the Actor-Transformer baseline for the volleyball dataset (reference infer_model.py:736-867): the shared trunk, the box-centre sine
+    embedding, one Actor_Transformer block over the N actors of every frame (of every clip, after the mean over T, with
+    `cfg.temporal_pooled_first`), max over N, fc_activities, mean over T.  Same constructor, `forward((images, boxes)) -> {'activities':
+    [B, A]}`, `loadmodel` and state_dict keys (backbone.*, fc_emb_1, nl_emb_1, AT.*, fc_activities, fc_actions), so the reference's
+    checkpoints load unchanged.
+
+    Deliberate differences from the reference: `fc_actions` is created, initialised and saved but has requires_grad False and is not
+    evaluated -- the reference computes its scores and throws them away (:840-851), so it never receives a gradient there either and
+    Adam skips it; here the optimiser and the all-reduce buckets (parallel.py) take only parameters that will receive one.  The three
+    dropout masks are the counter hash of the other models here (three seeds per step from `_dropout_seed`), not the host RNG stream.
+    No torch.cuda.empty_cache() per step (:836).  'res18' / 'vgg19' / 'alex' are out of scope (make_backbone)."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        NFB = cfg.num_features_boxes
+        self._build_trunk(cfg)
+        self.PE = Embfeature_PositionEmbedding(cfg=cfg, num_pos_feats=NFB // 2, pool_t=bool(cfg.temporal_pooled_first))   # :770
+        self.AT = Actor_Transformer(in_dim=NFB, temporal_pooled_first=cfg.temporal_pooled_first)       # :771
+        self.fc_activities = nn.Linear(NFB, cfg.num_activities)
+        self.fc_actions = nn.Linear(NFB, cfg.num_actions)
+        self._init_linears()
+        self.fc_actions.requires_grad_(False)
+
+    def forward(self, batch_data):
+        images_in, boxes_in = batch_data
+        cfg = self.cfg
+        B, T, N = images_in.shape[0], images_in.shape[1], cfg.num_boxes
+        x = self._embed(images_in, boxes_in, N)                                           # [B,T,N,NFB]  (:797-831)
+        x = self.PE(x, boxes_in.reshape(B * T * N, 4))                                    # :834 (+ the mean over T of :125-126)
+        states = self.AT(x, seeds=tuple(self._dropout_seed() for _ in range(3)))          # :835
+        s = states.reshape(B, 1 if cfg.temporal_pooled_first else T, N, -1)
+        scores = ops.HeadFunction.apply(s, self.fc_activities.weight, self.fc_activities.bias, None)   # :843-857
         return {"activities": scores}

@@ -654,6 +654,110 @@ class ArgGraphFunction(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# Actor-Transformer block (AT baseline)
+# ------------------------------------------------------------------------------------------------
+def actor_attn_workspace_floats(g: int, c: int) -> int:
+    """scratch din_actor_attn_bwd asks for (include/din_hip.h): the per-group partials of d gamma / d beta"""
+    return g * 2 * c
+
+
+class ActorPositionFunction(torch.autograd.Function):
+    """x [B, T, N, C], boxes [B, T, N, 4] (feature px), dim_t fp32 [C/2] -> x + PE(box centre) [B, T, N, C], or its mean over T [B, N, C]
+    when pool_t -- reference AT_infer_module.py:66-96 (+ torch.mean(x, dim=1) of :125-126).  The backward is the identity on x (g / T
+    broadcast over the frames when pooled); the boxes get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, boxes, dim_t, image_size, out_size, pool_t: bool):
+        lib = L.load()
+        x, dim_t = x.contiguous(), dim_t.contiguous()
+        boxes = boxes.detach().float().contiguous()
+        require_gpu(x, boxes, dim_t)
+        b, t, n, c = x.shape
+        assert boxes.numel() == b * t * n * 4 and dim_t.numel() * 2 == c, (x.shape, boxes.shape, dim_t.shape)
+        y = torch.empty((b, n, c) if pool_t else (b, t, n, c), dtype=torch.float32, device=x.device)
+        L.check(lib.din_actor_position_fwd(_ptr(x), _ptr(boxes), _ptr(dim_t), float(image_size[1]), float(image_size[0]), float(out_size[1]),
+                                           float(out_size[0]), b, t, n, c, int(bool(pool_t)), _ptr(y), _stream()), "actor_position_fwd")
+        ctx.dims = (b, t, n, c, bool(pool_t))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        b, t, n, c, pool_t = ctx.dims
+        if not pool_t:
+            return gy, None, None, None, None, None                    # (pass-through: no launch)
+        lib = L.load()
+        gy = gy.contiguous()
+        gx = torch.empty((b, t, n, c), dtype=torch.float32, device=gy.device)
+        L.check(lib.din_actor_position_bwd(_ptr(gy), b, t, n, c, 1, _ptr(gx), _stream()), "actor_position_bwd")
+        return gx, None, None, None, None, None
+
+
+class ActorAttentionFunction(torch.autograd.Function):
+    """proj [G, N, 3*C] = X [Q_W | K_W | V_W]^T, x [G, N, C], gamma / beta [C] -> (LayerNorm(x + dropout(softmax(Q K^T / sqrt(C)) V)) [G, N, C],
+    att [G, N, N]) -- reference AT_infer_module.py:130-138 after its three Linear layers.  The mask is the counter hash of (seed, element
+    index), regenerated in the backward.  want_keep: also return the keep mask (bool [G, N, C]), for inspection.
+    proj may be a view of rows padded to a multiple of 4 floats (the first 3*C columns of a wider buffer): it is read in place through its
+    row stride, and its gradient comes back with the same row stride."""
+
+    @staticmethod
+    def _rows_in_place(proj, n):
+        """True if proj [G, N, 3*C] can be handed to the kernels as it is: unit column stride, one row stride ld (a multiple of 4) for all rows"""
+        return proj.stride(2) == 1 and proj.stride(1) % 4 == 0 and proj.stride(1) >= proj.shape[2] and proj.stride(0) == n * proj.stride(1) \
+            and proj.data_ptr() % 16 == 0
+
+    @staticmethod
+    def forward(ctx, proj, x, gamma, beta, drop_p: float, seed: int, want_keep: bool = False):
+        lib = L.load()
+        x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
+        g, n, c = x.shape
+        require_gpu(x, gamma, beta)
+        if not ActorAttentionFunction._rows_in_place(proj, n):
+            proj = proj.contiguous()
+            require_gpu(proj)
+        elif not proj.is_cuda:
+            require_gpu(proj.contiguous())                              # (raises: no CPU fallback)
+        assert tuple(proj.shape) == (g, n, 3 * c) and gamma.numel() == c == beta.numel(), (proj.shape, x.shape, gamma.shape)
+        dev = x.device
+        out = torch.empty((g, n, c), dtype=torch.float32, device=dev)
+        att = torch.empty((g, n, n), dtype=torch.float32, device=dev)
+        stats = torch.empty((g * n, 2), dtype=torch.float32, device=dev)
+        keep = torch.empty((g, n, c), dtype=torch.uint8, device=dev) if want_keep else None
+        base, ld = proj.data_ptr(), proj.stride(1)
+        L.check(lib.din_actor_attn_fwd(base, base + 4 * c, base + 8 * c, ld, _ptr(x), _ptr(gamma), _ptr(beta), 1e-5, float(drop_p), int(seed),
+                                       _ptr(SEED_OFFSET), g, n, c, _ptr(out), _ptr(att), _ptr(stats), _ptr(keep), _stream()), "actor_attn_fwd")
+        ctx.save_for_backward(proj, x, gamma, att, stats)
+        ctx.args = (float(drop_p), int(seed))
+        ctx.seed_offset = SEED_OFFSET
+        ctx.mark_non_differentiable(att)
+        if want_keep:
+            keep = keep.view(torch.bool)
+            ctx.mark_non_differentiable(keep)
+            return out, att, keep
+        return out, att
+
+    @staticmethod
+    def backward(ctx, gout, *_):
+        lib = L.load()
+        proj, x, gamma, att, stats = ctx.saved_tensors
+        drop_p, seed = ctx.args
+        g, n, c = x.shape
+        gout = gout.contiguous()
+        ld = proj.stride(1)
+        # same row stride as proj; with padded rows (ld > 3*c) the padding columns stay uninitialised: they are outside the returned view, so no
+        # consumer of the gradient can read them (on the model path ld == 3*c and the view is the whole buffer)
+        dproj = torch.empty((g, n, ld), dtype=torch.float32, device=x.device)[..., :3 * c]
+        dx = torch.empty_like(x)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        nws = actor_attn_workspace_floats(g, c)
+        ws = torch.empty(nws, dtype=torch.float32, device=x.device)
+        base, gbase = proj.data_ptr(), dproj.data_ptr()
+        L.check(lib.din_actor_attn_bwd(_ptr(gout), base, base + 4 * c, base + 8 * c, ld, _ptr(x), _ptr(gamma), _ptr(att), _ptr(stats), drop_p,
+                                       seed, _ptr(ctx.seed_offset), g, n, c, gbase, gbase + 4 * c, gbase + 8 * c, ld, _ptr(dx), _ptr(dgamma),
+                                       _ptr(dbeta), _ptr(ws), nws, _stream()), "actor_attn_bwd")
+        return dproj, dx, dgamma, dbeta, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
 # layout views for API parity (NOT on the training path)
 # ------------------------------------------------------------------------------------------------
 class NHWCToNCHWFunction(torch.autograd.Function):

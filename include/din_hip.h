@@ -477,6 +477,44 @@ int din_arg_graph_bwd(const float* g_out, const float* theta, const float* phi, 
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Actor-Transformer block (the AT baseline): box-centre position embedding and single-head actor self-attention.
+ *
+ * Position (reference infer_module/AT_infer_module.py:52-96 Embfeature_PositionEmbedding): x fp32 [b][t][n][c], boxes fp32 [b][t][n][4]
+ *   (x1, y1, x2, y2) in feature px, dim_t fp32 [c/2] = temperature ** (2 * (i // 2) / (c/2)), built by the caller in fp32 exactly as the
+ *   reference builds it (:82-83).  Centre (x1 + x2) / 2 * img_w / out_w, (y1 + y2) / 2 * img_h / out_h (:77-80); column k of the first half
+ *   holds sin (k even) or cos (k odd) of centre_x / dim_t[k], the second half the same of centre_y (:85-90); true fp32 division and
+ *   full-precision sinf / cosf (the arguments reach 1280 rad).  y = PE + x [b][t][n][c]; with pool_t != 0 y [b][n][c] is the mean of that
+ *   over t (frames added in order, then divided by t): torch.mean(x, dim=1) of AT_infer_module.py:125-126 in the same pass.
+ *   Backward: gx [b][t][n][c] = gy, or gy [b][n][c] / t when pool_t; the boxes get no gradient.
+ *   Limits: b, t, n >= 1; c a positive multiple of 4; else DIN_E_ARG, nothing is read.  One launch each.
+ *
+ * Attention (AT_infer_module.py:130-138 Actor_Transformer.forward after the Q_W / K_W / V_W Linear layers, up to layernorm1): g groups of
+ *   n <= 16 actors (the b*t frames, or the b clips after the t-mean).  q, k, v fp32 [g*n][c] with ROW STRIDE ld floats: three column blocks
+ *   of ONE projection output X [Q_W | K_W | V_W]^T, as theta / phi / y of din_arg_graph_fwd; x fp32 [g][n][c] the block's input (residual).
+ *   A = softmax over j of (q k^T / sqrt(c)), the row maximum subtracted;  Z = x + dropout(A v);  out = LayerNorm over c (Z) * gamma + beta.
+ *   dropout: the counter-based keep mask of din_layernorm_* / din_act_dropout_* on the flat element index of out, scale 1/(1-p), drop_p = 0
+ *   disables; seed_offset (nullable, device) as there.  keep (nullable) uint8 [g][n][c]: the keep mask, for inspection.
+ *   Outputs: out [g][n][c]; att [g][n][n] = A; stats [g*n][2] = (mean, rstd); att and stats are all the backward keeps (Z and the mask are
+ *   recomputed).
+ *   Backward: g_out [g][n][c] -> d_q, d_k, d_v (row stride ld_grad, every element of the three blocks written: the projection's data and
+ *   weight gradients stay one contraction each), d_x [g][n][c] = gradient of the residual input, d_gamma / d_beta [c] overwritten:
+ *   per-group partials in ws, then one reduce launch that adds the groups in order.  ws: ws_floats >= g * 2 * c.
+ *   Limits: 1 <= n <= 16; c, ld, ld_grad multiples of 4, ld >= c; 0 <= drop_p < 1; q / k / v / x / out, g_out and the gradients 16-byte
+ *   aligned, every other float pointer 4-byte aligned (seed_offset 8); no null pointer (keep and seed_offset excepted); else DIN_E_ARG, nothing is read or written.
+ *   Forward 1 launch (one workgroup per group), backward 2; deterministic (fixed-order sums, no atomics), fp32 throughout.
+ * ---------------------------------------------------------------------------------------------- */
+int din_actor_position_fwd(const float* x, const float* boxes, const float* dim_t, float img_w, float img_h, float out_w, float out_h,
+                           int b, int t, int n, int c, int pool_t, float* y, void* stream);
+int din_actor_position_bwd(const float* gy, int b, int t, int n, int c, int pool_t, float* gx, void* stream);
+int din_actor_attn_fwd(const float* q, const float* k, const float* v, int64_t ld, const float* x, const float* gamma, const float* beta,
+                       float eps, float drop_p, uint64_t seed, const uint64_t* seed_offset, int g, int n, int c, float* out, float* att,
+                       float* stats, uint8_t* keep, void* stream);
+int din_actor_attn_bwd(const float* g_out, const float* q, const float* k, const float* v, int64_t ld, const float* x, const float* gamma,
+                       const float* att, const float* stats, float drop_p, uint64_t seed, const uint64_t* seed_offset, int g, int n, int c,
+                       float* d_q, float* d_k, float* d_v, int64_t ld_grad, float* d_x, float* d_gamma, float* d_beta, float* ws,
+                       int64_t ws_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Small helpers used by the host mirror
  * ---------------------------------------------------------------------------------------------- */
 /* out = alpha*x + beta*y (fp32, elementwise) -- ratio mean / beta-weighted sum (:144-147), residual sums */
