@@ -295,6 +295,10 @@ int fill(WalkK& p, int cp, int b, int t, int n, int c, int kh, int kw, int ratio
     DIN_REQUIRE(b > 0 && t > 0 && n > 0 && c > 0 && kh > 0 && kw > 0 && ratio > 0, "din_walk: bad shape");
     DIN_REQUIRE(kh * kw <= MAXK2, "din_walk: ST kernel larger than %d taps unsupported", MAXK2);
     DIN_REQUIRE(cp >= (scale_factor ? 3 : 2) * kh * kw, "din_walk: pred pixel stride too small");
+    // an even extent pads (k-1)/2*ratio rows but starts its lattice at floor(-(k-1)*ratio/2), one row further out: the reference's own
+    // gather then indexes outside its padded map (plain_infer_ratio :163-167), so the case is undefined there.  The walk clamps its
+    // corners into the tile; the plain gather reads the lattice point itself and would leave it.
+    DIN_REQUIRE(!plain || ((kh & 1) && (kw & 1)), "din_walk: plain gather needs odd ST kernel extents (%d x %d)", kh, kw);
     p.cp = cp; p.b = b; p.t = t; p.n = n; p.c = c; p.kh = kh; p.kw = kw; p.ratio = ratio; p.scale_factor = scale_factor;
     p.pt = (kh - 1) / 2 * ratio; p.pl = (kw - 1) / 2 * ratio;
     p.hp = t + 2 * p.pt; p.wp = n + 2 * p.pl; p.k2 = kh * kw;

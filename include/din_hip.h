@@ -399,7 +399,8 @@ int din_counter_add(uint64_t* counter, uint64_t delta, void* stream);
  *   The forward needs ONE padded (t+2pt) x (n+2pl) x 64-channel fp32 tile in LDS (<= 160 KiB, else DIN_E_ARG); the backward keeps a
  *   second one for the feature gradient when it fits and scatters into dx with global atomics when it does not.                 */
 /*   plain != 0: no walk -- S_k is the feature at lattice point k itself (plain_infer_ratio :154-181 and the relation half of
- *   parallel_infer :285-298); the offset channels of pred are ignored and receive no gradient.
+ *   parallel_infer :285-298); the offset channels of pred are ignored and receive no gradient.  kh and kw must be odd (else
+ *   DIN_E_ARG): with an even extent the reference's lattice leaves its own padded map.
  *   clamp (nullable HOST array of 4 ints {iy_max, ix_max, py_max, px_max}): clamp maxima of the corner indices and of the sampling
  *   position, for parallel_infer's walk half, which clamps with person_mat_shape (T + 2 ratio - 1, N + 2 ratio - 1; T + 2 ratio,
  *   N + 2 ratio: :307-317) instead of the padded grid; index maxima are additionally held inside the padded grid.              */
