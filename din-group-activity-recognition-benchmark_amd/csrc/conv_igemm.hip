@@ -24,6 +24,8 @@
 #include <unordered_map>
 #include <mutex>
 #include <stdlib.h>
+#include <string.h>
+#include <string>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -2618,7 +2620,8 @@ static bool conv_small_wanted() { return opt_int(DIN_OPT("DIN_CONV_SMALL"), 1) !
 struct GatherPlan { int bm, bn, n_co_tiles, n_px_tiles, cpt, Q, nk, splitk, ks_per_split, cout_pad; int64_t ws_bytes; };
 
 // geometry of a gather launch whose reduction runs over `cred` channels x taps and produces `cprod` channels
-GatherPlan plan_gather(int M, int cred, int cprod, int taps, int dtype, bool strided_out = false) {
+// retile: choose_gather will move the launch to the generic kernel (more than 32 taps, a strided dgrad not split by parity)
+GatherPlan plan_gather(int M, int cred, int cprod, int taps, int dtype, bool strided_out = false, bool retile = false) {
     GatherPlan g;
     int epc = epc_of(dtype);
     g.cpt = pad_to(cred, epc) / epc;
@@ -2676,7 +2679,11 @@ GatherPlan plan_gather(int M, int cred, int cprod, int taps, int dtype, bool str
     g.ks_per_split = (g.nk + g.splitk - 1) / g.splitk;
     if (g.ks_per_split < 1) g.ks_per_split = 1;                    // nk == 0: launch still runs its epilogue (zeros / accumulate)
     g.splitk = g.nk > 0 ? (g.nk + g.ks_per_split - 1) / g.ks_per_split : 1;
-    g.ws_bytes = g.splitk > 1 ? (int64_t)g.splitk * M * (g.n_co_tiles * g.bn) * 4 : 0;
+    // partial sums: [splitk][M][filter tiles x tile].  A launch that leaves the buffer-addressed kernels is re-tiled by choose_gather to 128
+    // filters and writes rows of that width (a 72-filter 7x7 launch planned on a 96-filter tile wrote 128-filter rows past a workspace
+    // sized for 96); every other plan keeps its own tile's width (a split 256-pixel plan falls back to 128 filters: never wider)
+    const int ws_cols = (retile && g.bn != 64 && g.bn != 128) ? g.cout_pad : g.n_co_tiles * g.bn;
+    g.ws_bytes = g.splitk > 1 ? (int64_t)g.splitk * M * ws_cols * 4 : 0;
     return g;
 }
 
@@ -3229,8 +3236,11 @@ int run_gather(ConvK& k, GatherPlan g0, int dtype, void* workspace, int64_t ws_b
                 k.M, k.NB, k.H, k.W, k.Cin, k.Cout, k.kh, k.kw, k.ay, k.cy, g.bm, g.bn, g.splitk, k.korder, k.remap, k.flags, dtype, (int)c.family);
     if (k.csplit > 0 && (c.family == GATHER_GENERIC || g.splitk > 1)) DIN_FAIL(DIN_E_ARG, "%s: two destinations need the staged epilogue of the buffer-addressed kernel", what);
     if (g.splitk > 1) {
-        if (ws_bytes < g.ws_bytes || workspace == nullptr)
-            DIN_FAIL(DIN_E_WORKSPACE, "%s: workspace %lld < %lld bytes", what, (long long)ws_bytes, (long long)g.ws_bytes);
+        // what the chosen (possibly re-tiled) kernel writes: never more than the plan reported, or the launch is refused
+        const int64_t written = (int64_t)g.splitk * k.M * g.n_co_tiles * g.bn * 4;
+        const int64_t need = written > g.ws_bytes ? written : g.ws_bytes;
+        if (ws_bytes < need || workspace == nullptr)
+            DIN_FAIL(DIN_E_WORKSPACE, "%s: workspace %lld < %lld bytes", what, (long long)ws_bytes, (long long)need);
         k.partial = reinterpret_cast<float*>(workspace);
     }
     DIN_REQUIRE(!k.u8 || c.family == GATHER_SMALL, "%s: in_u8 is only served by the image-layer kernel (see din_conv_accepts_u8)", what);
@@ -3267,8 +3277,10 @@ static int for_each_parity_class(const din_conv_desc* d, F f) {
 
 // plan of the launch `which` (0 forward, 1 data gradient; pc: one parity class of a strided data gradient)
 static GatherPlan plan_launch(const din_conv_desc* d, int which, const ParityClass* pc = nullptr) {
-    if (which == 0) return plan_gather(d->nb * d->oh * d->ow, d->cin, d->cout, d->kh * d->kw, d->dtype);
-    if (!pc) return plan_gather(d->nb * d->h * d->w, d->cout, d->cin, d->kh * d->kw, d->dtype);
+    // (the launches choose_gather calls !fast: more than 32 taps, or a data gradient that divides by its stride)
+    const bool retile = d->kh * d->kw > 32 || (which == 1 && !pc && (d->sh > 1 || d->sw > 1));
+    if (which == 0) return plan_gather(d->nb * d->oh * d->ow, d->cin, d->cout, d->kh * d->kw, d->dtype, false, retile);
+    if (!pc) return plan_gather(d->nb * d->h * d->w, d->cout, d->cin, d->kh * d->kw, d->dtype, false, retile);
     return plan_gather(d->nb * pc->Ha * pc->Wa, d->cout, d->cin, pc->khs * pc->kws, d->dtype, true);
 }
 
@@ -3323,6 +3335,70 @@ static GatherChoice canonical_choice(const din_conv_desc* d, int which) {
     ConvK k = conv_k_of(d, which, parity ? &first : nullptr);
     if (which == 1) { k.flags = DIN_CONV_MASK; k.ldm = d->ldi; k.moff = d->cioff; }
     return choose_gather(k, plan_launch(d, which, parity ? &first : nullptr), d->dtype);
+}
+
+
+// The launches din_conv_fwd (which 0) / din_conv_dgrad (which 1) make for a descriptor, flags and mask view, in launch order:
+// f(argument block without pointers, plan, what) per launch -- a strided data gradient: one per non-empty parity class.  The entry points
+// bind their pointers and launch from here; din_conv_kernel_names names the kernels from here.
+template <typename F>
+static int for_each_launch(const din_conv_desc* d, int which, int flags, int ldm, int moff, F f) {
+    if (which == 0) {
+        ConvK k = conv_k_of(d, 0);
+        k.flags = flags;
+        return f(k, plan_launch(d, 0), "conv_fwd");
+    }
+    if (!dgrad_by_parity(d)) {
+        ConvK k = conv_k_of(d, 1);
+        k.flags = flags; k.ldm = ldm; k.moff = moff;
+        return f(k, plan_launch(d, 1), "conv_dgrad");
+    }
+    return for_each_parity_class(d, [&](const ParityClass& pc) {
+        ConvK c = conv_k_of(d, 1, &pc);
+        c.flags = flags; c.ldm = ldm; c.moff = moff;
+        return f(c, plan_launch(d, 1, &pc), "conv_dgrad(strided)");
+    });
+}
+
+// the kernels launch_choice / run_gather launch for a choice, spelled as their instantiations: one line each, appended to `out`.
+// k: the argument block with its plan fields set (set_plan_fields)
+static void append_kernel_names(const ConvK& k, const GatherChoice& c, int dtype, std::string& out) {
+    const char* T = dtype == DIN_F32 ? "float" : "bf16";
+    char line[160];
+    line[0] = 0;
+    switch (c.family) {
+    case GATHER_REGW: {
+        const din_gather::RegwInst i = din_gather::conv1x1_regw_inst(k);
+        snprintf(line, sizeof line, "conv1x1_regw_kernel<%d,%d,%d,%d,%d>", i.nks, (int)i.masked, i.ns, i.occ, i.rt);
+        break;
+    }
+    case GATHER_STREAM: {
+        const din_gather::StreamInst i = din_gather::conv1x1_stream_inst(k);
+        snprintf(line, sizeof line, "conv1x1_stream_kernel<%d,%d,%d,%d,%d>", i.bn, i.nsw, (int)i.multi, (int)i.epi, (int)i.split);
+        break;
+    }
+    case GATHER_HALO: {                     // (the 8-wave forms leave the wave count to the template's default, as launch_choice spells them)
+        const HaloPlan& hp = c.halo;
+        if (hp.nwv == 16) snprintf(line, sizeof line, "conv_halo_kernel<%d,%d,%d,%d,%d,%d,16>", hp.bn, k.kh, k.kw, hp.th, hp.tw, hp.nsw);
+        else snprintf(line, sizeof line, "conv_halo_kernel<%d,%d,%d,%d,%d,%d>", hp.bn, k.kh, k.kw, hp.th, hp.tw, hp.nsw);
+        break;
+    }
+    case GATHER_SMALL: {
+        const SmallVariant& s = c.small;
+        snprintf(line, sizeof line, "conv_small_kernel<%d,%d,%d,3,3,%d,%d,%d,%d>", s.cpt, s.bn, s.nbuf, s.image ? 2 : 1, (int)(s.image && s.u8), s.waves, (int)s.epi);
+        break;
+    }
+    case GATHER_PIPE: snprintf(line, sizeof line, "conv_gather_pipe_kernel<%d>", c.g.bn); break;
+    case GATHER_GENERIC: snprintf(line, sizeof line, "conv_gather_generic_kernel<%s,%d>", T, c.tile.bn == 64 ? 64 : 128); break;
+    case GATHER_TILE: {
+        const TileInst& t = c.tile;
+        snprintf(line, sizeof line, "conv_gather_fast_kernel<%s,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", T, t.bm, t.bn, t.wm, t.wn, t.kcs, t.ns, (int)t.multi,
+                 (int)t.fastk, (int)t.xsrc, (int)t.lanek);
+        break;
+    }
+    }
+    out += line; out += '\n';
+    if (c.g.splitk > 1) { out += "conv_splitk_finish_kernel<"; out += T; out += ">\n"; }
 }
 
 
@@ -3450,6 +3526,32 @@ int din_conv_kernel_variant(const din_conv_desc* d, int which, int32_t* flags) {
     return DIN_OK;
 }
 
+int din_conv_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes) {
+    if (int e = check_desc(d)) return e;
+    DIN_REQUIRE((which == 0 || which == 1) && buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_kernel_names: bad argument");
+    if (which == 0) {
+        DIN_REQUIRE(!(flags & (DIN_CONV_ACCUM | DIN_CONV_MASK)), "conv_kernel_names: ACCUM/MASK are dgrad-only flags");
+        DIN_REQUIRE(!d->in_u8 || din_conv_accepts_u8(d), "conv_kernel_names: in_u8 on a layer din_conv_accepts_u8() rejects");
+    } else {
+        DIN_REQUIRE(!d->in_u8 && !(flags & (DIN_CONV_BIAS | DIN_CONV_RELU)), "conv_kernel_names: in_u8 / BIAS / RELU are fwd-only");
+    }
+    static const unsigned char raw_frames = 0;              // stands for the caller's uint8 frames: the selection only asks whether there are any
+    std::string names;
+    for_each_launch(d, which, flags, ldm, moff, [&](ConvK& k, const GatherPlan& g, const char*) {
+        if (d->in_u8) k.u8 = &raw_frames;
+        const GatherChoice c = choose_gather(k, g, d->dtype);
+        set_plan_fields(k, c);
+        append_kernel_names(k, c, d->dtype, names);
+        return 0;
+    });
+    if (buf_bytes > 0) {
+        const size_t n = names.size() < (size_t)buf_bytes - 1 ? names.size() : (size_t)buf_bytes - 1;
+        memcpy(buf, names.data(), n);
+        buf[n] = 0;
+    }
+    return (int)names.size() + 1;
+}
+
 int64_t din_conv_workspace_bytes(const din_conv_desc* d, int which) {
     if (!d) return 0;
     if (which != 0 && which != 1) return plan_wgrad(d).ws_bytes;
@@ -3465,13 +3567,12 @@ int din_conv_fwd(const din_conv_desc* d, const void* in, const void* wpk, const 
     DIN_REQUIRE(in && wpk && out, "conv_fwd: null pointer");
     DIN_REQUIRE(!(flags & DIN_CONV_BIAS) || bias, "conv_fwd: BIAS flag without bias");
     DIN_REQUIRE(!(flags & (DIN_CONV_ACCUM | DIN_CONV_MASK)), "conv_fwd: ACCUM/MASK are dgrad-only flags");
-    ConvK k = conv_k_of(d, 0);
-    k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.flags = flags;
-    if (d->in_u8) {
-        DIN_REQUIRE(din_conv_accepts_u8(d), "conv_fwd: in_u8 on a layer din_conv_accepts_u8() rejects");
-        k.u8 = reinterpret_cast<const unsigned char*>(in);
-    }
-    return run_gather(k, plan_launch(d, 0), d->dtype, workspace, workspace_bytes, as_stream(stream), "conv_fwd");
+    DIN_REQUIRE(!d->in_u8 || din_conv_accepts_u8(d), "conv_fwd: in_u8 on a layer din_conv_accepts_u8() rejects");
+    return for_each_launch(d, 0, flags, 0, 0, [&](ConvK& k, const GatherPlan& g, const char* what) {
+        k.in = in; k.w = wpk; k.out = out; k.bias = bias;
+        if (d->in_u8) k.u8 = reinterpret_cast<const unsigned char*>(in);
+        return run_gather(k, g, d->dtype, workspace, workspace_bytes, as_stream(stream), what);
+    });
 }
 
 int din_conv_accepts_u8(const din_conv_desc* d) {
@@ -3551,16 +3652,9 @@ static int conv_dgrad_impl(const din_conv_desc* d, const void* dout, const void*
                 "conv_dgrad: dout stride/offset must be multiples of %d and cover cout (+zero pad)", epc);
     DIN_REQUIRE(d->ldi % 4 == 0 && d->cioff % 4 == 0, "conv_dgrad: din stride/offset must be multiples of 4");
     hipStream_t st = as_stream(stream);
-    auto bind = [&](ConvK& k) { k.in = dout; k.w = wpk_t; k.out = din_; k.mask = mask; k.flags = flags; k.ldm = ldm; k.moff = moff; };
-    if (!dgrad_by_parity(d)) {
-        ConvK k = conv_k_of(d, 1);
-        bind(k);
-        return run_gather(k, plan_launch(d, 1), d->dtype, workspace, workspace_bytes, st, "conv_dgrad");
-    }
-    return for_each_parity_class(d, [&](const ParityClass& pc) {
-        ConvK c = conv_k_of(d, 1, &pc);
-        bind(c);
-        if (x) {                                   // extra 1x1 source at the output pixel (din_conv_dgrad_x)
+    return for_each_launch(d, 1, flags, ldm, moff, [&](ConvK& c, const GatherPlan& g, const char* what) {
+        c.in = dout; c.w = wpk_t; c.out = din_; c.mask = mask;
+        if (x) {                                   // extra 1x1 source at the output pixel (din_conv_dgrad_x: parity-class launches only)
             ConvK::Src& o = c.src[0];
             o.in = x->dout; o.w = x->wpk_t; o.ld = x->ldo; o.coff = x->cooff;
             o.cpt = pad_to(x->cout, epc) / epc;
@@ -3569,7 +3663,7 @@ static int conv_dgrad_impl(const din_conv_desc* d, const void* dout, const void*
             o.w_bytes = (long long)pad_to(d->cin, 256) * o.wld * 16;
             c.xsteps = (o.cpt + KC - 1) / KC;
         }
-        return run_gather(c, plan_launch(d, 1, &pc), d->dtype, workspace, workspace_bytes, st, "conv_dgrad(strided)");
+        return run_gather(c, g, d->dtype, workspace, workspace_bytes, st, what);
     });
 }
 

@@ -366,6 +366,22 @@ bool conv1x1_regw_eligible(const ConvK& k, int dtype) {
     return (long long)k.M >= (mp ? atoll(mp) : 64 * 1024);                           // (8 clips, 80 K pixels: 15.40 -> 15.29 ms; 40 K pixels: neutral)
 }
 
+// ring stages, workgroups per CU and 64-filter row tiles per wave of a launch with nks k-steps: <= 10 (the Mixed_5 block entries): classes of
+// 128 filters at two workgroups per CU; 20 / 24: classes of 192 filters, one workgroup per CU
+struct RegwShape { int ns, occ, rt; };
+constexpr RegwShape regw_shape(int nks) { return nks <= 10 ? RegwShape{4, 2, 2} : RegwShape{9, 1, 3}; }
+
+// the template arguments of conv1x1_regw_kernel a launch runs on (nks == 0: none): the launcher below instantiates from it,
+// din_conv_kernel_names prints it
+RegwInst conv1x1_regw_inst(const ConvK& k) {
+    RegwInst i{};
+    i.nks = regw_ksteps(k);
+    const RegwShape s = regw_shape(i.nks);
+    i.ns = s.ns; i.occ = s.occ; i.rt = s.rt;
+    i.masked = (k.flags & DIN_CONV_MASK) != 0;
+    return i;
+}
+
 int launch_conv1x1_regw(const ConvK& k, hipStream_t st) {
     RegwK r{};
     const int ns = k.nsrc > 0 ? k.nsrc : 1;
@@ -396,15 +412,13 @@ int launch_conv1x1_regw(const ConvK& k, hipStream_t st) {
         cus = n >= 8 ? n / 8 * 8 : 8;
         if (dev >= 0 && dev < 64) cus_of[dev].store(cus, std::memory_order_relaxed);
     }
-    const bool masked = (k.flags & DIN_CONV_MASK) != 0;
-    switch (ks) {
-        case 6: launch_regw_nks<6, 4, 2, 2>(r, masked, cus, st); break;
-        case 8: launch_regw_nks<8, 4, 2, 2>(r, masked, cus, st); break;
-        case 10: launch_regw_nks<10, 4, 2, 2>(r, masked, cus, st); break;
-        case 20: launch_regw_nks<20, 9, 1, 3>(r, masked, cus, st); break;
-        case 24: launch_regw_nks<24, 9, 1, 3>(r, masked, cus, st); break;
+    const RegwInst i = conv1x1_regw_inst(k);
+#define DIN_REGW_CASE(NKS_) case NKS_: launch_regw_nks<NKS_, regw_shape(NKS_).ns, regw_shape(NKS_).occ, regw_shape(NKS_).rt>(r, i.masked, cus, st); break;
+    switch (i.nks) {
+        DIN_REGW_CASE(6) DIN_REGW_CASE(8) DIN_REGW_CASE(10) DIN_REGW_CASE(20) DIN_REGW_CASE(24)
         default: return 1;
     }
+#undef DIN_REGW_CASE
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

@@ -379,12 +379,24 @@ static void launch_stream(const ConvK& k, dim3 grid, hipStream_t st) {
     din_raise_lds(reinterpret_cast<const void*>(kern), lds);
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, k);
 }
-template <int BN, int NSW>
-static void launch_stream_bn(const ConvK& k, dim3 grid, hipStream_t st) {
-    const bool multi = k.nsrc > 0, epi = (k.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM)) != 0, split = k.csplit > 0;
-    if (split) launch_stream<BN, NSW, false, false, true>(k, grid, st);
-    else if (multi) { if (epi) launch_stream<BN, NSW, true, true, false>(k, grid, st); else launch_stream<BN, NSW, true, false, false>(k, grid, st); }
-    else { if (epi) launch_stream<BN, NSW, false, true, false>(k, grid, st); else launch_stream<BN, NSW, false, false, false>(k, grid, st); }
+constexpr int stream_slots(int bn) { return bn == 192 ? 3 : 4; }          // ring slots of a filter tile (the 192-filter tile: a 3-slot ring)
+
+// the template arguments of conv1x1_stream_kernel a launch runs on: the launcher below instantiates from it, din_conv_kernel_names prints it
+StreamInst conv1x1_stream_inst(const ConvK& k) {
+    StreamInst i;
+    i.bn = conv1x1_stream_tile(k.Cout); i.nsw = stream_slots(i.bn);
+    i.split = k.csplit > 0;
+    i.multi = !i.split && k.nsrc > 0;
+    i.epi = !i.split && (k.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM)) != 0;
+    return i;
+}
+
+template <int BN>
+static void launch_stream_bn(const ConvK& k, const StreamInst& i, dim3 grid, hipStream_t st) {
+    constexpr int NSW = stream_slots(BN);
+    if (i.split) launch_stream<BN, NSW, false, false, true>(k, grid, st);
+    else if (i.multi) { if (i.epi) launch_stream<BN, NSW, true, true, false>(k, grid, st); else launch_stream<BN, NSW, true, false, false>(k, grid, st); }
+    else { if (i.epi) launch_stream<BN, NSW, false, true, false>(k, grid, st); else launch_stream<BN, NSW, false, false, false>(k, grid, st); }
 }
 
 int conv1x1_stream_tile(int cout) {
@@ -394,13 +406,14 @@ int conv1x1_stream_tile(int cout) {
 }
 
 int launch_conv1x1_stream(ConvK k, hipStream_t st) {
-    const int bn = conv1x1_stream_tile(k.Cout);
+    const StreamInst i = conv1x1_stream_inst(k);
+    const int bn = i.bn;
     k.n_co_tiles = (k.Cout + bn - 1) / bn;
     const long long items = (long long)((k.M + 127) / 128) * k.n_co_tiles;
     const dim3 grid((unsigned)(items < 256 ? items : 256));
-    if (bn == 64) launch_stream_bn<64, 4>(k, grid, st);
-    else if (bn == 96) launch_stream_bn<96, 4>(k, grid, st);
-    else launch_stream_bn<192, 3>(k, grid, st);
+    if (bn == 64) launch_stream_bn<64>(k, i, grid, st);
+    else if (bn == 96) launch_stream_bn<96>(k, i, grid, st);
+    else launch_stream_bn<192>(k, i, grid, st);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

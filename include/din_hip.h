@@ -127,6 +127,15 @@ int din_conv_kernel_tile(const din_conv_desc* d, int which, int32_t* bm, int32_t
 /* which instantiation of conv_gather_fast_kernel a fwd (0) / dgrad (1) launch resolves to: flags bit 0 = FASTK (scalar k-walk), bit 1 = 8 waves
  * (4 x 2) instead of 4 (2 x 2) -- so that a profiler-side caller can spell the exact kernel name rocprofv3 prints */
 int din_conv_kernel_variant(const din_conv_desc* d, int which, int32_t* flags);
+/* the kernels din_conv_fwd (which 0) / din_conv_dgrad (which 1) launch for this descriptor, flags and mask view (ldm, moff: read for
+ * DIN_CONV_MASK only), under the current option settings: one line per launch, in launch order, each the full template instantiation as the
+ * launcher spells it -- "conv_gather_fast_kernel<bf16,128,192,4,2,8,2,0,1,0,0>" (T, BM, BN, WM, WN, KCS, NS, MULTI, FASTK, XSRC, LANEK),
+ * "conv_gather_generic_kernel<float,128>", "conv_small_kernel<8,32,1,3,3,1,0,8,1>", "conv_halo_kernel<80,3,3,8,32,2,16>",
+ * "conv_gather_pipe_kernel<192>", "conv1x1_stream_kernel<96,4,0,1,0>", "conv1x1_regw_kernel<24,1,9,1,3>", and "conv_splitk_finish_kernel<bf16>"
+ * after a launch whose reduction is split.  A strided data gradient gives the line(s) of every non-empty parity class.  Host only: answers
+ * from the launcher's own selection, launches nothing, reads no pointer, needs no GPU.  Writes at most buf_bytes bytes (NUL-terminated) and
+ * returns the number of bytes the whole answer needs (terminator included), or a negative DIN_E_* code. */
+int din_conv_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes);
 /* workspace bytes needed by fwd / dgrad / wgrad for this descriptor (split-K partial sums) */
 int64_t din_conv_workspace_bytes(const din_conv_desc* d, int which /*0 fwd,1 dgrad,2 wgrad*/);
 

@@ -15,7 +15,11 @@ The reporter answers from the launcher's own selection function, so two builds t
     python tools/conv_dispatch_table.py > new.txt;  DIN_LIB_PATH=<other build>/libdin_hip.so python tools/conv_dispatch_table.py > old.txt
 
 The full table has ~47 000 lines.  --summary prints what profiles/conv_dispatch_table.txt holds: the no-option decision only, at 96 frames of
-720x1280 and at the small test geometry, forward and data gradient on one line (bm bn flags / bm bn flags  workspace bytes)."""
+720x1280 and at the small test geometry, forward and data gradient on one line (bm bn flags / bm bn flags  workspace bytes).
+
+--names prints what profiles/conv_kernel_names.txt holds: every distinct kernel instantiation din_conv_kernel_names reports over all those
+cases with no option set -- forward, and data gradient with flags 0 / MASK / ACCUM / MASK|ACCUM (mask view = the layer's input view) --
+each once, with one descriptor that reaches it.  tests/test_gpu_conv_fwd_dgrad.py holds a row for every name in that file."""
 import argparse
 import ctypes as C
 import os
@@ -93,9 +97,31 @@ def report(lib, d, which):
     return f"{bm.value} {bn.value} {fl.value} {lib.din_conv_workspace_bytes(C.byref(d), 0)} {lib.din_conv_workspace_bytes(C.byref(d), 1)}"
 
 
+def kernel_names(lib, d, which, flags, ldm=0, moff=0):
+    """the lines din_conv_kernel_names answers for one launch"""
+    buf = C.create_string_buffer(4096)
+    rc = lib.din_conv_kernel_names(C.byref(d), which, flags, ldm, moff, buf, len(buf))
+    assert 0 < rc <= len(buf), f"din_conv_kernel_names: {rc}"
+    return buf.value.decode().split()
+
+
+def names_table(L, lib, cases):
+    """{kernel name: label of the first launch that reaches it}; forward flags 0 (BIAS | RELU select the same kernel)"""
+    found = {}
+    for label, d in cases:
+        if d.in_u8 and not lib.din_conv_accepts_u8(C.byref(d)):      # (raw frames on a map too small for the image-layer kernel: din_conv_fwd rejects it)
+            continue
+        launches = [(0, 0)] + ([] if d.in_u8 else [(1, f) for f in (0, L.CONV_MASK, L.CONV_ACCUM, L.CONV_MASK | L.CONV_ACCUM)])
+        for which, flags in launches:
+            for name in kernel_names(lib, d, which, flags, d.ldi, d.cioff):
+                found.setdefault(name, f"{label} which={which} flags={flags}")
+    return found
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--summary", action="store_true", help="no-option decisions at 96 frames and at the small geometry, one line per descriptor")
+    ap.add_argument("--names", action="store_true", help="every distinct kernel instantiation of the no-option decisions, with one launch that reaches it")
     args = ap.parse_args()
     from din_amd import _lib as L, nhwc
     lib = L.load()
@@ -113,6 +139,10 @@ def main():
                         seen.add(key)
                         cases.append((f"{backbone} {dtn} nb{nb} {d.h}x{d.w} c{d.cin}>{d.cout} k{d.kh}x{d.kw} s{d.sh} p{d.ph},{d.pw} "
                                       f"ld{d.ldi}+{d.cioff}>{d.ldo}+{d.cooff}{' u8' if d.in_u8 else ''}", d))
+    if args.names:
+        for name, label in sorted(names_table(L, lib, cases).items()):
+            print(f"{name}  <-  {label}")
+        return
     if args.summary:
         for label, d in cases:
             if d.nb in (96, 6):
