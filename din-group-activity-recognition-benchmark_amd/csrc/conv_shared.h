@@ -1,0 +1,94 @@
+// Shared between conv_igemm.hip (forward / data gradient) and conv_wgrad.hip (weight gradient): the vector types, the workgroup size of the
+// 256-thread kernels, the uint8 image-layer halo loader of the two stem kernels, and the host helpers both planners use.
+#pragma once
+#include "din_common.h"
+#include <stdlib.h>
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+namespace {
+
+constexpr int NTHREADS = 256;
+
+// ---- image layer fed from raw uint8 frames (din_conv_desc::in_u8): the halo pixels of a tile are fetched as bytes from the three colour
+//      planes, normalised exactly like utils.prep_images ((x / 255 - 0.5) * 2: three separately rounded fp32 operations, utils.py:8-19),
+//      rounded to bf16 and written to the LDS position the LDS-DMA of a prepared NHWC tensor would have filled (16 bytes per pixel:
+//      r, g, b and five zero channels; pixels outside the image are zero).  Lane-linear: halo pixel id = (wave + 4 i) * 64 + lane.
+__device__ __forceinline__ float prep_u8(uint32_t v) {
+    float y = __fdiv_rn((float)v, 255.0f);
+    y = __fsub_rn(y, 0.5f);
+    return __fmul_rn(y, 2.0f);
+}
+__device__ __forceinline__ void u8_lut_init(bf16_t* lut, int tid) {          // NTHREADS == 256: one entry per thread
+    lut[tid] = (bf16_t)(pack_bf16x2(prep_u8((uint32_t)tid), 0.f) & 0xffffu);
+}
+template <int NTR>
+struct U8Halo {
+    // the three bytes of a pixel stay in separate registers until store(): nothing consumes them at load time, so the loads stay in flight
+    // under the tile's MFMAs instead of being waited for where they are issued
+    uint32_t r[NTR], g[NTR], b[NTR];
+    uint32_t valid;                                      // bit i: pixel i lies inside the image
+    // hyv / hxv: the lane's halo coordinates per transfer (the kernels' tile-independent DMA plans); inside[i]: the id is a halo pixel
+    template <int NSLOT>
+    __device__ __forceinline__ void load(const unsigned char* __restrict__ img, int n, int H, int W, int gy0, int gx0, int wid,
+                                         const short (&hyv)[NTR], const short (&hxv)[NTR], const int (&inside)[NTR]) {
+        // every lane ALWAYS loads (coordinates clamped into the image, validity kept as a bit): a load inside `if (inside)` merges with the zero
+        // of the other path at the end of the branch, and the compiler waits for it right there -- five exposed memory latencies per tile
+        // (vmcnt(2) / (1) / (0) after every pixel in the ISA; the image layer ran 5.5 us per tile = 2.7 TB/s because of it)
+        const int64_t plane = (int64_t)H * W;
+        const unsigned char* base = img + (int64_t)n * 3 * plane;
+        valid = 0u;
+#pragma unroll
+        for (int i = 0; i < NTR; ++i) {
+            const int gy = gy0 + hyv[i], gx = gx0 + hxv[i];
+            const bool ok = wid + 4 * i < NSLOT && inside[i] >= 0 && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            const unsigned char* q = base + (int64_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1);
+            // untracked loads (inline asm): the compiler would zero-extend the bytes -- i.e. wait for them -- right here; the caller waits by
+            // count (s_waitcnt vmcnt) before store() and calls landed()
+            asm volatile("global_load_ubyte %0, %1, off" : "=&v"(r[i]) : "v"(q) : "memory");
+            asm volatile("global_load_ubyte %0, %1, off" : "=&v"(g[i]) : "v"(q + plane) : "memory");
+            asm volatile("global_load_ubyte %0, %1, off" : "=&v"(b[i]) : "v"(q + 2 * plane) : "memory");
+            valid |= (ok ? 1u : 0u) << i;
+        }
+    }
+    __device__ __forceinline__ void landed() {                       // after the caller's s_waitcnt: ties the registers to this point
+#pragma unroll
+        for (int i = 0; i < NTR; ++i) { asm volatile("" : "+v"(r[i])); asm volatile("" : "+v"(g[i])); asm volatile("" : "+v"(b[i])); }
+    }
+    // lut: the 256 normalised bf16 values (prep_u8 of every byte, built once per workgroup by u8_lut_init) -- three LDS reads per pixel
+    // instead of three fp32 divisions
+    template <int NSLOT>
+    __device__ __forceinline__ void store(unsigned char* lds_buf, const bf16_t* lut, int wid, int lane) const {   // lds_buf: the halo buffer
+#pragma unroll
+        for (int i = 0; i < NTR; ++i) {
+            if (wid + 4 * i < NSLOT) {
+                u32x4 v = {0u, 0u, 0u, 0u};
+                if ((valid >> i) & 1u) {
+                    v[0] = (uint32_t)lut[r[i]] | ((uint32_t)lut[g[i]] << 16);
+                    v[1] = (uint32_t)lut[b[i]];
+                }
+                *reinterpret_cast<u32x4*>(lds_buf + ((wid + 4 * i) * 64 + lane) * 16) = v;
+            }
+        }
+    }
+};
+
+// ---- host side ---------------------------------------------------------------------------------------
+inline int epc_of(int dtype) { return dtype == DIN_F32 ? 4 : 8; }
+inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
+inline int opt_int(const char* v, int dflt) { return v ? atoi(v) : dflt; }
+// stem layers on conv_small_kernel / conv_wgrad_small_kernel (DIN_CONV_SMALL=0: off); din_conv_accepts_u8 answers from the same switch
+inline bool conv_small_wanted() { return opt_int(DIN_OPT("DIN_CONV_SMALL"), 1) != 0; }
+
+// hipFuncSetAttribute is a slow host call: raise a kernel's dynamic-LDS limit once per (thread, kernel), not per launch
+template <typename K>
+inline void raise_lds_limit(K kern, size_t lds) { din_raise_lds(reinterpret_cast<const void*>(kern), lds); }
+
+}  // namespace
+
+namespace din_conv {
+int check_desc(const din_conv_desc* d);          // conv_igemm.hip: the descriptor rules every conv entry point starts with
+}

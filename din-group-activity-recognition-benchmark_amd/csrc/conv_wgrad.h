@@ -1,6 +1,8 @@
-// Shared between conv_igemm.hip and conv_wgrad_pipe.hip: the weight-gradient kernel argument block and the wave-level LDS-DMA helper.
+// Shared between the weight-gradient sources (conv_wgrad.hip, conv_wgrad_pipe.hip, conv_wgrad_halo.hip, conv_wgrad_1x1.hip) and conv_igemm.hip:
+// the kernel argument blocks, the wave-level LDS-DMA helper, and the weight-gradient choice (plan_wgrad) with what answers from it.
 #pragma once
 #include "din_common.h"
+#include <string>
 
 namespace din_wgrad {
 
@@ -53,13 +55,46 @@ __device__ __forceinline__ void lds_dma16(uint32_t lds_addr, __amdgpu_buffer_rsr
                  :: "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
 }
 
-// host entry of conv_wgrad_pipe.hip: launches the software-pipelined 32x32x16 ring kernel for a plan with pipe != 0
-int launch_wgrad_pipe(const WgradK& k, int bco, int bk, dim3 grid, hipStream_t st);
+// ---- the weight-gradient choice: plan_wgrad (conv_wgrad.hip) decides everything about the main launch of din_conv_wgrad here, from the
+//      descriptor and the options, each option read once; the launch table, din_conv_kernel_tile / _names / _workspace_bytes(d, 2),
+//      din_conv_wgrad_group_key and the profiler's kernel names all answer from it.
+enum WgradFamily {
+    WGRAD_F32,          // conv_wgrad_f32_kernel
+    WGRAD_BF16_TAIL,    // conv_wgrad_bf16_tail_kernel (channels that are no whole 16-byte chunks)
+    WGRAD_BF16,         // conv_wgrad_bf16_kernel<BCO>: two workgroups per CU
+    WGRAD_RING,         // conv_wgrad_ring_kernel<BCO, BK>
+    WGRAD_PIPE,         // conv_wgrad_pipe_kernel<BCO, BK, WIDE, WN> (conv_wgrad_pipe.hip)
+    WGRAD_STEM,         // conv_wgrad_small_kernel<CPP, BN, ST, U8, NW, TH_, RING>
+    WGRAD_HALO          // conv_wgrad_halo_kernel<CPP, BNT, KH, KW, TH> (conv_wgrad_halo.hip)
+};
+struct PipeInst { int bco, bk; bool wide; int wn; };
+struct StemInst { int cpp, bn, st; bool u8; int nw, th, ring; };
+struct HaloInst { int cpp, bnt, kh, kw, th; };
+struct WgradChoice {
+    WgradFamily family;
+    int bco, bk;                       // filter rows x k columns of a workgroup tile: the whole tuple of WGRAD_BF16 (<bco>) and WGRAD_RING (<bco, bk>)
+    PipeInst pipe; StemInst stem; HaloInst halo;        // the tuple of the family chosen (the others stay zero)
+    dim3 grid, block; size_t lds;      // the main launch
+    bool bias_fused;                   // the kernel adds the bias gradient itself (no column-sum launch)
+    int atomic;                        // pipe kernel: fp32 atomics into ONE partial tile instead of one tile per pixel slice
+    int group_key;                     // din_conv_wgrad_group_key: 0, or 2 * bco + wide for a sixteen-wave pipe plan with slices to reduce
+    int cin_pad, kcols, kcols_pad, cout_pad, n_co_tiles, n_k_tiles, slices, m_per_slice;
+    int64_t ws_bytes;
+};
+WgradChoice plan_wgrad(const din_conv_desc* d);
+void wgrad_tile_code(const WgradChoice& c, int32_t* bm, int32_t* bn);                       // the codes of din_conv_kernel_tile(d, 2)
+void append_wgrad_names(const din_conv_desc* d, const WgradChoice& c, std::string& out);   // the lines of din_conv_kernel_names(d, 2, ...)
+
+// host entries of conv_wgrad_pipe.hip: the software-pipelined 32x32x16 ring kernel.  The launchers map the chosen tuple to its template;
+// a tuple that is not instantiated is DIN_E_ARG
+int launch_wgrad_pipe(const WgradK& k, const PipeInst& inst, dim3 grid, dim3 block, size_t lds, hipStream_t st);
 int launch_wgrad_pipe_group(const WgradGroupK& g, int bco, bool wide, hipStream_t st);     // 16-wave instantiations only; grid = g.first[g.n] blocks
 size_t wgrad_pipe_lds_bytes(int bco, int bk);
-// host entries of conv_wgrad_halo.hip: the halo-tiled weight gradient of the narrow mid-network layers (dW block stationary in registers)
-bool wgrad_halo_shape(int cin, int cout, int kh, int kw, int* bnt);
-int launch_wgrad_halo(const WgradK& k, int nwg, hipStream_t st);
+// host entries of conv_wgrad_halo.hip: the halo-tiled weight gradient of the narrow mid-network layers (dW block stationary in registers).
+// wgrad_halo_shape: the instantiation that serves (cin, cout, kh, kw) at stride 1, dilation 1, bf16 -- one table, which the launcher switches on
+bool wgrad_halo_shape(int cin, int cout, int kh, int kw, HaloInst* inst);
+size_t wgrad_halo_lds_bytes(const HaloInst& inst);
+int launch_wgrad_halo(const WgradK& k, const HaloInst& inst, dim3 grid, dim3 block, size_t lds, hipStream_t st);
 // host entries of conv_wgrad_1x1.hip
 bool plan_wgrad_1x1_multi(int nsrc, const int* couts, int cin, Wg1x1K* k);
 int launch_wgrad_1x1_multi(const Wg1x1K& k, int nwg, hipStream_t st);

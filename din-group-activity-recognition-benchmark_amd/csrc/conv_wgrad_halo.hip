@@ -215,27 +215,30 @@ constexpr size_t stage_bytes(int cpp, int bnt, int kh, int kw, int th) {
 
 }  // namespace
 
-// shape table: which (cin, cout, kh, kw) run the halo weight-gradient kernel (stride 1, dilation 1, bf16)
-bool wgrad_halo_shape(int cin, int cout, int kh, int kw, int* bnt) {
-    int b = 0;
-    if (kh == 5 && kw == 5 && cin == 48 && cout == 64) b = 32;
-    else if (kh == 3 && kw == 3 && cin == 64 && cout == 96) b = 48;
-    else if (kh == 3 && kw == 3 && cin == 96 && cout == 96) b = 48;
-    if (bnt) *bnt = b;
-    return b != 0;
+// shape table: which (cin, cout, kh, kw) run the halo weight-gradient kernel (stride 1, dilation 1, bf16), and on which instantiation
+//   X(cin, cout, CPP, BNT, KH, KW, TH)
+#define DIN_WGRAD_HALO_TABLE(X) X(48, 64, 6, 32, 5, 5, 8) X(64, 96, 8, 48, 3, 3, 8) X(96, 96, 12, 48, 3, 3, 4)
+
+bool wgrad_halo_shape(int cin, int cout, int kh, int kw, HaloInst* inst) {
+#define DIN_HALO_ROW(CIN_, COUT_, CPP_, BNT_, KH_, KW_, TH_) \
+    if (cin == CIN_ && cout == COUT_ && kh == KH_ && kw == KW_) { *inst = HaloInst{CPP_, BNT_, KH_, KW_, TH_}; return true; }
+    DIN_WGRAD_HALO_TABLE(DIN_HALO_ROW)
+#undef DIN_HALO_ROW
+    return false;
 }
 
-int launch_wgrad_halo(const WgradK& k, int nwg, hipStream_t st) {
-    dim3 grid(nwg, 2);
-    auto launch = [&](auto kern, size_t lds) {
-        raise_lds(kern, lds);
-        hipLaunchKernelGGL(kern, grid, dim3(1024), lds, st, k);
-    };
-    if (k.kh == 5 && k.Cin == 48 && k.Cout == 64) launch(conv_wgrad_halo_kernel<6, 32, 5, 5, 8>, 2 * stage_bytes(6, 32, 5, 5, 8));
-    else if (k.kh == 3 && k.Cin == 64 && k.Cout == 96) launch(conv_wgrad_halo_kernel<8, 48, 3, 3, 8>, 2 * stage_bytes(8, 48, 3, 3, 8));
-    else if (k.kh == 3 && k.Cin == 96 && k.Cout == 96) launch(conv_wgrad_halo_kernel<12, 48, 3, 3, 4>, 2 * stage_bytes(12, 48, 3, 3, 4));
-    else DIN_FAIL(DIN_E_ARG, "wgrad halo kernel: shape %dx%d %d -> %d not instantiated", k.kh, k.kw, k.Cin, k.Cout);
-    return DIN_OK;
+size_t wgrad_halo_lds_bytes(const HaloInst& i) { return 2 * stage_bytes(i.cpp, i.bnt, i.kh, i.kw, i.th); }
+
+int launch_wgrad_halo(const WgradK& k, const HaloInst& inst, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
+#define DIN_HALO_ROW(CIN_, COUT_, CPP_, BNT_, KH_, KW_, TH_)                                                          \
+    if (inst.cpp == CPP_ && inst.bnt == BNT_ && inst.kh == KH_ && inst.kw == KW_ && inst.th == TH_) {                 \
+        raise_lds(conv_wgrad_halo_kernel<CPP_, BNT_, KH_, KW_, TH_>, lds);                                            \
+        hipLaunchKernelGGL((conv_wgrad_halo_kernel<CPP_, BNT_, KH_, KW_, TH_>), grid, block, lds, st, k);             \
+        return DIN_OK;                                                                                                \
+    }
+    DIN_WGRAD_HALO_TABLE(DIN_HALO_ROW)
+#undef DIN_HALO_ROW
+    DIN_FAIL(DIN_E_ARG, "wgrad halo kernel: <%d, %d, %d, %d, %d> not instantiated", inst.cpp, inst.bnt, inst.kh, inst.kw, inst.th);
 }
 
 }  // namespace din_wgrad

@@ -3,7 +3,7 @@
 //   dW[co][(r,s,ci)] = sum_pix G[pix][co] * im2col(X)[pix][(r,s,ci)]        (reference: autograd of torch.nn.Conv2d reached from
 //   backbone/backbone.py:44-99; both operands are stored [pixel][channel], i.e. the reduction index is the STRIDED one on both sides)
 //
-// Same data movement as conv_wgrad_ring_kernel (conv_igemm.hip): BCO x 256 output tile per 8-wave workgroup, 32-pixel stages in a
+// Same data movement as conv_wgrad_ring_kernel (conv_wgrad.hip): BCO x 256 output tile per 8-wave workgroup, 32-pixel stages in a
 // 4-slot LDS ring filled by LDS-DMA three stages ahead, operands read with the transposing ds_read_b64_tr_b16.  What changes is the
 // schedule inside a wave -- the round-1 counters (profiles/r01_wgrad_ring.txt: MFMA busy 33 %, LDS conflicts 26 % of LDS cycles,
 // 2.7 SALU + 2.0 VALU per MFMA) showed every wave doing "barrier -> 4 DMA issues -> 20 transpose reads -> wait -> 24 MFMAs" in
@@ -419,35 +419,22 @@ void raise_lds(K kern, size_t lds) { din_raise_lds(reinterpret_cast<const void*>
 
 size_t wgrad_pipe_lds_bytes(int, int) { return 4 * 2 * 32 * 512; }
 
-int launch_wgrad_pipe(const WgradK& k, int bco, int bk, dim3 grid, hipStream_t st) {
-    DIN_REQUIRE(bk == 256 && (bco == 128 || bco == 192 || bco == 256), "wgrad pipe kernel: tile %dx%d not instantiated", bco, bk);
-    const size_t lds = wgrad_pipe_lds_bytes(bco, bk);
-    // wave grid of the workgroup: 2 x 8 (sixteen waves, four per SIMD, (BCO/2) x 32 wave tiles; default: +6 % on the dominant kernel inside
-    // the training step over 2 x 4, whose 60 % fewer fragment reads do not matter), DIN_WGRAD_PIPE_WAVES=8: 2 x 4, =4: 2 x 2 (-13 %)
-    const char* wv = DIN_OPT("DIN_WGRAD_PIPE_WAVES");
-    const int waves = wv ? atoi(wv) : 16;
-    const bool four = waves == 4 && bco <= 192, sixteen = waves == 16;   // (the four-wave 256-row tile spills: scratch traffic would break the vmcnt count)
-    auto launch = [&](auto kern, int threads) {
-        raise_lds(kern, lds);
-        hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, k);
-    };
-    const bool wide = k.OW >= 32;                                  // a feature-map row holds at least one 32-pixel stage
-    if (sixteen) {
-        if (bco == 128) { if (wide) launch(conv_wgrad_pipe_kernel<128, 256, true, 8>, 1024); else launch(conv_wgrad_pipe_kernel<128, 256, false, 8>, 1024); }
-        else if (bco == 192) { if (wide) launch(conv_wgrad_pipe_kernel<192, 256, true, 8>, 1024); else launch(conv_wgrad_pipe_kernel<192, 256, false, 8>, 1024); }
-        else { if (wide) launch(conv_wgrad_pipe_kernel<256, 256, true, 8>, 1024); else launch(conv_wgrad_pipe_kernel<256, 256, false, 8>, 1024); }
-        return DIN_OK;
+// wave grid of the workgroup, WN: 8 = 2 x 8 (sixteen waves, four per SIMD, (BCO/2) x 32 wave tiles; default: +6 % on the dominant kernel inside
+// the training step over 2 x 4, whose 60 % fewer fragment reads do not matter), 4 = 2 x 4, 2 = 2 x 2 (-13 %).  WIDE: a feature-map row holds at
+// least one 32-pixel stage.  (plan_wgrad never chooses the four-wave 256-row tile: it spills, and scratch traffic would break the vmcnt count)
+int launch_wgrad_pipe(const WgradK& k, const PipeInst& inst, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
+#define DIN_PIPE(BCO_, WIDE_, WN_)                                                                                \
+    if (inst.bco == BCO_ && inst.bk == 256 && inst.wide == WIDE_ && inst.wn == WN_) {                             \
+        raise_lds(conv_wgrad_pipe_kernel<BCO_, 256, WIDE_, WN_>, lds);                                            \
+        hipLaunchKernelGGL((conv_wgrad_pipe_kernel<BCO_, 256, WIDE_, WN_>), grid, block, lds, st, k);             \
+        return DIN_OK;                                                                                            \
     }
-    if (four) {
-        if (bco == 128) { if (wide) launch(conv_wgrad_pipe_kernel<128, 256, true, 2>, 256); else launch(conv_wgrad_pipe_kernel<128, 256, false, 2>, 256); }
-        else if (bco == 192) { if (wide) launch(conv_wgrad_pipe_kernel<192, 256, true, 2>, 256); else launch(conv_wgrad_pipe_kernel<192, 256, false, 2>, 256); }
-        else { if (wide) launch(conv_wgrad_pipe_kernel<256, 256, true, 2>, 256); else launch(conv_wgrad_pipe_kernel<256, 256, false, 2>, 256); }
-        return DIN_OK;
-    }
-    if (bco == 128) { if (wide) launch(conv_wgrad_pipe_kernel<128, 256, true>, 512); else launch(conv_wgrad_pipe_kernel<128, 256, false>, 512); }
-    else if (bco == 192) { if (wide) launch(conv_wgrad_pipe_kernel<192, 256, true>, 512); else launch(conv_wgrad_pipe_kernel<192, 256, false>, 512); }
-    else { if (wide) launch(conv_wgrad_pipe_kernel<256, 256, true>, 512); else launch(conv_wgrad_pipe_kernel<256, 256, false>, 512); }
-    return DIN_OK;
+#define DIN_PIPE_GRIDS(BCO_) DIN_PIPE(BCO_, true, 8) DIN_PIPE(BCO_, false, 8) DIN_PIPE(BCO_, true, 4) DIN_PIPE(BCO_, false, 4) \
+                             DIN_PIPE(BCO_, true, 2) DIN_PIPE(BCO_, false, 2)
+    DIN_PIPE_GRIDS(128) DIN_PIPE_GRIDS(192) DIN_PIPE_GRIDS(256)
+#undef DIN_PIPE_GRIDS
+#undef DIN_PIPE
+    DIN_FAIL(DIN_E_ARG, "wgrad pipe kernel: <%d, %d, %d, %d> not instantiated", inst.bco, inst.bk, (int)inst.wide, inst.wn);
 }
 
 int launch_wgrad_pipe_group(const WgradGroupK& g, int bco, bool wide, hipStream_t st) {

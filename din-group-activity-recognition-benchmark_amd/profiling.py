@@ -125,34 +125,31 @@ class hbm_survey:
 
 class LaunchTimer:
     """Brackets one conv launch with HIP events when profiling.PROFILE is a list; names the kernel the launch resolves to exactly as rocprofv3
-    prints it (din_conv_kernel_tile / din_conv_kernel_variant).  With PROFILE_ONLY set, launches of other kernels are left alone, so a
-    timed step that only needs the dominant kernel's launch times pays for ~20 event pairs instead of ~190."""
+    prints it (forward / data gradient: din_conv_kernel_tile / din_conv_kernel_variant; weight gradient: din_conv_kernel_names).  With
+    PROFILE_ONLY set, launches of other kernels are left alone, so a timed step that only needs the dominant kernel's launch times pays for
+    ~20 event pairs instead of ~190."""
     def __init__(self, kind, d, name=""):
         self.kind, self.d, self.name = kind, d, name
         self.rec = False
 
     def _variant(self) -> str:
         d = self.d
-        bm, bn = C.c_int32(0), C.c_int32(0)
-        which = {"fwd": 0, "dgrad": 1, "wgrad": 2}[self.kind]
-        L.load().din_conv_kernel_tile(C.byref(d), which, C.byref(bm), C.byref(bn))
-        tn = "unsigned short" if d.dtype == L.DIN_BF16 else "float"
         if self.kind == "wgrad":
             if self.name.startswith("1x1multi:"):
                 return f"conv_wgrad_1x1_multi_kernel<{d.cin // 8}>"
-            if self.name.startswith("group:"):                         # din_conv_wgrad_group: the sixteen-wave pipe instantiation of the items' tile
-                return f"conv_wgrad_pipe_group_kernel<{bm.value}, {bn.value - 2000}, {'true' if d.ow >= 32 else 'false'}, 8>"
-            if bm.value == 3:
-                return f"conv_wgrad_halo_kernel<..., {bn.value}, ...>"
-            if bm.value == 0:
-                return f"conv_wgrad_small_kernel<..., {bn.value}, ...>"
-            if bn.value >= 2000:
-                waves = int(L.get_option("DIN_WGRAD_PIPE_WAVES") or "16")      # wave grid 2 x WN (conv_wgrad_pipe.hip launch_wgrad_pipe)
-                wn = 8 if waves == 16 else (2 if waves == 4 and bm.value <= 192 else 4)
-                return f"conv_wgrad_pipe_kernel<{bm.value}, {bn.value - 2000}, {'true' if d.ow >= 32 else 'false'}, {wn}>"
-            if bn.value >= 1000:
-                return f"conv_wgrad_ring_kernel<{bm.value}, {bn.value - 1000}>"
-            return f"conv_wgrad_bf16_kernel<{bm.value}>" if d.dtype == L.DIN_BF16 else "conv_wgrad_f32_kernel"
+            # the first line din_conv_kernel_names answers for a weight gradient is its main kernel, spelled as rocprofv3 prints it
+            buf = C.create_string_buffer(256)
+            rc = L.load().din_conv_kernel_names(C.byref(d), 2, 0, 0, 0, buf, len(buf))
+            if rc < 0:
+                L.check(rc, "din_conv_kernel_names")
+            main = buf.value.decode().split("\n")[0]
+            if self.name.startswith("group:"):                         # din_conv_wgrad_group: the grouped form of the items' sixteen-wave pipe instantiation
+                return main.replace("conv_wgrad_pipe_kernel<", "conv_wgrad_pipe_group_kernel<")
+            return main
+        bm, bn = C.c_int32(0), C.c_int32(0)
+        which = {"fwd": 0, "dgrad": 1}[self.kind]
+        L.load().din_conv_kernel_tile(C.byref(d), which, C.byref(bm), C.byref(bn))
+        tn = "unsigned short" if d.dtype == L.DIN_BF16 else "float"
         if bm.value == 4 and not (self.kind == "dgrad" and "+" in self.name):
             return f"conv1x1_stream_kernel<{bn.value}>"
         if bm.value == 5:

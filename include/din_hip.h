@@ -122,7 +122,10 @@ int din_conv_fwd2(const din_conv_desc* d, const void* in, const void* wpk, const
  * k columns of conv_wgrad_*_kernel, bn = 1000 + k columns for conv_wgrad_ring_kernel; bm = 0 -> the stationary-filter stem kernels
  * conv_small_kernel / conv_wgrad_small_kernel with bn filters; bm = 1 -> conv_halo_kernel; bm = 2 -> conv_gather_pipe_kernel; bm = 4 ->
  * conv1x1_stream_kernel; bm = 5 -> conv1x1_regw_kernel, classes of bn = 192 filters resident in registers): lets a profiler-side caller
- * name the kernel a launch resolves to */
+ * name the kernel a launch resolves to.  which = 2: the codes are computed from the weight-gradient choice (plan_wgrad, csrc/conv_wgrad.hip),
+ * the one din_conv_wgrad launches from: bm = 3 -> conv_wgrad_halo_kernel with bn filter rows per class, bn = 2000 + k columns ->
+ * conv_wgrad_pipe_kernel.  Several instantiations share a code (the tail kernel and conv_wgrad_bf16_kernel<128>; the stem forms):
+ * din_conv_kernel_names(d, 2, ...) tells them apart */
 int din_conv_kernel_tile(const din_conv_desc* d, int which, int32_t* bm, int32_t* bn);
 /* which instantiation of conv_gather_fast_kernel a fwd (0) / dgrad (1) launch resolves to: flags bit 0 = FASTK (scalar k-walk), bit 1 = 8 waves
  * (4 x 2) instead of 4 (2 x 2) -- so that a profiler-side caller can spell the exact kernel name rocprofv3 prints */
@@ -134,7 +137,15 @@ int din_conv_kernel_variant(const din_conv_desc* d, int which, int32_t* flags);
  * "conv_gather_pipe_kernel<192>", "conv1x1_stream_kernel<96,4,0,1,0>", "conv1x1_regw_kernel<24,1,9,1,3>", and "conv_splitk_finish_kernel<bf16>"
  * after a launch whose reduction is split.  A strided data gradient gives the line(s) of every non-empty parity class.  Host only: answers
  * from the launcher's own selection, launches nothing, reads no pointer, needs no GPU.  Writes at most buf_bytes bytes (NUL-terminated) and
- * returns the number of bytes the whole answer needs (terminator included), or a negative DIN_E_* code. */
+ * returns the number of bytes the whole answer needs (terminator included), or a negative DIN_E_* code.
+ * which 2: the launches of a production-style din_conv_wgrad call (dbias, scale, w and wdot given) under the current options, from the
+ * weight-gradient choice din_conv_wgrad itself launches from: the main kernel, "conv_wgrad_reduce_kernel", and the column-sum kernel
+ * ("colsum_vec_kernel<unsigned short, 8>", "colsum_kernel<float>", ...) where the main kernel does not sum the bias gradient itself.  flags,
+ * ldm and moff must be 0 (DIN_E_ARG otherwise).  These lines are spelled DIFFERENTLY from the forward / data-gradient ones, on purpose: as the
+ * demangler spells the instantiation, which is what rocprofv3 prints -- every template argument with the defaults written out, ", "
+ * between them, true / false for bools ("conv_wgrad_small_kernel<4, 64, 1, false, 8, 6, 3>", "conv_wgrad_pipe_kernel<192, 256, true, 8>",
+ * "conv_wgrad_halo_kernel<8, 48, 3, 3, 8>", "conv_wgrad_ring_kernel<64, 128>", "conv_wgrad_bf16_kernel<128>", "conv_wgrad_bf16_tail_kernel",
+ * "conv_wgrad_f32_kernel") -- because profiling.LaunchTimer and the benchmark's dominant-kernel string use the first line verbatim. */
 int din_conv_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes);
 /* workspace bytes needed by fwd / dgrad / wgrad for this descriptor (split-K partial sums) */
 int64_t din_conv_workspace_bytes(const din_conv_desc* d, int which /*0 fwd,1 dgrad,2 wgrad*/);

@@ -1176,6 +1176,7 @@ PIPE_CASES = [
     ("pipe384_3x3_s2", 2, 96, 47, 63, 384, (3, 3), (2, 2), (0, 0)),               # Mixed_6a.branch3x3: two filter tiles, stride 2
     ("pipe128_1x1", 2, 512, 30, 40, 256, (1, 1), (1, 1), (0, 0)),                 # 128-filter tiles
     ("pipe128_3x3", 2, 64, 29, 37, 120, (3, 3), (1, 1), (1, 1)),                  # 128-row bank, 120 filters, 576 k columns (3 k tiles: paced)
+    ("pipe128_3x3_narrow", 3, 40, 13, 27, 120, (3, 3), (1, 1), (1, 1)),           # 128-row bank on OW < 32 (the 7x11 maps' 1x1 layers), 360 k columns, M % 32 != 0
     ("pipe256_1x7", 2, 96, 19, 45, 248, (1, 7), (1, 1), (0, 3)),                  # 256-row bank, 248 filters, 672 k columns
     ("pipe256_1x1_direct", 1, 16328, 5, 9, 1000, (1, 1), (1, 1), (0, 0)),         # 256 tiles: one slice, dW straight from the accumulators
 ]
@@ -1209,6 +1210,11 @@ def test_wgrad_pipe_kernel(env, case, atomic, waves, monkeypatch):
     bm, bn = C.c_int32(0), C.c_int32(0)
     lib.din_conv_kernel_tile(C.byref(d), 2, C.byref(bm), C.byref(bn))
     assert bn.value >= 2000, f"planner did not pick the pipe kernel for {name}: tile {bm.value} x {bn.value}"
+    # the instantiation of this wave grid, as din_conv_kernel_names reports it: WN = 8 / 4 / 2 (the 256-row tile has no 2 x 2 form: 2 x 4)
+    wn = {"16": 8, "8": 4, "4": 2 if bm.value <= 192 else 4}[waves]
+    names = C.create_string_buffer(512)
+    assert 0 < lib.din_conv_kernel_names(C.byref(d), 2, 0, 0, 0, names, len(names)) <= len(names)
+    assert names.value.decode().split("\n")[0] == f"conv_wgrad_pipe_kernel<{bm.value}, 256, {'true' if ow >= 32 else 'false'}, {wn}>"
     xin = to_nhwc(x, torch.bfloat16, ldi)
     gzd = to_nhwc(gz, torch.bfloat16, ldo, coff)
     dw = torch.empty(cout, cin, *k, device="cuda")

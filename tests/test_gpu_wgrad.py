@@ -1,8 +1,9 @@
 """GPU (-m gpu): every weight-gradient kernel din_conv_wgrad can launch, and the conv_wgrad_reduce_kernel epilogue it ends in, against a
 float64 reference on the bf16-rounded (fp32: exact) operands.
 
-One row of WGRAD_CASES per kernel instantiation; the row's DIN_* options force it and the kernel code din_conv_kernel_tile(d, 2) reports is
-asserted before anything runs.  Every row carries the edges where such kernels go wrong: M not a multiple of 32, cout not a multiple of
+One row of WGRAD_CASES per kernel instantiation; the row's DIN_* options force it, and both the kernel din_conv_kernel_names(d, 2) reports
+(the row's `kernel`: the exact instantiation, as rocprofv3 prints it) and the code of din_conv_kernel_tile(d, 2) are asserted before
+anything runs.  Every row carries the edges where such kernels go wrong: M not a multiple of 32, cout not a multiple of
 the filter tile, kh*kw*cin_pad not a multiple of the k tile, channel views (cioff / cooff != 0, ldi > cin, ldo > cout).  Each row runs in
 three epilogue modes:
   plain        scale = w = wdot = None, accumulate 0; dw / dbias prefilled with NaN, the launch must overwrite them;
@@ -30,13 +31,15 @@ NG = 256                                  # guard floats on each side (1 KiB: ke
 
 
 def _row(name, kernel, code, dtype, shape, ld, opts=None, **extra):
-    """shape = (nb, cin, h, w, cout, k, s, p, d); ld = (ldi, cioff, ldo, cooff); code = din_conv_kernel_tile(d, 2) (bm, bn)"""
+    """shape = (nb, cin, h, w, cout, k, s, p, d); ld = (ldi, cioff, ldo, cooff); kernel = the first line of din_conv_kernel_names(d, 2);
+    code = din_conv_kernel_tile(d, 2) (bm, bn)"""
     return dict(name=name, kernel=kernel, code=code, dtype=dtype, shape=shape, ld=ld, opts=opts or {}, **extra)
 
 
 def _pipe(name, bco, opts=None, **extra):
     nb, cin, h, w, cout, k, s, p = next(c[1:] for c in PIPE_CASES if c[0] == name)
-    return _row(name, f"conv_wgrad_pipe_kernel<{bco}, 256>", (bco, 2256), "bf16", (nb, cin, h, w, cout, k, s, p, 1),
+    wide = (w + 2 * p[1] - k[1]) // s[1] + 1 >= 32            # WIDE: an output row holds a 32-pixel stage; WN = 8: the default sixteen-wave grid
+    return _row(name, f"conv_wgrad_pipe_kernel<{bco}, 256, {'true' if wide else 'false'}, 8>", (bco, 2256), "bf16", (nb, cin, h, w, cout, k, s, p, 1),
                 (cin + 16, 8, cout + 16, 8), dict({"DIN_WGRAD_PIPE": "1"}, **(opts or {})), **extra)
 
 
@@ -72,6 +75,7 @@ WGRAD_CASES = [
     # software-pipelined kernel (conv_wgrad_pipe.hip): 128 / 192 / 256-row banks, slice partials and the atomic epilogue, paced (2-3 k
     # tiles) and unpaced (more k tiles, DIN_WGRAD_PACE=0), and the single-slice 1x1 form that writes dW straight from its accumulators
     _pipe("pipe128_3x3", 128),
+    _pipe("pipe128_3x3_narrow", 128),
     _pipe("pipe192_3x3_p0_tail", 192),
     _pipe("pipe192_7x1", 192),
     _pipe("pipe384_3x3_s2", 192, {"DIN_WGRAD_ATOMIC": "1"}),
@@ -79,15 +83,15 @@ WGRAD_CASES = [
     _pipe("pipe256_1x1_direct", 256, direct=True),
     # stem kernels (conv_wgrad_small_kernel, >= 256K output pixels): 32 -> <= 32, 32 -> <= 64 (three-slot ring, two-slot ring, four
     # waves), the image layer (prepared NHWC input and the raw uint8 frames)
-    _row("small1", "conv_wgrad_small_kernel<4, 32, 1>", (0, 32), "bf16", (2, 32, 363, 365, 24, K3, S1, P1, 1), (48, 8, 40, 8)),
+    _row("small1", "conv_wgrad_small_kernel<4, 32, 1, false, 4, 8, 2>", (0, 32), "bf16", (2, 32, 363, 365, 24, K3, S1, P1, 1), (48, 8, 40, 8)),
     _row("small2_ring3", "conv_wgrad_small_kernel<4, 64, 1, false, 8, 6, 3>", (0, 64), "bf16", (2, 32, 365, 367, 56, K3, S1, P0, 1),
          (40, 8, 64, 8)),
-    _row("small2_ring2", "conv_wgrad_small_kernel<4, 64, 1, false, 8>", (0, 64), "bf16", (2, 32, 363, 365, 40, K3, S1, P1, 1),
+    _row("small2_ring2", "conv_wgrad_small_kernel<4, 64, 1, false, 8, 8, 2>", (0, 64), "bf16", (2, 32, 363, 365, 40, K3, S1, P1, 1),
          (48, 8, 56, 8), {"DIN_WGRAD_SMALL_RING": "2"}),
-    _row("small2_w4", "conv_wgrad_small_kernel<4, 64, 1>", (0, 64), "bf16", (2, 32, 365, 367, 48, K3, S1, P0, 1), (40, 8, 64, 8),
+    _row("small2_w4", "conv_wgrad_small_kernel<4, 64, 1, false, 4, 8, 2>", (0, 64), "bf16", (2, 32, 365, 367, 48, K3, S1, P0, 1), (40, 8, 64, 8),
          {"DIN_WGRAD_SMALL_WAVES": "4"}),
-    _row("small3_image", "conv_wgrad_small_kernel<1, 32, 2>", (0, 32), "bf16", (1, 5, 1031, 1029, 24, K3, S2, P1, 1), (16, 8, 40, 8)),
-    _row("small3_image_u8", "conv_wgrad_small_kernel<1, 32, 2, true>", (0, 32), "bf16", (1, 3, 1031, 1029, 24, K3, S2, P0, 1),
+    _row("small3_image", "conv_wgrad_small_kernel<1, 32, 2, false, 4, 8, 2>", (0, 32), "bf16", (1, 5, 1031, 1029, 24, K3, S2, P1, 1), (16, 8, 40, 8)),
+    _row("small3_image_u8", "conv_wgrad_small_kernel<1, 32, 2, true, 4, 8, 2>", (0, 32), "bf16", (1, 3, 1031, 1029, 24, K3, S2, P0, 1),
          (8, 0, 40, 8), u8=True),
     # stationary halo kernel (conv_wgrad_halo_kernel, the three shapes of wgrad_halo_shape), forced on small maps
     _row("halo_5x5_48_64", "conv_wgrad_halo_kernel<6, 32, 5, 5, 8>", (3, 32), "bf16", (2, 48, 37, 45, 64, (5, 5), S1, (2, 2), 1),
@@ -201,6 +205,9 @@ def test_wgrad_kernel_against_fp64(env, row, mode, monkeypatch):
     d.kh, d.kw, d.sh, d.sw, d.ph, d.pw, d.dh, d.dw = k[0], k[1], s[0], s[1], p[0], p[1], dil, dil
     d.ldi, d.cioff, d.ldo, d.cooff = ldi, cioff, ldo, cooff
     d.dtype, d.in_u8 = (L.DIN_F32 if fp32 else L.DIN_BF16), int(bool(row.get("u8")))
+    names = C.create_string_buffer(512)
+    assert 0 < lib.din_conv_kernel_names(C.byref(d), 2, 0, 0, 0, names, len(names)) <= len(names), L.load().din_last_error_string()
+    assert names.value.decode().split("\n")[0] == row["kernel"], f"{row['name']}: the planner picked {names.value.decode().split()[0]}"
     bm, bn = C.c_int32(0), C.c_int32(0)
     L.check(lib.din_conv_kernel_tile(C.byref(d), 2, C.byref(bm), C.byref(bn)))
     assert (bm.value, bn.value) == row["code"], f"{row['name']}: planner picked kernel code {(bm.value, bn.value)}, not {row['kernel']}"

@@ -130,8 +130,9 @@ def _function_body(text, signature):
 
 
 def test_every_wgrad_kernel_instantiation_has_a_row_in_the_fp64_table():
-    """the conv_wgrad_*_kernel<...> instantiations din_conv_wgrad launches (directly, through launch_wgrad_halo, and the filter banks of
-    launch_wgrad_pipe) equal the kernels named by the rows of tests/test_gpu_wgrad.py: a kernel added without a row fails here, on the CPU"""
+    """the conv_wgrad_*_kernel<...> instantiations the launch tables of din_conv_wgrad hold (csrc/conv_wgrad.hip: the fp32 and tail kernels
+    and the DIN_WGRAD_*_TABLE rows; conv_wgrad_halo.hip: DIN_WGRAD_HALO_TABLE; conv_wgrad_pipe.hip: the filter banks of launch_wgrad_pipe)
+    equal the kernels named by the rows of tests/test_gpu_wgrad.py, spelled in full: a kernel added without a row fails here, on the CPU"""
     import re
     from tests.test_gpu_wgrad import WGRAD_CASES
     csrc = os.path.join(ROOT, "din-group-activity-recognition-benchmark_amd", "csrc")
@@ -140,19 +141,88 @@ def test_every_wgrad_kernel_instantiation_has_a_row_in_the_fp64_table():
         with open(os.path.join(csrc, name)) as fh:
             return re.sub(r"//[^\n]*", "", fh.read())
 
-    def norm(name):
-        return re.sub(r"\s+", "", name)
+    def table(text, macro, kernel, pick=lambda a: a):
+        body = re.search(r"#define " + macro + r"\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
+        return {f"{kernel}<{', '.join(pick([a.strip() for a in args.split(',')]))}>" for args in re.findall(r"X\(([^()]*)\)", body)}
 
-    pat = re.compile(r"\bconv_wgrad_\w+?_kernel\b(?:\s*<[^<>;()]*>)?")
-    bodies = [_function_body(src("conv_igemm.hip"), "int din_conv_wgrad(const din_conv_desc* d"),
-              _function_body(src("conv_wgrad_halo.hip"), "int launch_wgrad_halo(")]
-    launched = {norm(m) for b in bodies for m in pat.findall(b)} - {"conv_wgrad_reduce_kernel"}
-    assert "din_wgrad::launch_wgrad_pipe(" in bodies[0]
-    banks = set(re.findall(r"conv_wgrad_pipe_kernel<(\d+),\s*256\b", _function_body(src("conv_wgrad_pipe.hip"), "int launch_wgrad_pipe(")))
-    launched |= {f"conv_wgrad_pipe_kernel<{b},256>" for b in banks}
-    assert len(launched) >= 24, sorted(launched)
-    named = {norm(r["kernel"]) for r in WGRAD_CASES}
-    assert launched == named, f"launched without a row: {sorted(launched - named)}; rows naming no launch: {sorted(named - launched)}"
+    wgrad = src("conv_wgrad.hip")
+    body = _function_body(wgrad, "int launch_wgrad(const WgradK& k")
+    launched = set(re.findall(r"go\((conv_wgrad_\w+_kernel)\)", body))
+    assert launched == {"conv_wgrad_f32_kernel", "conv_wgrad_bf16_tail_kernel"}
+    for macro, kernel in (("DIN_WGRAD_BF16_TABLE", "conv_wgrad_bf16_kernel"), ("DIN_WGRAD_RING_TABLE", "conv_wgrad_ring_kernel"),
+                          ("DIN_WGRAD_STEM_TABLE", "conv_wgrad_small_kernel")):
+        assert f"{macro}(DIN_ROW)" in body and f"{kernel}<" in body
+        launched |= table(wgrad, macro, kernel)
+    halo = src("conv_wgrad_halo.hip")
+    assert "DIN_WGRAD_HALO_TABLE(DIN_HALO_ROW)" in _function_body(halo, "int launch_wgrad_halo(") and "din_wgrad::launch_wgrad_halo(" in body
+    launched |= table(halo, "DIN_WGRAD_HALO_TABLE", "conv_wgrad_halo_kernel", lambda a: a[2:])       # (cin, cout, then the template arguments)
+    assert "din_wgrad::launch_wgrad_pipe(" in body
+    pipe = _function_body(src("conv_wgrad_pipe.hip"), "int launch_wgrad_pipe(")
+    banks = set(re.findall(r"DIN_PIPE_GRIDS\((\d+)\)", pipe))
+    grids = set(re.findall(r"DIN_PIPE\(BCO_, (true|false), (\d)\)", pipe))
+    assert len(banks) == 3 and len(grids) == 6
+    pipes = {f"conv_wgrad_pipe_kernel<{b}, 256, {wide}, {wn}>" for b in banks for wide, wn in grids}
+    assert len(launched) >= 21, sorted(launched)
+    named = {r["kernel"] for r in WGRAD_CASES}
+    named_pipe = {n for n in named if n.startswith("conv_wgrad_pipe_kernel<")}
+    assert launched == named - named_pipe, (f"launched without a row: {sorted(launched - named)}; "
+                                            f"rows naming no launch: {sorted(named - named_pipe - launched)}")
+    # the pipe kernel: a row for every filter bank, on an instantiation of the sixteen-wave grid the launcher holds (the other wave grids:
+    # test_wgrad_pipe_kernel in tests/test_gpu_kernels.py)
+    assert named_pipe <= pipes and {re.match(r"conv_wgrad_pipe_kernel<(\d+), 256, \w+, 8>", n).group(1) for n in named_pipe} == banks
+
+
+def _reported_wgrad_kernels(row):
+    """what din_conv_kernel_names(d, 2) answers for a row of tests/test_gpu_wgrad.py under the row's options (host only)"""
+    from din_amd import _lib
+    from tests.test_gpu_wgrad import _geometry
+    nb, cin, h, w, cout, k, s, p, dil, oh, ow = _geometry(row)
+    d = _lib.ConvDesc()
+    d.nb, d.h, d.w, d.cin, d.oh, d.ow, d.cout = nb, h, w, cin, oh, ow, cout
+    d.kh, d.kw, d.sh, d.sw, d.ph, d.pw, d.dh, d.dw = k[0], k[1], s[0], s[1], p[0], p[1], dil, dil
+    d.ldi, d.cioff, d.ldo, d.cooff = row["ld"]
+    d.dtype, d.in_u8 = (_lib.DIN_F32 if row["dtype"] == "fp32" else _lib.DIN_BF16), int(bool(row.get("u8")))
+    buf = ctypes.create_string_buffer(512)
+    try:
+        for name, value in row["opts"].items():
+            _lib.set_option(name, value)
+        rc = _lib.load().din_conv_kernel_names(ctypes.byref(d), 2, 0, 0, 0, buf, len(buf))
+    finally:
+        for name in row["opts"]:
+            _lib.set_option(name, None)
+    assert 0 < rc <= len(buf), _lib.load().din_last_error_string()
+    assert _lib.load().din_conv_kernel_names(ctypes.byref(d), 2, 2, 0, 0, buf, 0) == -1, "flags are fwd / dgrad arguments"
+    return buf.value.decode().split("\n")[:-1]
+
+
+def test_wgrad_tail_kernel_reports_its_own_name():
+    """a bf16 layer whose channels are no whole 16-byte chunks runs conv_wgrad_bf16_tail_kernel and shares the tile code (128, 128) with
+    conv_wgrad_bf16_kernel<128>: the reporter names the kernel that runs (and the column-sum launch the tail kernel needs for its bias)"""
+    from tests.test_gpu_wgrad import WGRAD_CASES
+    rows = {r["name"]: r for r in WGRAD_CASES}
+    assert rows["tail_cin3"]["code"] == rows["v3_128"]["code"] == (128, 128)
+    assert _reported_wgrad_kernels(rows["tail_cin3"]) == [
+        "conv_wgrad_bf16_tail_kernel", "conv_wgrad_reduce_kernel", "colsum_vec_kernel<unsigned short, 8>"]
+    assert _reported_wgrad_kernels(rows["v3_128"]) == ["conv_wgrad_bf16_kernel<128>", "conv_wgrad_reduce_kernel"]
+
+
+def test_wgrad_stem_option_settings_report_three_kernels():
+    """the three forms of the 32 -> 64 stem layer share the tile code (0, 64); each option setting reports its own instantiation"""
+    from tests.test_gpu_wgrad import WGRAD_CASES
+    rows = [r for r in WGRAD_CASES if r["name"].startswith("small2_")]
+    assert len(rows) == 3 and {r["code"] for r in rows} == {(0, 64)}
+    got = [_reported_wgrad_kernels(r)[0] for r in rows]
+    assert got == [r["kernel"] for r in rows] and len(set(got)) == 3, got
+
+
+def test_every_weight_gradient_kernel_of_the_backbones_has_a_gpu_row():
+    """profiles/wgrad_kernel_names.txt (tools/conv_dispatch_table.py --names --wgrad: the main kernels the no-option decisions of both backbones
+    reach) against the rows of tests/test_gpu_wgrad.py: every kernel the product launches is tested by name"""
+    from tests.test_gpu_wgrad import WGRAD_CASES
+    with open(os.path.join(ROOT, "profiles", "wgrad_kernel_names.txt")) as fh:
+        reached = {line.split("  <-  ")[0] for line in fh.read().splitlines() if line}
+    assert len(reached) >= 18
+    assert reached <= {r["kernel"] for r in WGRAD_CASES}, sorted(reached - {r["kernel"] for r in WGRAD_CASES})
 
 
 def test_every_pool_kernel_instantiation_has_a_row_in_the_fp64_table():

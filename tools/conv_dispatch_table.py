@@ -8,7 +8,7 @@ din_conv_kernel_variant report it (no GPU needed): one line per case,
 Cases: every distinct conv descriptor of the Inception-v3 trunk (up to Mixed_6e, with the channel-offset views and the fused sibling
 groups nhwc.py lays out) and of VGG16, at 12 / 24 / 96 frames of 720x1280 and at the small test geometry, both dtypes, plus one view
 per kernel family whose channel offsets are not multiples of 8; each with no option set and with every selection option of
-csrc/conv_igemm.hip set alone to each value its comment documents.
+csrc/conv_igemm.hip (choose_gather) set alone to each value its comment documents.
 
 The reporter answers from the launcher's own selection function, so two builds that print the same table launch the same kernels:
 
@@ -19,7 +19,20 @@ The full table has ~47 000 lines.  --summary prints what profiles/conv_dispatch_
 
 --names prints what profiles/conv_kernel_names.txt holds: every distinct kernel instantiation din_conv_kernel_names reports over all those
 cases with no option set -- forward, and data gradient with flags 0 / MASK / ACCUM / MASK|ACCUM (mask view = the layer's input view) --
-each once, with one descriptor that reaches it.  tests/test_gpu_conv_fwd_dgrad.py holds a row for every name in that file."""
+each once, with one descriptor that reaches it.  tests/test_gpu_conv_fwd_dgrad.py holds a row for every name in that file.
+
+The weight gradient follows (--wgrad: only it): for the same descriptors, geometries and dtypes,
+
+    <label> which=2 <option>  ->  bm bn workspace_bytes(2) group_key
+
+with no option set and with every weight-gradient option of csrc/conv_wgrad.hip (plan_wgrad) set alone to each documented value, and for
+the 1x1 sibling groups of the Inception blocks
+
+    <label of the first sibling> multi<n> <option>  ->  din_conv1x1_wgrad_multi_workspace
+
+--names --wgrad prints what profiles/wgrad_kernel_names.txt holds: the first line of din_conv_kernel_names(d, 2) -- the main kernel, spelled
+as rocprofv3 prints it -- over all those cases with no option set.  Every name in that file has a row in tests/test_gpu_wgrad.py or in
+PIPE_CASES of tests/test_gpu_kernels.py."""
 import argparse
 import ctypes as C
 import os
@@ -36,12 +49,17 @@ OPTIONS = [
     ("DIN_CONV_ONESTAGE", ("0",)), ("DIN_CONV_SMALL_WAVES", ("4",)), ("DIN_CONV_SMALL_NBUF8", ("2",)), ("DIN_CONV_SMALL_EPI", ("0",)),
     ("DIN_GATHER_PIPE", ("1", "2")), ("DIN_HALO_WAVES", ("8",)),
 ]
+WGRAD_OPTIONS = [
+    ("DIN_CONV_BN", ("128",)), ("DIN_CONV_SMALL", ("0",)), ("DIN_WGRAD_HALO", ("0", "2")), ("DIN_WGRAD_RING", ("0", "2", "3")),
+    ("DIN_WGRAD_PIPE", ("0", "3")), ("DIN_WGRAD_PIPE_PAD", ("15",)), ("DIN_WGRAD_ATOMIC", ("1",)), ("DIN_WGRAD_BLOCKS", ("20", "100", "2000")),
+    ("DIN_WGRAD_SMALL_WAVES", ("4",)), ("DIN_WGRAD_SMALL_RING", ("2",)), ("DIN_WGRAD_PIPE_WAVES", ("8", "4")), ("DIN_WGRAD_GROUP", ("0",)),
+]
 GEOMETRIES = [(12, 720, 1280), (24, 720, 1280), (96, 720, 1280), (6, 139, 203)]
 FIELDS = ("cin", "h", "w", "cout", "oh", "ow", "kh", "kw", "sh", "sw", "ph", "pw", "ldi", "cioff", "ldo", "cooff", "in_u8")
 
 
-def descriptors(L, nhwc, backbone, nb, h, w, dt):
-    """the distinct conv descriptors of one backbone graph, in graph order"""
+def descriptors(L, nhwc, backbone, nb, h, w, dt, groups=None):
+    """the distinct conv descriptors of one backbone graph, in graph order; groups (a list): gains the 1x1 sibling groups' member descriptors"""
     from din_amd.backbone import backbone as B
     net = (B.MyInception_v3 if backbone == "inv3" else B.MyVGG16)(compute_dtype="bf16" if dt == L.DIN_BF16 else "fp32")
     g = net.build_graph(h, w, dt)
@@ -61,6 +79,8 @@ def descriptors(L, nhwc, backbone, nb, h, w, dt):
         d.cout = sum(g.ops[j].dst.c for j in idx)
         d.ldo, d.cooff = d.cout, 0
         out.append(d)
+        if groups is not None and d.kh == 1 and d.kw == 1:
+            groups.append([out_of(g, nhwc, j, nb, dt) for j in idx])
     return out
 
 
@@ -97,12 +117,37 @@ def report(lib, d, which):
     return f"{bm.value} {bn.value} {fl.value} {lib.din_conv_workspace_bytes(C.byref(d), 0)} {lib.din_conv_workspace_bytes(C.byref(d), 1)}"
 
 
-def kernel_names(lib, d, which, flags, ldm=0, moff=0):
+def report_wgrad(lib, d):
+    bm, bn = C.c_int32(-1), C.c_int32(-1)
+    assert lib.din_conv_kernel_tile(C.byref(d), 2, C.byref(bm), C.byref(bn)) == 0
+    return f"{bm.value} {bn.value} {lib.din_conv_workspace_bytes(C.byref(d), 2)} {lib.din_conv_wgrad_group_key(C.byref(d))}"
+
+
+def report_multi(L, lib, members):
+    """din_conv1x1_wgrad_multi_workspace of a sibling group (the siblings read one tensor: pixels and cin of the first)"""
+    d0 = members[0]
+    srcs = (L.ConvWSrc * len(members))()
+    for s, m in zip(srcs, members):
+        s.cout, s.ldo, s.cooff = m.cout, m.ldo, m.cooff
+    return str(lib.din_conv1x1_wgrad_multi_workspace(len(members), srcs, d0.dtype, d0.nb * d0.h * d0.w, d0.cin))
+
+
+def wgrad_names_table(lib, cases):
+    """{main weight-gradient kernel: label of the first descriptor that reaches it}"""
+    found = {}
+    for label, d in cases:
+        if d.in_u8 and not lib.din_conv_accepts_u8(C.byref(d)):
+            continue
+        found.setdefault(kernel_names(lib, d, 2, 0, sep="\n")[0], label)
+    return found
+
+
+def kernel_names(lib, d, which, flags, ldm=0, moff=0, sep=None):
     """the lines din_conv_kernel_names answers for one launch"""
     buf = C.create_string_buffer(4096)
     rc = lib.din_conv_kernel_names(C.byref(d), which, flags, ldm, moff, buf, len(buf))
     assert 0 < rc <= len(buf), f"din_conv_kernel_names: {rc}"
-    return buf.value.decode().split()
+    return buf.value.decode().split(sep)
 
 
 def names_table(L, lib, cases):
@@ -122,23 +167,31 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--summary", action="store_true", help="no-option decisions at 96 frames and at the small geometry, one line per descriptor")
     ap.add_argument("--names", action="store_true", help="every distinct kernel instantiation of the no-option decisions, with one launch that reaches it")
+    ap.add_argument("--wgrad", action="store_true", help="the weight-gradient part only (with --names: the weight-gradient kernel names)")
     args = ap.parse_args()
     from din_amd import _lib as L, nhwc
     lib = L.load()
-    for name, _ in OPTIONS:
+    for name, _ in OPTIONS + WGRAD_OPTIONS:
         L.set_option(name, None)
-    cases = []
+    cases, groups = [], []
     for backbone in ("inv3", "vgg16"):
         for dt, dtn in ((L.DIN_BF16, "bf16"), (L.DIN_F32, "fp32")):
             for nb, h, w in GEOMETRIES:
-                descs = descriptors(L, nhwc, backbone, nb, h, w, dt)
+                sib = []
+                descs = descriptors(L, nhwc, backbone, nb, h, w, dt, sib)
+                label = lambda d: (f"{backbone} {dtn} nb{nb} {d.h}x{d.w} c{d.cin}>{d.cout} k{d.kh}x{d.kw} s{d.sh} p{d.ph},{d.pw} "
+                                   f"ld{d.ldi}+{d.cioff}>{d.ldo}+{d.cooff}{' u8' if d.in_u8 else ''}")
+                groups += [(f"{label(m[0])} multi{len(m)}", m) for m in sib]
                 seen = set()
                 for d in descs + misaligned(L, nhwc, descs):
                     key = tuple(getattr(d, f) for f in FIELDS)
                     if key not in seen:
                         seen.add(key)
-                        cases.append((f"{backbone} {dtn} nb{nb} {d.h}x{d.w} c{d.cin}>{d.cout} k{d.kh}x{d.kw} s{d.sh} p{d.ph},{d.pw} "
-                                      f"ld{d.ldi}+{d.cioff}>{d.ldo}+{d.cooff}{' u8' if d.in_u8 else ''}", d))
+                        cases.append((label(d), d))
+    if args.names and args.wgrad:
+        for name, label in sorted(wgrad_names_table(lib, cases).items()):
+            print(f"{name}  <-  {label}")
+        return
     if args.names:
         for name, label in sorted(names_table(L, lib, cases).items()):
             print(f"{name}  <-  {label}")
@@ -148,6 +201,20 @@ def main():
             if d.nb in (96, 6):
                 f, g = report(lib, d, 0).split(), report(lib, d, 1).split()
                 print(f"{label}  ->  {' '.join(f[:3])} / {' '.join(g[:3])}  {f[3]} {f[4]}")
+        return
+    for opt, val in [(None, None)] + [(o, v) for o, vals in WGRAD_OPTIONS for v in vals]:
+        if opt:
+            L.set_option(opt, val)
+        try:
+            tag = opt + '=' + val if opt else '-'
+            for label, d in cases:
+                print(f"{label} which=2 {tag}  ->  {report_wgrad(lib, d)}")
+            for label, members in groups:
+                print(f"{label} {tag}  ->  {report_multi(L, lib, members)}")
+        finally:
+            if opt:
+                L.set_option(opt, None)
+    if args.wgrad:
         return
     for opt, val in [(None, None)] + [(o, v) for o, vals in OPTIONS for v in vals]:
         if opt:
