@@ -130,6 +130,14 @@ SIGNATURES: Dict[str, tuple] = {
     "din_actor_position_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "din_actor_attn_fwd": (_I, [_P, _P, _P, _L, _P, _P, _P, _F, _F, _U64, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "din_actor_attn_bwd": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P, _F, _U64, _P, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P]),
+    "din_lstm_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "din_lstm_bwd_workspace": (_L, [_I, _I, _I]),
+    "din_lstm_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "din_pctdm_pool_fwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "din_pctdm_pool_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "din_pctdm_att_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "din_pctdm_att_bwd_workspace": (_L, [_I, _I]),
+    "din_pctdm_att_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
     "din_axpby": (_I, [_P, _P, _P, _F, _F, _L, _P]),
     "din_mask_actors": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "din_scale_by_param": (_I, [_P, _P, _I, _P, _I, _L, _P]),

@@ -24,6 +24,7 @@ from .infer_module.ARG_infer_module import GCN_Module
 from .infer_module.AT_infer_module import Actor_Transformer, Embfeature_PositionEmbedding
 from .infer_module.dynamic_infer_module import (Dynamic_Person_Inference, Hierarchical_Dynamic_Inference,
                                                 Multi_Dynamic_Inference)
+from .infer_module.pctdm_infer_module import PCTDM
 from .infer_module.positional_encoding import Context_PositionEmbeddingSine
 from .infer_module.TCE_STBiP_module import MultiHeadLayerEmbfeatureContextEncoding
 from .roi_align.roi_align import RoIAlign
@@ -395,4 +396,56 @@ class AT_volleyball(_DynamicBase):
         states = self.AT(x, seeds=tuple(self._dropout_seed() for _ in range(3)))          # :835
         s = states.reshape(B, 1 if cfg.temporal_pooled_first else T, N, -1)
         scores = ops.HeadFunction.apply(s, self.fc_activities.weight, self.fc_activities.bias, None)   # :843-857
+        return {"activities": scores}
+
+
+class PCTDM_volleyball(_DynamicBase):
+    """the PCTDM baseline for the volleyball dataset (reference infer_model.py:472-608): the shared trunk, the PCTDM block over the N players
+    of every frame (a Bi-LSTM over the players, the direction max, intra-team attention, one LSTM over each team), LayerNorm([T, 2000]), ReLU,
+    dropout, fc_activities per frame, mean over T.  Same constructor, `forward((images, boxes)) -> {'activities': [B, A]}`, `loadmodel` and
+    state_dict keys (backbone.*, fc_emb_1, nl_emb_1, pctdm.*, pctdm_nl, fc_activities, fc_actions), so the reference's checkpoints load
+    unchanged.  `loadmodel` loads the backbone only: the reference comments the embedding out (:522).
+
+    PCTDM's sizes are fixed in the reference (Bi-LSTM input 1024, hidden 1000, LayerNorm([T, 2000]), Linear(2000, ...)), so
+    cfg.num_features_boxes must be 1024 -- at any other width the reference's own forward fails -- and anything else is refused before a
+    single module is built.
+
+    Deliberate differences from the reference: `fc_actions` is created, initialised and saved but has requires_grad False and is never
+    evaluated (the reference has its use commented out, :582-585), as in AT_volleyball.  The dropout mask is the counter hash of the other
+    models here, not the host RNG stream.  No torch.cuda.empty_cache() per step (:574).  'res18' / 'vgg19' / 'alex' are out of scope
+    (make_backbone)."""
+
+    FEATURES = 2000                                                                        # two teams x hidden 1000
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        if cfg.num_features_boxes != 1024:
+            raise NotImplementedError(f"pctdm_volleyball: PCTDM's Bi-LSTM input (1024) and pctdm_nl's 2000 columns are fixed in the reference; "
+                                      f"num_features_boxes = {cfg.num_features_boxes} is not on the MI355X hot path")
+        T = cfg.num_frames
+        self._build_trunk(cfg)
+        self.pctdm = PCTDM(cfg)                                                            # :505
+        self.pctdm_nl = nn.LayerNorm([T, self.FEATURES])
+        self.dropout_global = nn.Dropout(p=cfg.train_dropout_prob)      # holder of p; the mask is fused in the LN kernel
+        self.fc_activities = nn.Linear(self.FEATURES, cfg.num_activities)
+        self.fc_actions = nn.Linear(self.FEATURES, cfg.num_actions)
+        self._init_linears()
+        self.fc_actions.requires_grad_(False)
+
+    def loadmodel(self, filepath):
+        state = torch.load(filepath, map_location="cpu")
+        self.backbone.load_state_dict(state["backbone_state_dict"])                        # (:521; the embedding is not loaded, :522)
+        print("Load model states from: ", filepath)
+
+    def forward(self, batch_data):
+        images_in, boxes_in = batch_data
+        cfg = self.cfg
+        B, T, N = images_in.shape[0], images_in.shape[1], cfg.num_boxes
+        x = self._embed(images_in, boxes_in, N)                                           # [B,T,N,1024]  (:526-570)
+        states = self.pctdm(x).reshape(B, T, self.FEATURES)                               # :573-576
+        p = cfg.train_dropout_prob if self.training else 0.0
+        s = ops.layer_norm(states, self.pctdm_nl.weight, self.pctdm_nl.bias, relu=True, drop_p=p, seed=self._dropout_seed())   # :577-579
+        # fc_activities per frame, mean over T (:589-592): the head kernel with one "actor" per frame, whose max is the identity
+        scores = ops.HeadFunction.apply(s.reshape(B, T, 1, self.FEATURES), self.fc_activities.weight, self.fc_activities.bias, None)
         return {"activities": scores}

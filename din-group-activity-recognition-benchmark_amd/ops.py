@@ -758,6 +758,154 @@ class ActorAttentionFunction(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# PCTDM baseline: LSTM recurrence, direction pooling, intra-team attention
+# ------------------------------------------------------------------------------------------------
+def lstm_workspace_floats(rows: int, dirs: int, hidden: int) -> int:
+    """scratch din_lstm_bwd asks for (include/din_hip.h): W_hh^T of every direction and the carried cell-state gradient"""
+    return int(L.load().din_lstm_bwd_workspace(rows, dirs, hidden))
+
+
+def pctdm_att_workspace_floats(g: int, h: int) -> int:
+    """scratch din_pctdm_att_bwd asks for (include/din_hip.h): the per-frame partials of d w_e and d b_e"""
+    return int(L.load().din_pctdm_att_bwd_workspace(g, h))
+
+
+def _lstm_dw_hh(lib, h_prev, d_pre, w_hh):
+    """dW_hh [D, 4H, H] = d_pre^T h_prev per direction over the R*S rows: one call of the weight-gradient contraction each, reading the two
+    direction slices in place through their row stride (copies padded to a multiple of 4 columns when H is not one)"""
+    r, s, dirs, h = h_prev.shape
+    rows, st = r * s, _stream()
+    dw = torch.empty_like(w_hh)
+    for d in range(dirs):
+        if h % 4 == 0:
+            x, ldi, cioff = h_prev, dirs * h, d * h
+        else:
+            hp = (h + 3) // 4 * 4
+            x = torch.zeros((rows, hp), dtype=torch.float32, device=h_prev.device)
+            x[:, :h] = h_prev[:, :, d].reshape(rows, h)
+            ldi, cioff = hp, 0
+        desc = _desc(1, 1, rows, h, 4 * h, 1, 1, 0, 0, 1, ldi, dirs * 4 * h)
+        desc.cioff, desc.cooff = cioff, d * 4 * h
+        ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(desc), 2), h_prev.device, "wgrad")
+        L.check(lib.din_conv_wgrad(C.byref(desc), _ptr(x), _ptr(d_pre), _ptr(dw[d]), None, None, None, None, 0, _ptr(ws), wsb, st),
+                "lstm_wgrad")
+    return dw
+
+
+class LSTMFunction(torch.autograd.Function):
+    """pre [R, S, D, 4H] = x W_ih^T + b_ih + b_hh of all steps (gate order i, f, g, o), w_hh [D, 4H, H] -> h [R, S, D*H] in torch.nn.LSTM's
+    batch_first layout (forward half, then reverse half, each at its own position) -- reference pctdm_infer_module.py:83 / :114 after the
+    input projection.  Zero initial state; D = 2 walks the second direction from the last position.  One launch per step.
+    want_state: also return the activated gates [R, S, D, 4H] and the cell states [R, S, D, H], for inspection."""
+
+    @staticmethod
+    def forward(ctx, pre, w_hh, want_state: bool = False):
+        lib = L.load()
+        pre, w_hh = pre.contiguous(), w_hh.contiguous()
+        require_gpu(pre, w_hh)
+        r, s, dirs, h4 = pre.shape
+        h = h4 // 4
+        assert tuple(w_hh.shape) == (dirs, 4 * h, h) and h4 == 4 * h, (pre.shape, w_hh.shape)
+        dev = pre.device
+        out = torch.empty((r, s, dirs * h), dtype=torch.float32, device=dev)
+        gates = torch.empty((r, s, dirs, 4 * h), dtype=torch.float32, device=dev)
+        cells = torch.empty((r, s, dirs, h), dtype=torch.float32, device=dev)
+        L.check(lib.din_lstm_fwd(_ptr(pre), _ptr(w_hh), r, s, dirs, h, _ptr(out), _ptr(gates), _ptr(cells), _stream()), "lstm_fwd")
+        ctx.save_for_backward(w_hh, gates, cells)
+        if want_state:
+            ctx.mark_non_differentiable(gates, cells)
+            return out, gates, cells
+        return out
+
+    @staticmethod
+    def backward(ctx, gout, *_):
+        lib = L.load()
+        w_hh, gates, cells = ctx.saved_tensors
+        r, s, dirs, h = cells.shape
+        gout = gout.contiguous()
+        d_pre = torch.empty_like(gates)
+        h_prev = torch.empty_like(cells)
+        nws = lstm_workspace_floats(r, dirs, h)
+        ws = torch.empty(nws, dtype=torch.float32, device=gout.device)
+        L.check(lib.din_lstm_bwd(_ptr(gout), _ptr(gates), _ptr(cells), _ptr(w_hh), r, s, dirs, h, _ptr(d_pre), _ptr(h_prev), _ptr(ws), nws,
+                                 _stream()), "lstm_bwd")
+        dw = _lstm_dw_hh(lib, h_prev, d_pre, w_hh) if ctx.needs_input_grad[1] else None
+        return d_pre, dw, None
+
+
+class PctdmPoolFunction(torch.autograd.Function):
+    """lstm_out [G, N, 2H] -> (pooled [G, N, H] = max of the two direction halves, context [G, H] = mean of pooled over N, winner bool
+    [G, N, H] = the reverse half won) -- reference pctdm_infer_module.py:94-96 and :106"""
+
+    @staticmethod
+    def forward(ctx, lstm_out):
+        lib = L.load()
+        lstm_out = lstm_out.contiguous()
+        require_gpu(lstm_out)
+        g, n, h2 = lstm_out.shape
+        h = h2 // 2
+        assert h2 == 2 * h, lstm_out.shape
+        dev = lstm_out.device
+        pooled = torch.empty((g, n, h), dtype=torch.float32, device=dev)
+        winner = torch.empty((g, n, h), dtype=torch.uint8, device=dev)
+        context = torch.empty((g, h), dtype=torch.float32, device=dev)
+        L.check(lib.din_pctdm_pool_fwd(_ptr(lstm_out), g, n, h, _ptr(pooled), _ptr(winner), _ptr(context), _stream()), "pctdm_pool_fwd")
+        ctx.save_for_backward(winner)
+        wb = winner.view(torch.bool)
+        ctx.mark_non_differentiable(wb)
+        return pooled, context, wb
+
+    @staticmethod
+    def backward(ctx, g_pooled, g_context, _gw):
+        lib = L.load()
+        (winner,) = ctx.saved_tensors
+        g, n, h = winner.shape
+        g_pooled = (g_pooled if g_pooled is not None else torch.zeros((g, n, h), device=winner.device)).contiguous()
+        g_context = (g_context if g_context is not None else torch.zeros((g, h), device=winner.device)).contiguous()
+        d = torch.empty((g, n, 2 * h), dtype=torch.float32, device=winner.device)
+        L.check(lib.din_pctdm_pool_bwd(_ptr(g_pooled), _ptr(g_context), _ptr(winner), g, n, h, _ptr(d), _stream()), "pctdm_pool_bwd")
+        return d
+
+
+class PctdmAttentionFunction(torch.autograd.Function):
+    """pooled, src = att_source_weights(pooled) [G, N, H], ctx = att_context_weights(context) [G, H], w_e [1, H] | [H], b_e [1] ->
+    (y = pooled + pooled * gamma [G, N, H], gamma [G, N] = softmax inside each team of N / 2 players of w_e . tanh(src + ctx) + b_e) --
+    reference pctdm_infer_module.py:52-59 and :112-114 around its three Linear layers"""
+
+    @staticmethod
+    def forward(ctx, pooled, src, cx, w_e, b_e):
+        lib = L.load()
+        pooled, src, cx, w_e, b_e = pooled.contiguous(), src.contiguous(), cx.contiguous(), w_e.contiguous(), b_e.contiguous()
+        require_gpu(pooled, src, cx, w_e, b_e)
+        g, n, h = pooled.shape
+        assert tuple(src.shape) == (g, n, h) and tuple(cx.shape) == (g, h) and w_e.numel() == h and b_e.numel() == 1, \
+            (pooled.shape, src.shape, cx.shape, w_e.shape, b_e.shape)
+        y = torch.empty_like(pooled)
+        gamma = torch.empty((g, n), dtype=torch.float32, device=pooled.device)
+        L.check(lib.din_pctdm_att_fwd(_ptr(pooled), _ptr(src), _ptr(cx), _ptr(w_e), _ptr(b_e), g, n, h, _ptr(y), _ptr(gamma), _stream()),
+                "pctdm_att_fwd")
+        ctx.save_for_backward(pooled, src, cx, w_e, gamma)
+        ctx.shapes = (w_e.shape, b_e.shape)
+        ctx.mark_non_differentiable(gamma)
+        return y, gamma
+
+    @staticmethod
+    def backward(ctx, g_y, _gg):
+        lib = L.load()
+        pooled, src, cx, w_e, gamma = ctx.saved_tensors
+        g, n, h = pooled.shape
+        g_y = g_y.contiguous()
+        d_pooled, d_src, d_ctx = torch.empty_like(pooled), torch.empty_like(src), torch.empty_like(cx)
+        d_w_e = torch.empty(ctx.shapes[0], dtype=torch.float32, device=pooled.device)
+        d_b_e = torch.empty(ctx.shapes[1], dtype=torch.float32, device=pooled.device)
+        nws = pctdm_att_workspace_floats(g, h)
+        ws = torch.empty(nws, dtype=torch.float32, device=pooled.device)
+        L.check(lib.din_pctdm_att_bwd(_ptr(g_y), _ptr(pooled), _ptr(src), _ptr(cx), _ptr(w_e), _ptr(gamma), g, n, h, _ptr(d_pooled), _ptr(d_src),
+                                      _ptr(d_ctx), _ptr(d_w_e), _ptr(d_b_e), _ptr(ws), nws, _stream()), "pctdm_att_bwd")
+        return d_pooled, d_src, d_ctx, d_w_e, d_b_e
+
+
+# ------------------------------------------------------------------------------------------------
 # layout views for API parity (NOT on the training path)
 # ------------------------------------------------------------------------------------------------
 class NHWCToNCHWFunction(torch.autograd.Function):

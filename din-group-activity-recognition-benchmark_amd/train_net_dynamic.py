@@ -28,7 +28,8 @@ import torch.utils.data as data
 
 from . import parallel
 from .input_feed import DeviceFeed
-from .infer_model import ARG_volleyball, AT_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, Dynamic_volleyball
+from .infer_model import (ARG_volleyball, AT_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, Dynamic_volleyball,
+                          PCTDM_volleyball)
 from .optim import FusedAdam
 from .utils import AverageMeter, Timer, print_log
 
@@ -89,9 +90,9 @@ class SyntheticCollective(SyntheticVolleyball):
 def build_model(cfg):
     registry = {"dynamic_volleyball": Dynamic_volleyball, "dynamic_tce_volleyball": Dynamic_TCE_volleyball,
                 "dynamic_collective": Dynamic_collective, "arg_volleyball": ARG_volleyball,
-                "at_volleyball": AT_volleyball}                                                # reference train_net_dynamic.py:66-73
+                "at_volleyball": AT_volleyball, "pctdm_volleyball": PCTDM_volleyball}          # reference train_net_dynamic.py:66-73
     if cfg.inference_module_name not in registry:
-        raise NotImplementedError(f"{cfg.inference_module_name}: only the DIN models and the ARG / AT baselines are on the MI355X hot path")
+        raise NotImplementedError(f"{cfg.inference_module_name}: only the DIN models and the ARG / AT / PCTDM baselines are on the MI355X hot path")
     return registry[cfg.inference_module_name](cfg)
 
 

@@ -11,4 +11,4 @@ _ROOT = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
 if _ROOT not in _sys.path:
     _sys.path.insert(0, _ROOT)
 from din_amd.infer_model import *       # noqa: E402,F401,F403
-from din_amd.infer_model import Dynamic_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, ARG_volleyball, AT_volleyball   # noqa: E402,F401
+from din_amd.infer_model import Dynamic_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, ARG_volleyball, AT_volleyball, PCTDM_volleyball   # noqa: E402,F401

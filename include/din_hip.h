@@ -536,6 +536,54 @@ int din_actor_attn_bwd(const float* g_out, const float* q, const float* k, const
                        int64_t ws_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PCTDM baseline: the one-layer LSTM recurrence and the pooling / attention between its two LSTMs.
+ *
+ * LSTM (reference infer_module/pctdm_infer_module.py:23-24 Bi_Lstm and :47 Intra_Group_LSTM, run at :83 and :114), everything after the
+ *   input projection.  pre fp32 [rows][steps][dirs][4*hidden] = x W_ih^T + b_ih + b_hh of all steps (one contraction by the caller), gate
+ *   order i, f, g, o; w_hh fp32 [dirs][4*hidden][hidden]; dirs 1 or 2, direction 1 walks the positions steps-1 .. 0.  Zero initial state.
+ *     z = pre + h W_hh^T;  i, f, o = sigmoid;  g = tanh;  c = f * c + i * g;  h = o * tanh(c)     (accurate expf / tanhf, true division)
+ *   Outputs: h_out [rows][steps][dirs*hidden], torch's layout (position-major, forward half then reverse half, both at the position they
+ *   belong to); gates [rows][steps][dirs][4*hidden] (activated) and cells [rows][steps][dirs][hidden], kept for the backward.
+ *   One plain launch per step on the caller's stream, grid = (slices of 8 hidden units) x dirs: the step boundary is the all-to-all
+ *   dependency; no grid-wide barrier, no cooperative launch, no workgroup waits for another.  A workgroup streams its 4 x 8 rows of w_hh with
+ *   16-byte loads (4-byte loads when hidden % 4 != 0) against the previous h of 16 rows held in LDS; more rows are further chunks.
+ *   Backward: g_out [rows][steps][dirs*hidden] -> d_pre [rows][steps][dirs][4*hidden] and h_prev [rows][steps][dirs][hidden] = the hidden
+ *   state that entered each step (zeros at a direction's first step).  dW_hh is NOT formed here: it is one din_conv_wgrad per direction over
+ *   the rows*steps rows with x = h_prev and gy = d_pre.  steps + 1 launches: w_hh^T into the workspace, then one launch per step in reverse
+ *   walk order.  ws: ws_floats >= din_lstm_bwd_workspace(rows, dirs, hidden) = dirs*4*hidden^2 + rows*dirs*hidden floats.
+ *   Limits: rows, steps >= 1; 1 <= hidden <= 1024; every pointer 16-byte aligned; else DIN_E_ARG, nothing is read or written.
+ *   Deterministic (fixed-order sums, no atomics), fp32 throughout.
+ *
+ * Pool (pctdm_infer_module.py:94-96, :106): lstm_out fp32 [g][n][2*h] -> pooled [g][n][h] = max of the two direction halves of each player
+ *   (the reference's view(g, 1, 2n, h) + MaxPool2d((2, 1)) pairs exactly those two rows; the first of two equal values wins),
+ *   winner uint8 [g][n][h] (1 = the reverse half), context [g][h] = mean of pooled over n (players added in order, then divided by n).
+ *   Backward: g_pooled [g][n][h], g_context [g][h] -> d_lstm_out [g][n][2*h], every element written.  One launch each; n <= 32.
+ *
+ * Attention (pctdm_infer_module.py:52-59 get_att_weigths, :112-114): pooled, src = att_source_weights(pooled) fp32 [g][n][h],
+ *   ctx = att_context_weights(context) fp32 [g][h], w_e fp32 [h], b_e fp32 [1] (att_extra_weights, on the device).
+ *     score[g][i] = <w_e, tanh(src[g][i] + ctx[g])> + b_e;  gamma = softmax of the scores inside each of the two teams of n / 2 players, the
+ *     team's maximum subtracted;  y = pooled + pooled * gamma.
+ *   Outputs: y [g][n][h], gamma [g][n].  Backward: g_y -> d_pooled, d_src [g][n][h], d_ctx [g][h], d_w_e [h], d_b_e [1], all overwritten;
+ *   d_w_e / d_b_e are per-frame partials in ws, then one reduce launch that adds the frames in order (d_b_e is the plain sum of the score
+ *   gradients: zero up to rounding, since a softmax ignores a common shift).  ws: ws_floats >= din_pctdm_att_bwd_workspace(g, h) = g*h + g.
+ *   Limits: n even, 2 <= n <= 32; every pointer 4-byte aligned; else DIN_E_ARG.  Forward 1 launch, backward 2; deterministic, fp32.
+ * ---------------------------------------------------------------------------------------------- */
+int din_lstm_fwd(const float* pre, const float* w_hh, int rows, int steps, int dirs, int hidden, float* h_out, float* gates, float* cells,
+                 void* stream);
+int64_t din_lstm_bwd_workspace(int rows, int dirs, int hidden);
+int din_lstm_bwd(const float* g_out, const float* gates, const float* cells, const float* w_hh, int rows, int steps, int dirs, int hidden,
+                 float* d_pre, float* h_prev, float* ws, int64_t ws_floats, void* stream);
+int din_pctdm_pool_fwd(const float* lstm_out, int g, int n, int h, float* pooled, uint8_t* winner, float* context, void* stream);
+int din_pctdm_pool_bwd(const float* g_pooled, const float* g_context, const uint8_t* winner, int g, int n, int h, float* d_lstm_out,
+                       void* stream);
+int din_pctdm_att_fwd(const float* pooled, const float* src, const float* ctx, const float* w_e, const float* b_e, int g, int n, int h,
+                      float* y, float* gamma, void* stream);
+int64_t din_pctdm_att_bwd_workspace(int g, int h);
+int din_pctdm_att_bwd(const float* g_y, const float* pooled, const float* src, const float* ctx, const float* w_e, const float* gamma, int g,
+                      int n, int h, float* d_pooled, float* d_src, float* d_ctx, float* d_w_e, float* d_b_e, float* ws, int64_t ws_floats,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Small helpers used by the host mirror
  * ---------------------------------------------------------------------------------------------- */
 /* out = alpha*x + beta*y (fp32, elementwise) -- ratio mean / beta-weighted sum (:144-147), residual sums */
