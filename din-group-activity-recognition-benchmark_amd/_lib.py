@@ -18,6 +18,12 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "din_hip.h")
 
 DIN_F32, DIN_BF16 = 0, 1
+DIN_F32_BF16X3 = 2          # fp32 storage, three-part bf16 MFMA compute: a value of the CONTRACTION entry points' dtype only (din_hip.h)
+
+
+def storage_dtype(dt: int) -> int:
+    """the type tensors are stored in under compute type `dt` -- what bn, pool, roi, cast and prep entry points take"""
+    return DIN_F32 if dt == DIN_F32_BF16X3 else dt
 ABI_VERSION = 9
 CONV_BIAS, CONV_RELU, CONV_ACCUM, CONV_MASK = 1, 2, 4, 8
 

@@ -30,11 +30,13 @@ def _dt(compute_dtype: str) -> int:
         return L.DIN_F32
     if compute_dtype in ("bf16", "bfloat16"):
         return L.DIN_BF16
-    raise ValueError(f"compute_dtype must be 'fp32' or 'bf16', got {compute_dtype!r}")
+    if compute_dtype == "fp32_bf16x3":                     # fp32 storage (every storage decision follows 'fp32'), three-part bf16 MFMA compute
+        return L.DIN_F32_BF16X3
+    raise ValueError(f"compute_dtype must be 'fp32', 'bf16' or 'fp32_bf16x3', got {compute_dtype!r}")
 
 
 def _cpad_image(dt: int) -> int:
-    return 4 if dt == L.DIN_F32 else 8
+    return 4 if L.storage_dtype(dt) == L.DIN_F32 else 8
 
 
 class _GraphBackbone(nn.Module):

@@ -1,6 +1,7 @@
 """Config(dataset_name): attribute bag with the field names and defaults the DIN path reads from the reference's
 config.py:10-104 (only the fields that exist on the hot path; dataset paths and the other methods' knobs are omitted).
-Extra fields: backbone_dtype ('fp32' | 'bf16'); hier_dropout_p (the reference hard-codes F.dropout's defaults -- p = 0.5, always on --
+Extra fields: backbone_dtype ('fp32' | 'bf16' | 'fp32_bf16x3': fp32 storage and fp32 accuracy with every trunk / DIN-module contraction
+multiplied as three bf16 parts per operand on the bf16 matrix pipe -- DIN_F32_BF16X3, include/din_hip.h); hier_dropout_p (the reference hard-codes F.dropout's defaults -- p = 0.5, always on --
 at dynamic_infer_module.py:495; 0.5 keeps that, 0.0 switches it off)."""
 from __future__ import annotations
 

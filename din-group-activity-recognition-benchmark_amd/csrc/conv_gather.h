@@ -46,6 +46,7 @@ struct ConvK {
     void* out2; int ldo2, cooff2, csplit;
     int craw;                       // > 0: produced channels >= craw get neither bias nor ReLU (a sibling whose epilogue runs later, after its pool)
     const unsigned char* u8;        // image layer only: raw uint8 frames [NB][3][H][W], normalised on load (din_conv_desc::in_u8)
+    int mma;                        // host only: 1 = DIN_F32_BF16X3, the launch runs the <f32x3> instantiation of its fp32 kernel (three-part bf16 MFMA)
 };
 
 // host entries of conv_stream.hip: persistent streaming kernel for 1x1 convolutions with a short reduction (ring kept full across tiles)
@@ -143,52 +144,58 @@ __device__ __forceinline__ void staged_tile_store(const ConvK& p, unsigned char*
         // ReLU-backward mask / accumulate inputs of ALL this thread's rows are requested before the staged tile is read back: one
         // memory latency per tile instead of one per row (the per-row load -> wait -> store chain cost 60-80 us per launch on the
         // 288-channel dgrads; profiles/r01_stream_probe.txt)
-        u32x4 mkv[NROW], oldv[NROW];
-        int opx[NROW];
+        // (a tile of more than 24 rows per thread -- fp32 128 x 192 on four waves: 26 -- takes them in two batches: 26 x 9 registers of
+        //  prefetched operands beside the fragments ran the allocation over 256 registers into scratch)
+        constexpr int QB = NROW > 24 ? (NROW + 1) / 2 : NROW;
+        u32x4 mkv[QB], oldv[QB];
+        int opx[QB];
 #pragma unroll
-        for (int q = 0; q < NROW; ++q) {
-            mkv[q] = u32x4{0u, 0u, 0u, 0u}; oldv[q] = u32x4{0u, 0u, 0u, 0u}; opx[q] = -1;
-            const int row = rr + q * RPP, m = m_first + row;
-            if (act && row < BM && m < p.M) {
-                const int64_t px = out_pixel(p, m);
-                opx[q] = (int)px;
-                if (p.flags & DIN_CONV_MASK) mkv[q] = *reinterpret_cast<const u32x4*>(maskp + px * p.ldm + p.moff + co);
-                if (p.flags & DIN_CONV_ACCUM) oldv[q] = *reinterpret_cast<const u32x4*>(outp + px * p.ldo + p.cooff + co);
-            }
-        }
-        __syncthreads();
+        for (int q0 = 0; q0 < NROW; q0 += QB) {
 #pragma unroll
-        for (int q = 0; q < NROW; ++q) {
-            if (opx[q] < 0) continue;
-            const int row = rr + q * RPP;
-            u32x4 v = *reinterpret_cast<const u32x4*>(smem_raw + row * CPITCH + c * 16);
-            const bool second = p.csplit > 0 && co >= p.csplit;
-            if (second) outp = reinterpret_cast<T*>(p.out2);
-            const int64_t o = second ? (int64_t)opx[q] * p.ldo2 + p.cooff2 + (co - p.csplit) : (int64_t)opx[q] * p.ldo + p.cooff + co;
-            if (p.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM)) {
-                const u32x4 mk = mkv[q], old = oldv[q];
-                if constexpr (sizeof(T) == 4) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = __uint_as_float(v[e]);
-                        if ((p.flags & DIN_CONV_MASK) && !(__uint_as_float(mk[e]) > 0.f)) x = 0.f;
-                        if (p.flags & DIN_CONV_ACCUM) x += __uint_as_float(old[e]);
-                        v[e] = __float_as_uint(x);
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo = __uint_as_float(v[e] << 16), hi = __uint_as_float(v[e] & 0xffff0000u);
-                        if (p.flags & DIN_CONV_MASK) {
-                            if (!(__uint_as_float(mk[e] << 16) > 0.f)) lo = 0.f;
-                            if (!(__uint_as_float(mk[e] & 0xffff0000u) > 0.f)) hi = 0.f;
-                        }
-                        if (p.flags & DIN_CONV_ACCUM) { lo += __uint_as_float(old[e] << 16); hi += __uint_as_float(old[e] & 0xffff0000u); }
-                        v[e] = pack_bf16x2(lo, hi);
-                    }
+            for (int q = 0; q < QB; ++q) {
+                mkv[q] = u32x4{0u, 0u, 0u, 0u}; oldv[q] = u32x4{0u, 0u, 0u, 0u}; opx[q] = -1;
+                const int row = rr + (q0 + q) * RPP, m = m_first + row;
+                if (q0 + q < NROW && act && row < BM && m < p.M) {
+                    const int64_t px = out_pixel(p, m);
+                    opx[q] = (int)px;
+                    if (p.flags & DIN_CONV_MASK) mkv[q] = *reinterpret_cast<const u32x4*>(maskp + px * p.ldm + p.moff + co);
+                    if (p.flags & DIN_CONV_ACCUM) oldv[q] = *reinterpret_cast<const u32x4*>(outp + px * p.ldo + p.cooff + co);
                 }
             }
-            *reinterpret_cast<u32x4*>(outp + o) = v;
+            if (q0 == 0) __syncthreads();
+#pragma unroll
+            for (int q = 0; q < QB; ++q) {
+                if (opx[q] < 0) continue;
+                const int row = rr + (q0 + q) * RPP;
+                u32x4 v = *reinterpret_cast<const u32x4*>(smem_raw + row * CPITCH + c * 16);
+                const bool second = p.csplit > 0 && co >= p.csplit;
+                if (second) outp = reinterpret_cast<T*>(p.out2);
+                const int64_t o = second ? (int64_t)opx[q] * p.ldo2 + p.cooff2 + (co - p.csplit) : (int64_t)opx[q] * p.ldo + p.cooff + co;
+                if (p.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM)) {
+                    const u32x4 mk = mkv[q], old = oldv[q];
+                    if constexpr (sizeof(T) == 4) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float x = __uint_as_float(v[e]);
+                            if ((p.flags & DIN_CONV_MASK) && !(__uint_as_float(mk[e]) > 0.f)) x = 0.f;
+                            if (p.flags & DIN_CONV_ACCUM) x += __uint_as_float(old[e]);
+                            v[e] = __float_as_uint(x);
+                        }
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float lo = __uint_as_float(v[e] << 16), hi = __uint_as_float(v[e] & 0xffff0000u);
+                            if (p.flags & DIN_CONV_MASK) {
+                                if (!(__uint_as_float(mk[e] << 16) > 0.f)) lo = 0.f;
+                                if (!(__uint_as_float(mk[e] & 0xffff0000u) > 0.f)) hi = 0.f;
+                            }
+                            if (p.flags & DIN_CONV_ACCUM) { lo += __uint_as_float(old[e] << 16); hi += __uint_as_float(old[e] & 0xffff0000u); }
+                            v[e] = pack_bf16x2(lo, hi);
+                        }
+                    }
+                }
+                *reinterpret_cast<u32x4*>(outp + o) = v;
+            }
         }
 }
 

@@ -6,6 +6,7 @@
 // 16-byte "chunks" along the reduction axis (4 fp32 or 8 bf16).  A lane feeds the MFMA one chunk:
 //   bf16 : v_mfma_f32_16x16x32_bf16  -- the chunk is the lane's 8 k-values          (1 MFMA / chunk set)
 //   fp32 : v_mfma_f32_16x16x4_f32    -- element j of the chunk feeds the j-th of 4 MFMAs (exact fp32)
+//   f32x3: fp32 storage, the chunk's 4 values split into three bf16 parts each, 3 x v_mfma_f32_16x16x32_bf16 (DIN_F32_BF16X3)
 // (the k order inside a k-step is permuted identically for both operands, which a sum does not care about).
 //
 // Tile: 128 pixels x BN (128|64) filters per 256-thread workgroup (4 waves as 2x2), k-step = 8 chunks
@@ -54,6 +55,11 @@ template <> struct Mma<float> {
         for (int j = 0; j < 4; ++j)
             c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[j]), c, 0, 0, 0);
     }
+};
+// fp32 chunks multiplied as three bf16 parts (conv_shared.h).  The split is formed per fragment read: inside the unrolled fragment loops of a
+// k-step the compiler forms each fragment's parts once and reuses them across the (i, j) pairs.
+template <> struct Mma<f32x3_t> {
+    __device__ static void run(const u32x4& a, const u32x4& b, f32x4& c) { mma_f32_bf16x3(a, b, c); }
 };
 template <> struct Mma<bf16_t> {
     __device__ static void run(const u32x4& a, const u32x4& b, f32x4& c) {
@@ -1920,7 +1926,10 @@ int launch_choice(ConvK& k, const GatherChoice& c, int dtype, hipStream_t st, co
     case GATHER_GENERIC: {
         const dim3 grid(c.g.n_px_tiles * k.n_co_tiles, k.splitk);
         const size_t lds = 2 * (BM + 128) * KC * 16;
-        if (dtype == DIN_F32) {
+        if (k.mma) {
+            if (c.tile.bn == 64) hipLaunchKernelGGL((conv_gather_generic_kernel<f32x3_t, 64>), grid, dim3(NTHREADS), lds, st, k);
+            else hipLaunchKernelGGL((conv_gather_generic_kernel<f32x3_t, 128>), grid, dim3(NTHREADS), lds, st, k);
+        } else if (dtype == DIN_F32) {
             if (c.tile.bn == 64) hipLaunchKernelGGL((conv_gather_generic_kernel<float, 64>), grid, dim3(NTHREADS), lds, st, k);
             else hipLaunchKernelGGL((conv_gather_generic_kernel<float, 128>), grid, dim3(NTHREADS), lds, st, k);
         } else {
@@ -1932,7 +1941,7 @@ int launch_choice(ConvK& k, const GatherChoice& c, int dtype, hipStream_t st, co
     case GATHER_TILE: {
         const dim3 grid(c.g.n_px_tiles * k.n_co_tiles, k.splitk);
         const TileInst& t = c.tile;
-        if (!(dtype == DIN_F32 ? launch_tile<float>(k, t, grid, st) : launch_tile<bf16_t>(k, t, grid, st)))
+        if (!(k.mma ? launch_tile<f32x3_t>(k, t, grid, st) : dtype == DIN_F32 ? launch_tile<float>(k, t, grid, st) : launch_tile<bf16_t>(k, t, grid, st)))
             DIN_FAIL(DIN_E_LAUNCH, "%s: no conv_gather_fast_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d> for dtype %d", what, t.bm, t.bn, t.wm, t.wn, t.kcs,
                      t.ns, (int)t.multi, (int)t.fastk, (int)t.xsrc, (int)t.lanek, dtype);
         break;
@@ -2086,7 +2095,7 @@ static int for_each_launch(const din_conv_desc* d, int which, int flags, int ldm
 // the kernels launch_choice / run_gather launch for a choice, spelled as their instantiations: one line each, appended to `out`.
 // k: the argument block with its plan fields set (set_plan_fields)
 static void append_kernel_names(const ConvK& k, const GatherChoice& c, int dtype, std::string& out) {
-    const char* T = dtype == DIN_F32 ? "float" : "bf16";
+    const char* T = k.mma ? "f32x3" : dtype == DIN_F32 ? "float" : "bf16";
     char line[160];
     line[0] = 0;
     switch (c.family) {
@@ -2121,7 +2130,7 @@ static void append_kernel_names(const ConvK& k, const GatherChoice& c, int dtype
     }
     }
     out += line; out += '\n';
-    if (c.g.splitk > 1) { out += "conv_splitk_finish_kernel<"; out += T; out += ">\n"; }
+    if (c.g.splitk > 1) { out += "conv_splitk_finish_kernel<"; out += dtype == DIN_F32 ? "float" : "bf16"; out += ">\n"; }     // (f32x3 reuses <float>)
 }
 
 }  // namespace
@@ -2130,6 +2139,7 @@ extern "C" {
 
 int64_t din_conv_packed_elems(const din_conv_desc* d, int transposed) {
     if (!d) return 0;
+    const SplitDesc sd(d);
     int epc = epc_of(d->dtype);
     int cred = transposed ? d->cout : d->cin, cprod = transposed ? d->cin : d->cout;
     int cpt = pad_to(cred, epc) / epc;
@@ -2139,6 +2149,7 @@ int64_t din_conv_packed_elems(const din_conv_desc* d, int transposed) {
 
 int din_conv_pack_weights(const din_conv_desc* d, const float* w, const float* scale, void* wpk, int transposed, void* stream) {
     DIN_REQUIRE(d && w && wpk, "conv_pack: null pointer");
+    const SplitDesc sd(d);
     int epc = epc_of(d->dtype);
     int cred = transposed ? d->cout : d->cin, cprod = transposed ? d->cin : d->cout;
     int inner_pad = pad_to(cred, epc);
@@ -2168,6 +2179,7 @@ int din_conv_pack_weights(const din_conv_desc* d, const float* w, const float* s
 
 int din_conv_pack_desc(const din_conv_desc* d, const float* w, const float* scale, void* wpk, int transposed, din_pack_desc* out) {
     DIN_REQUIRE(d && w && wpk && out, "conv_pack_desc: null pointer");
+    const SplitDesc sd(d);
     const int epc = epc_of(d->dtype);
     const int cred = transposed ? d->cout : d->cin, cprod = transposed ? d->cin : d->cout;
     const int inner_pad = pad_to(cred, epc), cpt = inner_pad / epc;
@@ -2190,7 +2202,8 @@ int din_conv_pack_multi(const din_pack_desc* table, const int32_t* layer_of, con
 
 int din_conv_kernel_tile(const din_conv_desc* d, int which, int32_t* bm, int32_t* bn) {
     DIN_REQUIRE(d && bm && bn && which >= 0 && which <= 2, "conv_kernel_tile: bad argument");
-    if (which == 2) { din_wgrad::wgrad_tile_code(din_wgrad::plan_wgrad(d), bm, bn); return DIN_OK; }     // (the codes of the weight-gradient choice)
+    const SplitDesc sd(d);
+    if (which == 2) { din_wgrad::wgrad_tile_code(din_wgrad::plan_wgrad(d, sd.split), bm, bn); return DIN_OK; }     // (the codes of the weight-gradient choice)
     // the canonical launch of the descriptor (conv_k_of), as choose_gather resolves it
     const GatherChoice c = canonical_choice(d, which);
     switch (c.family) {
@@ -2207,6 +2220,7 @@ int din_conv_kernel_tile(const din_conv_desc* d, int which, int32_t* bm, int32_t
 
 int din_conv_kernel_variant(const din_conv_desc* d, int which, int32_t* flags) {
     DIN_REQUIRE(d && flags && which >= 0 && which <= 1, "conv_kernel_variant: bad argument");
+    const SplitDesc sd(d);
     const GatherChoice c = canonical_choice(d, which);
     *flags = 0;
     if (c.family != GATHER_TILE || c.tile.bm != 128) return DIN_OK;     // (the 256-pixel tiles have one wave grid per filter tile)
@@ -2215,13 +2229,14 @@ int din_conv_kernel_variant(const din_conv_desc* d, int which, int32_t* flags) {
 }
 
 int din_conv_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes) {
+    const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
     DIN_REQUIRE(which >= 0 && which <= 2 && buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_kernel_names: bad argument");
     std::string names;
     if (which == 2) {
         DIN_REQUIRE(!flags && !ldm && !moff, "conv_kernel_names: flags / ldm / moff are fwd / dgrad arguments");
         DIN_REQUIRE(!d->in_u8 || din_conv_accepts_u8(d), "conv_kernel_names: in_u8 on a layer din_conv_accepts_u8() rejects");
-        din_wgrad::append_wgrad_names(d, din_wgrad::plan_wgrad(d), names);
+        din_wgrad::append_wgrad_names(d, din_wgrad::plan_wgrad(d, sd.split), names);
     } else if (which == 0) {
         DIN_REQUIRE(!(flags & (DIN_CONV_ACCUM | DIN_CONV_MASK)), "conv_kernel_names: ACCUM/MASK are dgrad-only flags");
         DIN_REQUIRE(!d->in_u8 || din_conv_accepts_u8(d), "conv_kernel_names: in_u8 on a layer din_conv_accepts_u8() rejects");
@@ -2231,6 +2246,7 @@ int din_conv_kernel_names(const din_conv_desc* d, int which, int flags, int ldm,
     static const unsigned char raw_frames = 0;              // stands for the caller's uint8 frames: the selection only asks whether there are any
     if (which != 2) for_each_launch(d, which, flags, ldm, moff, [&](ConvK& k, const GatherPlan& g, const char*) {
         if (d->in_u8) k.u8 = &raw_frames;
+        k.mma = sd.split;
         const GatherChoice c = choose_gather(k, g, d->dtype);
         set_plan_fields(k, c);
         append_kernel_names(k, c, d->dtype, names);
@@ -2246,6 +2262,7 @@ int din_conv_kernel_names(const din_conv_desc* d, int which, int flags, int ldm,
 
 int64_t din_conv_workspace_bytes(const din_conv_desc* d, int which) {
     if (!d) return 0;
+    const SplitDesc sd(d);
     if (which != 0 && which != 1) return din_wgrad::plan_wgrad(d).ws_bytes;
     if (which == 0 || !dgrad_by_parity(d)) return plan_launch(d, which).ws_bytes;
     int64_t mx = 0;
@@ -2255,13 +2272,14 @@ int64_t din_conv_workspace_bytes(const din_conv_desc* d, int which) {
 
 int din_conv_fwd(const din_conv_desc* d, const void* in, const void* wpk, const float* bias, void* out, int flags,
                  void* workspace, int64_t workspace_bytes, void* stream) {
+    const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
     DIN_REQUIRE(in && wpk && out, "conv_fwd: null pointer");
     DIN_REQUIRE(!(flags & DIN_CONV_BIAS) || bias, "conv_fwd: BIAS flag without bias");
     DIN_REQUIRE(!(flags & (DIN_CONV_ACCUM | DIN_CONV_MASK)), "conv_fwd: ACCUM/MASK are dgrad-only flags");
     DIN_REQUIRE(!d->in_u8 || din_conv_accepts_u8(d), "conv_fwd: in_u8 on a layer din_conv_accepts_u8() rejects");
     return for_each_launch(d, 0, flags, 0, 0, [&](ConvK& k, const GatherPlan& g, const char* what) {
-        k.in = in; k.w = wpk; k.out = out; k.bias = bias;
+        k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.mma = sd.split;
         if (d->in_u8) k.u8 = reinterpret_cast<const unsigned char*>(in);
         return run_gather(k, g, d->dtype, workspace, workspace_bytes, as_stream(stream), what);
     });
@@ -2283,6 +2301,7 @@ int din_conv_accepts_u8(const din_conv_desc* d) {
 
 int din_conv_fwd2(const din_conv_desc* d, const void* in, const void* wpk, const float* bias, void* out, void* out2, int ldo2, int cooff2,
                   int csplit, int craw, int flags, void* workspace, int64_t workspace_bytes, void* stream) {
+    const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
     DIN_REQUIRE(in && wpk && out && out2, "conv_fwd2: null pointer");
     DIN_REQUIRE(!d->in_u8, "conv_fwd2: in_u8 is a din_conv_fwd / din_conv_wgrad option");
@@ -2295,7 +2314,7 @@ int din_conv_fwd2(const din_conv_desc* d, const void* in, const void* wpk, const
                 "conv_fwd2: split / strides / offsets must be multiples of %d and the destinations must hold their channel ranges", epc);
     DIN_REQUIRE(craw == 0 || (craw >= csplit && craw < d->cout && craw % epc == 0), "conv_fwd2: craw must be 0 or a multiple of %d in [csplit, cout)", epc);
     ConvK k = conv_k_of(d, 0);
-    k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.flags = flags;
+    k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.flags = flags; k.mma = sd.split;
     k.out2 = out2; k.ldo2 = ldo2; k.cooff2 = cooff2; k.csplit = csplit; k.craw = craw;
     const GatherPlan g = plan_launch(d, 0);
     if (g.splitk > 1) DIN_FAIL(DIN_E_ARG, "conv_fwd2: this shape runs split-K (%d pixels): launch the sibling convs separately", k.M);
@@ -2322,19 +2341,22 @@ int din_conv_dgrad_x_fused(const din_conv_desc* d) { return (d && check_desc(d) 
 
 int din_conv_dgrad_x(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din_, const void* mask, int ldm, int moff, int flags,
                      const din_conv_src* x, void* workspace, int64_t workspace_bytes, void* stream) {
+    const din_conv_desc* const d0 = d;             // (the two launches below normalise the dtype themselves)
+    const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
     DIN_REQUIRE(x && x->dout && x->wpk_t && x->cout > 0, "conv_dgrad_x: null extra source");
     const int epc = epc_of(d->dtype);
     DIN_REQUIRE(x->ldo % epc == 0 && x->cooff % epc == 0 && x->ldo >= x->cooff + pad_to(x->cout, epc),
                 "conv_dgrad_x: extra source stride/offset must be multiples of %d and cover cout (+zero pad)", epc);
-    if (dgrad_x_fused(d)) return conv_dgrad_impl(d, dout, wpk_t, din_, mask, ldm, moff, flags, workspace, workspace_bytes, stream, x);
+    if (dgrad_x_fused(d)) return conv_dgrad_impl(d0, dout, wpk_t, din_, mask, ldm, moff, flags, workspace, workspace_bytes, stream, x);
     // not a shape the fused kernel serves: the two launches it replaces (the second accumulates; the mask is linear)
-    if (int e = conv_dgrad_impl(d, dout, wpk_t, din_, mask, ldm, moff, flags, workspace, workspace_bytes, stream, nullptr)) return e;
-    return din_conv1x1_dgrad_multi(1, x, d->dtype, d->nb, d->h, d->w, d->cin, d->ldi, d->cioff, din_, mask, ldm, moff, flags | DIN_CONV_ACCUM, stream);
+    if (int e = conv_dgrad_impl(d0, dout, wpk_t, din_, mask, ldm, moff, flags, workspace, workspace_bytes, stream, nullptr)) return e;
+    return din_conv1x1_dgrad_multi(1, x, d0->dtype, d->nb, d->h, d->w, d->cin, d->ldi, d->cioff, din_, mask, ldm, moff, flags | DIN_CONV_ACCUM, stream);
 }
 
 static int conv_dgrad_impl(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din_, const void* mask, int ldm,
                            int moff, int flags, void* workspace, int64_t workspace_bytes, void* stream, const din_conv_src* x) {
+    const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
     DIN_REQUIRE(dout && wpk_t && din_, "conv_dgrad: null pointer");
     DIN_REQUIRE(!d->in_u8, "conv_dgrad: in_u8 is a din_conv_fwd / din_conv_wgrad option");
@@ -2346,7 +2368,7 @@ static int conv_dgrad_impl(const din_conv_desc* d, const void* dout, const void*
     DIN_REQUIRE(d->ldi % 4 == 0 && d->cioff % 4 == 0, "conv_dgrad: din stride/offset must be multiples of 4");
     hipStream_t st = as_stream(stream);
     return for_each_launch(d, 1, flags, ldm, moff, [&](ConvK& c, const GatherPlan& g, const char* what) {
-        c.in = dout; c.w = wpk_t; c.out = din_; c.mask = mask;
+        c.in = dout; c.w = wpk_t; c.out = din_; c.mask = mask; c.mma = sd.split;
         if (x) {                                   // extra 1x1 source at the output pixel (din_conv_dgrad_x: parity-class launches only)
             ConvK::Src& o = c.src[0];
             o.in = x->dout; o.w = x->wpk_t; o.ld = x->ldo; o.coff = x->cooff;
@@ -2363,6 +2385,8 @@ static int conv_dgrad_impl(const din_conv_desc* d, const void* dout, const void*
 int din_conv1x1_dgrad_multi(int nsrc, const din_conv_src* srcs, int dtype, int nb, int h, int w, int cin, int ldi, int cioff,
                             void* din_, const void* mask, int ldm, int moff, int flags, void* stream) {
     DIN_REQUIRE(nsrc >= 1 && nsrc <= 4 && srcs && din_, "conv1x1_dgrad_multi: 1..4 sources");
+    const bool split = dtype == DIN_F32_BF16X3;
+    dtype = storage_dtype(dtype);
     DIN_REQUIRE(dtype == DIN_F32 || dtype == DIN_BF16, "conv1x1_dgrad_multi: bad dtype");
     DIN_REQUIRE(!(flags & (DIN_CONV_BIAS | DIN_CONV_RELU)), "conv1x1_dgrad_multi: BIAS/RELU are fwd-only flags");
     DIN_REQUIRE(!(flags & DIN_CONV_MASK) || mask, "conv1x1_dgrad_multi: MASK flag without mask");
@@ -2373,7 +2397,7 @@ int din_conv1x1_dgrad_multi(int nsrc, const din_conv_src* srcs, int dtype, int n
     k.out = din_; k.mask = mask; k.bias = nullptr; k.partial = nullptr;
     k.NB = nb; k.H = h; k.W = w; k.OH = h; k.OW = w; k.Cout = cin; k.ldo = ldi; k.cooff = cioff;
     k.kh = k.kw = 1; k.ay = k.ax = 1; k.by = k.bx = 0; k.cy = k.cx = 1; k.divy = k.divx = 1;
-    k.M = nb * h * w; k.flags = flags; k.ldm = ldm; k.moff = moff;
+    k.M = nb * h * w; k.flags = flags; k.ldm = ldm; k.moff = moff; k.mma = split;
     int steps = 0;
     for (int b = 0; b < nsrc; ++b) {
         const din_conv_src& sc = srcs[b];

@@ -13,6 +13,41 @@ namespace {
 
 constexpr int NTHREADS = 256;
 
+// ---- DIN_F32_BF16X3: fp32 operands multiplied as three bf16 parts each --------------------------------------------------------
+// x = x0 + x1 + x2 exactly, 8 + 8 + 8 significand bits: x0 = the top 16 bits of x (TRUNCATED, so the high part of a value near FLT_MAX
+// stays finite), x1 = the remainder rounded to nearest bf16, x2 = what is left (at most 8 significant bits: exact); both subtractions are
+// exact.  Rounding the MIDDLE part to nearest instead of truncating it again halves the dropped cross terms a1 b2 + a2 b1 and makes them
+// unbiased: with two truncations every part has the sign of x and the dropped terms add up one-sidedly -- tools/split_bf16_sim.py measures
+// rms(err) 1.17x an fp32-accumulated exact product at K = 64 that way, 0.89x this way.  The parts come back as fp32 bit patterns whose
+// bf16 half is the top one (the low halves are zero).
+__device__ __forceinline__ void split_bf16x3(uint32_t x, uint32_t& x0, uint32_t& x1, uint32_t& x2) {
+    x0 = x & 0xffff0000u;
+    const float r1 = __uint_as_float(x) - __uint_as_float(x0);
+    x1 = (uint32_t)f32_to_bf16(r1) << 16;
+    x2 = __float_as_uint(r1 - __uint_as_float(x1));
+}
+// one 32-bit MFMA operand word = two bf16 k-slots: the top half of `hi` above the top half of `lo` (v_perm_b32)
+__device__ __forceinline__ uint32_t bf16_halves(uint32_t hi, uint32_t lo) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
+// c += A * B over the lane's 4 fp32 k-values of each operand (a: the MFMA's i side, b: its j side), as the six leading cross products of
+// the parts in three v_mfma_f32_16x16x32_bf16: the lane's 8 k-slots hold two parts of its 4 values, word e = (slot 2e, slot 2e + 1):
+//   [a2 | a0] x [b0 | b2]  = a2 b0 + a0 b2        [a1 | a0] x [b1 | b1]  = a1 b1 + a0 b1        [a1 | a0] x [b0 | b0]  = a1 b0 + a0 b0
+// (smallest terms first; a1 b2, a2 b1, a2 b2 <= 2^-23 of a product are dropped).  3 x 16 matrix-pipe cycles against the 4 x 32 of four
+// v_mfma_f32_16x16x4_f32, for 8-9 VALU instructions per fp32 value (measured: profiles/fp32_split_step_time.txt).
+__device__ __forceinline__ void mma_f32_bf16x3(const u32x4& a, const u32x4& b, f32x4& c) {
+    u32x4 a01, a02, b00, b11, b20;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        uint32_t p0, p1, p2, q0, q1, q2;
+        split_bf16x3(a[e], p0, p1, p2);
+        split_bf16x3(b[e], q0, q1, q2);
+        a01[e] = bf16_halves(p0, p1); a02[e] = bf16_halves(p0, p2);
+        b00[e] = bf16_halves(q0, q0); b11[e] = bf16_halves(q1, q1); b20[e] = bf16_halves(q2, q0);
+    }
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a02), __builtin_bit_cast(bf16x8, b20), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a01), __builtin_bit_cast(bf16x8, b11), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a01), __builtin_bit_cast(bf16x8, b00), c, 0, 0, 0);
+}
+
 // ---- image layer fed from raw uint8 frames (din_conv_desc::in_u8): the halo pixels of a tile are fetched as bytes from the three colour
 //      planes, normalised exactly like utils.prep_images ((x / 255 - 0.5) * 2: three separately rounded fp32 operations, utils.py:8-19),
 //      rounded to bf16 and written to the LDS position the LDS-DMA of a prepared NHWC tensor would have filled (16 bytes per pixel:
@@ -80,6 +115,17 @@ struct U8Halo {
 inline int epc_of(int dtype) { return dtype == DIN_F32 ? 4 : 8; }
 inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 inline int opt_int(const char* v, int dflt) { return v ? atoi(v) : dflt; }
+// DIN_F32_BF16X3 is DIN_F32 in everything but the MMA.  Every contraction entry point starts with `const SplitDesc sd(d);`: from there on
+// `d` is the same descriptor with DIN_F32 (plan, tile choice, workspace, packing and every byte-size rule are that descriptor's), and
+// sd.split travels to the launch (ConvK::mma, plan_wgrad's second argument) to pick the kernels that multiply in three bf16 parts.
+inline int storage_dtype(int dtype) { return dtype == DIN_F32_BF16X3 ? DIN_F32 : dtype; }
+struct SplitDesc {
+    din_conv_desc copy;
+    bool split = false;
+    explicit SplitDesc(const din_conv_desc*& d) {
+        if (d && d->dtype == DIN_F32_BF16X3) { copy = *d; copy.dtype = DIN_F32; d = &copy; split = true; }
+    }
+};
 // stem layers on conv_small_kernel / conv_wgrad_small_kernel (DIN_CONV_SMALL=0: off); din_conv_accepts_u8 answers from the same switch
 inline bool conv_small_wanted() { return opt_int(DIN_OPT("DIN_CONV_SMALL"), 1) != 0; }
 

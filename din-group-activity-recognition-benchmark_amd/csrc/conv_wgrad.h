@@ -60,6 +60,7 @@ __device__ __forceinline__ void lds_dma16(uint32_t lds_addr, __amdgpu_buffer_rsr
 //      din_conv_wgrad_group_key and the profiler's kernel names all answer from it.
 enum WgradFamily {
     WGRAD_F32,          // conv_wgrad_f32_kernel
+    WGRAD_F32X3,        // conv_wgrad_f32x3_kernel (DIN_F32_BF16X3: the fp32 plan, three-part bf16 MFMA)
     WGRAD_BF16_TAIL,    // conv_wgrad_bf16_tail_kernel (channels that are no whole 16-byte chunks)
     WGRAD_BF16,         // conv_wgrad_bf16_kernel<BCO>: two workgroups per CU
     WGRAD_RING,         // conv_wgrad_ring_kernel<BCO, BK>
@@ -81,7 +82,7 @@ struct WgradChoice {
     int cin_pad, kcols, kcols_pad, cout_pad, n_co_tiles, n_k_tiles, slices, m_per_slice;
     int64_t ws_bytes;
 };
-WgradChoice plan_wgrad(const din_conv_desc* d);
+WgradChoice plan_wgrad(const din_conv_desc* d, bool split = false);   // split: d is the DIN_F32 form of a DIN_F32_BF16X3 descriptor
 void wgrad_tile_code(const WgradChoice& c, int32_t* bm, int32_t* bn);                       // the codes of din_conv_kernel_tile(d, 2)
 void append_wgrad_names(const din_conv_desc* d, const WgradChoice& c, std::string& out);   // the lines of din_conv_kernel_names(d, 2, ...)
 

@@ -28,7 +28,10 @@ namespace {
 constexpr int WG_TILE = 128;
 
 // fp32: 16 pixels per k-step, operands read with ds_read_b32 (lane k-index = pixel row)
-__global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_f32_kernel(WgradK p) {
+// SPLIT (conv_wgrad_f32x3_kernel, DIN_F32_BF16X3): the same tiles, slices, LDS images and partial layout; the k-step's 16 pixels go through
+// ONE three-MFMA group (mma_f32_bf16x3: each lane group holds 4 pixels x 2 parts) instead of four v_mfma_f32_16x16x4_f32.
+template <bool SPLIT>
+__device__ __forceinline__ void conv_wgrad_f32_body(const WgradK& p) {
     constexpr int PK = 16;
     constexpr int RS = WG_TILE + 16;     // padded row (floats): 4 k-rows hit 4 disjoint bank ranges
     __shared__ float Gs[2][PK][RS];
@@ -114,6 +117,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_f32_kernel(WgradK p) {
             const int cur = it & 1;
             const bool more = m0 + PK < m_end;
             if (more) load_global(m0 + PK);
+            if constexpr (SPLIT) {
+                // lane group g holds pixels g, g + 4, g + 8, g + 12: read e touches the rows the exact kernel's MFMA e touches (rows 4 e + g
+                // of the four groups lie in four disjoint bank ranges), and a sum does not care about the k order
+                u32x4 gf[4], xf[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) gf[i][e] = __float_as_uint(Gs[cur][e * 4 + frow][wm * 64 + i * 16 + fcol]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) xf[j][e] = __float_as_uint(Xs[cur][e * 4 + frow][wn * 64 + j * 16 + fcol]);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) mma_f32_bf16x3(gf[i], xf[j], acc[i][j]);
+            } else
 #pragma unroll
             for (int kk = 0; kk < PK / 4; ++kk) {
                 float gf[4], xf[4];
@@ -143,6 +162,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_f32_kernel(WgradK p) {
             for (int e = 0; e < 4; ++e) dst[(int64_t)(co + e) * p.kcols_pad + kc] = acc[i][j][e];
         }
 }
+__global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_f32_kernel(WgradK p) { conv_wgrad_f32_body<false>(p); }
+__global__ __launch_bounds__(NTHREADS, 2) void conv_wgrad_f32x3_kernel(WgradK p) { conv_wgrad_f32_body<true>(p); }
 
 // bf16: 32 pixels per k-step; operands are stored [pixel][channel] in LDS (as they sit in HBM) and read with the
 // gfx950 transpose read ds_read_b64_tr_b16, which hands lane i of a 16-lane group column i of a 4x16 block.
@@ -1089,6 +1110,7 @@ std::string wgrad_kernel_name(const WgradChoice& c) {
     const auto tf = [](bool b) { return b ? "true" : "false"; };
     switch (c.family) {
     case din_wgrad::WGRAD_F32: return "conv_wgrad_f32_kernel";
+    case din_wgrad::WGRAD_F32X3: return "conv_wgrad_f32x3_kernel";
     case din_wgrad::WGRAD_BF16_TAIL: return "conv_wgrad_bf16_tail_kernel";
     case din_wgrad::WGRAD_BF16: snprintf(s, sizeof s, "conv_wgrad_bf16_kernel<%d>", c.bco); break;
     case din_wgrad::WGRAD_RING: snprintf(s, sizeof s, "conv_wgrad_ring_kernel<%d, %d>", c.bco, c.bk); break;
@@ -1103,6 +1125,12 @@ std::string wgrad_kernel_name(const WgradChoice& c) {
     return s;
 }
 
+// DIN_F32_BF16X3: the fp32 plan (grid, slices, partial layout) on the kernel that multiplies in three bf16 parts
+int launch_wgrad_f32x3(const WgradK& k, const WgradChoice& c, hipStream_t st) {
+    hipLaunchKernelGGL(conv_wgrad_f32x3_kernel, c.grid, c.block, 0, st, k);
+    return DIN_OK;
+}
+
 // the launch table: family and tuple -> template
 int launch_wgrad(const WgradK& k, const WgradChoice& c, hipStream_t st) {
     auto go = [&](auto kern) {
@@ -1112,6 +1140,7 @@ int launch_wgrad(const WgradK& k, const WgradChoice& c, hipStream_t st) {
     };
     switch (c.family) {
     case din_wgrad::WGRAD_F32: return go(conv_wgrad_f32_kernel);
+    case din_wgrad::WGRAD_F32X3: return launch_wgrad_f32x3(k, c, st);
     case din_wgrad::WGRAD_BF16_TAIL: return go(conv_wgrad_bf16_tail_kernel);
     case din_wgrad::WGRAD_BF16:
 #define DIN_ROW(BCO_) if (c.bco == BCO_) return go(conv_wgrad_bf16_kernel<BCO_>);
@@ -1196,7 +1225,7 @@ namespace din_wgrad {
 // The weight-gradient choice.  Every option that selects a kernel is read HERE, each once: DIN_CONV_BN (its weight-gradient use), DIN_CONV_SMALL
 // (conv_small_wanted) and the DIN_WGRAD_* switches of the main launch and of the grouped launch's key.  What is left to din_conv_wgrad are the
 // per-call run-time switches that choose no kernel: DIN_WGRAD_PACE, DIN_WGRAD_DIRECT (and the atomic epilogue's memset).
-WgradChoice plan_wgrad(const din_conv_desc* d) {
+WgradChoice plan_wgrad(const din_conv_desc* d, bool split) {
     const int conv_bn = opt_int(DIN_OPT("DIN_CONV_BN"), 0);                  // 128: filter tiles of 128 rows only
     const bool stem_wanted = conv_small_wanted();
     const int halo_mode = opt_int(DIN_OPT("DIN_WGRAD_HALO"), 1);             // 0: off, 1: launches of >= 128K pixels (12 frames of 87x157 measured +3..34 %), 2: any size (tests)
@@ -1356,7 +1385,7 @@ WgradChoice plan_wgrad(const din_conv_desc* d) {
     w.grid = dim3(w.n_co_tiles * w.n_k_tiles, w.slices);
     w.block = dim3(NTHREADS);
     if (d->dtype == DIN_F32) {
-        w.family = WGRAD_F32;
+        w.family = split ? WGRAD_F32X3 : WGRAD_F32;      // (split: d is the DIN_F32 form of a DIN_F32_BF16X3 descriptor -- SplitDesc)
     } else if (pipe) {
         // wave grid 2 x WN: sixteen waves by default, DIN_WGRAD_PIPE_WAVES=8: 2 x 4, =4: 2 x 2 (not for the 256-row tile, which would spill)
         w.family = WGRAD_PIPE;
@@ -1378,7 +1407,7 @@ WgradChoice plan_wgrad(const din_conv_desc* d) {
         w.family = WGRAD_BF16_TAIL;
         w.lds = 2 * 2 * 32 * (WG_TILE * 2 + 32);
     }
-    w.bias_fused = w.family != WGRAD_F32 && w.family != WGRAD_BF16_TAIL;
+    w.bias_fused = w.family != WGRAD_F32 && w.family != WGRAD_F32X3 && w.family != WGRAD_BF16_TAIL;
     return w;
 }
 
@@ -1412,6 +1441,7 @@ extern "C" {
 
 int din_conv_wgrad(const din_conv_desc* d, const void* in, const void* dout, float* dw, float* dbias, const float* scale,
                    const float* w, float* wdot, int accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
+    const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
     DIN_REQUIRE(in && dout && dw, "conv_wgrad: null pointer");
     DIN_REQUIRE(!wdot || w, "conv_wgrad: wdot needs w");
@@ -1419,7 +1449,7 @@ int din_conv_wgrad(const din_conv_desc* d, const void* in, const void* dout, flo
     hipStream_t st = as_stream(stream);
     const bool prezeroed = (accumulate & 2) != 0;            // dbias / wdot were zeroed by the caller (one memset for a whole backbone)
     accumulate &= 1;
-    const WgradChoice c = din_wgrad::plan_wgrad(d);
+    const WgradChoice c = din_wgrad::plan_wgrad(d, sd.split);
     if (workspace_bytes < c.ws_bytes || !workspace)
         DIN_FAIL(DIN_E_WORKSPACE, "conv_wgrad: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)c.ws_bytes);
     DIN_REQUIRE(d->dtype == DIN_F32 || (d->ldo % 8 == 0 && d->cooff % 8 == 0), "conv_wgrad: bf16 dout stride/offset must be multiples of 8");
@@ -1626,6 +1656,7 @@ int din_conv_wgrad_group(int n, const din_conv_wgrad_item* items, void* workspac
 }
 
 static bool wgrad_multi_plan(int nsrc, const din_conv_wsrc* srcs, int dtype, int64_t pixels, int cin, din_wgrad::Wg1x1K* k) {
+    dtype = storage_dtype(dtype);                              // (DIN_F32_BF16X3 answers as DIN_F32 does: the kernel serves bf16 groups)
     const char* ev = DIN_OPT("DIN_WGRAD_1X1_MULTI");
     const int mode = ev ? atoi(ev) : 1;                        // 0: off, 1: launches of >= 128K pixels, 2: any size (tests)
     if (!mode || dtype != DIN_BF16 || !srcs || nsrc < 2 || nsrc > 4 || (pixels < 128 * 1024 && mode != 2) || pixels <= 0) return false;

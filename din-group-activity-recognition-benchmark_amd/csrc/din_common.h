@@ -63,6 +63,14 @@ template <> struct Elem<bf16_t> {
     __device__ static void st(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 };
 
+// DIN_F32_BF16X3: stored, loaded and written exactly as float; only the kernels' MMA differs (conv_shared.h: mma_f32_bf16x3)
+struct f32x3_t { float v; };
+template <> struct Elem<f32x3_t> {
+    static constexpr int EPC = 4;
+    __device__ static float ld(const f32x3_t* p) { return p->v; }
+    __device__ static void st(f32x3_t* p, float v) { p->v = v; }
+};
+
 __device__ __forceinline__ float load_as_f32(const void* base, int dtype, int64_t i) {
     return dtype == DIN_F32 ? ((const float*)base)[i] : bf16_to_f32(((const bf16_t*)base)[i]);
 }

@@ -9,7 +9,10 @@ Deliberate differences from the reference (all documented in DESIGN.md):
   * `cfg.backbone == 'inv3'` works (the reference has no head branch for it, infer_model.py:203-216 -> crash);
     it uses the vgg16 residual -> LN -> ReLU -> dropout order.
   * no torch.cuda.empty_cache() per step (infer_model.py:200 is a perf bug), images may be uint8.
-  * new optional cfg field `backbone_dtype` ('fp32' parity mode | 'bf16' throughput mode), default 'fp32'.
+  * new optional cfg field `backbone_dtype` ('fp32' parity mode | 'bf16' throughput mode | 'fp32_bf16x3'), default 'fp32'.
+    'fp32_bf16x3': fp32 storage and fp32 accuracy, every conv / linear contraction of the trunk (backbone, fc_emb_1, point_conv) and of the
+    DIN module (p_conv / scale_conv, hidden_weight) multiplied as three bf16 parts per operand on the bf16 matrix pipe
+    (DIN_F32_BF16X3, include/din_hip.h); the baselines' own blocks and the TCE context transformer stay on exact fp32.
 """
 from __future__ import annotations
 
@@ -78,7 +81,8 @@ def embed_boxes(model, images_in, boxes_in, N, fc):
         maps = [(b, c, graph.tensors[tid].relu_masked) for b, (tid, _coff, c) in zip(bufs, views)]
         crops = model.roi_align.forward_multiscale(maps, boxes_flat, boxes_idx, (OH, OW))
     feats = crops.reshape(B, T, N, D * K * K)
-    y = ops.linear(feats, fc.weight, fc.bias, lowp=getattr(cfg, "backbone_dtype", "fp32") == "bf16")              # :184
+    bdt = getattr(cfg, "backbone_dtype", "fp32")
+    y = ops.linear(feats, fc.weight, fc.bias, lowp=bdt == "bf16", split=bdt == "fp32_bf16x3")                    # :184
     return y, bufs, views, graph
 
 
@@ -177,7 +181,8 @@ class Dynamic_volleyball(_DynamicBase):
         B, T, N = images_in.shape[0], images_in.shape[1], cfg.num_boxes
         x = self._embed(images_in, boxes_in, N)                                       # [B,T,N,NFB]
         if cfg.lite_dim:                                                              # :188-193
-            x = ops.GridConvFunction.apply(x, self.point_conv.weight, self.point_conv.bias, 1)
+            x = ops.GridConvFunction.apply(x, self.point_conv.weight, self.point_conv.bias, 1, False,
+                                           getattr(cfg, "backbone_dtype", "fp32") == "fp32_bf16x3")
             x = ops.layer_norm(x, self.point_ln.weight, self.point_ln.bias, relu=True)
         graph, _mad = self.DPI(x)                                                     # :199
         p = cfg.train_dropout_prob if self.training else 0.0
@@ -292,7 +297,8 @@ class Dynamic_collective(_DynamicBase):
         B, T, MAX_N = images_in.shape[0], images_in.shape[1], cfg.num_boxes
         x = self._embed(images_in, boxes_in, MAX_N)                                   # [B,T,MAX_N,NFB]
         if cfg.lite_dim:
-            x = ops.GridConvFunction.apply(x, self.point_conv.weight, self.point_conv.bias, 1)
+            x = ops.GridConvFunction.apply(x, self.point_conv.weight, self.point_conv.bias, 1, False,
+                                           getattr(cfg, "backbone_dtype", "fp32") == "fp32_bf16x3")
             x = ops.layer_norm(x, self.point_ln.weight, self.point_ln.bias, relu=True)
         # Variable actors per clip WITHOUT a host loop or a device->host read (the reference loops over clips and slices
         # boxes_features_all[b, :, :N], infer_model.py:1284-1316): the per-clip counts stay on the device and the kernels take them.

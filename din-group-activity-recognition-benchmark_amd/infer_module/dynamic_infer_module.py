@@ -59,6 +59,10 @@ class Dynamic_Person_Inference(nn.Module):
                 nn.init.zeros_(sc.weight), nn.init.zeros_(sc.bias)
                 self.scale_conv[str(r)] = sc
 
+    def _split(self) -> bool:
+        """cfg.backbone_dtype == 'fp32_bf16x3': p_conv / scale_conv and hidden_weight run the three-part bf16 MFMA kernels (fp32 storage)"""
+        return getattr(self.cfg, "backbone_dtype", "fp32") == "fp32_bf16x3"
+
     def _ratio(self, x, r, n_per_clip=None):
         kh, kw = self.kernel_size
         k2 = kh * kw
@@ -68,7 +72,7 @@ class Dynamic_Person_Inference(nn.Module):
                 sc = self.scale_conv[str(r)]
                 w = torch.cat([sc.weight.new_zeros((2 * k2,) + tuple(sc.weight.shape[1:])), sc.weight], 0)     # offset channels unused
                 b = torch.cat([sc.bias.new_zeros(2 * k2), sc.bias], 0)
-                pred = ops.GridConvFunction.apply(x, w, b, r)
+                pred = ops.GridConvFunction.apply(x, w, b, r, False, self._split())
             else:
                 pred = x.new_zeros(x.shape[:3] + (2 * k2,))
             z, a, idx, mad = ops.DynamicWalkFunction.apply(x, pred, kh, kw, r, self.scale_factor, False, n_per_clip, True, None)
@@ -80,7 +84,7 @@ class Dynamic_Person_Inference(nn.Module):
             b = torch.cat([pc.bias, sc.bias], 0)
         else:
             w, b = pc.weight, pc.bias
-        pred = ops.GridConvFunction.apply(x, w, b, r)                       # [B,T,N,pad4(3*k2)]
+        pred = ops.GridConvFunction.apply(x, w, b, r, False, self._split())                       # [B,T,N,pad4(3*k2)]
         if self.parallel_inference:
             # parallel_infer (:285-341): relation-weighted lattice gather + MEAN over k2 of the dynamic walk, the latter clamped with
             # person_mat_shape: indices to (T + 2r - 1, N + 2r - 1), positions to (T + 2r, N + 2r)   (:307-317)
@@ -108,7 +112,7 @@ class Dynamic_Person_Inference(nn.Module):
                 agg = z if agg is None else ops.AxpbyFunction.apply(agg, z, 1.0, 1.0)
         if not self.beta_factor and nr > 1:
             agg = ops.AxpbyFunction.apply(agg, agg, 1.0 / nr, 0.0)
-        out = ops.linear(agg, self.hidden_weight.weight, None)
+        out = ops.linear(agg, self.hidden_weight.weight, None, split=self._split())
         return out, (mad if self.return_mad else None)
 
 

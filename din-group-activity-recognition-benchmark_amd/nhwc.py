@@ -29,7 +29,7 @@ def _stream():
 
 
 def torch_dtype(dt: int):
-    return torch.float32 if dt == L.DIN_F32 else torch.bfloat16
+    return torch.float32 if L.storage_dtype(dt) == L.DIN_F32 else torch.bfloat16
 
 
 def din_dtype(t: torch.Tensor) -> int:
@@ -306,7 +306,7 @@ def _pool_desc(g: Graph, op: Op, nb: int, dt: int) -> L.PoolDesc:
     d.nb, d.h, d.w, d.c, d.oh, d.ow = nb, ts.h, ts.w, op.src.c, td.h, td.w
     d.k, d.stride, d.pad = op.k[0], op.s[0], op.p[0]
     d.ldi, d.cioff, d.ldo, d.cooff = ts.c, op.src.coff, td.c, op.dst.coff
-    d.dtype = dt
+    d.dtype = L.storage_dtype(dt)                          # (pools move data: the storage type)
     return d
 
 
@@ -319,7 +319,7 @@ def _pooled_descs(g: Graph, op: Op, nb: int, dt: int) -> Tuple[L.ConvDesc, L.Poo
     pd.nb, pd.h, pd.w, pd.c, pd.oh, pd.ow = nb, ts.h, ts.w, op.dst.c, td.h, td.w
     pd.k, pd.stride, pd.pad = op.pooled
     pd.ldi, pd.cioff, pd.ldo, pd.cooff = op.dst.c, 0, td.c, op.dst.coff
-    pd.dtype = dt
+    pd.dtype = L.storage_dtype(dt)
     return d, pd
 
 
@@ -408,7 +408,7 @@ def _pack_cache(g: Graph, params: Sequence[torch.Tensor], dt: int, dev, with_tra
             chunk_index += list(range(nchunk))
     # forward groups: the siblings' banks packed row after row into ONE bank (each member writes exactly its own rows; the tail rows of
     # the zero-initialised buffer stay zero), so the fused launch sees a single conv with cout = sum of the members
-    esz = 4 if dt == L.DIN_F32 else 2
+    esz = 4 if L.storage_dtype(dt) == L.DIN_F32 else 2
     for grp in g.fwd_groups:
         a = g.ops[grp[0]]
         dF = _conv_desc(g, a, 1, dt, a.src.c)
@@ -448,6 +448,7 @@ def _bn_train_forward(lib, raw: torch.Tensor, dt: int, rows: int, cout: int, gam
     """batch-statistics BatchNorm (+ReLU) of a raw conv output [rows][cout] into the channel view (ldd, coffd) of dst; updates the
     running statistics in place; returns (batch mean, rstd) for the backward pass"""
     dev = raw.device
+    dt = L.storage_dtype(dt)
     ws = torch.empty(lib.din_bn_workspace(rows, cout) // 8, dtype=torch.float64, device=dev)   # reduced sums + one slab per workgroup
     ab = torch.empty(4 * cout, dtype=torch.float32, device=dev)
     a, b, bmean, rstd = ab[:cout], ab[cout:2 * cout], ab[2 * cout:3 * cout], ab[3 * cout:]
@@ -607,6 +608,7 @@ def graph_backward(g: Graph, bufs, aux, params: Sequence[torch.Tensor], dt: int,
     nb = bufs[g.input_tid].shape[0]
     dev = bufs[g.input_tid].device
     tdt = torch_dtype(dt)
+    sdt = L.storage_dtype(dt)                  # what the data-moving entry points (bn, colsum) take; conv descriptors carry dt itself
     st = _stream()
     main = torch.cuda.current_stream()
     side = side_stream(dev) if (switch("WGRAD_SIDE_STREAM") and not TIMING_ACTIVE()) else None
@@ -942,11 +944,11 @@ def graph_backward(g: Graph, bufs, aux, params: Sequence[torch.Tensor], dt: int,
                 td_ = g.tensors[op.dst.tid]
                 rows = nb * td_.h * td_.w
                 sums = torch.empty(lib.din_bn_workspace(rows, op.dst.c) // 8, dtype=torch.float64, device=dev)
-                L.check(lib.din_bn_bwd_stats(_ptr(gout), g_ld, g_coff, _ptr(raw), op.dst.c, 0, dt, rows, op.dst.c, _ptr(bmean), _ptr(rstd),
+                L.check(lib.din_bn_bwd_stats(_ptr(gout), g_ld, g_coff, _ptr(raw), op.dst.c, 0, sdt, rows, op.dst.c, _ptr(bmean), _ptr(rstd),
                                              _ptr(sums), st), "bn_bwd_stats")
                 dy = torch.empty((nb, td_.h, td_.w, op.dst.c), dtype=tdt, device=dev)
                 dgb = torch.empty(2 * op.dst.c, dtype=torch.float32, device=dev)
-                L.check(lib.din_bn_bwd_apply(_ptr(gout), g_ld, g_coff, _ptr(raw), op.dst.c, 0, dt, rows, op.dst.c, _ptr(params[po + 1]), _ptr(bmean),
+                L.check(lib.din_bn_bwd_apply(_ptr(gout), g_ld, g_coff, _ptr(raw), op.dst.c, 0, sdt, rows, op.dst.c, _ptr(params[po + 1]), _ptr(bmean),
                                              _ptr(rstd), _ptr(sums), _ptr(dy), op.dst.c, 0, _ptr(dgb), _ptr(dgb[op.dst.c:]), st), "bn_bwd_apply")
                 grads[po + 1], grads[po + 2] = dgb[:op.dst.c], dgb[op.dst.c:]
                 gout, g_ld, g_coff = dy, op.dst.c, 0
@@ -966,7 +968,7 @@ def graph_backward(g: Graph, bufs, aux, params: Sequence[torch.Tensor], dt: int,
                         dshift_pre = bn_dshift[bn.off_list[bn_index[oi]]:bn.off_list[bn_index[oi] + 1]]
                     else:
                         dshift_pre = torch.empty(op.dst.c, dtype=torch.float32, device=dev)
-                    L.check(lib.din_colsum(_ptr(gout), dt, nb * td_.h * td_.w, op.dst.c, td_.c, op.dst.coff, _ptr(dshift_pre), st), "colsum")
+                    L.check(lib.din_colsum(_ptr(gout), sdt, nb * td_.h * td_.w, op.dst.c, td_.c, op.dst.coff, _ptr(dshift_pre), st), "colsum")
                 gtmp = torch.empty((nb, pd.h, pd.w, pd.c), dtype=tdt, device=dev)
                 L.check(lib.din_avgpool_bwd(C.byref(pd), _ptr(gout), _ptr(gtmp), None, 0, st), "avgpool_bwd(epilogue)")
                 gout, g_ld, g_coff = gtmp, pd.c, 0
@@ -1149,14 +1151,14 @@ class NHWCGraphFunction(torch.autograd.Function):
             img = torch.empty((nb, h, w, ti.c), dtype=torch_dtype(dt), device=images.device)
             if ti.c > 3:
                 img.zero_()
-            L.check(lib.din_nchw_f32_to_nhwc(_ptr(images.float().contiguous()), nb, h, w, 3, _ptr(img), dt, ti.c, 0, st),
+            L.check(lib.din_nchw_f32_to_nhwc(_ptr(images.float().contiguous()), nb, h, w, 3, _ptr(img), L.storage_dtype(dt), ti.c, 0, st),
                     "nchw_to_nhwc")
         else:
             img = torch.empty((nb, h, w, ti.c), dtype=torch_dtype(dt), device=images.device)
             if images.dtype == torch.uint8:
-                L.check(lib.din_prep_images_nhwc(_ptr(images), 1, _ptr(img), dt, nb, h, w, ti.c, st), "prep_nhwc")
+                L.check(lib.din_prep_images_nhwc(_ptr(images), 1, _ptr(img), L.storage_dtype(dt), nb, h, w, ti.c, st), "prep_nhwc")
             else:
-                L.check(lib.din_prep_images_nhwc(_ptr(images.float().contiguous()), 0, _ptr(img), dt, nb, h, w, ti.c, st),
+                L.check(lib.din_prep_images_nhwc(_ptr(images.float().contiguous()), 0, _ptr(img), L.storage_dtype(dt), nb, h, w, ti.c, st),
                         "prep_nhwc")
         with torch.no_grad():
             bufs, aux = graph_forward(graph, img, params, dt, save_for_backward=any(p.requires_grad for p in params), bn_train=bn_train)

@@ -148,9 +148,13 @@ class GridConvFunction(torch.autograd.Function):
     the fused p_conv/scale_conv (dynamic_infer_module.py:191,195)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, dil: int, lowp: bool = False):
+    def forward(ctx, x, weight, bias, dil: int, lowp: bool = False, split: bool = False):
         """lowp: bf16 operands / fp32 MFMA accumulation (throughput mode, used for the 26400-wide embedding GEMM when the backbone
-        already runs in bf16); x, y and all gradients stay fp32 tensors at the interface."""
+        already runs in bf16); x, y and all gradients stay fp32 tensors at the interface.
+        split: fp32 storage, three-part bf16 MFMA compute (DIN_F32_BF16X3: fp32 accuracy on the bf16 matrix pipe) for the forward, the data
+        gradient and the weight gradient; every tensor and buffer is what the exact fp32 call makes.  Not together with lowp."""
+        if lowp and split:
+            raise ValueError("lowp and split are mutually exclusive: bf16 storage or fp32 storage with three-part bf16 compute")
         lib = L.load()
         x = x.contiguous()
         weight = weight.contiguous()
@@ -164,6 +168,8 @@ class GridConvFunction(torch.autograd.Function):
         if lowp:
             d.dtype = L.DIN_BF16
             x = x.to(torch.bfloat16)
+        elif split:
+            d.dtype = L.DIN_F32_BF16X3
         st = _stream()
         y = (torch.zeros if ldo != cout else torch.empty)((nb, h, w, ldo), dtype=tdt, device=x.device)
         wpk = torch.empty(lib.din_conv_packed_elems(C.byref(d), 0), dtype=tdt, device=x.device)
@@ -208,14 +214,17 @@ class GridConvFunction(torch.autograd.Function):
             L.check(lib.din_conv_dgrad(C.byref(d), _ptr(gy), _ptr(wpt), _ptr(dx), None, 0, 0, 0, _ptr(ws), wsb, st), "grid_conv_dgrad")
             if ctx.lowp:
                 dx = dx.float()
-        return dx, (None if dw_installed else dw), db, None, None
+        return dx, (None if dw_installed else dw), db, None, None, None
 
 
-def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], lowp: bool = False) -> torch.Tensor:
-    """y = x @ weight.T + bias over the last dim, on the MFMA contraction kernel (cout must be a multiple of 4)."""
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], lowp: bool = False, split: bool = False) -> torch.Tensor:
+    """y = x @ weight.T + bias over the last dim, on the MFMA contraction kernel (cout must be a multiple of 4).
+    lowp / split: GridConvFunction's two other numeric modes (mutually exclusive)."""
+    if lowp and split:
+        raise ValueError("lowp and split are mutually exclusive: bf16 storage or fp32 storage with three-part bf16 compute")
     shp = x.shape
     rows = x.numel() // shp[-1]
-    y = GridConvFunction.apply(x.reshape(1, 1, rows, shp[-1]), weight.reshape(weight.shape[0], weight.shape[1], 1, 1), bias, 1, lowp)
+    y = GridConvFunction.apply(x.reshape(1, 1, rows, shp[-1]), weight.reshape(weight.shape[0], weight.shape[1], 1, 1), bias, 1, lowp, split)
     cout = weight.shape[0]
     if y.shape[-1] != cout:
         y = y[..., :cout]

@@ -25,7 +25,7 @@ def _conv_flops(d) -> float:
 
 
 def _esz(dt: int) -> int:
-    return 4 if dt == L.DIN_F32 else 2
+    return 4 if L.storage_dtype(dt) == L.DIN_F32 else 2
 
 
 def _stem_bytes(kind: str, d) -> float:
@@ -149,7 +149,7 @@ class LaunchTimer:
         bm, bn = C.c_int32(0), C.c_int32(0)
         which = {"fwd": 0, "dgrad": 1}[self.kind]
         L.load().din_conv_kernel_tile(C.byref(d), which, C.byref(bm), C.byref(bn))
-        tn = "unsigned short" if d.dtype == L.DIN_BF16 else "float"
+        tn = {L.DIN_BF16: "unsigned short", L.DIN_F32_BF16X3: "f32x3_t"}.get(d.dtype, "float")      # (as the demangler spells the element tag)
         if bm.value == 4 and not (self.kind == "dgrad" and "+" in self.name):
             return f"conv1x1_stream_kernel<{bn.value}>"
         if bm.value == 5:

@@ -32,7 +32,26 @@ extern "C" {
 
 #define DIN_ABI_VERSION 9   /* 9: din_conv_wgrad_group (the weight gradients of several layers in one launch); din_basenet_head_fwd / _bwd were added later as a purely additive change (no existing signature changed), so the version stays 9.   8: din_set_option / din_get_option replace every getenv() of the library (tests select kernels through the ABI; a stray environment variable can no longer change a launch).   7: din_conv_dgrad_x (a strided dgrad that carries the 1x1 / stride-1 dgrad of a sibling conv reading the same view).   6: batch-statistics BatchNorm is deterministic: din_bn_stats / din_bn_bwd_stats write per-workgroup fp64 slabs into a workspace (din_bn_workspace), din_bn_finalize / din_bn_reduce add them in slab order -- no atomics, nothing for the caller to zero.   5: dropout seeds take an optional device-side offset (din_layernorm_*, din_act_dropout_*), din_counter_add, din_conv1x1_wgrad_multi.   2: din_walk_* take plain / clamp / n_per_clip; + bn, mask_actors.  3: din_roi_align_* take the box grid and a crop channel range.  4: din_conv_desc.in_u8, context-encoding entry points */
 
-enum { DIN_F32 = 0, DIN_BF16 = 1 };
+enum {
+    DIN_F32 = 0, DIN_BF16 = 1,
+    /* fp32 STORAGE, three-part bf16 MFMA COMPUTE (an additive value: no entry point, no signature changed).  Accepted wherever a
+     * contraction takes DIN_F32 -- din_conv_fwd / _fwd2 / _dgrad / _dgrad_x, din_conv1x1_dgrad_multi, din_conv_wgrad / _wgrad_group,
+     * din_conv1x1_wgrad_multi, the pack / packed_elems / workspace_bytes calls, din_conv_kernel_tile / _variant / _names,
+     * din_conv_accepts_u8 (answers 0) -- and means: every tensor, the packed filter bank (bit-identical), the plan, the tile, the workspace
+     * and every byte-size rule are those of the same descriptor with DIN_F32; only the multiply differs.  Each fp32 operand is split into
+     * three bf16 parts, x = x0 + x1 + x2 exactly (8 + 8 + 8 significand bits: x0 = the top 16 bits, TRUNCATED so that it stays finite near
+     * FLT_MAX; x1 = the remainder rounded to nearest, which keeps the dropped terms unbiased; x2 = what is left), and the six leading cross products
+     * a0b0, a1b0, a0b1, a1b1, a0b2, a2b0 are accumulated in fp32 by three v_mfma_f32_16x16x32_bf16 in place of four
+     * v_mfma_f32_16x16x4_f32; the dropped terms are <= 2^-23 of a product, so the result has fp32 accuracy (the tests hold it to the
+     * fp32 bars unchanged).  din_conv_kernel_names spells these kernels with their own type token (conv_gather_fast_kernel<f32x3,...>,
+     * conv_wgrad_f32x3_kernel).  Limits of the mode:
+     *   - a lower part that falls below the bf16 normal range is lost: in practice values with |x| below about 2^-100 keep fewer than
+     *     24 bits (their high part is always kept);
+     *   - a non-finite operand reaches the result through its high part only: NaN stays NaN, and +-Inf gives a non-finite result that
+     *     may be NaN where exact fp32 gives Inf (the lower parts of Inf are Inf - Inf).
+     * Entry points that only move or normalise data (bn, pool, roi, cast, prep, colsum) keep taking the storage type, DIN_F32.          */
+    DIN_F32_BF16X3 = 2
+};
 
 enum {
     DIN_OK = 0,
@@ -77,7 +96,8 @@ typedef struct din_conv_desc {
     int32_t oh, ow, cout;           /* output tensor [nb,oh,ow,cout], pixel stride ldo, channel offset cooff */
     int32_t kh, kw, sh, sw, ph, pw, dh, dw;
     int32_t ldi, cioff, ldo, cooff;
-    int32_t dtype;                  /* DIN_F32 / DIN_BF16 : storage type of in, out and packed weights       */
+    int32_t dtype;                  /* DIN_F32 / DIN_BF16 : storage type of in, out and packed weights; DIN_F32_BF16X3: DIN_F32
+                                       storage, three-part bf16 multiply (see the enum above)                  */
     int32_t in_u8;                  /* 1: `in` is the raw uint8 clip batch [nb][3][h][w] (volleyball.py:223-275 frames before
                                        utils.prep_images) and the image layer normalises on load -- (x/255 - 0.5)*2 in the reference's
                                        three fp32 roundings, utils.py:8-19 -- instead of reading a prepared NHWC tensor; ldi / cioff are
