@@ -21,7 +21,7 @@ import numpy as np
 import torch
 from torch.utils import data
 
-from .volleyball import load_frame_u8
+from .volleyball import build_frame_table, load_frame_u8, load_missing_frames
 
 # per-sequence frame counts and frame sizes of the Collective Activity dataset (data, collective.py:12-24)
 FRAMES_NUM = dict(zip(range(1, 45), [
@@ -78,14 +78,25 @@ def collective_all_frames(anns) -> List[Tuple[int, int]]:
 
 class CollectiveDataset(data.Dataset):
     """reference collective.py:96-225; item = (images, bboxes, actions, activities, bboxes_num): images uint8 [T, 3, H, W], bboxes float32
-    [T, MAX_N, 4] (zero rows beyond the real count), actions int64 [T, MAX_N] (-1 beyond), activities int64 [T], bboxes_num int32 [T]."""
+    [T, MAX_N, 4] (zero rows beyond the real count), actions int64 [T, MAX_N] (-1 beyond), activities int64 [T], bboxes_num int32 [T].
+    frame_ids=True (frame cache): as VolleyballDataset -- `frame_table`, `resident`, and an item is (frame_ids int64 [T], miss_images
+    uint8 [M, 3, H, W], bboxes, actions, activities, bboxes_num, miss_index int64 [M])."""
 
     def __init__(self, anns, frames, images_path, image_size, feature_size, num_boxes=13, num_frames=10, is_training=True, is_finetune=False,
-                 uint8_images=True):
+                 uint8_images=True, frame_ids=False):
         self.anns, self.frames, self.images_path = anns, frames, images_path
         self.image_size, self.feature_size = tuple(image_size), tuple(feature_size)
         self.num_boxes, self.num_frames = num_boxes, num_frames
         self.is_training, self.is_finetune, self.uint8_images = is_training, is_finetune, uint8_images
+        self.frame_ids = frame_ids
+        if frame_ids:
+            if not uint8_images:
+                raise ValueError("frame_ids=True caches uint8 frames: uint8_images must stay True")
+            self.frame_table, self._frame_index, self.resident = build_frame_table(
+                self.frame_path(sid, fid) for sid, src in frames for fid in range(src, src + num_frames))
+
+    def frame_path(self, sid, fid):
+        return os.path.join(self.images_path, "seq%02d" % sid, "frame%04d.jpg" % fid)
 
     def __len__(self):
         return len(self.frames)
@@ -102,8 +113,9 @@ class CollectiveDataset(data.Dataset):
     def load_samples_sequence(self, select_frames):
         oh, ow = self.feature_size
         T, N = len(select_frames), self.num_boxes
-        images = np.stack([load_frame_u8(os.path.join(self.images_path, "seq%02d" % sid, "frame%04d.jpg" % fid), self.image_size)
-                           for sid, _, fid in select_frames])
+        paths = [self.frame_path(sid, fid) for sid, _, fid in select_frames]
+        if not self.frame_ids:
+            images = np.stack([load_frame_u8(p, self.image_size) for p in paths])
         boxes = np.zeros((T, N, 4), dtype=np.float64)
         actions = np.full((T, N), -1, dtype=np.int64)
         activities = np.empty(T, dtype=np.int64)
@@ -119,6 +131,10 @@ class CollectiveDataset(data.Dataset):
                 actions[t, :n] = [Action6to5[a] for a in ann["actions"]]
             activities[t] = Activity5to4[ann["group_activity"]]
             count[t] = n
+        if self.frame_ids:
+            ids, miss, miss_index = load_missing_frames(paths, self._frame_index, self.resident, self.image_size, load_frame_u8)
+            return (ids, miss, torch.from_numpy(boxes.astype(np.float32)), torch.from_numpy(actions), torch.from_numpy(activities),
+                    torch.from_numpy(count), miss_index)
         img = torch.from_numpy(images)
         return (img if self.uint8_images else img.float(), torch.from_numpy(boxes.astype(np.float32)), torch.from_numpy(actions),
                 torch.from_numpy(activities), torch.from_numpy(count))

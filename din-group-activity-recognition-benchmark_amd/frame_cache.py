@@ -1,0 +1,320 @@
+"""Frame cache: decoded uint8 frames stay in HBM, and a batch of clips is one gather launch out of them.
+
+The reference decodes, resizes and stacks every frame of every epoch on the host (volleyball.py:223-275) and uploads the batch with a
+blocking copy (train_net_dynamic.py:174).  One core decodes about 13 ten-frame 720p clips a second, the trained step runs some 650: on
+real data the loader, not the GPU, sets the pace.  The whole Volleyball set is 133.5 GB as uint8 at 720x1280 and an MI355X has 288 GB,
+so after the first epoch nothing needs decoding or crossing PCIe again:
+
+  * datasets built with `frame_ids=True` name frames by their index in a fixed table and decode only those whose `resident` flag is
+    clear (the flags live in shared memory, so forked loader workers see what the main process marks);
+  * `collate` concatenates the decoded frames of a batch and records where they belong;
+  * `CachedFeed` uploads only those (through input_feed.DeviceFeed: same copy stream, double buffer, pinned staging) and then, on the
+    compute stream, (1) copies the new frames into free slots, (2) marks them resident, (3) builds the uint8 [B, T, 3, H, W] batch the
+    models take with one din_copy_rows_u8 launch over all B*T rows -- from a slot, or from the uploaded row where the cache is full.
+    Everything is in stream order on one stream: a gather always sees the inserts enqueued before it.
+
+No eviction: an epoch touches every frame once in random order, so least-recently-used would throw away exactly what is needed next; a
+full cache stops inserting and the remaining frames keep coming from the loader.  Each rank owns its caches; DistributedSampler
+reshuffles clips across ranks every epoch, so a rank's hit rate grows over several epochs instead of reaching 100 % in the second
+(rank-stable sharding would change the sampling and is not done here).
+"""
+from __future__ import annotations
+
+import collections
+import logging
+from typing import Callable, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+import torch.utils.data as data
+
+from .input_feed import DeviceFeed
+
+log = logging.getLogger(__name__)
+
+LOADER_TIMEOUT_S = 300          # DataLoader(timeout=...): a stuck worker raises instead of hanging the trainer
+
+
+class SlotTable:
+    """Host bookkeeping of the cache (no device needed): frame id -> slot, slab growth, capacity, counters.
+
+    Slots are `stride` bytes apart (frame_bytes rounded up to 16) and allocated in slabs of `chunk_frames` slots, the last slab shorter
+    when the capacity is not a whole number of slabs.  `grow(n_slots) -> bool` is asked for one more slab when the allocated slots run out;
+    a False answer freezes the table at its current size."""
+
+    def __init__(self, frame_bytes: int, capacity_bytes: int, chunk_frames: int = 64):
+        if frame_bytes <= 0 or chunk_frames <= 0 or capacity_bytes < 0:
+            raise ValueError(f"SlotTable: frame_bytes {frame_bytes}, chunk_frames {chunk_frames}, capacity_bytes {capacity_bytes}")
+        self.frame_bytes, self.chunk_frames = int(frame_bytes), int(chunk_frames)
+        self.stride = (self.frame_bytes + 15) // 16 * 16
+        self.max_slots = int(capacity_bytes) // self.stride
+        self.slot_of: Dict[int, int] = {}
+        self.slab_slots: List[int] = []             # slots of every allocated slab
+        self.allocated = 0                          # slots in allocated slabs
+        self.frozen = False
+        self.hits = self.misses = self.inserted = 0
+
+    @property
+    def bytes(self) -> int:
+        """device bytes the allocated slabs take"""
+        return self.allocated * self.stride
+
+    @property
+    def full(self) -> bool:
+        return len(self.slot_of) >= self.max_slots
+
+    def lookup(self, fid: int) -> int:
+        """slot of a frame, or -1; counts a hit or a miss"""
+        slot = self.slot_of.get(int(fid), -1)
+        if slot < 0:
+            self.misses += 1
+        else:
+            self.hits += 1
+        return slot
+
+    def insert(self, fid: int, grow: Callable[[int], bool] = lambda n: True) -> int:
+        """slot for a new frame, or -1 when the cache is full or frozen; an id that is already there is a hit and keeps its slot"""
+        fid = int(fid)
+        slot = self.slot_of.get(fid, -1)
+        if slot >= 0:
+            self.hits += 1
+            return slot
+        if self.full:
+            return -1
+        if len(self.slot_of) == self.allocated:
+            n = min(self.chunk_frames, self.max_slots - self.allocated)
+            if not grow(n):
+                self.max_slots, self.frozen = self.allocated, True
+                return -1
+            self.slab_slots.append(n)
+            self.allocated += n
+        slot = len(self.slot_of)
+        self.slot_of[fid] = slot
+        self.inserted += 1
+        return slot
+
+    def locate(self, slot: int) -> Tuple[int, int]:
+        """(slab index, byte offset inside the slab): every slab but the last holds chunk_frames slots"""
+        return slot // self.chunk_frames, (slot % self.chunk_frames) * self.stride
+
+    def counters(self) -> dict:
+        return {"hits": self.hits, "misses": self.misses, "inserted": self.inserted, "bytes": self.bytes}
+
+
+class FrameCache:
+    """Device-resident uint8 frame store with fixed-size slots, filled on first use, never beyond `capacity_bytes`, no eviction."""
+
+    TABLE_SLOTS = 4                                  # pinned address-table buffers in rotation (one batch uses one)
+
+    def __init__(self, device, frame_shape: Sequence[int], capacity_bytes: int, chunk_frames: int = 64):
+        self.device = torch.device(device)
+        self.frame_shape = tuple(int(v) for v in frame_shape)
+        self.frame_bytes = int(np.prod(self.frame_shape))
+        self.table = SlotTable(self.frame_bytes, capacity_bytes, chunk_frames)
+        self.slabs: List[torch.Tensor] = []
+        self._pinned: List[Optional[torch.Tensor]] = [None] * self.TABLE_SLOTS
+        self._sent: List[Optional[torch.cuda.Event]] = [None] * self.TABLE_SLOTS
+        self._turn = 0
+
+    hits = property(lambda self: self.table.hits)
+    misses = property(lambda self: self.table.misses)
+    inserted = property(lambda self: self.table.inserted)
+    bytes = property(lambda self: self.table.bytes)
+
+    def _grow(self, n_slots: int) -> bool:
+        try:
+            self.slabs.append(torch.empty(n_slots * self.table.stride, dtype=torch.uint8, device=self.device))
+            return True
+        except RuntimeError as e:                    # (torch.cuda.OutOfMemoryError is one)
+            log.warning("frame cache frozen at %d frames (%.2f GB): a slab of %d frames could not be allocated: %s",
+                        self.table.allocated, self.table.bytes / 1e9, n_slots, str(e).splitlines()[0])
+            return False
+
+    def slot_address(self, slot: int) -> int:
+        slab, off = self.table.locate(slot)
+        return self.slabs[slab].data_ptr() + off
+
+    def _upload(self, *tables: Sequence[int]) -> List[torch.Tensor]:
+        """int64 address tables -> device, in ONE asynchronous copy on the current stream out of a pinned buffer that is reused only after
+        the copy it last fed has finished"""
+        total = sum(len(t) for t in tables)
+        k = self._turn = (self._turn + 1) % self.TABLE_SLOTS
+        if self._sent[k] is not None:
+            self._sent[k].synchronize()
+        buf = self._pinned[k]
+        if buf is None or buf.numel() < total:
+            buf = self._pinned[k] = torch.empty(max(total, 1024), dtype=torch.int64).pin_memory()
+        host = buf.numpy()
+        at, views = 0, []
+        for t in tables:
+            host[at:at + len(t)] = t
+            views.append((at, len(t)))
+            at += len(t)
+        dev = buf[:total].to(self.device, non_blocking=True)
+        self._sent[k] = torch.cuda.Event()
+        self._sent[k].record(torch.cuda.current_stream(self.device))
+        return [dev[a:a + n] for a, n in views]
+
+    def build_batch(self, frame_ids, miss_pos=(), miss_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[int]]:
+        """frame_ids [R] (host), miss_pos [M] (host: which of the R rows the uploaded frames are), miss_rows uint8 [M, *frame_shape] on
+        the device -> (uint8 [R, *frame_shape] on the device, the frame ids inserted by this call).  On the current stream: one launch
+        that copies the new frames into free slots, then one launch that gathers all R rows (slot, or uploaded row where the cache has
+        no room)."""
+        from . import ops
+        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
+        if len(pos):
+            if miss_rows is None or not miss_rows.is_cuda or miss_rows.dtype != torch.uint8 or not miss_rows.is_contiguous() \
+                    or tuple(miss_rows.shape) != (len(pos),) + self.frame_shape:
+                raise ValueError(f"build_batch: {len(pos)} missed frames need a contiguous uint8 device tensor "
+                                 f"{(len(pos),) + self.frame_shape}, got {None if miss_rows is None else tuple(miss_rows.shape)}")
+            if pos.min() < 0 or pos.max() >= len(ids):
+                raise ValueError("build_batch: miss_pos outside the batch")
+        fb = self.frame_bytes
+        row_of = {}                                  # frame id -> address of its uploaded pixels (the first copy serves all)
+        for j, p in enumerate(pos):
+            row_of.setdefault(int(ids[p]), miss_rows.data_ptr() + j * fb)
+        out = torch.empty((len(ids),) + self.frame_shape, dtype=torch.uint8, device=self.device)
+        out_ptr = out.data_ptr()
+        ins_src, ins_dst, new_ids, src = [], [], [], []
+        for fid in ids:
+            fid = int(fid)
+            slot = self.table.lookup(fid)
+            if slot < 0 and fid in row_of:
+                slot = self.table.insert(fid, self._grow)
+                if slot >= 0:
+                    ins_src.append(row_of[fid])
+                    ins_dst.append(self.slot_address(slot))
+                    new_ids.append(fid)
+            if slot >= 0:
+                src.append(self.slot_address(slot))
+            elif fid in row_of:
+                src.append(row_of[fid])
+            else:
+                raise KeyError(f"frame {fid} is neither resident nor among the uploaded frames of this batch")
+        dst = [out_ptr + i * fb for i in range(len(ids))]
+        d_ins_src, d_ins_dst, d_src, d_dst = self._upload(ins_src, ins_dst, src, dst)
+        ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)                 # (no launch when nothing is new)
+        ops.copy_rows_u8(d_src, d_dst, fb)
+        return out, new_ids
+
+    def insert(self, frame_ids, rows: torch.Tensor) -> List[int]:
+        """store rows[i] as frame frame_ids[i]; returns the ids that are resident afterwards (all of them unless the cache is full)"""
+        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        fb, ins_src, ins_dst = self.frame_bytes, [], []
+        if tuple(rows.shape) != (len(ids),) + self.frame_shape or rows.dtype != torch.uint8 or not rows.is_cuda or not rows.is_contiguous():
+            raise ValueError(f"insert: {len(ids)} frames need a contiguous uint8 device tensor {(len(ids),) + self.frame_shape}")
+        from . import ops
+        for j, fid in enumerate(ids):
+            known = int(fid) in self.table.slot_of
+            slot = self.table.insert(int(fid), self._grow)
+            if slot >= 0 and not known:
+                ins_src.append(rows.data_ptr() + j * fb)
+                ins_dst.append(self.slot_address(slot))
+        d_src, d_dst = self._upload(ins_src, ins_dst)
+        ops.copy_rows_u8(d_src, d_dst, fb)
+        rows.record_stream(torch.cuda.current_stream(self.device))
+        return [int(f) for f in ids if int(f) in self.table.slot_of]
+
+    def resident(self, fid: int) -> bool:
+        return int(fid) in self.table.slot_of
+
+    def gather(self, frame_ids) -> torch.Tensor:
+        """uint8 [R, *frame_shape] of resident frames (KeyError for one that is not)"""
+        return self.build_batch(frame_ids)[0]
+
+
+def collate(items):
+    """DataLoader collate_fn for `frame_ids=True` datasets.  items: (frame_ids [T], miss_images [M_i, 3, H, W], *labels, miss_index [M_i])
+    -> (frame_ids [B, T], miss_images [sum M_i, 3, H, W], miss_pos int64 [sum M_i], *labels stacked as the default collate does):
+    miss_pos[j] = b * T + t is the row of the batch that uploaded frame j belongs to."""
+    T = items[0][0].shape[0]
+    frame_ids = torch.stack([it[0] for it in items])
+    miss_images = torch.cat([it[1] for it in items])
+    miss_pos = torch.cat([it[-1] + b * T for b, it in enumerate(items)])
+    labels = data.default_collate([tuple(it[2:-1]) for it in items])
+    return (frame_ids, miss_images, miss_pos, *labels)
+
+
+class _HostSide:
+    """what CachedFeed hands to DeviceFeed: the tensors to upload, with the host-only part (ids, positions) kept back in order"""
+
+    def __init__(self, loader, kept: collections.deque):
+        self.loader, self.kept = loader, kept
+
+    def __iter__(self):
+        for frame_ids, miss_images, miss_pos, *labels in self.loader:
+            self.kept.append((tuple(frame_ids.shape), frame_ids.numpy().reshape(-1), miss_pos.numpy()))
+            yield (miss_images, *labels)
+
+    def __len__(self):
+        return len(self.loader)
+
+
+class CachedFeed:
+    """DeviceFeed's iteration contract over a loader of `collate`d batches: yields (images uint8 [B, T, 3, H, W], *labels) on the
+    device.  Only the frames the workers decoded are uploaded (DeviceFeed overlaps that with the previous step); the batch is built on
+    the compute stream by `cache.build_batch`, and `dataset.resident` is marked for what went in."""
+
+    def __init__(self, loader: Iterable, device, cache: FrameCache, dataset):
+        self.loader, self.device, self.cache, self.dataset = loader, torch.device(device), cache, dataset
+        self._kept: collections.deque = collections.deque()
+        self._feed = DeviceFeed(_HostSide(loader, self._kept), self.device)
+
+    def __iter__(self) -> Iterator:
+        self._kept.clear()
+        for miss_rows, *labels in self._feed:
+            shape, ids, pos = self._kept.popleft()
+            images, new_ids = self.cache.build_batch(ids, pos, miss_rows)
+            if new_ids:
+                self.dataset.resident[torch.as_tensor(new_ids, dtype=torch.int64)] = 1
+            yield (images.view(shape + self.cache.frame_shape), *labels)
+
+    def __len__(self):
+        return len(self.loader)
+
+
+class CachedLoader:
+    """a DataLoader of a `frame_ids=True` dataset together with the cache its batches are built from: what the trainers' passes receive
+    in place of the loader when cfg.frame_cache_gb > 0 (`feed_for` turns either into the right feed)"""
+
+    def __init__(self, loader, cache: FrameCache, dataset):
+        self.loader, self.cache, self.dataset = loader, cache, dataset
+
+    def feed(self, device) -> CachedFeed:
+        return CachedFeed(self.loader, device, self.cache, self.dataset)
+
+    def __iter__(self):
+        return iter(self.loader)
+
+    def __len__(self):
+        return len(self.loader)
+
+
+def feed_for(loader, device):
+    """the device feed of a pass: CachedFeed for a CachedLoader, input_feed.DeviceFeed for anything else"""
+    return loader.feed(device) if isinstance(loader, CachedLoader) else DeviceFeed(loader, device)
+
+
+def wants_frame_ids(cfg) -> bool:
+    return float(getattr(cfg, "frame_cache_gb", 0) or 0) > 0
+
+
+def build_loaders(cfg, training_set, validation_set, per_rank: int, sampler, device, real_tree: bool):
+    """the two DataLoaders of train_net / train_net_dynamic.  With cfg.num_workers = 0 and cfg.frame_cache_gb = 0 (the defaults), or
+    without the real dataset tree, exactly the loaders the trainers always built.  Otherwise cfg.num_workers worker processes per loader
+    (the platform's default start method; they decode and never touch the GPU; a stuck worker raises after LOADER_TIMEOUT_S), and, when
+    the datasets carry frame ids, one FrameCache of cfg.frame_cache_gb per dataset behind a CachedLoader."""
+    workers = int(getattr(cfg, "num_workers", 0) or 0) if real_tree else 0
+    extra = dict(num_workers=workers, timeout=LOADER_TIMEOUT_S) if workers > 0 else dict(num_workers=0)
+    cached = real_tree and wants_frame_ids(cfg) and getattr(training_set, "frame_ids", False) and getattr(validation_set, "frame_ids", False)
+    if cached:
+        extra["collate_fn"] = collate
+    training_loader = data.DataLoader(training_set, batch_size=per_rank, shuffle=sampler is None, sampler=sampler, **extra)
+    validation_loader = data.DataLoader(validation_set, batch_size=cfg.test_batch_size, shuffle=False, **extra)
+    if not cached:
+        return training_loader, validation_loader
+    capacity = int(float(cfg.frame_cache_gb) * 1e9)
+    frame_shape = (3,) + tuple(cfg.image_size)
+    return (CachedLoader(training_loader, FrameCache(device, frame_shape, capacity), training_set),
+            CachedLoader(validation_loader, FrameCache(device, frame_shape, capacity), validation_set))

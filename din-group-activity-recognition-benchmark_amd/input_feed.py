@@ -27,13 +27,18 @@ class DeviceFeed:
         self._copied: List[Optional[torch.cuda.Event]] = [None] * slots   # slot -> completion of the last transfer out of its pinned buffers
 
     def _stage(self, slot: int, pos: int, t: torch.Tensor) -> torch.Tensor:
-        if t.is_pinned():
+        if t.numel() == 0 or t.is_pinned():
             return t
+        # the staging buffer only grows along dim 0: a shorter last batch, or the frame cache's varying number of missed frames
+        # (frame_cache.CachedFeed), is staged through a view of it instead of a fresh hipHostMalloc
+        rows = t.shape[0] if t.dim() else None
         buf = self._pinned[slot].get(pos)
-        if buf is None or buf.shape != t.shape or buf.dtype != t.dtype:
+        if (buf is None or buf.dtype != t.dtype or buf.dim() != t.dim() or buf.shape[1:] != t.shape[1:]
+                or (rows is not None and buf.shape[0] < rows)):
             buf = self._pinned[slot][pos] = torch.empty(t.shape, dtype=t.dtype).pin_memory()
-        buf.copy_(t)
-        return buf
+        view = buf if rows is None else buf[:rows]
+        view.copy_(t)
+        return view
 
     def _enqueue(self, slot: int, host_batch):
         single = isinstance(host_batch, torch.Tensor)

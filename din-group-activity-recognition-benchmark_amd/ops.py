@@ -950,3 +950,16 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=
     require_gpu(p, g, m, v)
     L.check(lib.din_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                               _stream()), "adam_step")
+
+
+def copy_rows_u8(src: torch.Tensor, dst: torch.Tensor, nbytes: int, n: Optional[int] = None) -> None:
+    """row i: `nbytes` bytes from device address src[i] to device address dst[i], one launch on the current stream; src[i] == 0 leaves
+    row i alone.  src, dst: int64 device tables (din_copy_rows_u8: the frame cache's insert and gather)."""
+    lib = L.load()
+    require_gpu(src, dst)
+    if src.dtype != torch.int64 or dst.dtype != torch.int64:
+        raise L.DinError("copy_rows_u8: address tables are int64 device tensors")
+    n = min(src.numel(), dst.numel()) if n is None else n
+    if n > min(src.numel(), dst.numel()):
+        raise L.DinError(f"copy_rows_u8: n = {n} rows but the tables hold {src.numel()} / {dst.numel()} addresses")
+    L.check(lib.din_copy_rows_u8(_ptr(src), _ptr(dst), n, nbytes, _stream()), "copy_rows_u8")

@@ -30,7 +30,8 @@ import torch.utils.data as data
 from . import parallel
 from .base_model import Basenet_collective, Basenet_volleyball
 from .config import Config  # noqa: F401  (the reference's launchers do `from train_net import *` and then `Config('volleyball')`)
-from .input_feed import DeviceFeed
+from . import frame_cache
+from .input_feed import DeviceFeed  # noqa: F401  (re-exported: `from train_net import *` launchers)
 from .optim import FusedAdam
 from .train_net_dynamic import SyntheticCollective, SyntheticVolleyball, adjust_lr, set_bn_eval
 from .utils import Timer, print_log
@@ -102,7 +103,7 @@ def _losses(actions_scores, activities_scores, actions_in, activities_in, batch_
 
 def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets, collective, max_batches=None):
     meters = _Meters(cfg, device)
-    for bi, batch_data in enumerate(DeviceFeed(data_loader, device)):
+    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device)):
         if max_batches is not None and bi >= max_batches:
             break
         model.train()
@@ -126,7 +127,7 @@ def _test_pass(data_loader, model, device, epoch, cfg, collective):
     model.eval()
     meters = _Meters(cfg, device)
     with torch.no_grad():
-        for batch_data in DeviceFeed(data_loader, device):
+        for batch_data in frame_cache.feed_for(data_loader, device):
             inputs, actions_in, activities_in, batch_size = _step_inputs(batch_data, cfg, collective)
             actions_scores, activities_scores = model(inputs)
             total_loss, actions_in = _losses(actions_scores, activities_scores, actions_in, activities_in, batch_data, cfg, collective)
@@ -173,17 +174,20 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     torch.cuda.set_device(device)
     collective = cfg.dataset_name == "collective"
     synth = SyntheticCollective if collective else SyntheticVolleyball
+    real_tree = False
     if training_set is None and validation_set is None and getattr(cfg, "data_path", None) and os.path.isdir(cfg.data_path):
         from .dataset import return_dataset                           # stage-1 frame sampling (is_finetune) follows cfg.training_stage
-        training_set, validation_set = return_dataset(cfg)
+        training_set, validation_set = return_dataset(cfg, frame_ids=frame_cache.wants_frame_ids(cfg))
+        real_tree = True
     training_set = training_set or synth(cfg, length=max(cfg.batch_size * 2, 4))
     validation_set = validation_set or synth(cfg, length=max(cfg.test_batch_size, 2), seed=1)
     if cfg.batch_size % world != 0:
         raise ValueError(f"batch_size {cfg.batch_size} must be divisible by the number of ranks {world}")
     per_rank = cfg.batch_size // world
     sampler = data.distributed.DistributedSampler(training_set, world, rank, shuffle=True) if world > 1 else None
-    training_loader = data.DataLoader(training_set, batch_size=per_rank, shuffle=sampler is None, sampler=sampler, num_workers=0)
-    validation_loader = data.DataLoader(validation_set, batch_size=cfg.test_batch_size, shuffle=False, num_workers=0)
+    # cfg.num_workers / cfg.frame_cache_gb (both 0 by default: the loaders below are then the plain num_workers=0 DataLoaders) apply to
+    # the real dataset tree only: worker processes decode, and decoded frames stay in HBM from their first use on (frame_cache.py)
+    training_loader, validation_loader = frame_cache.build_loaders(cfg, training_set, validation_set, per_rank, sampler, device, real_tree)
     log_path = getattr(cfg, "log_path", None)
     model = model.to(device)
     parallel.broadcast_parameters(model)

@@ -27,7 +27,8 @@ import torch.nn.functional as F
 import torch.utils.data as data
 
 from . import parallel
-from .input_feed import DeviceFeed
+from . import frame_cache
+from .input_feed import DeviceFeed  # noqa: F401  (re-exported: `from train_net import *` launchers)
 from .infer_model import (ARG_volleyball, AT_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, Dynamic_volleyball,
                           PCTDM_volleyball)
 from .optim import FusedAdam
@@ -123,7 +124,7 @@ class _Epoch:
 
 def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets, collective, max_batches=None):
     meters = _Epoch(cfg, device)
-    for bi, batch_data in enumerate(DeviceFeed(data_loader, device)):      # batch k+1 crosses PCIe on the copy stream during step k
+    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device)):      # batch k+1 crosses PCIe on the copy stream during step k
         if max_batches is not None and bi >= max_batches:
             break
         model.train()
@@ -150,7 +151,7 @@ def _test_pass(data_loader, model, device, epoch, cfg, collective):
     model.eval()
     meters = _Epoch(cfg, device)
     with torch.no_grad():
-        for batch_data in DeviceFeed(data_loader, device):
+        for batch_data in frame_cache.feed_for(data_loader, device):
             batch_size, num_frames = batch_data[0].shape[0], batch_data[0].shape[1]
             activities_in = batch_data[3].reshape((batch_size, num_frames))[:, 0].reshape((batch_size,))
             inputs = (batch_data[0], batch_data[1], batch_data[4]) if collective else (batch_data[0], batch_data[1])
@@ -202,11 +203,13 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     torch.cuda.set_device(device)
     collective = cfg.dataset_name == "collective"
     synth = SyntheticCollective if collective else SyntheticVolleyball
+    real_tree = False
     if training_set is None and validation_set is None and getattr(cfg, "data_path", None) and os.path.isdir(cfg.data_path):
         # the real datasets (reference train_net_dynamic.py:57-58 -> dataset.return_dataset): annotation trees + JPEG frames -> uint8 clips,
         # feature-px boxes, padded tracks (din_amd/volleyball.py, collective.py); without a data tree the synthetic clips stand in
         from .dataset import return_dataset
-        training_set, validation_set = return_dataset(cfg)
+        training_set, validation_set = return_dataset(cfg, frame_ids=frame_cache.wants_frame_ids(cfg))
+        real_tree = True
     training_set = training_set or synth(cfg, length=max(cfg.batch_size * 2, 4))
     if validation_set is None and cfg.inference_module_name == "arg_volleyball":
         # ARG test clips hold three sub-clips of num_frames frames each (volleyball.py:212-214, infer_model.py:939-943)
@@ -219,8 +222,9 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
                          f"per-rank means, which is the global mean only for equal shards")
     per_rank = cfg.batch_size // world
     sampler = data.distributed.DistributedSampler(training_set, world, rank, shuffle=True) if world > 1 else None
-    training_loader = data.DataLoader(training_set, batch_size=per_rank, shuffle=sampler is None, sampler=sampler, num_workers=0)
-    validation_loader = data.DataLoader(validation_set, batch_size=cfg.test_batch_size, shuffle=False, num_workers=0)
+    # cfg.num_workers / cfg.frame_cache_gb (both 0 by default: the loaders below are then the plain num_workers=0 DataLoaders) apply to
+    # the real dataset tree only: worker processes decode, and decoded frames stay in HBM from their first use on (frame_cache.py)
+    training_loader, validation_loader = frame_cache.build_loaders(cfg, training_set, validation_set, per_rank, sampler, device, real_tree)
     log_path = getattr(cfg, "log_path", None)
     if cfg.training_stage != 2:
         raise NotImplementedError("training_stage 1 (Basenet) is out of scope: the MI355X hot path is the stage-2 DIN step")

@@ -75,6 +75,28 @@ def load_frame_u8(path: str, image_size: Tuple[int, int]) -> np.ndarray:
     return np.ascontiguousarray(arr.transpose(2, 0, 1))
 
 
+def build_frame_table(paths):
+    """frame cache (din_amd/frame_cache.py): the sorted table of every distinct frame path a dataset can select, path -> frame id, and
+    the `resident` flags, one uint8 per frame in SHARED memory so that forked loader workers see what the main process marks"""
+    table = sorted(set(paths))
+    resident = torch.zeros(len(table), dtype=torch.uint8).share_memory_()
+    return table, {p: i for i, p in enumerate(table)}, resident
+
+
+def load_missing_frames(paths, index, resident, image_size, load):
+    """(frame_ids int64 [T], miss_images uint8 [M, 3, H, W], miss_index int64 [M]): only the frames whose resident flag is clear are
+    decoded (`load` = the caller's load_frame_u8), in clip order; miss_index says which of the T frames they are -- the flags may change
+    between this read and the consumer's, so the consumer cannot derive it"""
+    ids = [index[p] for p in paths]
+    flags = resident.numpy()
+    miss = [t for t, i in enumerate(ids) if not flags[i]]
+    if miss:
+        images = torch.from_numpy(np.stack([load(paths[t], image_size) for t in miss]))
+    else:
+        images = torch.empty((0, 3) + tuple(image_size), dtype=torch.uint8)
+    return torch.tensor(ids, dtype=torch.int64), images, torch.tensor(miss, dtype=torch.int64)
+
+
 def tracks_to_boxes(track: np.ndarray, feature_size: Tuple[int, int]) -> np.ndarray:
     """normalised (y1, x1, y2, x2) [n, 4] -> (x1*OW, y1*OH, x2*OW, y2*OH) in the track's own dtype (volleyball.py:246-251)"""
     oh, ow = feature_size
@@ -96,21 +118,42 @@ def pad_by_repetition(rows, num: int):
 class VolleyballDataset(data.Dataset):
     """reference volleyball.py:146-275 (constructor arguments in the same order); item = (images, bboxes, actions, activities):
     images uint8 [T, 3, H, W] (float32 when uint8_images=False), bboxes float32 [T, N, 4] in feature px, actions int64 [T, N],
-    activities int64 [T]."""
+    activities int64 [T].
+    frame_ids=True (frame cache, din_amd/frame_cache.py): `frame_table` is the sorted list of every frame path the dataset can select,
+    `resident` one shared-memory flag per entry, and an item is (frame_ids int64 [T], miss_images uint8 [M, 3, H, W], bboxes, actions,
+    activities, miss_index int64 [M]): only frames whose flag is clear are decoded (M may be 0).  Frame selection, boxes, labels and
+    their random draws are the same either way."""
 
     def __init__(self, anns, tracks, frames, images_path, image_size, feature_size, inference_module_name="dynamic_volleyball", num_boxes=12,
-                 num_before=4, num_after=4, is_training=True, is_finetune=False, uint8_images=True):
+                 num_before=4, num_after=4, is_training=True, is_finetune=False, uint8_images=True, frame_ids=False):
         self.anns, self.tracks, self.frames = anns, tracks, frames
         self.images_path, self.image_size, self.feature_size = images_path, tuple(image_size), tuple(feature_size)
         self.inference_module_name = inference_module_name
         self.num_boxes, self.num_before, self.num_after = num_boxes, num_before, num_after
         self.is_training, self.is_finetune, self.uint8_images = is_training, is_finetune, uint8_images
+        self.frame_ids = frame_ids
+        if frame_ids:
+            if not uint8_images:
+                raise ValueError("frame_ids=True caches uint8 frames: uint8_images must stay True")
+            self.frame_table, self._frame_index, self.resident = build_frame_table(
+                self.frame_path(*f) for frame in frames for f in self.selectable_frames(frame))
 
     def __len__(self):
         return len(self.frames)
 
     def __getitem__(self, index):
         return self.load_samples_sequence(self.volley_frames_sample(self.frames[index]))
+
+    def frame_path(self, sid, src, fid):
+        return os.path.join(self.images_path, str(sid), str(src), f"{fid}.jpg")
+
+    def selectable_frames(self, frame):
+        """every (sid, src, fid) volley_frames_sample can return for this clip: the window, plus ARG's nine fixed test offsets"""
+        sid, src = frame
+        fids = set(range(src - self.num_before, src + self.num_after + 1))
+        if not self.is_finetune and self.inference_module_name == "arg_volleyball" and not self.is_training:
+            fids.update(src + d for d in range(-4, 5))
+        return [(sid, src, fid) for fid in sorted(fids)]
 
     def volley_frames_sample(self, frame):
         """stage 2 (DIN): the whole window src-num_before .. src+num_after, training and test alike (volleyball.py:214-219); stage 1
@@ -126,13 +169,18 @@ class VolleyballDataset(data.Dataset):
         return volley_frames_around(frame, self.num_before, self.num_after)
 
     def load_samples_sequence(self, select_frames):
-        images = np.stack([load_frame_u8(os.path.join(self.images_path, str(sid), str(src), f"{fid}.jpg"), self.image_size)
-                           for sid, src, fid in select_frames])
+        paths = [self.frame_path(sid, src, fid) for sid, src, fid in select_frames]
+        if not self.frame_ids:
+            images = np.stack([load_frame_u8(p, self.image_size) for p in paths])
         boxes = np.stack([pad_by_repetition(tracks_to_boxes(self.tracks[(sid, src)][fid], self.feature_size), self.num_boxes)
                           for sid, src, fid in select_frames])
         actions = np.array([pad_by_repetition(list(self.anns[sid][src]["actions"]), self.num_boxes) for sid, src, _ in select_frames],
                            dtype=np.int64)
         activities = np.array([self.anns[sid][src]["group_activity"] for sid, src, _ in select_frames], dtype=np.int64)
+        if self.frame_ids:
+            ids, miss, miss_index = load_missing_frames(paths, self._frame_index, self.resident, self.image_size, load_frame_u8)
+            return (ids, miss, torch.from_numpy(boxes.astype(np.float32)), torch.from_numpy(actions), torch.from_numpy(activities),
+                    miss_index)
         img = torch.from_numpy(images)
         return (img if self.uint8_images else img.float(), torch.from_numpy(boxes.astype(np.float32)),
                 torch.from_numpy(actions), torch.from_numpy(activities))

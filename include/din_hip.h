@@ -631,6 +631,19 @@ int din_adam_step_multi(const uint64_t* ptrs, const int64_t* sizes, const int32_
                         int nchunks, int chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay,
                         int step, float grad_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Frame cache: n byte-row copies in one launch (din_amd/frame_cache.py).  Replaces, from the second epoch on, what the reference does
+ * for every frame of every epoch: decode + resize + stack on the host (volleyball.py:223-275) and a blocking upload of the batch
+ * (train_net_dynamic.py:174) -- decoded uint8 frames stay in HBM slots and a batch is gathered from them.
+ * src, dst: DEVICE arrays of n device addresses; row i copies `bytes` bytes from src[i] to dst[i]; src[i] == 0 leaves row i alone.
+ * Rows may start at any byte alignment and `bytes` may be any value >= 0 (16-byte vectors wherever src[i] and dst[i] agree mod 16,
+ * narrower vectors otherwise, single bytes for head and tail).  Sources may repeat; destinations must not overlap each other or any
+ * source.  One plain launch over (row, segment) on `stream`: no allocation, no synchronisation, capturable.  n == 0 or bytes == 0
+ * returns DIN_OK without a launch; n < 0, bytes < 0 or a null table with n > 0 returns DIN_E_ARG before any launch.  Additive: the ABI
+ * version stays 9.
+ * ---------------------------------------------------------------------------------------------- */
+int din_copy_rows_u8(const uint64_t* src, const uint64_t* dst, int n, int64_t bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
