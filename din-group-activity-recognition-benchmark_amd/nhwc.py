@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -600,282 +600,116 @@ def graph_forward(g: Graph, image_buf: torch.Tensor, params: Sequence[torch.Tens
     return bufs, aux
 
 
-def graph_backward(g: Graph, bufs, aux, params: Sequence[torch.Tensor], dt: int,
-                   out_grads: Dict[int, torch.Tensor], need_param_grad: Sequence[bool], bn_train: bool = False):
-    """Reverse pass.  out_grads: tid -> gradient buffer (same geometry/dtype as the tensor, already ReLU-masked where
-    the tensor is relu_masked).  Returns the list of parameter gradients aligned with `params` (None for buffers)."""
+# ------------------------------------------------------------------------------------------------
+# reverse pass: plan_backward decides (no tensor, no stream), _BackwardPass does, graph_backward is the loop over the ops.
+# profiles/backward_launch_trace.txt (tools/backward_trace.py, tests/test_backward_trace_cpu.py) pins every launch and hook of it.
+# ------------------------------------------------------------------------------------------------
+ViewKey = Tuple[int, int, int]                 # (tensor id, channel offset, channels)
+
+
+@dataclass
+class BackwardPlan:
+    """What one reverse pass of a graph will fuse, group and defer: a function of the graph, the frame count, the dtype, the BatchNorm
+    mode, the switches / options and the library's planning queries (plan_backward)."""
+    offsets: List[int]                              # op index -> index of its weight in params (-1: not a conv)
+    bn_index: Dict[int, int]                        # conv + BatchNorm op index -> its slot in the graph's BatchNorm tables
+    bn_train: bool                                  # batch-statistics BatchNorm (and the graph has BatchNorm layers)
+    side: bool                                      # weight gradients run on the second stream
+    u8: bool                                        # the image layer reads raw uint8 frames
+    dgrad_groups: Dict[ViewKey, List[int]]          # 1x1 / stride-1 convs reading one view: their dgrads are ONE launch (din_conv1x1_dgrad_multi)
+    member_of: Dict[int, ViewKey]                   # op index -> its dgrad group
+    x_host: Dict[int, int]                          # lone 1x1 op index -> the strided op whose dgrad will carry its dgrad (din_conv_dgrad_x)
+    siblings: Dict[int, Tuple[int, ...]]            # last member -> the forward-group members that share a tensor: one wgrad launch
+    multi_w: Dict[ViewKey, Tuple[List[Tuple[int, ...]], int]]   # dgrad group -> (sources, workspace bytes) of its ONE wgrad launch (din_conv1x1_wgrad_multi)
+    group_on: bool                                  # weight gradients queue up for grouped launches (din_conv_wgrad_group) ...
+    group_max: int                                  # ... of at most this many layers ...
+    group_bytes: int                                # ... holding back at most this many bytes of operands
+    partitioned: set                                # tensors whose gradient is first WRITTEN range by range by its readers (see _partitioned)
+    first_writer: Dict[int, int]                    # tensor id -> the first op in program order that writes it (its gradient is dead after it)
+
+
+def _partitioned(readers: List[Tuple[int, int]], writers: Sequence[Tuple[int, int]]) -> bool:
+    """True when the readers of a tensor use pairwise identical-or-disjoint channel views (`readers`: sorted distinct (offset, channels))
+    that together cover every producer's view: then each channel range of the gradient is first WRITTEN by its first reader (no zero
+    fill, no accumulate), and nothing is read before it was written (temporaries of sibling convs that share one tensor)."""
+    for (a0, ac), (b0, _bc) in zip(readers, readers[1:]):
+        if b0 < a0 + ac:
+            return False
+    for lo, c in writers:
+        hi = lo + c
+        for c0, cc in readers:
+            if c0 <= lo < c0 + cc:
+                lo = min(hi, c0 + cc)
+        if lo < hi:
+            return False
+    return True
+
+
+def wgrad_queue_full(layers: int, held_bytes: int, max_layers: int, max_bytes: int) -> bool:
+    """the flush rule of a grouped weight-gradient queue (held_bytes grows with the local batch, so ranks with different
+    batches flush at different layers)"""
+    return layers >= max_layers or held_bytes >= max_bytes
+
+
+def plan_backward(g: Graph, nb: int, dt: int, bn_train: bool, side_ok: bool, u8: bool) -> BackwardPlan:
+    """Decide the reverse pass of g on nb frames.  side_ok: a second stream may be used (no launch timing in progress).  The only place
+    of the pass that reads the host switches and the DIN_GROUP_WGRAD_* options; built on every call (options change between passes)."""
     lib = L.load()
-    nb = bufs[g.input_tid].shape[0]
-    dev = bufs[g.input_tid].device
-    tdt = torch_dtype(dt)
-    sdt = L.storage_dtype(dt)                  # what the data-moving entry points (bn, colsum) take; conv descriptors carry dt itself
-    st = _stream()
-    main = torch.cuda.current_stream()
-    side = side_stream(dev) if (switch("WGRAD_SIDE_STREAM") and not TIMING_ACTIVE()) else None
-    wtag = ""
-    gbufs: Dict[int, torch.Tensor] = dict(out_grads)
-
-    def on_side(tensors):
-        """the main stream's work so far is visible to the side stream; the listed tensors stay alive for it"""
-        ev = torch.cuda.Event()
-        ev.record(main)
-        side.wait_event(ev)
-        for t_ in tensors:
-            if t_ is not None:
-                t_.record_stream(side)
-        return C.c_void_p(side.cuda_stream)
-
-    gwritten: Dict[int, List[Tuple[int, int]]] = {}          # tid -> channel ranges already written (buffers this pass allocated un-zeroed)
-
-    def partitioned(tid: int) -> bool:
-        """True when the readers of tensor tid use pairwise identical-or-disjoint channel views that together cover every producer's view:
-        then each channel range of the gradient is first WRITTEN by its first reader (no zero fill, no accumulate), and nothing is read
-        before it was written (temporaries of sibling convs that share one tensor)."""
-        cons = sorted({(o.src.coff, o.src.c) for o in g.ops if o.src.tid == tid})
-        for (a0, ac), (b0, bc_) in zip(cons, cons[1:]):
-            if b0 < a0 + ac:
-                return False
-        for o in g.ops:
-            if o.dst.tid == tid:
-                lo, hi = o.dst.coff, o.dst.coff + o.dst.c
-                for c0, cc in cons:
-                    if c0 <= lo < c0 + cc:
-                        lo = min(hi, c0 + cc)
-                if lo < hi:
-                    return False
-        return True
-
-    def grad_target(view: View) -> Tuple[torch.Tensor, bool]:
-        """gradient buffer of view.tid and whether to accumulate into it"""
-        ts = g.tensors[view.tid]
-        rng = (view.coff, view.c)
-        if view.tid in gbufs:
-            wr = gwritten.get(view.tid)
-            if wr is None:                                  # handed in by the caller or zero-filled: always add
-                return gbufs[view.tid], True
-            acc = any(rng[0] < r0 + rc and r0 < rng[0] + rng[1] for r0, rc in wr)
-            wr.append(rng)
-            return gbufs[view.tid], acc
-        full = view.coff == 0 and view.c == ts.c
-        if full or partitioned(view.tid):
-            buf = torch.empty((nb, ts.h, ts.w, ts.c), dtype=tdt, device=dev)
-            gwritten[view.tid] = [rng]
-            gbufs[view.tid] = buf
-            return buf, False
-        buf = torch.zeros((nb, ts.h, ts.w, ts.c), dtype=tdt, device=dev)
-        gbufs[view.tid] = buf
-        return buf, True
-
-    # index params per conv op
-    offsets, pos = [], 0
-    for op in g.ops:
+    offsets, bn_index, pos = [], {}, 0
+    readers: Dict[int, set] = {}
+    writers: Dict[int, list] = {}
+    first_writer: Dict[int, int] = {}
+    for oi, op in enumerate(g.ops):
         if op.kind == "conv":
             offsets.append(pos)
+            if op.bn:
+                bn_index[oi] = len(bn_index)
             pos += 5 if op.bn else (2 if op.bias else 1)
         else:
             offsets.append(-1)
-    grads: List[Optional[torch.Tensor]] = [None] * len(params)
-    bn = _bn_tables(g, params, dev)
-    pcache = _pack_cache(g, params, dt, dev, True, bn)          # the forward pass of this step packed both orientations
-    if bn is not None:
-        # flat, pre-zeroed accumulators for every layer's shift gradient and <W, dW> dot (one memset instead of two per layer)
-        bn_acc = torch.zeros(2 * bn.total, dtype=torch.float32, device=dev)
-        bn_dshift, bn_wdot = bn_acc[:bn.total], bn_acc[bn.total:]
-        bn_index = {}
-        k_ = 0
-        for oi_, op_ in enumerate(g.ops):
-            if op_.kind == "conv" and op_.bn:
-                bn_index[oi_] = k_
-                k_ += 1
-        bn_touched = False
+        readers.setdefault(op.src.tid, set()).add((op.src.coff, op.src.c))
+        writers.setdefault(op.dst.tid, []).append((op.dst.coff, op.dst.c))
+        first_writer.setdefault(op.dst.tid, oi)
+    partitioned = {tid for tid, views in readers.items() if views != {(0, g.tensors[tid].c)} and _partitioned(sorted(views), writers.get(tid, ()))}
+    bn_train = bool(bn_train) and bool(bn_index)
+    side = bool(side_ok) and switch("WGRAD_SIDE_STREAM")
+    bf16 = dt == L.DIN_BF16
 
+    def entry_1x1(op):
+        return op.kind == "conv" and op.k == (1, 1) and op.s == (1, 1) and op.p == (0, 0) and op.src.tid != g.input_tid
     # 1x1 / stride-1 convs that read the same view (branch-entry convs of the Inception blocks): their dgrads are fused into ONE
     # multi-source launch, issued when the last member (first in program order) has been visited
-    groups: Dict[Tuple[int, int, int], List[int]] = {}
+    groups: Dict[ViewKey, List[int]] = {}
     if switch("FUSE_1X1_DGRAD"):
         for oi, op in enumerate(g.ops):
-            if op.kind == "conv" and op.k == (1, 1) and op.s == (1, 1) and op.p == (0, 0) and op.src.tid != g.input_tid:
+            if entry_1x1(op):
                 groups.setdefault((op.src.tid, op.src.coff, op.src.c), []).append(oi)
     groups = {k: v for k, v in groups.items() if 2 <= len(v) <= 4}
     member_of = {oi: key for key, v in groups.items() for oi in v}
-    remaining = {key: len(v) for key, v in groups.items()}
-    pending: Dict[Tuple[int, int, int], list] = {key: [] for key in groups}
     # a lone 1x1 / stride-1 conv whose input view is also read by a STRIDED conv earlier in program order (InceptionB: branch3x3dbl_1 beside
     # branch3x3): the reverse pass meets the 1x1 first, parks its dgrad operands, and the strided conv's dgrad carries them (din_conv_dgrad_x)
-    x_host: Dict[int, int] = {}                               # 1x1 op index -> strided op index that will carry its dgrad
-    x_parked: Dict[int, tuple] = {}                           # strided op index -> (1x1 op index, its gout, pixel stride, channel offset)
-    if switch("FUSE_DGRAD_X") and dt == L.DIN_BF16:
+    x_host: Dict[int, int] = {}
+    if switch("FUSE_DGRAD_X") and bf16:
         for oi, op in enumerate(g.ops):
-            if (op.kind == "conv" and op.k == (1, 1) and op.s == (1, 1) and op.p == (0, 0) and op.src.tid != g.input_tid and oi not in member_of
-                    and op.pooled is None):
+            if entry_1x1(op) and oi not in member_of and op.pooled is None:
                 for oj in range(oi - 1, -1, -1):
                     o2 = g.ops[oj]
                     if o2.kind == "conv" and o2.src == op.src and (o2.s[0] > 1 or o2.s[1] > 1) and oj not in x_host.values():
                         x_host[oi] = oj
                         break
-
-    def flush_wgrad_multi(key, items):
-        """the deferred weight gradients of a 1x1 group (multi_w): ONE launch reads the block input once and produces every member's dW"""
-        nonlocal bn_touched
-        by_oi = {it[0]: it for it in items}
-        op0 = g.ops[items[0][0]]
-        ts0 = g.tensors[op0.src.tid]
-        plan, wsb_need = multi_w[key]
-        if any(i not in by_oi for mem in plan for i in mem):
-            # A member received no gradient (a graph that consumes only some branch outputs -- partial heads; not the backbones here): the
-            # fused launch's plan does not apply, so the members that DID get one degrade to the per-layer kernel (ADVICE r3: this used
-            # to raise in the middle of backward, after the weight gradients had already been deferred)
-            for oi_, gout_, w_, scale_, ldj, coffj, pre in items:
-                opj = g.ops[oi_]
-                dj = _conv_desc(g, opj, nb, dt)
-                dj.ldo, dj.cooff = ldj, coffj
-                o0, o1 = bn.off_list[bn_index[oi_]], bn.off_list[bn_index[oi_] + 1]
-                dwj = _dw_buffer(w_)
-                ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(dj), 2), dev, wtag)
-                with _timed("wgrad", dj, opj.name):
-                    L.check(lib.din_conv_wgrad(C.byref(dj), _ptr(bufs[opj.src.tid]), _ptr(gout_), _ptr(dwj), None if pre else _ptr(bn_dshift[o0:o1]),
-                                               _ptr(scale_), _ptr(w_), _ptr(bn_wdot[o0:o1]), 2, _ptr(ws), wsb, st), "conv_wgrad " + opj.name)
-                grads[offsets[oi_]] = dwj
-                if GRAD_HOOK is not None:
-                    GRAD_HOOK(w_, dwj)
-            bn_touched = True
-            return
-        srcs = (L.ConvWSrc * len(plan))()
-        keep, outs = [], []
-        for j, mem in enumerate(plan):
-            _oi, gout_, _w, _scale, ldj, coffj, pre = by_oi[mem[0]]
-            o0, o1 = bn.off_list[bn_index[mem[0]]], bn.off_list[bn_index[mem[-1]] + 1]
-            if len(mem) == 1:
-                wj = params[offsets[mem[0]]]
-                dwj = _dw_buffer(wj)
-            else:
-                wj = torch.cat([params[offsets[i]] for i in mem])
-                dwj = torch.empty_like(wj)
-            keep += [wj, dwj, gout_]
-            srcs[j].dout, srcs[j].dw = gout_.data_ptr(), dwj.data_ptr()
-            srcs[j].dbias = 0 if pre else bn_dshift[o0:o1].data_ptr()
-            srcs[j].scale, srcs[j].w, srcs[j].wdot = pcache.bn_scale[o0:o1].data_ptr(), wj.data_ptr(), bn_wdot[o0:o1].data_ptr()
-            srcs[j].cout, srcs[j].ldo, srcs[j].cooff = o1 - o0, ldj, coffj
-            outs.append((mem, dwj))
-        bn_touched = True
-        ws, wsb = workspace(wsb_need, dev, wtag)
-        dM = _conv_desc(g, op0, nb, dt)
-        dM.cout = sum(s_.cout for s_ in srcs)                    # FLOP accounting of the fused launch
-        with _timed("wgrad", dM, "1x1multi:" + "+".join(g.ops[i].name for mem in plan for i in mem)):
-            L.check(lib.din_conv1x1_wgrad_multi(len(plan), srcs, dt, nb * ts0.h * ts0.w, op0.src.c, ts0.c, op0.src.coff, _ptr(bufs[op0.src.tid]), 2,
-                                                _ptr(ws), wsb, st), "conv1x1_wgrad_multi")
-        for mem, dwj in outs:
-            r0 = 0
-            for i in mem:
-                c = g.ops[i].dst.c
-                grads[offsets[i]] = dwj if len(mem) == 1 else dwj[r0:r0 + c]
-                r0 += c
-                if GRAD_HOOK is not None:
-                    GRAD_HOOK(params[offsets[i]], grads[offsets[i]])
-
-    # ---- layer-grouped weight gradients (din_conv_wgrad_group).  A weight gradient has no consumer inside the reverse pass, so layers whose
-    # kernel allows it (the pipelined wide-bank kernel, equal tile instantiation) are QUEUED with their operands and launched up to
-    # GROUP_WGRAD_MAX at a time: the launch's 256 workgroups are shared, every layer is cut into a fraction of the pixel slices it would get
-    # alone, and its fp32 slice partials (slices x |dW|, ~50 MB per layer and launch whatever the batch) shrink by the same factor.
-    wq: Dict[int, list] = {}
-    group_on = switch("GROUP_WGRAD") and dt == L.DIN_BF16 and side is None
-    group_max = max(2, min(16, int(L.get_option("DIN_GROUP_WGRAD_MAX") or GROUP_WGRAD_MAX))) if group_on else 0
-    group_bytes = int(L.get_option("DIN_GROUP_WGRAD_MB") or GROUP_WGRAD_MB) << 20 if group_on else 0
-    wq_bytes: Dict[int, int] = {}
-
-    def wgrad_now(d, x, go, dw_, dshift_, scale_, w_, wdot_, acc, name, after):
-        ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(d), 2), dev, wtag)
-        with _timed("wgrad", d, name):
-            L.check(lib.din_conv_wgrad(C.byref(d), _ptr(x), _ptr(go), _ptr(dw_), _ptr(dshift_), _ptr(scale_), _ptr(w_), _ptr(wdot_), acc,
-                                       _ptr(ws), wsb, st), "conv_wgrad " + name)
-        if after is not None:
-            after()
-
-    def flush_wq(key):
-        q = wq.pop(key, None)
-        wq_bytes.pop(key, None)
-        if not q:
-            return
-        need = 0
-        if len(q) > 1:
-            items = (L.ConvWgradItem * len(q))()
-            for it, (d, x, go, dw_, dshift_, scale_, w_, wdot_, acc, _name, _after) in zip(items, q):
-                it.desc = d
-                it.in_, it.dout, it.dw = x.data_ptr(), go.data_ptr(), dw_.data_ptr()
-                it.dbias = dshift_.data_ptr() if dshift_ is not None else None
-                it.scale = scale_.data_ptr() if scale_ is not None else None
-                it.w = w_.data_ptr() if w_ is not None else None
-                it.wdot = wdot_.data_ptr() if wdot_ is not None else None
-                it.accumulate = acc
-            need = lib.din_conv_wgrad_group_workspace(len(q), items)
-        if need <= 0:                                           # a single layer (or a list the library does not take as one launch)
-            for args in q:
-                wgrad_now(*args)
-            return
-        ws, wsb = workspace(need, dev, "wgroup")
-        dG = _copy_desc(q[0][0])
-        dG.flops_override = float(sum(2.0 * a[0].nb * a[0].oh * a[0].ow * a[0].cout * a[0].cin * a[0].kh * a[0].kw for a in q))
-        with _timed("wgrad", dG, "group:" + "+".join(a[9] for a in q)):
-            L.check(lib.din_conv_wgrad_group(len(q), items, _ptr(ws), wsb, st), "conv_wgrad_group " + q[0][9] + "+")
-        for a in q:
-            if a[10] is not None:
-                a[10]()
-
-    def wgrad_launch(d, x, go, dw_, dshift_, scale_, w_, wdot_, acc, name, after=None):
-        """one layer's weight gradient: queued for a grouped launch when its kernel allows it, launched at once otherwise"""
-        key = lib.din_conv_wgrad_group_key(C.byref(d)) if group_on else 0
-        if not key:
-            wgrad_now(d, x, go, dw_, dshift_, scale_, w_, wdot_, acc, name, after)
-            return
-        q = wq.setdefault(key, [])
-        q.append((_copy_desc(d), x, go, dw_, dshift_, scale_, w_, wdot_, acc, name, after))
-        wq_bytes[key] = wq_bytes.get(key, 0) + 2 * (d.nb * d.h * d.w * d.cin + d.nb * d.oh * d.ow * d.cout)      # bf16 operands held back
-        if len(q) >= group_max or wq_bytes[key] >= group_bytes:
-            flush_wq(key)
-
-    def flush_group(key):
-        items = pending[key]
-        if not items:
-            return
-        if key in multi_w:
-            flush_wgrad_multi(key, items)
-        op0 = g.ops[items[0][0]]
-        ts0 = g.tensors[op0.src.tid]
-        gsrc, acc = grad_target(op0.src)
-        srcs = (L.ConvSrc * len(items))()
-        keep = []
-        for j, (oi_, gout_, w_, scale_, ldj, coffj, _pre) in enumerate(items):
-            opj = g.ops[oi_]
-            dj = _conv_desc(g, opj, nb, dt)
-            wpt = pcache.wpt[oi_]
-            keep.append(wpt)
-            srcs[j].dout, srcs[j].wpk_t = gout_.data_ptr(), wpt.data_ptr()
-            srcs[j].cout, srcs[j].ldo, srcs[j].cooff = opj.dst.c, ldj, coffj
-        flags = (L.CONV_ACCUM if acc else 0) | (L.CONV_MASK if ts0.relu_masked else 0)
-        d0 = _conv_desc(g, op0, nb, dt)
-        d0.cout = sum(g.ops[it[0]].dst.c for it in items)          # FLOP accounting of the fused launch
-        d0.src_couts = tuple(g.ops[it[0]].dst.c for it in items)   # (measurement side: profiling.LaunchTimer names the instantiation from it)
-        with _timed("dgrad", d0, "+".join(g.ops[it[0]].name for it in items)):
-            L.check(lib.din_conv1x1_dgrad_multi(len(items), srcs, dt, nb, ts0.h, ts0.w, op0.src.c, ts0.c, op0.src.coff, _ptr(gsrc),
-                                                _ptr(bufs[op0.src.tid]) if ts0.relu_masked else None, ts0.c, op0.src.coff, flags, st),
-                    "conv1x1_dgrad_multi")
-        pending[key] = []
-
     # sibling groups: the members behind the first one share a tensor -> one wgrad launch, issued when the LAST of them comes up (the
     # reverse pass reaches it first; by then the consumers of every member have written their slice of the shared gradient buffer)
-    wgrad_group = {}
-    bn_train = bool(bn_train) and bn is not None
-    if switch("FUSE_WGRAD_SIBLINGS") and not bn_train:
+    siblings: Dict[int, Tuple[int, ...]] = {}
+    if switch("FUSE_WGRAD_SIBLINGS") and not bn_train and not side:
         for grp in g.fwd_groups:
             mem = tuple(i for i in grp[1:] if g.ops[i].pooled is None)      # (a commuted-pool member keeps its own wgrad: its gradient
-            if len(mem) >= 2:                                               #  operand is the un-pooled map, a separate buffer)
-                wgrad_group[mem[-1]] = mem
-    wgrad_done = set()
+            if len(mem) >= 2 and g.ops[mem[-1]].bn:                         #  operand is the un-pooled map, a separate buffer)
+                siblings[mem[-1]] = mem
     # 1x1 groups whose weight gradients run as ONE launch (din_conv1x1_wgrad_multi): sources = the members, sibling pairs that share a
-    # tensor (wgrad_group) counted as one source; the library says whether the group fits its kernel (0 bytes of workspace: it does not)
-    multi_w: Dict[Tuple[int, int, int], tuple] = {}
-    if switch("FUSE_WGRAD_1X1") and bn is not None and not bn_train and side is None and dt == L.DIN_BF16:
-        pair_of = {i: mem for mem in wgrad_group.values() for i in mem}
+    # tensor (siblings) counted as one source; the library says whether the group fits its kernel (0 bytes of workspace: it does not)
+    multi_w: Dict[ViewKey, Tuple[List[Tuple[int, ...]], int]] = {}
+    if switch("FUSE_WGRAD_1X1") and bn_index and not bn_train and not side and bf16:
+        pair_of = {i: mem for mem in siblings.values() for i in mem}
         for key, members in groups.items():
             if not all(g.ops[i].bn for i in members):
                 continue
@@ -893,229 +727,510 @@ def graph_backward(g: Graph, bufs, aux, params: Sequence[torch.Tensor], dt: int,
                 o = g.ops[mem[0]]
                 probe[j].cout = sum(g.ops[i].dst.c for i in mem)
                 probe[j].ldo, probe[j].cooff = (o.dst.c, 0) if o.pooled is not None else (g.tensors[o.dst.tid].c, o.dst.coff)
-            ts_ = g.tensors[g.ops[members[0]].src.tid]
-            need = lib.din_conv1x1_wgrad_multi_workspace(len(plan), probe, dt, nb * ts_.h * ts_.w, g.ops[members[0]].src.c) if 2 <= len(plan) <= 4 else 0
+            o0 = g.ops[members[0]]
+            ts0 = g.tensors[o0.src.tid]
+            need = lib.din_conv1x1_wgrad_multi_workspace(len(plan), probe, dt, nb * ts0.h * ts0.w, o0.src.c) if 2 <= len(plan) <= 4 else 0
             if need > 0:
                 multi_w[key] = (plan, need)
-    def dgrad_parked(host_oi):
-        """the strided conv that was to carry a parked 1x1 dgrad received no gradient itself: the 1x1's dgrad runs alone"""
-        oi_, gout_, ldj, coffj = x_parked.pop(host_oi)
-        opj = g.ops[oi_]
-        tsj = g.tensors[opj.src.tid]
-        dj = _conv_desc(g, opj, nb, dt)
-        dj.ldo, dj.cooff = ldj, coffj
-        gsrc, acc = grad_target(opj.src)
-        flags = (L.CONV_ACCUM if acc else 0) | (L.CONV_MASK if tsj.relu_masked else 0)
-        ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(dj), 1), dev)
-        with _timed("dgrad", dj, opj.name):
-            L.check(lib.din_conv_dgrad(C.byref(dj), _ptr(gout_), _ptr(pcache.wpt[oi_]), _ptr(gsrc),
-                                       _ptr(bufs[opj.src.tid]) if tsj.relu_masked else None, tsj.c, opj.src.coff, flags,
-                                       _ptr(ws), wsb, st), "conv_dgrad " + opj.name)
+    # layer-grouped weight gradients (din_conv_wgrad_group).  A weight gradient has no consumer inside the reverse pass, so layers whose
+    # kernel allows it (the pipelined wide-bank kernel, equal tile instantiation) are QUEUED with their operands and launched up to
+    # GROUP_WGRAD_MAX at a time: the launch's 256 workgroups are shared, every layer is cut into a fraction of the pixel slices it would get
+    # alone, and its fp32 slice partials (slices x |dW|, ~50 MB per layer and launch whatever the batch) shrink by the same factor.
+    group_on = switch("GROUP_WGRAD") and bf16 and not side
+    group_max = max(2, min(16, int(L.get_option("DIN_GROUP_WGRAD_MAX") or GROUP_WGRAD_MAX))) if group_on else 0
+    group_bytes = int(L.get_option("DIN_GROUP_WGRAD_MB") or GROUP_WGRAD_MB) << 20 if group_on else 0
+    return BackwardPlan(offsets, bn_index, bn_train, side, bool(u8), groups, member_of, x_host, siblings, multi_w, group_on, group_max,
+                        group_bytes, partitioned, first_writer)
 
+
+class _Pending(NamedTuple):
+    """a member of a 1x1 dgrad group that has been visited: what the group's launches need from it"""
+    oi: int
+    gout: torch.Tensor          # gradient at its conv output, as a view (ld, coff) of this buffer
+    w: torch.Tensor
+    scale: Optional[torch.Tensor]
+    ld: int
+    coff: int
+    pre: bool                   # its shift gradient was already taken in front of a commuted pool (din_colsum)
+
+
+class _Parked(NamedTuple):
+    """a lone 1x1's dgrad operands, waiting for the strided sibling that carries them"""
+    oi: int
+    gout: torch.Tensor
+    ld: int
+    coff: int
+
+
+class _Wgrad(NamedTuple):
+    """the arguments of one din_conv_wgrad call, launched at once or queued for a grouped launch"""
+    d: L.ConvDesc
+    x: torch.Tensor
+    gout: torch.Tensor
+    dw: torch.Tensor
+    dshift: Optional[torch.Tensor]
+    scale: Optional[torch.Tensor]
+    w: Optional[torch.Tensor]
+    wdot: Optional[torch.Tensor]
+    acc: int
+    name: str
+    outs: Tuple[Tuple[int, torch.Tensor], ...]      # (op index, its weight gradient inside dw): reported once the launch is enqueued
+
+
+@dataclass
+class _ConvStep:
+    """a conv op's turn in the reverse pass: the descriptor of its wgrad / dgrad launches and where the gradient at its conv output lives
+    (BatchNorm-train backward and the commuted-pool epilogue replace both)"""
+    d: L.ConvDesc
+    gout: torch.Tensor
+    ld: int
+    coff: int
+    dshift_pre: Optional[torch.Tensor] = None       # shift gradient already produced in front of a commuted pool
+
+
+class _BackwardPass:
+    """The state of one reverse pass -- gradient buffers and their written ranges, the parameter gradients, the BatchNorm accumulators,
+    pending dgrad groups, parked dgrads, weight-gradient queues -- and the steps that change it.  Everything here does; what to fuse,
+    group and defer was decided by plan_backward."""
+
+    def __init__(self, g: Graph, plan: BackwardPlan, bufs, aux, params: Sequence[torch.Tensor], dt: int, out_grads: Dict[int, torch.Tensor]):
+        self.g, self.plan, self.bufs, self.aux, self.params, self.dt = g, plan, bufs, aux, params, dt
+        self.lib = L.load()
+        self.nb, self.dev = bufs[g.input_tid].shape[0], bufs[g.input_tid].device
+        self.tdt = torch_dtype(dt)
+        self.sdt = L.storage_dtype(dt)             # what the data-moving entry points (bn, colsum) take; conv descriptors carry dt itself
+        self.st = _stream()
+        self.main = torch.cuda.current_stream()
+        self.side = side_stream(self.dev) if plan.side else None
+        self.gbufs: Dict[int, torch.Tensor] = dict(out_grads)
+        self.gwritten: Dict[int, List[Tuple[int, int]]] = {}    # tid -> channel ranges already written (buffers this pass allocated un-zeroed)
+        self.grads: List[Optional[torch.Tensor]] = [None] * len(params)
+        self.bn = _bn_tables(g, params, self.dev)
+        self.pcache = _pack_cache(g, params, dt, self.dev, True, self.bn)     # the forward pass of this step packed both orientations
+        if self.bn is not None:
+            # flat, pre-zeroed accumulators for every layer's shift gradient and <W, dW> dot (one memset instead of two per layer)
+            self.bn_acc = torch.zeros(2 * self.bn.total, dtype=torch.float32, device=self.dev)
+            self.bn_dshift, self.bn_wdot = self.bn_acc[:self.bn.total], self.bn_acc[self.bn.total:]
+        self.bn_touched = False
+        self.remaining = {key: len(v) for key, v in plan.dgrad_groups.items()}
+        self.pending: Dict[ViewKey, List[_Pending]] = {key: [] for key in plan.dgrad_groups}
+        self.parked: Dict[int, _Parked] = {}                    # strided op index -> the 1x1 dgrad it will carry
+        self.wq: Dict[int, List[_Wgrad]] = {}                   # group key -> queued weight gradients
+        self.wq_bytes: Dict[int, int] = {}
+        self.wgrad_done = set()                                 # members whose weight gradient a sibling's launch produces
+
+    # ---- helpers
+    def bn_range(self, first: int, last: Optional[int] = None) -> Tuple[int, int]:
+        """the slice of the flat BatchNorm arrays that belongs to op `first` (.. op `last`: adjacent slots)"""
+        off, k = self.bn.off_list, self.plan.bn_index
+        return off[k[first]], off[k[first if last is None else last] + 1]
+
+    def mask_of(self, view: View):
+        """the forward values that mask a gradient into `view` (ReLU backward), or None"""
+        return _ptr(self.bufs[view.tid]) if self.g.tensors[view.tid].relu_masked else None
+
+    def on_side(self, tensors):
+        """the main stream's work so far is visible to the side stream; the listed tensors stay alive for it"""
+        ev = torch.cuda.Event()
+        ev.record(self.main)
+        self.side.wait_event(ev)
+        for t in tensors:
+            if t is not None:
+                t.record_stream(self.side)
+        return C.c_void_p(self.side.cuda_stream)
+
+    def grad_target(self, view: View) -> Tuple[torch.Tensor, bool]:
+        """gradient buffer of view.tid and whether to accumulate into it"""
+        ts = self.g.tensors[view.tid]
+        rng = (view.coff, view.c)
+        if view.tid in self.gbufs:
+            wr = self.gwritten.get(view.tid)
+            if wr is None:                                  # handed in by the caller or zero-filled: always add
+                return self.gbufs[view.tid], True
+            acc = any(rng[0] < r0 + rc and r0 < rng[0] + rng[1] for r0, rc in wr)
+            wr.append(rng)
+            return self.gbufs[view.tid], acc
+        full = view.coff == 0 and view.c == ts.c
+        if full or view.tid in self.plan.partitioned:
+            buf = torch.empty((self.nb, ts.h, ts.w, ts.c), dtype=self.tdt, device=self.dev)
+            self.gwritten[view.tid] = [rng]
+            self.gbufs[view.tid] = buf
+            return buf, False
+        buf = torch.zeros((self.nb, ts.h, ts.w, ts.c), dtype=self.tdt, device=self.dev)
+        self.gbufs[view.tid] = buf
+        return buf, True
+
+    def dgrad_flags(self, view: View, acc: bool) -> int:
+        return (L.CONV_ACCUM if acc else 0) | (L.CONV_MASK if self.g.tensors[view.tid].relu_masked else 0)
+
+    def report(self, oi: int, dw: torch.Tensor) -> None:
+        """op oi's weight gradient is dw and the launch that produces it has been enqueued (on the main stream: GRAD_HOOK may start its
+        all-reduce; the side stream's gradients are complete only when the pass ends)"""
+        po = self.plan.offsets[oi]
+        self.grads[po] = dw
+        if GRAD_HOOK is not None and self.side is None:
+            GRAD_HOOK(self.params[po], dw)
+
+    # ---- weight gradients: at once, queued for a grouped launch, or one launch for a 1x1 group
+    def wgrad_now(self, it: _Wgrad, side_tensors=None) -> None:
+        """launch one layer's weight gradient; side_tensors (the tensors it touches): on the side stream, behind everything the main
+        stream has enqueued so far"""
+        wsbytes = self.lib.din_conv_workspace_bytes(C.byref(it.d), 2)
+        if side_tensors is None:
+            st = self.st
+            ws, wsb = workspace(wsbytes, self.dev)
+        else:
+            st = self.on_side(side_tensors)
+            with torch.cuda.stream(self.side):
+                ws, wsb = workspace(wsbytes, self.dev, "side")
+        with _timed("wgrad", it.d, it.name):
+            L.check(self.lib.din_conv_wgrad(C.byref(it.d), _ptr(it.x), _ptr(it.gout), _ptr(it.dw), _ptr(it.dshift), _ptr(it.scale), _ptr(it.w),
+                                            _ptr(it.wdot), it.acc, _ptr(ws), wsb, st), "conv_wgrad " + it.name)
+        for oi, dw in it.outs:
+            self.report(oi, dw)
+
+    def wgrad_launch(self, it: _Wgrad) -> None:
+        """one layer's weight gradient: queued for a grouped launch when its kernel allows it, launched at once otherwise"""
+        plan = self.plan
+        key = self.lib.din_conv_wgrad_group_key(C.byref(it.d)) if plan.group_on else 0
+        if not key:
+            self.wgrad_now(it)
+            return
+        d = it.d
+        q = self.wq.setdefault(key, [])
+        q.append(it._replace(d=_copy_desc(d)))
+        held = self.wq_bytes.get(key, 0) + 2 * (d.nb * d.h * d.w * d.cin + d.nb * d.oh * d.ow * d.cout)      # bf16 operands held back
+        self.wq_bytes[key] = held
+        if wgrad_queue_full(len(q), held, plan.group_max, plan.group_bytes):
+            self.flush_wq(key)
+
+    def flush_wq(self, key: int) -> None:
+        q = self.wq.pop(key, None)
+        self.wq_bytes.pop(key, None)
+        if not q:
+            return
+        need = 0
+        if len(q) > 1:
+            items = (L.ConvWgradItem * len(q))()
+            for item, it in zip(items, q):
+                item.desc = it.d
+                item.in_, item.dout, item.dw = it.x.data_ptr(), it.gout.data_ptr(), it.dw.data_ptr()
+                item.dbias = it.dshift.data_ptr() if it.dshift is not None else None
+                item.scale = it.scale.data_ptr() if it.scale is not None else None
+                item.w = it.w.data_ptr() if it.w is not None else None
+                item.wdot = it.wdot.data_ptr() if it.wdot is not None else None
+                item.accumulate = it.acc
+            need = self.lib.din_conv_wgrad_group_workspace(len(q), items)
+        if need <= 0:                                           # a single layer (or a list the library does not take as one launch)
+            for it in q:
+                self.wgrad_now(it)
+            return
+        ws, wsb = workspace(need, self.dev, "wgroup")
+        dG = _copy_desc(q[0].d)
+        dG.flops_override = float(sum(2.0 * it.d.nb * it.d.oh * it.d.ow * it.d.cout * it.d.cin * it.d.kh * it.d.kw for it in q))
+        with _timed("wgrad", dG, "group:" + "+".join(it.name for it in q)):
+            L.check(self.lib.din_conv_wgrad_group(len(q), items, _ptr(ws), wsb, self.st), "conv_wgrad_group " + q[0].name + "+")
+        for it in q:
+            for oi, dw in it.outs:
+                self.report(oi, dw)
+
+    def flush_wgrad_multi(self, key: ViewKey, items: List[_Pending]) -> None:
+        """the deferred weight gradients of a 1x1 group (plan.multi_w): ONE launch reads the block input once and produces every member's dW"""
+        g, lib, params, offsets = self.g, self.lib, self.params, self.plan.offsets
+        by_oi = {it.oi: it for it in items}
+        op0 = g.ops[items[0].oi]
+        ts0 = g.tensors[op0.src.tid]
+        sources, wsb_need = self.plan.multi_w[key]
+        self.bn_touched = True
+        if any(i not in by_oi for mem in sources for i in mem):
+            # A member received no gradient (a graph that consumes only some branch outputs -- partial heads; not the backbones here): the
+            # fused launch's plan does not apply, so the members that DID get one degrade to the per-layer kernel (ADVICE r3: this used
+            # to raise in the middle of backward, after the weight gradients had already been deferred)
+            for it in items:
+                opj = g.ops[it.oi]
+                dj = _conv_desc(g, opj, self.nb, self.dt)
+                dj.ldo, dj.cooff = it.ld, it.coff
+                o0, o1 = self.bn_range(it.oi)
+                dwj = _dw_buffer(it.w)
+                self.wgrad_now(_Wgrad(dj, self.bufs[opj.src.tid], it.gout, dwj, None if it.pre else self.bn_dshift[o0:o1], it.scale, it.w,
+                                      self.bn_wdot[o0:o1], 2, opj.name, ((it.oi, dwj),)))
+            return
+        srcs = (L.ConvWSrc * len(sources))()
+        outs = []
+        for j, mem in enumerate(sources):
+            first = by_oi[mem[0]]
+            o0, o1 = self.bn_range(mem[0], mem[-1])
+            if len(mem) == 1:
+                wj = params[offsets[mem[0]]]
+                dwj = _dw_buffer(wj)
+            else:
+                wj = torch.cat([params[offsets[i]] for i in mem])
+                dwj = torch.empty_like(wj)
+            srcs[j].dout, srcs[j].dw = first.gout.data_ptr(), dwj.data_ptr()
+            srcs[j].dbias = 0 if first.pre else self.bn_dshift[o0:o1].data_ptr()
+            srcs[j].scale, srcs[j].w, srcs[j].wdot = self.pcache.bn_scale[o0:o1].data_ptr(), wj.data_ptr(), self.bn_wdot[o0:o1].data_ptr()
+            srcs[j].cout, srcs[j].ldo, srcs[j].cooff = o1 - o0, first.ld, first.coff
+            outs.append((mem, wj, dwj))                          # (wj: a concatenation lives until the launch below is enqueued)
+        ws, wsb = workspace(wsb_need, self.dev)
+        dM = _conv_desc(g, op0, self.nb, self.dt)
+        dM.cout = sum(s.cout for s in srcs)                      # FLOP accounting of the fused launch
+        with _timed("wgrad", dM, "1x1multi:" + "+".join(g.ops[i].name for mem in sources for i in mem)):
+            L.check(lib.din_conv1x1_wgrad_multi(len(sources), srcs, self.dt, self.nb * ts0.h * ts0.w, op0.src.c, ts0.c, op0.src.coff,
+                                                _ptr(self.bufs[op0.src.tid]), 2, _ptr(ws), wsb, self.st), "conv1x1_wgrad_multi")
+        for mem, _wj, dwj in outs:
+            r0 = 0
+            for i in mem:
+                c = g.ops[i].dst.c
+                self.report(i, dwj if len(mem) == 1 else dwj[r0:r0 + c])
+                r0 += c
+
+    # ---- data gradients of the 1x1 groups and of a parked 1x1
+    def visited(self, key: ViewKey) -> None:
+        """one more member of a 1x1 group has had its turn (with or without a gradient): the last one launches the group"""
+        self.remaining[key] -= 1
+        if self.remaining[key] == 0:
+            self.flush_group(key)
+
+    def flush_group(self, key: ViewKey) -> None:
+        items = self.pending[key]
+        if not items:
+            return
+        g = self.g
+        if key in self.plan.multi_w:
+            self.flush_wgrad_multi(key, items)
+        op0 = g.ops[items[0].oi]
+        ts0 = g.tensors[op0.src.tid]
+        gsrc, acc = self.grad_target(op0.src)
+        srcs = (L.ConvSrc * len(items))()
+        for j, it in enumerate(items):
+            srcs[j].dout, srcs[j].wpk_t = it.gout.data_ptr(), self.pcache.wpt[it.oi].data_ptr()
+            srcs[j].cout, srcs[j].ldo, srcs[j].cooff = g.ops[it.oi].dst.c, it.ld, it.coff
+        d0 = _conv_desc(g, op0, self.nb, self.dt)
+        d0.src_couts = tuple(g.ops[it.oi].dst.c for it in items)   # (measurement side: profiling.LaunchTimer names the instantiation from it)
+        d0.cout = sum(d0.src_couts)                                # FLOP accounting of the fused launch
+        with _timed("dgrad", d0, "+".join(g.ops[it.oi].name for it in items)):
+            L.check(self.lib.din_conv1x1_dgrad_multi(len(items), srcs, self.dt, self.nb, ts0.h, ts0.w, op0.src.c, ts0.c, op0.src.coff, _ptr(gsrc),
+                                                     self.mask_of(op0.src), ts0.c, op0.src.coff, self.dgrad_flags(op0.src, acc), self.st),
+                    "conv1x1_dgrad_multi")
+        self.pending[key] = []
+
+    def dgrad_parked(self, host_oi: int) -> None:
+        """the strided conv that was to carry a parked 1x1 dgrad received no gradient itself: the 1x1's dgrad runs alone"""
+        pk = self.parked.pop(host_oi)
+        opj = self.g.ops[pk.oi]
+        dj = _conv_desc(self.g, opj, self.nb, self.dt)
+        dj.ldo, dj.cooff = pk.ld, pk.coff
+        self.dgrad(pk.oi, dj, pk.gout)
+
+    def dgrad(self, oi: int, d: L.ConvDesc, gout: torch.Tensor) -> None:
+        """one conv's data gradient into its source view; a strided conv carries the 1x1 parked with it in the same launches"""
+        op = self.g.ops[oi]
+        ts = self.g.tensors[op.src.tid]
+        gsrc, acc = self.grad_target(op.src)
+        wpt = self.pcache.wpt[oi]
+        flags = self.dgrad_flags(op.src, acc)
+        ws, wsb = workspace(self.lib.din_conv_workspace_bytes(C.byref(d), 1), self.dev)
+        pk = self.parked.pop(oi, None)
+        if pk is not None:
+            xs = L.ConvSrc()
+            xs.dout, xs.wpk_t = pk.gout.data_ptr(), self.pcache.wpt[pk.oi].data_ptr()
+            xs.cout, xs.ldo, xs.cooff = self.g.ops[pk.oi].dst.c, pk.ld, pk.coff
+            with _timed("dgrad", d, op.name + "+" + self.g.ops[pk.oi].name):
+                L.check(self.lib.din_conv_dgrad_x(C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc), self.mask_of(op.src), ts.c, op.src.coff, flags,
+                                                  C.byref(xs), _ptr(ws), wsb, self.st), "conv_dgrad_x " + op.name)
+        else:
+            with _timed("dgrad", d, op.name):
+                L.check(self.lib.din_conv_dgrad(C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc), self.mask_of(op.src), ts.c, op.src.coff, flags,
+                                                _ptr(ws), wsb, self.st), "conv_dgrad " + op.name)
+
+    # ---- the steps of the loop, one op at a time
+    def skip(self, oi: int) -> None:
+        """nothing flows back through op oi: it still counts as a visited group member, and what was parked with it runs alone"""
+        key = self.plan.member_of.get(oi)
+        if key is not None:
+            self.visited(key)
+        if oi in self.parked:
+            self.dgrad_parked(oi)
+
+    def conv_step(self, oi: int, gout: torch.Tensor) -> _ConvStep:
+        g, op = self.g, self.g.ops[oi]
+        image = op.src.tid == g.input_tid
+        d = _conv_desc(g, op, self.nb, self.dt, g.cin_image if image else op.src.c)
+        if image and self.plan.u8:
+            d.in_u8, d.ldi, d.cioff = 1, 8, 0
+        return _ConvStep(d, gout, g.tensors[op.dst.tid].c, op.dst.coff)
+
+    def bn_train_backward(self, oi: int, c: _ConvStep) -> None:
+        """batch-statistics BatchNorm backward: gz (masked by the ReLU that follows) -> dy at the raw conv output, dgamma, dbeta"""
+        g, lib, op, nb, dev, st = self.g, self.lib, self.g.ops[oi], self.nb, self.dev, self.st
+        po, cout = self.plan.offsets[oi], op.dst.c
+        _, raw, bmean, rstd = self.aux[oi]
+        td = g.tensors[op.dst.tid]
+        rows = nb * td.h * td.w
+        sums = torch.empty(lib.din_bn_workspace(rows, cout) // 8, dtype=torch.float64, device=dev)
+        L.check(lib.din_bn_bwd_stats(_ptr(c.gout), c.ld, c.coff, _ptr(raw), cout, 0, self.sdt, rows, cout, _ptr(bmean), _ptr(rstd),
+                                     _ptr(sums), st), "bn_bwd_stats")
+        dy = torch.empty((nb, td.h, td.w, cout), dtype=self.tdt, device=dev)
+        dgb = torch.empty(2 * cout, dtype=torch.float32, device=dev)
+        L.check(lib.din_bn_bwd_apply(_ptr(c.gout), c.ld, c.coff, _ptr(raw), cout, 0, self.sdt, rows, cout, _ptr(self.params[po + 1]), _ptr(bmean),
+                                     _ptr(rstd), _ptr(sums), _ptr(dy), cout, 0, _ptr(dgb), _ptr(dgb[cout:]), st), "bn_bwd_apply")
+        self.grads[po + 1], self.grads[po + 2] = dgb[:cout], dgb[cout:]
+        c.gout, c.ld, c.coff = dy, cout, 0
+        c.d.ldo, c.d.cooff = cout, 0                               # the gradient operand of wgrad / dgrad is the contiguous dy
+        if op.pooled is not None:
+            c.d, pd = _pooled_descs(g, op, nb, self.dt)
+            gtmp = torch.empty((nb, pd.h, pd.w, pd.c), dtype=self.tdt, device=dev)
+            pd.ldo, pd.cooff = cout, 0                             # the pooled-side gradient is the contiguous dy
+            L.check(lib.din_avgpool_bwd(C.byref(pd), _ptr(c.gout), _ptr(gtmp), None, 0, st), "avgpool_bwd(raw)")
+            c.gout = gtmp
+
+    def pooled_epilogue(self, oi: int, c: _ConvStep) -> None:
+        """y = relu(avgpool(conv1x1(x)) + shift): shift gradient = column sums of gout, conv-output gradient = avgpool^T(gout)"""
+        g, lib, op = self.g, self.lib, self.g.ops[oi]
+        c.d, pd = _pooled_descs(g, op, self.nb, self.dt)
+        td = g.tensors[op.dst.tid]
+        if op.bn or op.bias:
+            if op.bn:                                   # straight into this layer's slice of the flat accumulator
+                o0, o1 = self.bn_range(oi)
+                c.dshift_pre = self.bn_dshift[o0:o1]
+            else:
+                c.dshift_pre = torch.empty(op.dst.c, dtype=torch.float32, device=self.dev)
+            L.check(lib.din_colsum(_ptr(c.gout), self.sdt, self.nb * td.h * td.w, op.dst.c, td.c, op.dst.coff, _ptr(c.dshift_pre), self.st), "colsum")
+        gtmp = torch.empty((self.nb, pd.h, pd.w, pd.c), dtype=self.tdt, device=self.dev)
+        L.check(lib.din_avgpool_bwd(C.byref(pd), _ptr(c.gout), _ptr(gtmp), None, 0, self.st), "avgpool_bwd(epilogue)")
+        c.gout, c.ld, c.coff = gtmp, pd.c, 0
+
+    def weight_gradient(self, oi: int, c: _ConvStep) -> None:
+        """op oi's weight gradient (+ bias / BatchNorm parameter gradients): deferred to its 1x1 group's launch, produced by a sibling's
+        launch, one launch for the siblings that share a tensor, or its own -- queued, at once, or on the side stream"""
+        g, plan, lib, op, params = self.g, self.plan, self.lib, self.g.ops[oi], self.params
+        if plan.member_of.get(oi) in plan.multi_w and op.src.tid != g.input_tid:
+            return                                                # produced when its 1x1 group is flushed (flush_wgrad_multi)
+        if oi in self.wgrad_done:
+            return                                                # produced by the launch of a sibling (below)
+        po = plan.offsets[oi]
+        w, scale, x, d = params[po], self.aux[oi][0], self.bufs[op.src.tid], c.d
+        if oi in plan.siblings:
+            # the members of a forward group that share the second tensor: their output gradients are adjacent channel views of ONE
+            # buffer, their BatchNorm slots adjacent -> one wgrad over the concatenated filter rows; dW lands in one buffer whose
+            # row ranges are the members' gradients
+            mem = plan.siblings[oi]
+            mops = [g.ops[i] for i in mem]
+            dF = _conv_desc(g, mops[0], self.nb, self.dt, d.cin)
+            dF.cout = sum(o.dst.c for o in mops)
+            o0, o1 = self.bn_range(mem[0], mem[-1])
+            assert o1 - o0 == dF.cout
+            wcat = torch.cat([params[plan.offsets[i]] for i in mem])
+            dwf = torch.empty_like(wcat)
+            self.bn_touched = True
+            outs, r0 = [], 0
+            for i, o in zip(mem, mops):
+                outs.append((i, dwf[r0:r0 + o.dst.c]))
+                r0 += o.dst.c
+            self.wgrad_done.update(mem)
+            self.wgrad_launch(_Wgrad(dF, x, c.gout, dwf, self.bn_dshift[o0:o1], self.pcache.bn_scale[o0:o1], wcat, self.bn_wdot[o0:o1], 2,
+                                     "+".join(o.name for o in mops), tuple(outs)))
+        elif op.bn and plan.bn_train:
+            dw = _dw_buffer(w)
+            self.wgrad_now(_Wgrad(d, x, c.gout, dw, None, None, None, None, 0, op.name, ((oi, dw),)))
+        elif op.bn:
+            dw = _dw_buffer(w)
+            o0, o1 = self.bn_range(oi)
+            dshift = None if c.dshift_pre is not None else self.bn_dshift[o0:o1]     # views of the pre-zeroed flat accumulators
+            it = _Wgrad(d, x, c.gout, dw, dshift, scale, w, self.bn_wdot[o0:o1], 2, op.name, ((oi, dw),))
+            self.bn_touched = True
+            if self.side is not None:
+                self.wgrad_now(it, [x, c.gout, dw, self.bn_acc, scale])
+            else:
+                self.wgrad_launch(it)
+        else:
+            dw = _dw_buffer(w)
+            db = (c.dshift_pre if c.dshift_pre is not None else torch.empty_like(params[po + 1])) if op.bias else None
+            it = _Wgrad(d, x, c.gout, dw, None if c.dshift_pre is not None else db, None, None, None, 0, op.name, ((oi, dw),))
+            self.wgrad_now(it, [x, c.gout, dw, db] if self.side is not None else None)
+            if op.bias:
+                self.grads[po + 1] = db
+
+    def data_gradient(self, oi: int, c: _ConvStep) -> None:
+        """op oi's data gradient: with its 1x1 group, parked for the strided sibling that will carry it, or its own launch"""
+        plan, op = self.plan, self.g.ops[oi]
+        key = plan.member_of.get(oi)
+        if key is not None:
+            self.pending[key].append(_Pending(oi, c.gout, self.params[plan.offsets[oi]], self.aux[oi][0], c.ld, c.coff, c.dshift_pre is not None))
+            self.visited(key)
+        elif oi in plan.x_host and c.dshift_pre is None:
+            self.parked[plan.x_host[oi]] = _Parked(oi, c.gout, c.ld, c.coff)      # carried by the strided sibling's dgrad, when the pass reaches it
+        else:
+            self.dgrad(oi, c.d, c.gout)
+
+    def pool_backward(self, oi: int, gout: torch.Tensor) -> None:
+        op, lib = self.g.ops[oi], self.lib
+        relu_masked = self.g.tensors[op.src.tid].relu_masked
+        d = _pool_desc(self.g, op, self.nb, self.dt)
+        gsrc, acc = self.grad_target(op.src)
+        if op.kind == "maxpool":
+            (amax,) = self.aux[oi]
+            L.check(lib.din_maxpool_bwd(C.byref(d), _ptr(self.bufs[op.src.tid]), _ptr(amax), _ptr(gout), _ptr(gsrc), int(relu_masked), int(acc),
+                                        self.st), "maxpool_bwd")
+        elif op.kind == "avgpool":
+            L.check(lib.din_avgpool_bwd(C.byref(d), _ptr(gout), _ptr(gsrc), self.mask_of(op.src), int(acc), self.st), "avgpool_bwd")
+        else:
+            L.check(lib.din_bilinear_bwd(C.byref(d), _ptr(gout), _ptr(gsrc), self.mask_of(op.src), int(acc), self.st), "bilinear_bwd")
+
+    def finish(self) -> List[Optional[torch.Tensor]]:
+        """the final flushes and the BatchNorm parameter gradients; returns the parameter gradients"""
+        for key in list(self.wq):
+            self.flush_wq(key)                         # weight gradients still queued for a grouped launch
+        # (ADVICE r4) a 1x1's parked data gradient is only consumed when its strided host op has its turn: a graph whose host takes
+        # another path must not drop it silently
+        if self.parked:
+            raise L.DinError(f"graph_backward: parked 1x1 data gradients were never carried by their strided sibling (ops {sorted(self.parked)}): "
+                             "the fused strided + 1x1 dgrad (din_conv_dgrad_x) does not serve this graph shape")
+        if self.side is not None:
+            self.main.wait_stream(self.side)           # parameter gradients are complete for whoever runs next on the main stream
+        bn, grads, offsets = self.bn, self.grads, self.plan.offsets
+        if bn is not None and self.bn_touched and not self.plan.bn_train:
+            # BatchNorm parameter gradients of every layer in one launch: dgamma = (wdot - dshift * mean) * rstd, dbeta = dshift
+            bn_out = torch.empty(2 * bn.total, dtype=torch.float32, device=self.dev)
+            L.check(self.lib.din_bn_fold_bwd_multi(_ptr(bn.ptrs), _ptr(bn.offs), bn.n, bn.total, BN_EPS, _ptr(self.bn_wdot), _ptr(self.bn_dshift),
+                                                   _ptr(bn_out), _ptr(bn_out[bn.total:]), self.st), "bn_fold_bwd_multi")
+            for oi, k in self.plan.bn_index.items():
+                if grads[offsets[oi]] is not None:     # the layer took part in this backward
+                    o0, o1 = bn.off_list[k], bn.off_list[k + 1]
+                    grads[offsets[oi] + 1], grads[offsets[oi] + 2] = bn_out[o0:o1], bn_out[bn.total + o0:bn.total + o1]
+        return grads
+
+
+def graph_backward(g: Graph, bufs, aux, params: Sequence[torch.Tensor], dt: int,
+                   out_grads: Dict[int, torch.Tensor], need_param_grad: Sequence[bool], bn_train: bool = False):
+    """Reverse pass.  out_grads: tid -> gradient buffer (same geometry/dtype as the tensor, already ReLU-masked where
+    the tensor is relu_masked).  Returns the list of parameter gradients aligned with `params` (None for buffers).
+    need_param_grad is not read (every weight gradient is computed; NHWCGraphFunction.backward drops the unwanted ones)."""
+    image = bufs[g.input_tid]
+    plan = plan_backward(g, image.shape[0], dt, bn_train, not TIMING_ACTIVE(), image.dtype == torch.uint8)
+    bp = _BackwardPass(g, plan, bufs, aux, params, dt, out_grads)
     for oi in range(len(g.ops) - 1, -1, -1):
         op = g.ops[oi]
-        if op.dst.tid not in gbufs:
-            if oi in member_of:                       # a group member without gradient still counts as visited
-                remaining[member_of[oi]] -= 1
-                if remaining[member_of[oi]] == 0:
-                    flush_group(member_of[oi])
-            if oi in x_parked:
-                dgrad_parked(oi)
-            continue                                  # nothing flows back through this op
-        gout = gbufs[op.dst.tid]
+        if op.dst.tid not in bp.gbufs:
+            bp.skip(oi)                                # nothing flows back through this op
+            continue
+        gout = bp.gbufs[op.dst.tid]
         if GRAD_TAP is not None:
             GRAD_TAP(op.dst.tid, op.name, gout)
-        src_needs_grad = op.src.tid != g.input_tid
-        ts = g.tensors[op.src.tid]
         if op.kind == "conv":
-            cin = g.cin_image if op.src.tid == g.input_tid else op.src.c
-            d = _conv_desc(g, op, nb, dt, cin)
-            if op.src.tid == g.input_tid and bufs[g.input_tid].dtype == torch.uint8:
-                d.in_u8, d.ldi, d.cioff = 1, 8, 0
-            po = offsets[oi]
-            w = params[po]
-            scale = aux[oi][0]
-            g_ld, g_coff = g.tensors[op.dst.tid].c, op.dst.coff        # where the gradient at the conv output lives
-            dshift_pre = None
-            bn_live = op.bn and bn_train
-            if bn_live:
-                # batch-statistics BatchNorm backward: gz (masked by the ReLU that follows) -> dy at the raw conv output, dgamma, dbeta
-                _, raw, bmean, rstd = aux[oi]
-                td_ = g.tensors[op.dst.tid]
-                rows = nb * td_.h * td_.w
-                sums = torch.empty(lib.din_bn_workspace(rows, op.dst.c) // 8, dtype=torch.float64, device=dev)
-                L.check(lib.din_bn_bwd_stats(_ptr(gout), g_ld, g_coff, _ptr(raw), op.dst.c, 0, sdt, rows, op.dst.c, _ptr(bmean), _ptr(rstd),
-                                             _ptr(sums), st), "bn_bwd_stats")
-                dy = torch.empty((nb, td_.h, td_.w, op.dst.c), dtype=tdt, device=dev)
-                dgb = torch.empty(2 * op.dst.c, dtype=torch.float32, device=dev)
-                L.check(lib.din_bn_bwd_apply(_ptr(gout), g_ld, g_coff, _ptr(raw), op.dst.c, 0, sdt, rows, op.dst.c, _ptr(params[po + 1]), _ptr(bmean),
-                                             _ptr(rstd), _ptr(sums), _ptr(dy), op.dst.c, 0, _ptr(dgb), _ptr(dgb[op.dst.c:]), st), "bn_bwd_apply")
-                grads[po + 1], grads[po + 2] = dgb[:op.dst.c], dgb[op.dst.c:]
-                gout, g_ld, g_coff = dy, op.dst.c, 0
-                d.ldo, d.cooff = op.dst.c, 0                           # the gradient operand of wgrad / dgrad is the contiguous dy
-                if op.pooled is not None:
-                    d, pd = _pooled_descs(g, op, nb, dt)
-                    gtmp = torch.empty((nb, pd.h, pd.w, pd.c), dtype=tdt, device=dev)
-                    pd.ldo, pd.cooff = op.dst.c, 0                     # the pooled-side gradient is the contiguous dy
-                    L.check(lib.din_avgpool_bwd(C.byref(pd), _ptr(gout), _ptr(gtmp), None, 0, st), "avgpool_bwd(raw)")
-                    gout = gtmp
+            c = bp.conv_step(oi, gout)
+            if op.bn and plan.bn_train:
+                bp.bn_train_backward(oi, c)
             elif op.pooled is not None:
-                # y = relu(avgpool(conv1x1(x)) + shift): shift gradient = column sums of gout, conv-output gradient = avgpool^T(gout)
-                d, pd = _pooled_descs(g, op, nb, dt)
-                td_ = g.tensors[op.dst.tid]
-                if op.bn or op.bias:
-                    if op.bn:                                   # straight into this layer's slice of the flat accumulator
-                        dshift_pre = bn_dshift[bn.off_list[bn_index[oi]]:bn.off_list[bn_index[oi] + 1]]
-                    else:
-                        dshift_pre = torch.empty(op.dst.c, dtype=torch.float32, device=dev)
-                    L.check(lib.din_colsum(_ptr(gout), sdt, nb * td_.h * td_.w, op.dst.c, td_.c, op.dst.coff, _ptr(dshift_pre), st), "colsum")
-                gtmp = torch.empty((nb, pd.h, pd.w, pd.c), dtype=tdt, device=dev)
-                L.check(lib.din_avgpool_bwd(C.byref(pd), _ptr(gout), _ptr(gtmp), None, 0, st), "avgpool_bwd(epilogue)")
-                gout, g_ld, g_coff = gtmp, pd.c, 0
-            # ---- wgrad (+ bias / BN parameter gradients): on the side stream when enabled
-            defer_w = oi in member_of and member_of[oi] in multi_w and src_needs_grad      # produced when its 1x1 group is flushed (flush_wgrad_multi)
-            hooked = False
-            if defer_w or oi in wgrad_done:
-                pass                                              # produced by the group launch of a sibling (below)
-            elif oi in wgrad_group and op.bn and side is None:
-                # the members of a forward group that share the second tensor: their output gradients are adjacent channel views of ONE
-                # buffer, their BatchNorm slots adjacent -> one wgrad over the concatenated filter rows; dW lands in one buffer whose
-                # row ranges are the members' gradients
-                mem = wgrad_group[oi]
-                mops = [g.ops[i] for i in mem]
-                ctot = sum(o.dst.c for o in mops)
-                dF = _conv_desc(g, mops[0], nb, dt, cin)
-                dF.cout = ctot
-                o0, o1 = bn.off_list[bn_index[mem[0]]], bn.off_list[bn_index[mem[-1]] + 1]
-                assert o1 - o0 == ctot
-                wcat = torch.cat([params[offsets[i]] for i in mem])
-                dwf = torch.empty_like(wcat)
-                bn_touched = True
-                r0 = 0
-                for i, o in zip(mem, mops):
-                    grads[offsets[i]] = dwf[r0:r0 + o.dst.c]
-                    r0 += o.dst.c
-
-                def _hooks(mem=mem):
-                    if GRAD_HOOK is not None:
-                        for i in mem:
-                            GRAD_HOOK(params[offsets[i]], grads[offsets[i]])
-                wgrad_launch(dF, bufs[op.src.tid], gout, dwf, bn_dshift[o0:o1], pcache.bn_scale[o0:o1], wcat, bn_wdot[o0:o1], 2,
-                             "+".join(o.name for o in mops), _hooks)
-                wgrad_done.update(mem)
-            if defer_w:
-                dw = None
-            elif oi in wgrad_done:
-                dw = grads[po]
-            elif bn_live:
-                dw = _dw_buffer(w)
-                ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(d), 2), dev, wtag)
-                with _timed("wgrad", d, op.name):
-                    L.check(lib.din_conv_wgrad(C.byref(d), _ptr(bufs[op.src.tid]), _ptr(gout), _ptr(dw), None, None, None, None, 0,
-                                               _ptr(ws), wsb, st), "conv_wgrad " + op.name)
-                grads[po] = dw
-            elif op.bn:
-                dw = _dw_buffer(w)
-                wsbytes = lib.din_conv_workspace_bytes(C.byref(d), 2)
-                o0, o1 = bn.off_list[bn_index[oi]], bn.off_list[bn_index[oi] + 1]
-                dshift, wdot = bn_dshift[o0:o1], bn_wdot[o0:o1]          # views of the pre-zeroed flat accumulators
-                bn_touched = True
-                if side is not None:
-                    stw = on_side([bufs[op.src.tid], gout, dw, bn_acc, scale])
-                    with torch.cuda.stream(side):
-                        ws, wsb = workspace(wsbytes, dev, "side")
-                    with _timed("wgrad", d, op.name):
-                        L.check(lib.din_conv_wgrad(C.byref(d), _ptr(bufs[op.src.tid]), _ptr(gout), _ptr(dw),
-                                                   None if dshift_pre is not None else _ptr(dshift), _ptr(scale),
-                                                   _ptr(w), _ptr(wdot), 2, _ptr(ws), wsb, stw), "conv_wgrad " + op.name)
-                else:
-                    hooked = True                                  # (the hook fires when the launch that produces dw has been enqueued)
-                    wgrad_launch(d, bufs[op.src.tid], gout, dw, None if dshift_pre is not None else dshift, scale, w, wdot, 2, op.name,
-                                 (lambda w=w, dw=dw: GRAD_HOOK(w, dw)) if GRAD_HOOK is not None else None)
-                grads[po] = dw
-            else:
-                dw = _dw_buffer(w)
-                wsbytes = lib.din_conv_workspace_bytes(C.byref(d), 2)
-                db = (dshift_pre if dshift_pre is not None else torch.empty_like(params[po + 1])) if op.bias else None
-                if side is not None:
-                    stw = on_side([bufs[op.src.tid], gout, dw, db])
-                    with torch.cuda.stream(side):
-                        ws, wsb = workspace(wsbytes, dev, "side")
-                else:
-                    stw = st
-                    ws, wsb = workspace(wsbytes, dev, wtag)
-                with _timed("wgrad", d, op.name):
-                    L.check(lib.din_conv_wgrad(C.byref(d), _ptr(bufs[op.src.tid]), _ptr(gout), _ptr(dw),
-                                               None if dshift_pre is not None else _ptr(db), None, None, None, 0,
-                                               _ptr(ws), wsb, stw), "conv_wgrad " + op.name)
-                grads[po] = dw
-                if op.bias:
-                    grads[po + 1] = db
-            if GRAD_HOOK is not None and side is None and oi not in wgrad_done and not defer_w and not hooked:
-                GRAD_HOOK(w, dw)
-            # ---- dgrad
-            if src_needs_grad and oi in member_of:
-                key = member_of[oi]
-                pending[key].append((oi, gout, w, scale, g_ld, g_coff, dshift_pre is not None))
-                remaining[key] -= 1
-                if remaining[key] == 0:
-                    flush_group(key)
-            elif src_needs_grad and oi in x_host and dshift_pre is None:
-                x_parked[x_host[oi]] = (oi, gout, g_ld, g_coff)        # carried by the strided sibling's dgrad (below, when the pass reaches it)
-            elif src_needs_grad:
-                gsrc, acc = grad_target(op.src)
-                wpt = pcache.wpt[oi]
-                flags = (L.CONV_ACCUM if acc else 0) | (L.CONV_MASK if ts.relu_masked else 0)
-                ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(d), 1), dev)
-                if oi in x_parked:
-                    xi, xg, xld, xcoff = x_parked.pop(oi)
-                    xs = L.ConvSrc()
-                    xs.dout, xs.wpk_t = xg.data_ptr(), pcache.wpt[xi].data_ptr()
-                    xs.cout, xs.ldo, xs.cooff = g.ops[xi].dst.c, xld, xcoff
-                    with _timed("dgrad", d, op.name + "+" + g.ops[xi].name):
-                        L.check(lib.din_conv_dgrad_x(C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc),
-                                                     _ptr(bufs[op.src.tid]) if ts.relu_masked else None, ts.c, op.src.coff, flags,
-                                                     C.byref(xs), _ptr(ws), wsb, st), "conv_dgrad_x " + op.name)
-                else:
-                    with _timed("dgrad", d, op.name):
-                        L.check(lib.din_conv_dgrad(C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc),
-                                                   _ptr(bufs[op.src.tid]) if ts.relu_masked else None, ts.c, op.src.coff, flags,
-                                                   _ptr(ws), wsb, st), "conv_dgrad " + op.name)
-        elif src_needs_grad:
-            d = _pool_desc(g, op, nb, dt)
-            gsrc, acc = grad_target(op.src)
-            mask = _ptr(bufs[op.src.tid]) if ts.relu_masked else None
-            if op.kind == "maxpool":
-                (amax,) = aux[oi]
-                L.check(lib.din_maxpool_bwd(C.byref(d), _ptr(bufs[op.src.tid]), _ptr(amax), _ptr(gout), _ptr(gsrc),
-                                            int(ts.relu_masked), int(acc), st), "maxpool_bwd")
-            elif op.kind == "avgpool":
-                L.check(lib.din_avgpool_bwd(C.byref(d), _ptr(gout), _ptr(gsrc), mask, int(acc), st), "avgpool_bwd")
-            else:
-                L.check(lib.din_bilinear_bwd(C.byref(d), _ptr(gout), _ptr(gsrc), mask, int(acc), st), "bilinear_bwd")
-        # the gradient of dst is dead once all its producers ran; producers of one tensor are contiguous in program
-        # order for our graphs only per view, so free conservatively when no earlier op writes this tensor
-        if not any(o.dst.tid == op.dst.tid for o in g.ops[:oi]):
-            gbufs.pop(op.dst.tid, None)
-    # (ADVICE r4) a 1x1's parked data gradient is only consumed when its strided host op reaches its own dgrad branch: a graph whose host
-    # takes another path must not drop it silently
-    for key in list(wq):
-        flush_wq(key)                                  # weight gradients still queued for a grouped launch
-    if x_parked:
-        raise L.DinError(f"graph_backward: parked 1x1 data gradients were never carried by their strided sibling (ops {sorted(x_parked)}): "
-                         "the fused strided + 1x1 dgrad (din_conv_dgrad_x) does not serve this graph shape")
-    if side is not None:
-        main.wait_stream(side)                        # parameter gradients are complete for whoever runs next on the main stream
-    if bn is not None and bn_touched and not bn_train:
-        # BatchNorm parameter gradients of every layer in one launch: dgamma = (wdot - dshift * mean) * rstd, dbeta = dshift
-        bn_out = torch.empty(2 * bn.total, dtype=torch.float32, device=dev)
-        L.check(lib.din_bn_fold_bwd_multi(_ptr(bn.ptrs), _ptr(bn.offs), bn.n, bn.total, BN_EPS, _ptr(bn_wdot), _ptr(bn_dshift),
-                                          _ptr(bn_out), _ptr(bn_out[bn.total:]), st), "bn_fold_bwd_multi")
-        for oi_, k_ in bn_index.items():
-            if grads[offsets[oi_]] is not None:       # the layer took part in this backward
-                o0, o1 = bn.off_list[k_], bn.off_list[k_ + 1]
-                grads[offsets[oi_] + 1], grads[offsets[oi_] + 2] = bn_out[o0:o1], bn_out[bn.total + o0:bn.total + o1]
-    return grads
+                bp.pooled_epilogue(oi, c)
+            bp.weight_gradient(oi, c)
+            if op.src.tid != g.input_tid:
+                bp.data_gradient(oi, c)
+        elif op.src.tid != g.input_tid:
+            bp.pool_backward(oi, gout)
+        if plan.first_writer[op.dst.tid] == oi:        # the gradient of dst is dead once all its producers ran
+            bp.gbufs.pop(op.dst.tid, None)
+    return bp.finish()
 
 
 def _accepts_u8_frames(g: Graph, nb: int, dt: int) -> bool:

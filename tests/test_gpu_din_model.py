@@ -1371,6 +1371,43 @@ def test_partial_1x1_group_degrades_to_per_layer_wgrad(gpu, monkeypatch):
             assert g2 is not None and g0 is not None and rel(g2, g0) <= 1e-4, n
 
 
+def test_side_stream_wgrad_matches_main_stream(gpu, monkeypatch):
+    """bf16 backbone backward with every weight gradient on the second stream (nhwc.WGRAD_SIDE_STREAM: events order it behind the main
+    stream's data gradients, the main stream waits for it at the end) against the same weights with everything on the main stream and the
+    three weight-gradient fusions the side stream switches off by itself (grouped, 1x1 multi, siblings) off as well: the same kernels
+    either way, whose epilogues add fp32 partial sums with atomics -> every parameter gradient to 1e-4 (the bar of
+    test_partial_1x1_group_degrades_to_per_layer_wgrad), not bitwise."""
+    from din_amd import nhwc
+    from din_amd.backbone.backbone import MyInception_v3
+    g = torch.Generator().manual_seed(53)
+    images = torch.randint(0, 256, (2, 3, 139, 203), generator=g, dtype=torch.uint8)
+    sd = {}
+    for k, v in MyInception_v3(compute_dtype="bf16").state_dict().items():
+        if not v.dtype.is_floating_point:
+            sd[k] = v
+        elif k.endswith("running_var"):
+            sd[k] = torch.rand(v.shape, generator=g) + 0.5
+        elif k.endswith("conv.weight"):
+            sd[k] = torch.randn(v.shape, generator=g) * (2.0 / (v.shape[1] * v.shape[2] * v.shape[3])) ** 0.5
+        else:
+            sd[k] = torch.randn(v.shape, generator=g) * 0.1 + (1.0 if k.endswith("bn.weight") else 0.0)
+    outs = []
+    for side in (True, False):
+        monkeypatch.setattr(nhwc, "WGRAD_SIDE_STREAM", side)
+        for fusion in ("GROUP_WGRAD", "FUSE_WGRAD_1X1", "FUSE_WGRAD_SIBLINGS"):
+            monkeypatch.setattr(nhwc, fusion, None if side else False)
+        m = MyInception_v3(compute_dtype="bf16")
+        m.load_state_dict(sd)
+        m = m.to(gpu).eval()
+        feats = m(images.to(gpu))
+        sum((f.float() ** 2).mean() for f in feats).backward()
+        torch.cuda.synchronize()
+        outs.append({k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None})
+    assert outs[0].keys() == outs[1].keys() and len(outs[0]) == 3 * 70        # conv weight, gamma, beta of every BasicConv2d
+    for k, gb_ in outs[1].items():
+        assert rel(outs[0][k], gb_) <= 1e-4, (k, rel(outs[0][k], gb_))
+
+
 def test_dataset_loader_feeds_model_through_device_feed(gpu, golden_dir):
     """SURVEY 8(f)-1 end to end: annotation tree + JPEG frames -> din_amd.volleyball / collective datasets (uint8 clips, feature-px boxes,
     padded tracks / zero boxes + bboxes_num) -> DataLoader -> input_feed.DeviceFeed (copy stream, double buffer) -> Dynamic_volleyball /
