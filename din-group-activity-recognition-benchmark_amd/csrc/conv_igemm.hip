@@ -2133,6 +2133,171 @@ static void append_kernel_names(const ConvK& k, const GatherChoice& c, int dtype
     if (c.g.splitk > 1) { out += "conv_splitk_finish_kernel<"; out += dtype == DIN_F32 ? "float" : "bf16"; out += ">\n"; }     // (f32x3 reuses <float>)
 }
 
+// one launch as append_kernel_names spells it: choose, set the plan fields, append
+static void append_launch_names(ConvK& k, const GatherPlan& g, int dtype, std::string& out) {
+    const GatherChoice c = choose_gather(k, g, dtype);
+    set_plan_fields(k, c);
+    append_kernel_names(k, c, dtype, out);
+}
+
+// the answer of a *_kernel_names entry point: at most buf_bytes bytes (NUL-terminated) written, the bytes the whole answer needs returned
+static int copy_names(const std::string& names, char* buf, int buf_bytes) {
+    if (buf_bytes > 0) {
+        const size_t n = names.size() < (size_t)buf_bytes - 1 ? names.size() : (size_t)buf_bytes - 1;
+        memcpy(buf, names.data(), n);
+        buf[n] = 0;
+    }
+    return (int)names.size() + 1;
+}
+
+// The launch din_conv_fwd2 makes for a checked descriptor (dtype normalised, split: it was DIN_F32_BF16X3): every argument check that reads
+// no pointer, then f(argument block without pointers, plan).  din_conv_fwd2 binds its pointers and launches from here;
+// din_conv_fwd2_kernel_names names the kernel from here.
+template <typename F>
+static int for_fwd2_launch(const din_conv_desc* d, bool split, int ldo2, int cooff2, int csplit, int craw, int flags, F f) {
+    DIN_REQUIRE(!d->in_u8, "conv_fwd2: in_u8 is a din_conv_fwd / din_conv_wgrad option");
+    DIN_REQUIRE(!(flags & (DIN_CONV_ACCUM | DIN_CONV_MASK)), "conv_fwd2: ACCUM/MASK are dgrad-only flags");
+    const int epc = epc_of(d->dtype);
+    DIN_REQUIRE(d->kh * d->kw <= 32 && d->dh == 1 && d->dw == 1, "conv_fwd2: needs the buffer-addressed gather kernel (<= 32 taps)");
+    DIN_REQUIRE(csplit > 0 && csplit < d->cout && csplit % epc == 0 && d->cout % epc == 0 && d->ldo % epc == 0 && d->cooff % epc == 0 &&
+                ldo2 % epc == 0 && cooff2 % epc == 0 && ldo2 >= cooff2 + (d->cout - csplit) && d->ldo >= d->cooff + csplit,
+                "conv_fwd2: split / strides / offsets must be multiples of %d and the destinations must hold their channel ranges", epc);
+    DIN_REQUIRE(craw == 0 || (craw >= csplit && craw < d->cout && craw % epc == 0), "conv_fwd2: craw must be 0 or a multiple of %d in [csplit, cout)", epc);
+    ConvK k = conv_k_of(d, 0);
+    k.flags = flags; k.mma = split;
+    k.ldo2 = ldo2; k.cooff2 = cooff2; k.csplit = csplit; k.craw = craw;
+    const GatherPlan g = plan_launch(d, 0);
+    if (g.splitk > 1) DIN_FAIL(DIN_E_ARG, "conv_fwd2: this shape runs split-K (%d pixels): launch the sibling convs separately", k.M);
+    return f(k, g);
+}
+
+// The launch din_conv1x1_dgrad_multi makes: every argument check that reads no pointer (of a source: cout, ldo, cooff), the argument block
+// without pointers, its plan and choice, then f(argument block with its plan fields set, choice, storage dtype).  din_conv1x1_dgrad_multi
+// binds its pointers and launches from here; din_conv1x1_dgrad_multi_kernel_names names the kernel from here.
+template <typename F>
+static int for_multi_launch(int nsrc, const din_conv_src* srcs, int dtype, int nb, int h, int w, int cin, int ldi, int cioff, int ldm, int moff,
+                            int flags, F f) {
+    DIN_REQUIRE(nsrc >= 1 && nsrc <= 4 && srcs, "conv1x1_dgrad_multi: 1..4 sources");
+    const bool split = dtype == DIN_F32_BF16X3;
+    dtype = storage_dtype(dtype);
+    DIN_REQUIRE(dtype == DIN_F32 || dtype == DIN_BF16, "conv1x1_dgrad_multi: bad dtype");
+    DIN_REQUIRE(!(flags & (DIN_CONV_BIAS | DIN_CONV_RELU)), "conv1x1_dgrad_multi: BIAS/RELU are fwd-only flags");
+    const int epc = epc_of(dtype), esz = dtype == DIN_F32 ? 4 : 2;
+    DIN_REQUIRE(nb > 0 && h > 0 && w > 0 && cin > 0 && ldi % 4 == 0 && cioff % 4 == 0 && ldi >= cioff + cin, "conv1x1_dgrad_multi: bad output geometry");
+    DIN_REQUIRE((int64_t)nb * h * w < (1ll << 31), "conv1x1_dgrad_multi: too many pixels");
+    ConvK k{};
+    k.NB = nb; k.H = h; k.W = w; k.OH = h; k.OW = w; k.Cout = cin; k.ldo = ldi; k.cooff = cioff;
+    k.kh = k.kw = 1; k.ay = k.ax = 1; k.by = k.bx = 0; k.cy = k.cx = 1; k.divy = k.divx = 1;
+    k.M = nb * h * w; k.flags = flags; k.ldm = ldm; k.moff = moff; k.mma = split;
+    int steps = 0;
+    for (int b = 0; b < nsrc; ++b) {
+        const din_conv_src& sc = srcs[b];
+        DIN_REQUIRE(sc.cout > 0, "conv1x1_dgrad_multi: null source %d", b);
+        DIN_REQUIRE(sc.ldo % epc == 0 && sc.cooff % epc == 0 && sc.ldo >= sc.cooff + pad_to(sc.cout, epc),
+                    "conv1x1_dgrad_multi: source %d stride/offset must be multiples of %d and cover cout (+zero pad)", b, epc);
+        ConvK::Src& o = k.src[b];
+        o.ld = sc.ldo; o.coff = sc.cooff;
+        o.cpt = pad_to(sc.cout, epc) / epc;
+        o.wld = (o.cpt + KC - 1) / KC * KC;
+        o.in_bytes = (long long)nb * h * w * sc.ldo * esz;
+        o.w_bytes = (long long)pad_to(cin, 256) * o.wld * 16;
+        steps += (o.cpt + KC - 1) / KC;
+    }
+    k.nsrc = nsrc;
+    k.in_bytes = k.src[0].in_bytes; k.w_bytes = k.src[0].w_bytes;
+    k.Cin = srcs[0].cout; k.ldi = srcs[0].ldo; k.cioff = srcs[0].cooff;
+    // the reduction runs over the sources' k-steps, every source padded to whole k-steps; no tap remap, no split
+    k.cpt = KC; k.Q = steps * KC; k.nk = steps; k.wld = k.src[0].wld;
+    GatherPlan g = plan_gather(k.M, 64, cin, 1, dtype);
+    g.ks_per_split = steps;
+    const GatherChoice c = choose_gather(k, g, dtype);
+    set_plan_fields(k, c);
+    return f(k, c, dtype);
+}
+
+// the argument checks of a data-gradient launch that read no pointer (din_conv_dgrad, din_conv_dgrad_x and the latter's reporter)
+static int check_dgrad_args(const din_conv_desc* d, int flags) {
+    DIN_REQUIRE(!d->in_u8, "conv_dgrad: in_u8 is a din_conv_fwd / din_conv_wgrad option");
+    DIN_REQUIRE(!(flags & (DIN_CONV_BIAS | DIN_CONV_RELU)), "conv_dgrad: BIAS/RELU are fwd-only flags");
+    const int epc = epc_of(d->dtype);
+    DIN_REQUIRE(d->ldo % epc == 0 && d->cooff % epc == 0 && d->ldo >= d->cooff + pad_to(d->cout, epc),
+                "conv_dgrad: dout stride/offset must be multiples of %d and cover cout (+zero pad)", epc);
+    DIN_REQUIRE(d->ldi % 4 == 0 && d->cioff % 4 == 0, "conv_dgrad: din stride/offset must be multiples of 4");
+    return DIN_OK;
+}
+// ... and those of din_conv_dgrad_x's extra source (cout, ldo, cooff)
+static int check_dgrad_xsrc(const din_conv_desc* d, const din_conv_src* x) {
+    DIN_REQUIRE(x && x->cout > 0, "conv_dgrad_x: null extra source");
+    const int epc = epc_of(d->dtype);
+    DIN_REQUIRE(x->ldo % epc == 0 && x->cooff % epc == 0 && x->ldo >= x->cooff + pad_to(x->cout, epc),
+                "conv_dgrad_x: extra source stride/offset must be multiples of %d and cover cout (+zero pad)", epc);
+    return DIN_OK;
+}
+
+// The launches of a data gradient (for_each_launch), each with the geometry of the extra 1x1 source `x` at the output pixel where one is
+// given (din_conv_dgrad_x's fused form: parity-class launches only); the pointers of x are not read.  din_conv_dgrad binds its pointers
+// and launches from here; for_dgrad_x_launches walks it for din_conv_dgrad_x and its reporter.
+template <typename F>
+static int for_each_dgrad_launch(const din_conv_desc* d, int flags, int ldm, int moff, const din_conv_src* x, F f) {
+    const int epc = epc_of(d->dtype);
+    return for_each_launch(d, 1, flags, ldm, moff, [&](ConvK& c, const GatherPlan& g, const char* what) {
+        if (x) {
+            ConvK::Src& o = c.src[0];
+            o.ld = x->ldo; o.coff = x->cooff;
+            o.cpt = pad_to(x->cout, epc) / epc;
+            o.wld = (o.cpt + KC - 1) / KC * KC;
+            o.in_bytes = (long long)d->nb * d->h * d->w * x->ldo * 2;
+            o.w_bytes = (long long)pad_to(d->cin, 256) * o.wld * 16;
+            c.xsteps = (o.cpt + KC - 1) / KC;
+        }
+        return f(c, g, what);
+    });
+}
+
+// whether the parity-class launches of this strided dgrad can carry an extra 1x1 source (conv_gather_fast_kernel<..., XSRC>: bf16, 128 x 96
+// tiles, no split-K)
+static bool dgrad_x_fused(const din_conv_desc* d) {
+    if (DIN_OPT("DIN_DGRAD_X") && atoi(DIN_OPT("DIN_DGRAD_X")) == 0) return false;
+    if (d->dtype != DIN_BF16 || !dgrad_by_parity(d)) return false;
+    return !for_each_parity_class(d, [&](const ParityClass& pc) { const GatherPlan g = plan_launch(d, 1, &pc); return (g.bn != 96 || g.splitk != 1) ? 1 : 0; });
+}
+
+// The launches din_conv_dgrad_x makes for a checked descriptor (dtype normalised; dtype0: as the caller gave it): every argument check that
+// reads no pointer, then the fused form -- dg(argument block without pointers, plan, what) per parity class, x's geometry in src[0] -- or,
+// for a shape the fused kernel does not serve, the two launches it replaces: dg(...) per launch of the plain data gradient, then
+// mu(argument block, choice, storage dtype) for the one-source multi launch, which accumulates (the mask is linear).  din_conv_dgrad_x binds
+// its pointers and launches from here; din_conv_dgrad_x_kernel_names names the kernels from here.
+template <typename DG, typename MU>
+static int for_dgrad_x_launches(const din_conv_desc* d, int dtype0, const din_conv_src* x, int ldm, int moff, int flags, DG dg, MU mu) {
+    if (int e = check_dgrad_xsrc(d, x)) return e;
+    if (int e = check_dgrad_args(d, flags)) return e;
+    const bool fused = dgrad_x_fused(d);
+    if (int e = for_each_dgrad_launch(d, flags, ldm, moff, fused ? x : nullptr, dg)) return e;
+    if (fused) return DIN_OK;
+    return for_multi_launch(1, x, dtype0, d->nb, d->h, d->w, d->cin, d->ldi, d->cioff, ldm, moff, flags | DIN_CONV_ACCUM, mu);
+}
+
+// a data-gradient launch of for_each_dgrad_launch with its pointers bound (x: the extra 1x1 source where the launch carries one), run
+static int run_dgrad_launch(ConvK& c, const GatherPlan& g, const char* what, int dtype, bool split, const void* dout, const void* wpk_t, void* din_,
+                            const void* mask, const din_conv_src* x, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+    c.in = dout; c.w = wpk_t; c.out = din_; c.mask = mask; c.mma = split;
+    if (c.xsteps > 0) { c.src[0].in = x->dout; c.src[0].w = x->wpk_t; }
+    return run_gather(c, g, dtype, workspace, workspace_bytes, st, what);
+}
+
+// the launch of for_multi_launch with its pointers bound, launched
+static int run_multi_launch(ConvK& k, const GatherChoice& c, int dtype, int nsrc, const din_conv_src* srcs, void* din_, const void* mask, hipStream_t st) {
+    k.out = din_; k.mask = mask;
+    for (int b = 0; b < nsrc; ++b) { k.src[b].in = srcs[b].dout; k.src[b].w = srcs[b].wpk_t; }
+    k.in = srcs[0].dout; k.w = srcs[0].wpk_t;
+    if (DIN_OPT("DIN_DEBUG_PLAN"))
+        fprintf(stderr, "[din] conv1x1_dgrad_multi M=%d nsrc=%d couts=%d,%d,%d,%d ld=%d,%d,%d,%d coff=%d,%d,%d,%d cin=%d flags=%d regw=%d\n", k.M, nsrc, srcs[0].cout,
+                nsrc > 1 ? srcs[1].cout : 0, nsrc > 2 ? srcs[2].cout : 0, nsrc > 3 ? srcs[3].cout : 0, srcs[0].ldo, nsrc > 1 ? srcs[1].ldo : 0,
+                nsrc > 2 ? srcs[2].ldo : 0, nsrc > 3 ? srcs[3].ldo : 0, srcs[0].cooff, nsrc > 1 ? srcs[1].cooff : 0, nsrc > 2 ? srcs[2].cooff : 0,
+                nsrc > 3 ? srcs[3].cooff : 0, k.Cout, k.flags, (int)(c.family == GATHER_REGW));
+    return launch_choice(k, c, dtype, st, "conv1x1_dgrad_multi");
+}
+
 }  // namespace
 
 extern "C" {
@@ -2247,17 +2412,10 @@ int din_conv_kernel_names(const din_conv_desc* d, int which, int flags, int ldm,
     if (which != 2) for_each_launch(d, which, flags, ldm, moff, [&](ConvK& k, const GatherPlan& g, const char*) {
         if (d->in_u8) k.u8 = &raw_frames;
         k.mma = sd.split;
-        const GatherChoice c = choose_gather(k, g, d->dtype);
-        set_plan_fields(k, c);
-        append_kernel_names(k, c, d->dtype, names);
+        append_launch_names(k, g, d->dtype, names);
         return 0;
     });
-    if (buf_bytes > 0) {
-        const size_t n = names.size() < (size_t)buf_bytes - 1 ? names.size() : (size_t)buf_bytes - 1;
-        memcpy(buf, names.data(), n);
-        buf[n] = 0;
-    }
-    return (int)names.size() + 1;
+    return copy_names(names, buf, buf_bytes);
 }
 
 int64_t din_conv_workspace_bytes(const din_conv_desc* d, int which) {
@@ -2304,129 +2462,86 @@ int din_conv_fwd2(const din_conv_desc* d, const void* in, const void* wpk, const
     const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
     DIN_REQUIRE(in && wpk && out && out2, "conv_fwd2: null pointer");
-    DIN_REQUIRE(!d->in_u8, "conv_fwd2: in_u8 is a din_conv_fwd / din_conv_wgrad option");
     DIN_REQUIRE(!(flags & DIN_CONV_BIAS) || bias, "conv_fwd2: BIAS flag without bias");
-    DIN_REQUIRE(!(flags & (DIN_CONV_ACCUM | DIN_CONV_MASK)), "conv_fwd2: ACCUM/MASK are dgrad-only flags");
-    const int epc = epc_of(d->dtype);
-    DIN_REQUIRE(d->kh * d->kw <= 32 && d->dh == 1 && d->dw == 1, "conv_fwd2: needs the buffer-addressed gather kernel (<= 32 taps)");
-    DIN_REQUIRE(csplit > 0 && csplit < d->cout && csplit % epc == 0 && d->cout % epc == 0 && d->ldo % epc == 0 && d->cooff % epc == 0 &&
-                ldo2 % epc == 0 && cooff2 % epc == 0 && ldo2 >= cooff2 + (d->cout - csplit) && d->ldo >= d->cooff + csplit,
-                "conv_fwd2: split / strides / offsets must be multiples of %d and the destinations must hold their channel ranges", epc);
-    DIN_REQUIRE(craw == 0 || (craw >= csplit && craw < d->cout && craw % epc == 0), "conv_fwd2: craw must be 0 or a multiple of %d in [csplit, cout)", epc);
-    ConvK k = conv_k_of(d, 0);
-    k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.flags = flags; k.mma = sd.split;
-    k.out2 = out2; k.ldo2 = ldo2; k.cooff2 = cooff2; k.csplit = csplit; k.craw = craw;
-    const GatherPlan g = plan_launch(d, 0);
-    if (g.splitk > 1) DIN_FAIL(DIN_E_ARG, "conv_fwd2: this shape runs split-K (%d pixels): launch the sibling convs separately", k.M);
-    return run_gather(k, g, d->dtype, workspace, workspace_bytes, as_stream(stream), "conv_fwd2");
+    return for_fwd2_launch(d, sd.split, ldo2, cooff2, csplit, craw, flags, [&](ConvK& k, const GatherPlan& g) {
+        k.in = in; k.w = wpk; k.out = out; k.bias = bias; k.out2 = out2;
+        return run_gather(k, g, d->dtype, workspace, workspace_bytes, as_stream(stream), "conv_fwd2");
+    });
 }
 
-static int conv_dgrad_impl(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din_, const void* mask, int ldm,
-                           int moff, int flags, void* workspace, int64_t workspace_bytes, void* stream, const din_conv_src* x);
+int din_conv_fwd2_kernel_names(const din_conv_desc* d, int ldo2, int cooff2, int csplit, int craw, int flags, char* buf, int buf_bytes) {
+    const SplitDesc sd(d);
+    if (int e = check_desc(d)) return e;
+    DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_fwd2_kernel_names: bad argument");
+    std::string names;
+    if (int e = for_fwd2_launch(d, sd.split, ldo2, cooff2, csplit, craw, flags, [&](ConvK& k, const GatherPlan& g) {
+            append_launch_names(k, g, d->dtype, names);
+            return 0;
+        }))
+        return e;
+    return copy_names(names, buf, buf_bytes);
+}
 
 int din_conv_dgrad(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din_, const void* mask, int ldm,
                    int moff, int flags, void* workspace, int64_t workspace_bytes, void* stream) {
-    return conv_dgrad_impl(d, dout, wpk_t, din_, mask, ldm, moff, flags, workspace, workspace_bytes, stream, nullptr);
-}
-
-// whether the parity-class launches of this strided dgrad can carry an extra 1x1 source (conv_gather_fast_kernel<..., XSRC>: bf16, 128 x 96
-// tiles, no split-K)
-static bool dgrad_x_fused(const din_conv_desc* d) {
-    if (DIN_OPT("DIN_DGRAD_X") && atoi(DIN_OPT("DIN_DGRAD_X")) == 0) return false;
-    if (d->dtype != DIN_BF16 || !dgrad_by_parity(d)) return false;
-    return !for_each_parity_class(d, [&](const ParityClass& pc) { const GatherPlan g = plan_launch(d, 1, &pc); return (g.bn != 96 || g.splitk != 1) ? 1 : 0; });
+    const SplitDesc sd(d);
+    if (int e = check_desc(d)) return e;
+    DIN_REQUIRE(dout && wpk_t && din_, "conv_dgrad: null pointer");
+    DIN_REQUIRE(!(flags & DIN_CONV_MASK) || mask, "conv_dgrad: MASK flag without mask");
+    if (int e = check_dgrad_args(d, flags)) return e;
+    return for_each_dgrad_launch(d, flags, ldm, moff, nullptr, [&](ConvK& c, const GatherPlan& g, const char* what) {
+        return run_dgrad_launch(c, g, what, d->dtype, sd.split, dout, wpk_t, din_, mask, nullptr, workspace, workspace_bytes, as_stream(stream));
+    });
 }
 
 int din_conv_dgrad_x_fused(const din_conv_desc* d) { return (d && check_desc(d) == DIN_OK && dgrad_x_fused(d)) ? 1 : 0; }
 
 int din_conv_dgrad_x(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din_, const void* mask, int ldm, int moff, int flags,
                      const din_conv_src* x, void* workspace, int64_t workspace_bytes, void* stream) {
-    const din_conv_desc* const d0 = d;             // (the two launches below normalise the dtype themselves)
+    const int dtype0 = d ? d->dtype : 0;
     const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
-    DIN_REQUIRE(x && x->dout && x->wpk_t && x->cout > 0, "conv_dgrad_x: null extra source");
-    const int epc = epc_of(d->dtype);
-    DIN_REQUIRE(x->ldo % epc == 0 && x->cooff % epc == 0 && x->ldo >= x->cooff + pad_to(x->cout, epc),
-                "conv_dgrad_x: extra source stride/offset must be multiples of %d and cover cout (+zero pad)", epc);
-    if (dgrad_x_fused(d)) return conv_dgrad_impl(d0, dout, wpk_t, din_, mask, ldm, moff, flags, workspace, workspace_bytes, stream, x);
-    // not a shape the fused kernel serves: the two launches it replaces (the second accumulates; the mask is linear)
-    if (int e = conv_dgrad_impl(d0, dout, wpk_t, din_, mask, ldm, moff, flags, workspace, workspace_bytes, stream, nullptr)) return e;
-    return din_conv1x1_dgrad_multi(1, x, d0->dtype, d->nb, d->h, d->w, d->cin, d->ldi, d->cioff, din_, mask, ldm, moff, flags | DIN_CONV_ACCUM, stream);
+    DIN_REQUIRE(x && x->dout && x->wpk_t, "conv_dgrad_x: null extra source");
+    DIN_REQUIRE(dout && wpk_t && din_, "conv_dgrad: null pointer");
+    DIN_REQUIRE(!(flags & DIN_CONV_MASK) || mask, "conv_dgrad: MASK flag without mask");
+    hipStream_t st = as_stream(stream);
+    return for_dgrad_x_launches(d, dtype0, x, ldm, moff, flags,
+        [&](ConvK& c, const GatherPlan& g, const char* what) {
+            return run_dgrad_launch(c, g, what, d->dtype, sd.split, dout, wpk_t, din_, mask, x, workspace, workspace_bytes, st);
+        },
+        [&](ConvK& k, const GatherChoice& c, int sdt) { return run_multi_launch(k, c, sdt, 1, x, din_, mask, st); });
 }
 
-static int conv_dgrad_impl(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din_, const void* mask, int ldm,
-                           int moff, int flags, void* workspace, int64_t workspace_bytes, void* stream, const din_conv_src* x) {
+int din_conv_dgrad_x_kernel_names(const din_conv_desc* d, const din_conv_src* x, int ldm, int moff, int flags, char* buf, int buf_bytes) {
+    const int dtype0 = d ? d->dtype : 0;
     const SplitDesc sd(d);
     if (int e = check_desc(d)) return e;
-    DIN_REQUIRE(dout && wpk_t && din_, "conv_dgrad: null pointer");
-    DIN_REQUIRE(!d->in_u8, "conv_dgrad: in_u8 is a din_conv_fwd / din_conv_wgrad option");
-    DIN_REQUIRE(!(flags & (DIN_CONV_BIAS | DIN_CONV_RELU)), "conv_dgrad: BIAS/RELU are fwd-only flags");
-    DIN_REQUIRE(!(flags & DIN_CONV_MASK) || mask, "conv_dgrad: MASK flag without mask");
-    int epc = epc_of(d->dtype);
-    DIN_REQUIRE(d->ldo % epc == 0 && d->cooff % epc == 0 && d->ldo >= d->cooff + pad_to(d->cout, epc),
-                "conv_dgrad: dout stride/offset must be multiples of %d and cover cout (+zero pad)", epc);
-    DIN_REQUIRE(d->ldi % 4 == 0 && d->cioff % 4 == 0, "conv_dgrad: din stride/offset must be multiples of 4");
-    hipStream_t st = as_stream(stream);
-    return for_each_launch(d, 1, flags, ldm, moff, [&](ConvK& c, const GatherPlan& g, const char* what) {
-        c.in = dout; c.w = wpk_t; c.out = din_; c.mask = mask; c.mma = sd.split;
-        if (x) {                                   // extra 1x1 source at the output pixel (din_conv_dgrad_x: parity-class launches only)
-            ConvK::Src& o = c.src[0];
-            o.in = x->dout; o.w = x->wpk_t; o.ld = x->ldo; o.coff = x->cooff;
-            o.cpt = pad_to(x->cout, epc) / epc;
-            o.wld = (o.cpt + KC - 1) / KC * KC;
-            o.in_bytes = (long long)d->nb * d->h * d->w * x->ldo * 2;
-            o.w_bytes = (long long)pad_to(d->cin, 256) * o.wld * 16;
-            c.xsteps = (o.cpt + KC - 1) / KC;
-        }
-        return run_gather(c, g, d->dtype, workspace, workspace_bytes, st, what);
-    });
+    DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_dgrad_x_kernel_names: bad argument");
+    std::string names;
+    if (int e = for_dgrad_x_launches(d, dtype0, x, ldm, moff, flags,
+            [&](ConvK& k, const GatherPlan& g, const char*) { k.mma = sd.split; append_launch_names(k, g, d->dtype, names); return 0; },
+            [&](ConvK& k, const GatherChoice& c, int sdt) { append_kernel_names(k, c, sdt, names); return 0; }))
+        return e;
+    return copy_names(names, buf, buf_bytes);
 }
 
 int din_conv1x1_dgrad_multi(int nsrc, const din_conv_src* srcs, int dtype, int nb, int h, int w, int cin, int ldi, int cioff,
                             void* din_, const void* mask, int ldm, int moff, int flags, void* stream) {
     DIN_REQUIRE(nsrc >= 1 && nsrc <= 4 && srcs && din_, "conv1x1_dgrad_multi: 1..4 sources");
-    const bool split = dtype == DIN_F32_BF16X3;
-    dtype = storage_dtype(dtype);
-    DIN_REQUIRE(dtype == DIN_F32 || dtype == DIN_BF16, "conv1x1_dgrad_multi: bad dtype");
-    DIN_REQUIRE(!(flags & (DIN_CONV_BIAS | DIN_CONV_RELU)), "conv1x1_dgrad_multi: BIAS/RELU are fwd-only flags");
     DIN_REQUIRE(!(flags & DIN_CONV_MASK) || mask, "conv1x1_dgrad_multi: MASK flag without mask");
-    const int epc = epc_of(dtype), esz = dtype == DIN_F32 ? 4 : 2;
-    DIN_REQUIRE(nb > 0 && h > 0 && w > 0 && cin > 0 && ldi % 4 == 0 && cioff % 4 == 0 && ldi >= cioff + cin, "conv1x1_dgrad_multi: bad output geometry");
-    DIN_REQUIRE((int64_t)nb * h * w < (1ll << 31), "conv1x1_dgrad_multi: too many pixels");
-    ConvK k{};
-    k.out = din_; k.mask = mask; k.bias = nullptr; k.partial = nullptr;
-    k.NB = nb; k.H = h; k.W = w; k.OH = h; k.OW = w; k.Cout = cin; k.ldo = ldi; k.cooff = cioff;
-    k.kh = k.kw = 1; k.ay = k.ax = 1; k.by = k.bx = 0; k.cy = k.cx = 1; k.divy = k.divx = 1;
-    k.M = nb * h * w; k.flags = flags; k.ldm = ldm; k.moff = moff; k.mma = split;
-    int steps = 0;
-    for (int b = 0; b < nsrc; ++b) {
-        const din_conv_src& sc = srcs[b];
-        DIN_REQUIRE(sc.dout && sc.wpk_t && sc.cout > 0, "conv1x1_dgrad_multi: null source %d", b);
-        DIN_REQUIRE(sc.ldo % epc == 0 && sc.cooff % epc == 0 && sc.ldo >= sc.cooff + pad_to(sc.cout, epc),
-                    "conv1x1_dgrad_multi: source %d stride/offset must be multiples of %d and cover cout (+zero pad)", b, epc);
-        ConvK::Src& o = k.src[b];
-        o.in = sc.dout; o.w = sc.wpk_t; o.ld = sc.ldo; o.coff = sc.cooff;
-        o.cpt = pad_to(sc.cout, epc) / epc;
-        o.wld = (o.cpt + KC - 1) / KC * KC;
-        o.in_bytes = (long long)nb * h * w * sc.ldo * esz;
-        o.w_bytes = (long long)pad_to(cin, 256) * o.wld * 16;
-        steps += (o.cpt + KC - 1) / KC;
-    }
-    k.nsrc = nsrc;
-    k.in = srcs[0].dout; k.w = srcs[0].wpk_t; k.in_bytes = k.src[0].in_bytes; k.w_bytes = k.src[0].w_bytes;
-    k.Cin = srcs[0].cout; k.ldi = srcs[0].ldo; k.cioff = srcs[0].cooff;
-    // the reduction runs over the sources' k-steps, every source padded to whole k-steps; no tap remap, no split
-    k.cpt = KC; k.Q = steps * KC; k.nk = steps; k.wld = k.src[0].wld;
-    GatherPlan g = plan_gather(k.M, 64, cin, 1, dtype);
-    g.ks_per_split = steps;
-    const GatherChoice c = choose_gather(k, g, dtype);
-    set_plan_fields(k, c);
-    if (DIN_OPT("DIN_DEBUG_PLAN"))
-        fprintf(stderr, "[din] conv1x1_dgrad_multi M=%d nsrc=%d couts=%d,%d,%d,%d ld=%d,%d,%d,%d coff=%d,%d,%d,%d cin=%d flags=%d regw=%d\n", k.M, nsrc, srcs[0].cout,
-                nsrc > 1 ? srcs[1].cout : 0, nsrc > 2 ? srcs[2].cout : 0, nsrc > 3 ? srcs[3].cout : 0, srcs[0].ldo, nsrc > 1 ? srcs[1].ldo : 0,
-                nsrc > 2 ? srcs[2].ldo : 0, nsrc > 3 ? srcs[3].ldo : 0, srcs[0].cooff, nsrc > 1 ? srcs[1].cooff : 0, nsrc > 2 ? srcs[2].cooff : 0,
-                nsrc > 3 ? srcs[3].cooff : 0, cin, flags, (int)(c.family == GATHER_REGW));
-    return launch_choice(k, c, dtype, as_stream(stream), "conv1x1_dgrad_multi");
+    for (int b = 0; b < nsrc; ++b) DIN_REQUIRE(srcs[b].dout && srcs[b].wpk_t, "conv1x1_dgrad_multi: null source %d", b);
+    return for_multi_launch(nsrc, srcs, dtype, nb, h, w, cin, ldi, cioff, ldm, moff, flags,
+                            [&](ConvK& k, const GatherChoice& c, int sdt) { return run_multi_launch(k, c, sdt, nsrc, srcs, din_, mask, as_stream(stream)); });
+}
+
+int din_conv1x1_dgrad_multi_kernel_names(int nsrc, const din_conv_src* srcs, int dtype, int nb, int h, int w, int cin, int ldi, int cioff,
+                                         int ldm, int moff, int flags, char* buf, int buf_bytes) {
+    DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv1x1_dgrad_multi_kernel_names: bad argument");
+    std::string names;
+    if (int e = for_multi_launch(nsrc, srcs, dtype, nb, h, w, cin, ldi, cioff, ldm, moff, flags,
+                                 [&](ConvK& k, const GatherChoice& c, int sdt) { append_kernel_names(k, c, sdt, names); return 0; }))
+        return e;
+    return copy_names(names, buf, buf_bytes);
 }
 
 int din_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale,

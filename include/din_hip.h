@@ -157,7 +157,8 @@ int din_conv_kernel_variant(const din_conv_desc* d, int which, int32_t* flags);
  * "conv_gather_pipe_kernel<192>", "conv1x1_stream_kernel<96,4,0,1,0>", "conv1x1_regw_kernel<24,1,9,1,3>", and "conv_splitk_finish_kernel<bf16>"
  * after a launch whose reduction is split.  A strided data gradient gives the line(s) of every non-empty parity class.  Host only: answers
  * from the launcher's own selection, launches nothing, reads no pointer, needs no GPU.  Writes at most buf_bytes bytes (NUL-terminated) and
- * returns the number of bytes the whole answer needs (terminator included), or a negative DIN_E_* code.
+ * returns the number of bytes the whole answer needs (terminator included), or a negative DIN_E_* code.  (din_conv_fwd2,
+ * din_conv1x1_dgrad_multi and din_conv_dgrad_x have reporters of their own, declared after them: din_conv_fwd2_kernel_names, ...)
  * which 2: the launches of a production-style din_conv_wgrad call (dbias, scale, w and wdot given) under the current options, from the
  * weight-gradient choice din_conv_wgrad itself launches from: the main kernel, "conv_wgrad_reduce_kernel", and the column-sum kernel
  * ("colsum_vec_kernel<unsigned short, 8>", "colsum_kernel<float>", ...) where the main kernel does not sum the bias gradient itself.  flags,
@@ -203,6 +204,18 @@ int din_conv_dgrad_x(const din_conv_desc* d, const void* dout, const void* wpk_t
                      const din_conv_src* x, void* workspace, int64_t workspace_bytes, void* stream);
 /* 1 when din_conv_dgrad_x serves this descriptor with the fused kernel, 0 when it runs the two-launch form.  Host-only planning call. */
 int din_conv_dgrad_x_fused(const din_conv_desc* d);
+/* din_conv_kernel_names for the three multi-source / two-destination entry points: the kernels din_conv_fwd2, din_conv1x1_dgrad_multi and
+ * din_conv_dgrad_x launch for these arguments under the current option settings, spelled and returned as din_conv_kernel_names does (one
+ * line per launch, in launch order; at most buf_bytes bytes written, the bytes the whole answer needs returned, or a negative DIN_E_*
+ * code).  Host only: each answers from the very function its entry point builds its argument block, plan and choice in, launches nothing,
+ * needs no GPU and reads no pointer -- of a din_conv_src only cout, ldo and cooff.  The argument checks are the entry point's own (a
+ * din_conv_fwd2 shape that would run split-K is DIN_E_ARG from both).  din_conv_dgrad_x_kernel_names gives the parity-class lines of the
+ * fused form ("conv_gather_fast_kernel<bf16,128,96,4,2,8,2,0,0,1,0>" each) and, where din_conv_dgrad_x_fused() is 0, the lines of the
+ * din_conv_dgrad launch followed by those of the one-source din_conv1x1_dgrad_multi launch (flags | DIN_CONV_ACCUM). */
+int din_conv_fwd2_kernel_names(const din_conv_desc* d, int ldo2, int cooff2, int csplit, int craw, int flags, char* buf, int buf_bytes);
+int din_conv1x1_dgrad_multi_kernel_names(int nsrc, const din_conv_src* srcs, int dtype, int nb, int h, int w, int cin, int ldi, int cioff,
+                                         int ldm, int moff, int flags, char* buf, int buf_bytes);
+int din_conv_dgrad_x_kernel_names(const din_conv_desc* d, const din_conv_src* x, int ldm, int moff, int flags, char* buf, int buf_bytes);
 /* dw: [cout][cin][kh][kw] fp32, overwritten (or += when accumulate bit 0 (value 1) is set; bit 1 alone leaves dw overwritten),
  * multiplied by scale[cout] when scale is given.  dbias (nullable) [cout] fp32 = column sums of dout.  wdot (nullable) [cout] fp32 =
  * <w[co,:], dw_raw[co,:]> (needs w) -- the BatchNorm-eval scale gradient.  accumulate bit 1 (value 2): dbias / wdot were zeroed by

@@ -291,20 +291,28 @@ def _survey(monkeypatch):
     lib, calls = L.load(), []
 
     def wrap(name, real):
-        def call(*args):
-            if name == "din_conv1x1_dgrad_multi":
-                calls.append((name, int(args[2]), []))
+        def call(*a):
+            buf = C.create_string_buffer(2048)
+            rc = real(*a)
+            if name == "din_conv1x1_dgrad_multi":          # (nsrc, srcs, dtype, nb, h, w, cin, ldi, cioff, din, mask, ldm, moff, flags, stream)
+                dtype = int(a[2])
+                n = lib.din_conv1x1_dgrad_multi_kernel_names(*a[:9], *a[11:14], buf, len(buf))
+            elif name == "din_conv_fwd2":                  # (d, in, wpk, bias, out, out2, ldo2, cooff2, csplit, craw, flags, ...)
+                dtype = int(a[0]._obj.dtype)
+                n = lib.din_conv_fwd2_kernel_names(a[0], *a[6:11], buf, len(buf))
+            elif name == "din_conv_dgrad_x":               # (d, dout, wpk_t, din, mask, ldm, moff, flags, x, ...)
+                dtype = int(a[0]._obj.dtype)
+                n = lib.din_conv_dgrad_x_kernel_names(a[0], a[8], *a[5:8], buf, len(buf))
             else:
-                d = args[0]._obj
-                which = {"din_conv_fwd": 0, "din_conv_fwd2": 0, "din_conv_wgrad": 2}.get(name, 1)
-                buf = C.create_string_buffer(1024)
-                flags = 0 if which == 2 else int(args[{"din_conv_fwd": 5, "din_conv_fwd2": 10, "din_conv_dgrad": 7, "din_conv_dgrad_x": 7}[name]])
-                ldm, moff = (int(args[5]), int(args[6])) if which == 1 else (0, 0)
-                rc = real(*args)
-                lib.din_conv_kernel_names(C.byref(d), which, flags, ldm if flags & MASK else 0, moff if flags & MASK else 0, buf, len(buf))
-                calls.append((name, int(d.dtype), buf.value.decode().split()))
-                return rc
-            return real(*args)
+                d = a[0]._obj
+                dtype = int(d.dtype)
+                which = {"din_conv_fwd": 0, "din_conv_wgrad": 2}.get(name, 1)
+                flags = 0 if which == 2 else int(a[{"din_conv_fwd": 5, "din_conv_dgrad": 7}[name]])
+                ldm, moff = (int(a[5]), int(a[6])) if which == 1 else (0, 0)
+                n = lib.din_conv_kernel_names(C.byref(d), which, flags, ldm if flags & MASK else 0, moff if flags & MASK else 0, buf, len(buf))
+            assert rc != 0 or 0 < n <= len(buf), f"{name}: launched, but its reporter returned {n}"
+            calls.append((name, dtype, buf.value.decode().split()))
+            return rc
         return call
 
     for name in CONTRACTIONS + ("din_conv1x1_dgrad_multi",):
@@ -317,7 +325,7 @@ def _assert_survey(calls, L, want=("din_conv_fwd", "din_conv_dgrad", "din_conv_w
     for name, dtype, names in calls:
         assert dtype == L.DIN_F32_BF16X3, f"{name} was called with dtype {dtype}"
         assert not any(n.startswith(("conv_gather_fast_kernel<float", "conv_gather_generic_kernel<float", "conv_wgrad_f32_kernel")) for n in names), (name, names)
-        assert name == "din_conv1x1_dgrad_multi" or any("f32x3" in n for n in names), (name, names)
+        assert any("f32x3" in n for n in names), (name, names)
     print(f"{len(calls)} conv entry-point calls, all DIN_F32_BF16X3: " + ", ".join(f"{n} x{sum(c[0] == n for c in calls)}" for n in sorted({c[0] for c in calls})))
 
 

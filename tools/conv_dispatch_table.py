@@ -21,6 +21,13 @@ The full table has ~47 000 lines.  --summary prints what profiles/conv_dispatch_
 cases with no option set -- forward, and data gradient with flags 0 / MASK / ACCUM / MASK|ACCUM (mask view = the layer's input view) --
 each once, with one descriptor that reaches it.  tests/test_gpu_conv_fwd_dgrad.py holds a row for every name in that file.
 
+--names --multi prints what profiles/conv_multi_kernel_names.txt holds: every distinct kernel instantiation the reporters of the three
+multi-source / two-destination entry points (din_conv_fwd2_kernel_names, din_conv1x1_dgrad_multi_kernel_names,
+din_conv_dgrad_x_kernel_names) answer, with no option set, over the launches nhwc.py makes through them -- the fwd_groups of both backbones
+(BIAS | RELU), and the dgrad_groups and x_host pairs of plan_backward with the mask flag forms the reverse pass uses (MASK where the source
+tensor is ReLU-masked, with and without ACCUM) -- in bf16, fp32 and fp32_bf16x3 at the four geometries, each once PER ENTRY POINT
+(fwd2 | dgrad_multi | dgrad_x, the first word of the line), with one launch that reaches it.  tests/test_gpu_conv_multi.py holds a row for every name in that file.
+
 The weight gradient follows (--wgrad: only it): for the same descriptors, geometries and dtypes,
 
     <label> which=2 <option>  ->  bm bn workspace_bytes(2) group_key
@@ -163,16 +170,87 @@ def names_table(L, lib, cases):
     return found
 
 
+def _reporter_lines(rc, buf, what):
+    assert 0 < rc <= len(buf), f"{what}: {rc}"
+    return buf.value.decode().split()
+
+
+def multi_names_table(L, lib, nhwc):
+    """{(entry point: fwd2 | dgrad_multi | dgrad_x, kernel name): label of the first launch of a backbone through that entry point that reaches it}"""
+    from din_amd.backbone import backbone as B
+    found = {}
+    buf = C.create_string_buffer(4096)
+    for backbone in ("inv3", "vgg16"):
+        for dt, dtn in ((L.DIN_BF16, "bf16"), (L.DIN_F32, "fp32"), (L.DIN_F32_BF16X3, "fp32_bf16x3")):
+            net = (B.MyInception_v3 if backbone == "inv3" else B.MyVGG16)(compute_dtype="bf16" if dt == L.DIN_BF16 else "fp32")
+            for nb, h, w in GEOMETRIES:
+                g = net.build_graph(h, w, L.DIN_BF16 if dt == L.DIN_BF16 else L.DIN_F32)
+                head = f"{backbone} {dtn} nb{nb}"
+                for grp in g.fwd_groups:                   # graph_forward: one launch, first member into its view, the others into theirs
+                    op, rest = g.ops[grp[0]], [g.ops[i] for i in grp[1:]]
+                    ctot = op.dst.c + sum(o.dst.c for o in rest)
+                    craw = ctot - sum(o.dst.c for o in rest if o.pooled is not None)
+                    d = nhwc._conv_desc(g, op, nb, dt)
+                    d.cout = ctot
+                    v2 = nhwc.group_view(rest[0])
+                    if lib.din_conv_workspace_bytes(C.byref(d), 0) != 0:
+                        continue                           # (would run split-K: graph_forward launches the members separately)
+                    flags = L.CONV_BIAS | (L.CONV_RELU if op.relu else 0)
+                    rc = lib.din_conv_fwd2_kernel_names(C.byref(d), g.tensors[v2.tid].c, v2.coff, op.dst.c, craw if craw < ctot else 0, flags, buf, len(buf))
+                    for name in _reporter_lines(rc, buf, "din_conv_fwd2_kernel_names"):
+                        found.setdefault(("fwd2", name), f"{head} {'+'.join(g.ops[i].name for i in grp)} {d.h}x{d.w} c{d.cin}>{ctot} csplit{op.dst.c} flags={flags}")
+                plan = nhwc.plan_backward(g, nb, dt, False, False, False)
+
+                def source(oi):                            # the gradient operand of op oi as the reverse pass hands it on (_ConvStep)
+                    o = g.ops[oi]
+                    s = L.ConvSrc()
+                    s.cout = o.dst.c
+                    s.ldo, s.cooff = (o.dst.c, 0) if o.pooled is not None else (g.tensors[o.dst.tid].c, o.dst.coff)
+                    return s
+
+                def flag_forms(view):
+                    base = L.CONV_MASK if g.tensors[view.tid].relu_masked else 0
+                    return (base, base | L.CONV_ACCUM)
+
+                for key, members in plan.dgrad_groups.items():
+                    op0 = g.ops[members[0]]
+                    ts = g.tensors[op0.src.tid]
+                    srcs = (L.ConvSrc * len(members))(*[source(oi) for oi in reversed(members)])      # (the reverse pass meets the last member first)
+                    for flags in flag_forms(op0.src):
+                        rc = lib.din_conv1x1_dgrad_multi_kernel_names(len(members), srcs, dt, nb, ts.h, ts.w, op0.src.c, ts.c, op0.src.coff, ts.c, op0.src.coff,
+                                                                      flags, buf, len(buf))
+                        for name in _reporter_lines(rc, buf, "din_conv1x1_dgrad_multi_kernel_names"):
+                            found.setdefault(("dgrad_multi", name), f"{head} {'+'.join(g.ops[i].name for i in reversed(members))} {ts.h}x{ts.w} "
+                                                   f"c{'+'.join(str(s.cout) for s in srcs)}>{op0.src.c} flags={flags}")
+                for oi, host in plan.x_host.items():
+                    oph = g.ops[host]
+                    ts = g.tensors[oph.src.tid]
+                    d, x = nhwc._conv_desc(g, oph, nb, dt), source(oi)
+                    for flags in flag_forms(oph.src):
+                        rc = lib.din_conv_dgrad_x_kernel_names(C.byref(d), C.byref(x), ts.c, oph.src.coff, flags, buf, len(buf))
+                        for name in _reporter_lines(rc, buf, "din_conv_dgrad_x_kernel_names"):
+                            found.setdefault(("dgrad_x", name), f"{head} {oph.name}+{g.ops[oi].name} {d.h}x{d.w} c{d.cout}+{x.cout}>{d.cin} k{d.kh}x{d.kw} s{d.sh} "
+                                                   f"p{d.ph},{d.pw} flags={flags}")
+    return found
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--summary", action="store_true", help="no-option decisions at 96 frames and at the small geometry, one line per descriptor")
     ap.add_argument("--names", action="store_true", help="every distinct kernel instantiation of the no-option decisions, with one launch that reaches it")
     ap.add_argument("--wgrad", action="store_true", help="the weight-gradient part only (with --names: the weight-gradient kernel names)")
+    ap.add_argument("--multi", action="store_true", help="with --names: the kernels of din_conv_fwd2 / din_conv1x1_dgrad_multi / din_conv_dgrad_x")
     args = ap.parse_args()
+    if args.multi and not args.names:
+        ap.error("--multi selects which names --names prints: use --names --multi")
     from din_amd import _lib as L, nhwc
     lib = L.load()
     for name, _ in OPTIONS + WGRAD_OPTIONS:
         L.set_option(name, None)
+    if args.names and args.multi:
+        for (entry, name), label in sorted(multi_names_table(L, lib, nhwc).items()):
+            print(f"{entry} {name}  <-  {label}")
+        return
     cases, groups = [], []
     for backbone in ("inv3", "vgg16"):
         for dt, dtn in ((L.DIN_BF16, "bf16"), (L.DIN_F32, "fp32")):
