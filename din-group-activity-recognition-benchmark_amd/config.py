@@ -4,8 +4,10 @@ Extra fields: backbone_dtype ('fp32' | 'bf16' | 'fp32_bf16x3': fp32 storage and 
 multiplied as three bf16 parts per operand on the bf16 matrix pipe -- DIN_F32_BF16X3, include/din_hip.h); hier_dropout_p (the reference hard-codes F.dropout's defaults -- p = 0.5, always on --
 at dynamic_infer_module.py:495; 0.5 keeps that, 0.0 switches it off); frame_cache_gb (> 0: decoded uint8 frames of the real dataset tree
 stay in HBM, up to that many GB per dataset, and batches are gathered from them -- din_amd/frame_cache.py; 0 = off) and num_workers (the
-DataLoader worker processes of both trainers; the reference hard-codes 4, train_net_dynamic.py:40-48; 0 = decode in the main process).
-Both are opt-in: at 0 the trainers behave exactly as without them."""
+DataLoader worker processes of both trainers; the reference hard-codes 4, train_net_dynamic.py:40-48; 0 = decode in the main process);
+feature_cache_gb (> 0, stage-2 trainer with a frozen backbone only: the fp32 RoIAlign output of every frame stays in HBM, up to that many
+GB per dataset, and a step skips the backbone for resident frames -- din_amd/feature_cache.py; 0 = off).
+All are opt-in: at 0 the trainers behave exactly as without them."""
 from __future__ import annotations
 
 import os
@@ -26,7 +28,7 @@ _DEFAULTS = dict(
     load_backbone_stage2=False, parallel_inference=False, hierarchical_inference=False, lite_dim=None, num_DIM=1,
     load_stage2model=False, stage2model=None, temporal_pooled_first=False,
     backbone_dtype="fp32", hier_dropout_p=0.5,
-    frame_cache_gb=0, num_workers=0,
+    frame_cache_gb=0, num_workers=0, feature_cache_gb=0,
 )
 
 

@@ -1,0 +1,241 @@
+"""Box-feature cache: with a frozen backbone the trunk's output for a frame stays in HBM, and a step skips the trunk for it.
+
+`Config` defaults to train_backbone=False and the ARG launcher trains that way; the backbone forward and RoIAlign (reference
+infer_model.py:152-184) are then nearly the whole step and do the same work on the same frames every epoch: the volleyball dataset has
+no augmentation and a frame's boxes come from the track file, so the fp32 row [N, D, K, K] RoIAlign emits for a frame never changes.
+At the launchers' sizes that row is 614 400 bytes for VGG16 (12 x 512 x 25 x 4) and 1 267 200 bytes for Inception-v3 (D = 1056); the
+48 300 frames of the whole set are 29.7 GB / 61.2 GB, and an MI355X has 288 GB.  From the second epoch on a step is: gather rows,
+fc_emb_1, the head -- nothing decoded, nothing uploaded, no backbone launch.
+
+  * datasets built with `frame_ids=True` and `frame_cache.collate` are the frame cache's (frame_cache.py): a frame whose `resident`
+    flag is set is not decoded;
+  * `FeatureFeed` uploads only the decoded frames (input_feed.DeviceFeed) and hands the model a `FrameRefs` in place of the images
+    tensor: frame ids, the decoded frames, which rows of the batch they are, and the cache;
+  * `infer_model.embed_boxes` runs the trunk on those frames only and calls `FeatureCache.rows`: ONE din_feat_rows launch that builds
+    feats [B*T, N*D*K*K], stores the new rows in free slots together with their boxes (the slot's trailer), and compares the boxes of
+    every row served from a slot with the ones stored there;
+  * the feed then marks `dataset.resident` for what went in, and the pass ends with `check()`: one synchronisation, RuntimeError if a
+    served row was computed for other boxes than the step's.
+
+Same store as the frame cache (frame_cache.SlotStore): lazy slabs, no eviction, a full cache stops inserting and the remaining frames
+keep being decoded and computed.  Refusals and the cache's lifetime: train_net_dynamic.train_net.
+"""
+from __future__ import annotations
+
+import collections
+from typing import Iterable, Iterator, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .frame_cache import CachedLoader, SlotStore
+from .input_feed import DeviceFeed
+
+
+class FeatureCache(SlotStore):
+    """Device-resident store of fp32 box-feature rows: each slot holds `row_bytes` of features followed by the `box_bytes` of the boxes
+    they were computed for.  Filled on first use, never beyond `capacity_bytes`, no eviction."""
+
+    WHAT, UNIT = "feature cache", "frames"
+    FLAG_ROWS = 1 << 20                              # rows between two check() calls the flags buffer holds without an extra check
+
+    def __init__(self, device, row_bytes: int, box_bytes: int, capacity_bytes: int, chunk_frames: int = 64):
+        if row_bytes <= 0 or box_bytes <= 0 or row_bytes % 16 or box_bytes % 16:
+            raise ValueError(f"FeatureCache: row_bytes {row_bytes} and box_bytes {box_bytes} must be positive multiples of 16")
+        self.row_bytes, self.box_bytes = int(row_bytes), int(box_bytes)
+        super().__init__(device, self.row_bytes + self.box_bytes, capacity_bytes, chunk_frames)
+        self.flags: Optional[torch.Tensor] = None    # one uint8 per row gathered since the last check(); din_feat_rows only ever writes 1
+        self._flagged: List[np.ndarray] = []         # the frame ids of those rows, in order
+        self._used = 0
+
+    def _flag_rows(self, ids: np.ndarray) -> torch.Tensor:
+        if self.flags is None:
+            self.flags = torch.zeros(max(self.FLAG_ROWS, len(ids)), dtype=torch.uint8, device=self.device)
+        if self._used + len(ids) > self.flags.numel():
+            self.check()
+            if len(ids) > self.flags.numel():
+                self.flags = torch.zeros(len(ids), dtype=torch.uint8, device=self.device)
+        view = self.flags[self._used:self._used + len(ids)]
+        self._flagged.append(ids)
+        self._used += len(ids)
+        return view
+
+    def rows(self, frame_ids, boxes: torch.Tensor, miss_pos=(), miss_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[int]]:
+        """frame_ids [R] (host), boxes fp32 [R, box_bytes / 4] on the device (this step's boxes of every row), miss_pos [M] (host: which
+        of the R rows the computed rows are), miss_rows fp32 [M, row_bytes / 4] on the device -> (fp32 [R, row_bytes / 4] on the device,
+        the frame ids inserted by this call).  One launch on the current stream: a row comes from its slot (and its boxes are compared
+        with the slot's) or from the computed row, which also goes into a free slot with its boxes while the cache has room.  A frame
+        that occurs twice is served both times from the computed row, never from the slot written by this launch."""
+        from . import ops
+        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
+        rb, bb = self.row_bytes, self.box_bytes
+        if not boxes.is_cuda or boxes.dtype != torch.float32 or boxes.numel() * 4 != len(ids) * bb:
+            raise ValueError(f"rows: {len(ids)} rows need fp32 device boxes of {bb} bytes each, got {tuple(boxes.shape)} {boxes.dtype}")
+        boxes = boxes.contiguous()
+        if boxes.data_ptr() % 16:
+            boxes = boxes.clone()
+        if len(pos):
+            if miss_rows is None or not miss_rows.is_cuda or miss_rows.dtype != torch.float32 or not miss_rows.is_contiguous() \
+                    or tuple(miss_rows.shape) != (len(pos), rb // 4) or miss_rows.data_ptr() % 16:
+                raise ValueError(f"rows: {len(pos)} computed rows need a contiguous, 16-byte aligned fp32 device tensor "
+                                 f"{(len(pos), rb // 4)}, got {None if miss_rows is None else tuple(miss_rows.shape)}")
+            if pos.min() < 0 or pos.max() >= len(ids):
+                raise ValueError("rows: miss_pos outside the batch")
+        row_of = {}                                  # frame id -> address of its computed row (the first one serves all)
+        for j, p in enumerate(pos):
+            row_of.setdefault(int(ids[p]), miss_rows.data_ptr() + j * rb)
+        out = torch.empty((len(ids), rb // 4), dtype=torch.float32, device=self.device)
+        out_ptr = out.data_ptr()
+        src, keep, ref, new_ids, fresh = [], [], [], [], set()
+        for fid in ids:
+            fid = int(fid)
+            slot = -1 if fid in fresh else self.table.lookup(fid)
+            if slot >= 0:                            # resident before this launch: served from the slot, boxes compared
+                src.append(self.slot_address(slot))
+                keep.append(0)
+                ref.append(src[-1] + rb)
+                continue
+            if fid not in row_of:
+                raise KeyError(f"frame {fid} is neither resident nor among the computed rows of this batch")
+            slot = -1 if fid in fresh else self.table.insert(fid, self._grow)
+            if slot >= 0:
+                fresh.add(fid)
+                new_ids.append(fid)
+            src.append(row_of[fid])
+            keep.append(self.slot_address(slot) if slot >= 0 else 0)
+            ref.append(0)
+        dst = [out_ptr + i * rb for i in range(len(ids))]
+        flags = self._flag_rows(ids)
+        d_src, d_dst, d_keep, d_ref = self._upload(src, dst, keep, ref)
+        ops.feat_rows(d_src, d_dst, rb, d_keep, d_ref, boxes, flags, bb)
+        return out, new_ids
+
+    def check(self) -> None:
+        """end of a pass: synchronise once, read the flags of every row gathered since the last check, clear them; RuntimeError naming
+        the frames whose boxes differ from the ones stored with their features"""
+        if self.flags is None or self._used == 0:
+            return
+        got = self.flags[:self._used].cpu().numpy()                  # (the copy synchronises)
+        ids = np.concatenate(self._flagged)
+        self.flags[:self._used].zero_()
+        self._flagged, self._used = [], 0
+        bad = np.flatnonzero(got)
+        if bad.size:
+            raise RuntimeError(f"feature cache: {bad.size} rows were served for other boxes than the ones stored with their features "
+                               f"(row, frame id): {[(int(r), int(ids[r])) for r in bad[:16]]}{' ...' if bad.size > 16 else ''}")
+
+
+class FrameRefs:
+    """what a model receives in place of the images tensor when box features are cached: the frame ids of the batch [B, T] (host), the
+    frames that were decoded (uint8 [M, 3, H, W] on the device), which of the B*T rows they are (`miss_pos`, host; `miss_pos_dev` the
+    same on the device when the feed uploaded it), and the cache.  `shape` and `reshape` of the two leading dimensions are all the
+    models and trainers use of an images tensor besides handing it to infer_model.embed_boxes, which sets `inserted`."""
+
+    def __init__(self, frame_ids, miss_images: torch.Tensor, miss_pos, cache: FeatureCache, miss_pos_dev: Optional[torch.Tensor] = None):
+        self.frame_ids = np.asarray(frame_ids, dtype=np.int64)
+        if self.frame_ids.ndim != 2:
+            raise ValueError(f"FrameRefs: frame_ids is [B, T], got shape {self.frame_ids.shape}")
+        if miss_images.dim() != 4 or miss_images.shape[1] != 3:
+            raise ValueError(f"FrameRefs: miss_images is [M, 3, H, W], got {tuple(miss_images.shape)}")
+        self.miss_images, self.cache = miss_images, cache
+        self.miss_pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
+        if len(self.miss_pos) != miss_images.shape[0]:
+            raise ValueError(f"FrameRefs: {miss_images.shape[0]} decoded frames but {len(self.miss_pos)} positions")
+        self.miss_pos_dev = miss_pos_dev
+        self.inserted: List[int] = []
+
+    @property
+    def shape(self) -> Tuple[int, ...]:
+        return tuple(self.frame_ids.shape) + tuple(self.miss_images.shape[1:])
+
+    def reshape(self, *shape) -> "FrameRefs":
+        shape = tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list)) else tuple(shape)
+        if len(shape) != 5 or tuple(shape[2:]) != self.shape[2:] or shape[0] * shape[1] != self.frame_ids.size:
+            raise ValueError(f"FrameRefs.reshape: only the two leading dimensions of {self.shape} can be reshaped, got {shape}")
+        out = FrameRefs(self.frame_ids.reshape(shape[0], shape[1]), self.miss_images, self.miss_pos, self.cache, self.miss_pos_dev)
+        out.inserted = self.inserted                 # (shared: the feed reads it off the object it yielded)
+        return out
+
+
+class _HostSide:
+    """what FeatureFeed hands to DeviceFeed: the tensors to upload (decoded frames, their positions, labels), the frame ids kept back"""
+
+    def __init__(self, loader, kept: collections.deque):
+        self.loader, self.kept = loader, kept
+
+    def __iter__(self):
+        for frame_ids, miss_images, miss_pos, *labels in self.loader:
+            self.kept.append((frame_ids.numpy(), miss_pos.numpy()))
+            yield (miss_images, miss_pos, *labels)
+
+    def __len__(self):
+        return len(self.loader)
+
+
+class FeatureFeed:
+    """frame_cache.CachedFeed's contract over the same `collate`d batches: yields (FrameRefs, *labels) with the labels on the device.
+    Only the frames the workers decoded are uploaded; after the model call `dataset.resident` is marked for the frames whose features
+    went into the cache, so the loader stops decoding them."""
+
+    def __init__(self, loader: Iterable, device, cache: FeatureCache, dataset):
+        self.loader, self.device, self.cache, self.dataset = loader, torch.device(device), cache, dataset
+        self._kept: collections.deque = collections.deque()
+        self._feed = DeviceFeed(_HostSide(loader, self._kept), self.device)
+
+    def __iter__(self) -> Iterator:
+        self._kept.clear()
+        for miss_images, miss_pos_dev, *labels in self._feed:
+            ids, pos = self._kept.popleft()
+            refs = FrameRefs(ids, miss_images, pos, self.cache, miss_pos_dev)
+            yield (refs, *labels)
+            if refs.inserted:                        # (filled by embed_boxes during the model call)
+                self.dataset.resident[torch.as_tensor(refs.inserted, dtype=torch.int64)] = 1
+
+    def check(self) -> None:
+        self.cache.check()
+
+    def __len__(self):
+        return len(self.loader)
+
+
+class FeatureLoader(CachedLoader):
+    """a DataLoader of a `frame_ids=True` dataset together with the feature cache of that dataset: what the stage-2 trainer's passes
+    receive in place of the loader when cfg.feature_cache_gb > 0"""
+
+    def feed(self, device) -> FeatureFeed:
+        return FeatureFeed(self.loader, device, self.cache, self.dataset)
+
+
+def row_and_box_bytes(cfg) -> Tuple[int, int]:
+    """bytes of one frame's fp32 RoIAlign output [N, D, K, K] and of its fp32 boxes [N, 4]"""
+    K = cfg.crop_size[0]
+    return cfg.num_boxes * cfg.emb_features * K * K * 4, cfg.num_boxes * 16
+
+
+def feature_loaders(cfg, training_loader, validation_loader, training_set, validation_set, device):
+    """frame_cache.build_loaders with cfg.feature_cache_gb > 0: one FeatureCache of that many GB per dataset"""
+    capacity = int(float(cfg.feature_cache_gb) * 1e9)
+    rb, bb = row_and_box_bytes(cfg)
+    return (FeatureLoader(training_loader, FeatureCache(device, rb, bb, capacity), training_set),
+            FeatureLoader(validation_loader, FeatureCache(device, rb, bb, capacity), validation_set))
+
+
+def refusal(cfg) -> Optional[str]:
+    """why cfg.feature_cache_gb > 0 cannot be honoured, or None (train_net_dynamic.train_net raises ValueError with it)"""
+    if float(getattr(cfg, "feature_cache_gb", 0) or 0) <= 0:
+        return None
+    pre = f"feature_cache_gb = {cfg.feature_cache_gb}: "
+    if cfg.train_backbone:
+        return pre + "cached box features are the output of a FROZEN backbone; train_backbone is set"
+    if float(getattr(cfg, "frame_cache_gb", 0) or 0) > 0:
+        return pre + (f"frame_cache_gb = {cfg.frame_cache_gb} is set as well; the pixels of a frame whose features are resident are never "
+                      f"needed: choose one of the two caches")
+    if cfg.inference_module_name == "dynamic_tce_volleyball":
+        return pre + "dynamic_tce_volleyball reads the backbone's context map of every frame, which the feature cache does not keep"
+    if cfg.dataset_name == "collective":
+        return pre + "the collective dataset is not covered (volleyball only)"
+    if cfg.backbone == "inv3" and not cfg.set_bn_eval:
+        return pre + ("backbone 'inv3' without set_bn_eval normalises with batch statistics, so a frame's features depend on the batch it "
+                      "is in and cannot be cached")
+    return None

@@ -101,16 +101,16 @@ class SlotTable:
         return {"hits": self.hits, "misses": self.misses, "inserted": self.inserted, "bytes": self.bytes}
 
 
-class FrameCache:
-    """Device-resident uint8 frame store with fixed-size slots, filled on first use, never beyond `capacity_bytes`, no eviction."""
+class SlotStore:
+    """Device side of a SlotTable: the lazily allocated slabs, slot addresses and the rotating pinned buffers the address tables of a
+    launch travel in.  FrameCache (uint8 frames) and feature_cache.FeatureCache (fp32 box features) are the two stores."""
 
     TABLE_SLOTS = 4                                  # pinned address-table buffers in rotation (one batch uses one)
+    WHAT, UNIT = "frame cache", "frames"             # the words of the freeze log line
 
-    def __init__(self, device, frame_shape: Sequence[int], capacity_bytes: int, chunk_frames: int = 64):
+    def __init__(self, device, slot_bytes: int, capacity_bytes: int, chunk_frames: int = 64):
         self.device = torch.device(device)
-        self.frame_shape = tuple(int(v) for v in frame_shape)
-        self.frame_bytes = int(np.prod(self.frame_shape))
-        self.table = SlotTable(self.frame_bytes, capacity_bytes, chunk_frames)
+        self.table = SlotTable(slot_bytes, capacity_bytes, chunk_frames)
         self.slabs: List[torch.Tensor] = []
         self._pinned: List[Optional[torch.Tensor]] = [None] * self.TABLE_SLOTS
         self._sent: List[Optional[torch.cuda.Event]] = [None] * self.TABLE_SLOTS
@@ -126,13 +126,16 @@ class FrameCache:
             self.slabs.append(torch.empty(n_slots * self.table.stride, dtype=torch.uint8, device=self.device))
             return True
         except RuntimeError as e:                    # (torch.cuda.OutOfMemoryError is one)
-            log.warning("frame cache frozen at %d frames (%.2f GB): a slab of %d frames could not be allocated: %s",
-                        self.table.allocated, self.table.bytes / 1e9, n_slots, str(e).splitlines()[0])
+            log.warning("%s frozen at %d %s (%.2f GB): a slab of %d %s could not be allocated: %s", self.WHAT,
+                        self.table.allocated, self.UNIT, self.table.bytes / 1e9, n_slots, self.UNIT, str(e).splitlines()[0])
             return False
 
     def slot_address(self, slot: int) -> int:
         slab, off = self.table.locate(slot)
         return self.slabs[slab].data_ptr() + off
+
+    def resident(self, fid: int) -> bool:
+        return int(fid) in self.table.slot_of
 
     def _upload(self, *tables: Sequence[int]) -> List[torch.Tensor]:
         """int64 address tables -> device, in ONE asynchronous copy on the current stream out of a pinned buffer that is reused only after
@@ -154,6 +157,15 @@ class FrameCache:
         self._sent[k] = torch.cuda.Event()
         self._sent[k].record(torch.cuda.current_stream(self.device))
         return [dev[a:a + n] for a, n in views]
+
+
+class FrameCache(SlotStore):
+    """Device-resident uint8 frame store with fixed-size slots, filled on first use, never beyond `capacity_bytes`, no eviction."""
+
+    def __init__(self, device, frame_shape: Sequence[int], capacity_bytes: int, chunk_frames: int = 64):
+        self.frame_shape = tuple(int(v) for v in frame_shape)
+        self.frame_bytes = int(np.prod(self.frame_shape))
+        super().__init__(device, self.frame_bytes, capacity_bytes, chunk_frames)
 
     def build_batch(self, frame_ids, miss_pos=(), miss_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[int]]:
         """frame_ids [R] (host), miss_pos [M] (host: which of the R rows the uploaded frames are), miss_rows uint8 [M, *frame_shape] on
@@ -215,9 +227,6 @@ class FrameCache:
         ops.copy_rows_u8(d_src, d_dst, fb)
         rows.record_stream(torch.cuda.current_stream(self.device))
         return [int(f) for f in ids if int(f) in self.table.slot_of]
-
-    def resident(self, fid: int) -> bool:
-        return int(fid) in self.table.slot_of
 
     def gather(self, frame_ids) -> torch.Tensor:
         """uint8 [R, *frame_shape] of resident frames (KeyError for one that is not)"""
@@ -296,15 +305,28 @@ def feed_for(loader, device):
     return loader.feed(device) if isinstance(loader, CachedLoader) else DeviceFeed(loader, device)
 
 
+def end_pass(feed) -> None:
+    """what a trainer's pass calls after its last batch: the feature cache's box check (feature_cache.FeatureFeed.check); the other
+    feeds have nothing to check"""
+    check = getattr(feed, "check", None)
+    if check is not None:
+        check()
+
+
+def wants_features(cfg) -> bool:
+    return float(getattr(cfg, "feature_cache_gb", 0) or 0) > 0
+
+
 def wants_frame_ids(cfg) -> bool:
-    return float(getattr(cfg, "frame_cache_gb", 0) or 0) > 0
+    return float(getattr(cfg, "frame_cache_gb", 0) or 0) > 0 or wants_features(cfg)
 
 
 def build_loaders(cfg, training_set, validation_set, per_rank: int, sampler, device, real_tree: bool):
     """the two DataLoaders of train_net / train_net_dynamic.  With cfg.num_workers = 0 and cfg.frame_cache_gb = 0 (the defaults), or
     without the real dataset tree, exactly the loaders the trainers always built.  Otherwise cfg.num_workers worker processes per loader
     (the platform's default start method; they decode and never touch the GPU; a stuck worker raises after LOADER_TIMEOUT_S), and, when
-    the datasets carry frame ids, one FrameCache of cfg.frame_cache_gb per dataset behind a CachedLoader."""
+    the datasets carry frame ids, one FrameCache of cfg.frame_cache_gb per dataset behind a CachedLoader -- or, with cfg.feature_cache_gb > 0
+    (train_net_dynamic only, frozen backbone), one feature_cache.FeatureCache of that many GB per dataset behind a FeatureLoader."""
     workers = int(getattr(cfg, "num_workers", 0) or 0) if real_tree else 0
     extra = dict(num_workers=workers, timeout=LOADER_TIMEOUT_S) if workers > 0 else dict(num_workers=0)
     cached = real_tree and wants_frame_ids(cfg) and getattr(training_set, "frame_ids", False) and getattr(validation_set, "frame_ids", False)
@@ -314,6 +336,9 @@ def build_loaders(cfg, training_set, validation_set, per_rank: int, sampler, dev
     validation_loader = data.DataLoader(validation_set, batch_size=cfg.test_batch_size, shuffle=False, **extra)
     if not cached:
         return training_loader, validation_loader
+    if wants_features(cfg):
+        from .feature_cache import feature_loaders
+        return feature_loaders(cfg, training_loader, validation_loader, training_set, validation_set, device)
     capacity = int(float(cfg.frame_cache_gb) * 1e9)
     frame_shape = (3,) + tuple(cfg.image_size)
     return (CachedLoader(training_loader, FrameCache(device, frame_shape, capacity), training_set),

@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import ops
 from .backbone.backbone import MyInception_v3, MyVGG16
+from .feature_cache import FrameRefs
 from .infer_module.ARG_infer_module import GCN_Module
 from .infer_module.AT_infer_module import Actor_Transformer, Embfeature_PositionEmbedding
 from .infer_module.dynamic_infer_module import (Dynamic_Person_Inference, Hierarchical_Dynamic_Inference,
@@ -60,12 +61,24 @@ def embed_boxes(model, images_in, boxes_in, N, fc):
     .roi_align.  No activation: the callers apply their own (LayerNorm + ReLU in stage 2, ReLU + dropout in the stage-1 head)."""
     cfg = model.cfg
     B, T = images_in.shape[0], images_in.shape[1]
+    bdt = getattr(cfg, "backbone_dtype", "fp32")
+    if isinstance(images_in, FrameRefs):
+        feats = _cached_crops(model, images_in, boxes_in, N).reshape(B, T, N, -1)
+        return ops.linear(feats, fc.weight, fc.bias, lowp=bdt == "bf16", split=bdt == "fp32_bf16x3"), None, None, None
     H, W = cfg.image_size
+    crops, bufs, views, graph = _crops(model, images_in.reshape(B * T, 3, H, W), boxes_in.reshape(B * T * N, 4), N)
+    feats = crops.reshape(B, T, N, -1)
+    y = ops.linear(feats, fc.weight, fc.bias, lowp=bdt == "bf16", split=bdt == "fp32_bf16x3")                    # :184
+    return y, bufs, views, graph
+
+
+def _crops(model, images_flat, boxes_flat, N):
+    """images [F,3,H,W], boxes [F*N,4] -> (RoIAlign(backbone(images)) fp32 [F*N, D, K, K], bufs, views, graph): infer_model.py:155-180"""
+    cfg = model.cfg
+    F = images_flat.shape[0]
     OH, OW = cfg.out_size
-    D, K = cfg.emb_features, cfg.crop_size[0]
-    images_flat = images_in.reshape(B * T, 3, H, W)
-    boxes_flat = boxes_in.reshape(B * T * N, 4)
-    boxes_idx = ops.boxes_frame_index(B * T, N, boxes_in.device)                  # infer_model.py:155-157
+    D = cfg.emb_features
+    boxes_idx = ops.boxes_frame_index(F, N, boxes_flat.device)                   # infer_model.py:155-157
     bufs, graph = model.backbone.forward_nhwc(images_flat)                       # prep fused (:161-162)
     fm = bufs[0]
     assert tuple(fm.shape[1:3]) == (OH, OW), f"backbone output {tuple(fm.shape[1:3])} != cfg.out_size {(OH, OW)}"   # (:164)
@@ -73,17 +86,39 @@ def embed_boxes(model, images_in, boxes_in, N, fc):
     if fm.shape[3] >= D:                                                         # one map holds all D channels (VGG; materialised fuse)
         tid = graph.output_tids[0]
         crops = model.roi_align(fm, boxes_flat, boxes_idx, nhwc=True, channels=D,
-                                relu_masked=graph.tensors[tid].relu_masked)      # [BTN, D, K, K]  (:178-180)
+                                relu_masked=graph.tensors[tid].relu_masked)      # [FN, D, K, K]  (:178-180)
     else:
         # multi-scale fuse + RoIAlign in one step (:165-180): every backbone output is sampled through its virtual align_corners
         # resize to (OH, OW); the resized / concatenated map is never built, forward or backward
         assert sum(c for _, _, c in views) == D, f"backbone outputs hold {sum(c for _, _, c in views)} channels, cfg.emb_features = {D}"
         maps = [(b, c, graph.tensors[tid].relu_masked) for b, (tid, _coff, c) in zip(bufs, views)]
         crops = model.roi_align.forward_multiscale(maps, boxes_flat, boxes_idx, (OH, OW))
-    feats = crops.reshape(B, T, N, D * K * K)
-    bdt = getattr(cfg, "backbone_dtype", "fp32")
-    y = ops.linear(feats, fc.weight, fc.bias, lowp=bdt == "bf16", split=bdt == "fp32_bf16x3")                    # :184
-    return y, bufs, views, graph
+    return crops, bufs, views, graph
+
+
+def _cached_crops(model, refs, boxes_in, N):
+    """the trunk behind the box-feature cache (feature_cache.py): the backbone and RoIAlign run, without autograd, on the M frames of
+    `refs` that were decoded -- no launch when M == 0 -- and one din_feat_rows launch builds fp32 [B*T, N*D*K*K] from those rows and the
+    cache's slots, stores the new rows with their boxes and checks the boxes of the rows served from slots"""
+    cfg = model.cfg
+    if cfg.train_backbone:
+        raise ValueError("cached box features (cfg.feature_cache_gb) are the output of a frozen backbone; this model trains its backbone")
+    B, T = refs.shape[0], refs.shape[1]
+    H, W = cfg.image_size
+    D, K = cfg.emb_features, cfg.crop_size[0]
+    boxes = boxes_in.reshape(B * T, N * 4)
+    if boxes.dtype != torch.float32:
+        boxes = boxes.float()
+    M = refs.miss_images.shape[0]
+    rows = None
+    if M:
+        pos = refs.miss_pos_dev if refs.miss_pos_dev is not None else torch.from_numpy(refs.miss_pos).to(boxes.device)
+        with torch.no_grad():
+            crops = _crops(model, refs.miss_images.reshape(M, 3, H, W), boxes.index_select(0, pos).reshape(M * N, 4), N)[0]
+        rows = crops.reshape(M, N * D * K * K).contiguous()
+    feats, new_ids = refs.cache.rows(refs.frame_ids, boxes, refs.miss_pos, rows)
+    refs.inserted.extend(new_ids)
+    return feats
 
 
 class _DynamicBase(nn.Module):

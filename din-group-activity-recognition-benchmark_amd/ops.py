@@ -963,3 +963,31 @@ def copy_rows_u8(src: torch.Tensor, dst: torch.Tensor, nbytes: int, n: Optional[
     if n > min(src.numel(), dst.numel()):
         raise L.DinError(f"copy_rows_u8: n = {n} rows but the tables hold {src.numel()} / {dst.numel()} addresses")
     L.check(lib.din_copy_rows_u8(_ptr(src), _ptr(dst), n, nbytes, _stream()), "copy_rows_u8")
+
+
+FEAT_ROWS_SEGMENT = 16384        # DIN_FEAT_ROWS_SEGMENT (include/din_hip.h): bytes of one row per work item of din_feat_rows
+
+
+def feat_rows(src: torch.Tensor, dst: torch.Tensor, row_bytes: int, keep: Optional[torch.Tensor] = None,
+              ref_boxes: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None,
+              box_bytes: int = 0, n: Optional[int] = None) -> None:
+    """row i: `row_bytes` bytes from device address src[i] to dst[i] and, where keep[i] != 0, to keep[i] too, followed there by row i of
+    `boxes` (`box_bytes` bytes); where ref_boxes[i] != 0, row i of `boxes` is compared with the bytes at that address and flags[i] = 1 is
+    written on a difference.  One launch on the current stream; src[i] == 0 leaves row i alone.  src, dst, keep, ref_boxes: int64 device
+    tables; boxes: a contiguous device tensor of n rows of box_bytes bytes; flags: uint8 on the device, one per row (din_feat_rows: the
+    feature cache's gather + insert + box check).  Every address and both sizes are multiples of 16."""
+    lib = L.load()
+    tables = [t for t in (src, dst, keep, ref_boxes) if t is not None]
+    require_gpu(*tables, boxes, flags)
+    if any(t.dtype != torch.int64 for t in tables):
+        raise L.DinError("feat_rows: address tables are int64 device tensors")
+    rows = min(t.numel() for t in tables)
+    n = rows if n is None else n
+    if n > rows:
+        raise L.DinError(f"feat_rows: n = {n} rows but the tables hold {[t.numel() for t in tables]} addresses")
+    if boxes is not None and (not boxes.is_contiguous() or boxes.numel() * boxes.element_size() < n * box_bytes):
+        raise L.DinError(f"feat_rows: boxes must be contiguous and hold n * box_bytes = {n * box_bytes} bytes")
+    if flags is not None and (flags.dtype != torch.uint8 or not flags.is_contiguous() or flags.numel() < n):
+        raise L.DinError(f"feat_rows: flags is a contiguous uint8 tensor of at least n = {n} entries")
+    L.check(lib.din_feat_rows(_ptr(src), _ptr(dst), _ptr(keep), _ptr(ref_boxes), _ptr(boxes), _ptr(flags), n, row_bytes, box_bytes,
+                              _stream()), "feat_rows")

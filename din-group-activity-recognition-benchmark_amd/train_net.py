@@ -19,6 +19,7 @@ Deliberate differences from the reference:
 """
 from __future__ import annotations
 
+import copy
 import os
 import random
 
@@ -175,9 +176,11 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     collective = cfg.dataset_name == "collective"
     synth = SyntheticCollective if collective else SyntheticVolleyball
     real_tree = False
+    lcfg = copy.copy(cfg)
+    lcfg.feature_cache_gb = 0                                          # stage 1 trains the backbone: the box-feature cache is stage 2's
     if training_set is None and validation_set is None and getattr(cfg, "data_path", None) and os.path.isdir(cfg.data_path):
         from .dataset import return_dataset                           # stage-1 frame sampling (is_finetune) follows cfg.training_stage
-        training_set, validation_set = return_dataset(cfg, frame_ids=frame_cache.wants_frame_ids(cfg))
+        training_set, validation_set = return_dataset(cfg, frame_ids=frame_cache.wants_frame_ids(lcfg))
         real_tree = True
     training_set = training_set or synth(cfg, length=max(cfg.batch_size * 2, 4))
     validation_set = validation_set or synth(cfg, length=max(cfg.test_batch_size, 2), seed=1)
@@ -187,7 +190,7 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     sampler = data.distributed.DistributedSampler(training_set, world, rank, shuffle=True) if world > 1 else None
     # cfg.num_workers / cfg.frame_cache_gb (both 0 by default: the loaders below are then the plain num_workers=0 DataLoaders) apply to
     # the real dataset tree only: worker processes decode, and decoded frames stay in HBM from their first use on (frame_cache.py)
-    training_loader, validation_loader = frame_cache.build_loaders(cfg, training_set, validation_set, per_rank, sampler, device, real_tree)
+    training_loader, validation_loader = frame_cache.build_loaders(lcfg, training_set, validation_set, per_rank, sampler, device, real_tree)
     log_path = getattr(cfg, "log_path", None)
     model = model.to(device)
     parallel.broadcast_parameters(model)

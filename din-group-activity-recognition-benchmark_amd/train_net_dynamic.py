@@ -27,7 +27,7 @@ import torch.nn.functional as F
 import torch.utils.data as data
 
 from . import parallel
-from . import frame_cache
+from . import feature_cache, frame_cache
 from .input_feed import DeviceFeed  # noqa: F401  (re-exported: `from train_net import *` launchers)
 from .infer_model import (ARG_volleyball, AT_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, Dynamic_volleyball,
                           PCTDM_volleyball)
@@ -124,7 +124,8 @@ class _Epoch:
 
 def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets, collective, max_batches=None):
     meters = _Epoch(cfg, device)
-    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device)):      # batch k+1 crosses PCIe on the copy stream during step k
+    feed = frame_cache.feed_for(data_loader, device)
+    for bi, batch_data in enumerate(feed):                             # batch k+1 crosses PCIe on the copy stream during step k
         if max_batches is not None and bi >= max_batches:
             break
         model.train()
@@ -144,19 +145,22 @@ def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets,
         else:
             optimizer.step()
         meters.add(activities_scores.detach(), activities_in, total_loss)
+    frame_cache.end_pass(feed)                                         # (the feature cache's box check; nothing for the other feeds)
     return meters.info(epoch)
 
 
 def _test_pass(data_loader, model, device, epoch, cfg, collective):
     model.eval()
     meters = _Epoch(cfg, device)
+    feed = frame_cache.feed_for(data_loader, device)
     with torch.no_grad():
-        for batch_data in frame_cache.feed_for(data_loader, device):
+        for batch_data in feed:
             batch_size, num_frames = batch_data[0].shape[0], batch_data[0].shape[1]
             activities_in = batch_data[3].reshape((batch_size, num_frames))[:, 0].reshape((batch_size,))
             inputs = (batch_data[0], batch_data[1], batch_data[4]) if collective else (batch_data[0], batch_data[1])
             scores = model(inputs)["activities"]
             meters.add(scores, activities_in, F.cross_entropy(scores, activities_in))
+    frame_cache.end_pass(feed)
     return meters.info(epoch)
 
 
@@ -195,6 +199,9 @@ def _mask_counters(model):
 def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     """Reference train_net (:27-157).  Launch one process per GPU with torchrun; a single process works too.  max_steps bounds the number
     of epochs (smoke runs)."""
+    why_not = feature_cache.refusal(cfg)                               # cfg.feature_cache_gb > 0 where cached features would be wrong
+    if why_not:
+        raise ValueError(why_not)
     rank, local_rank, world = parallel.init_from_env()
     np.random.seed(cfg.train_random_seed)
     torch.manual_seed(cfg.train_random_seed)
@@ -223,7 +230,8 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     per_rank = cfg.batch_size // world
     sampler = data.distributed.DistributedSampler(training_set, world, rank, shuffle=True) if world > 1 else None
     # cfg.num_workers / cfg.frame_cache_gb (both 0 by default: the loaders below are then the plain num_workers=0 DataLoaders) apply to
-    # the real dataset tree only: worker processes decode, and decoded frames stay in HBM from their first use on (frame_cache.py)
+    # the real dataset tree only: worker processes decode, and decoded frames stay in HBM from their first use on (frame_cache.py); with
+    # cfg.feature_cache_gb > 0 the frozen trunk's box features stay there instead (feature_cache.py).  The caches live for this call.
     training_loader, validation_loader = frame_cache.build_loaders(cfg, training_set, validation_set, per_rank, sampler, device, real_tree)
     log_path = getattr(cfg, "log_path", None)
     if cfg.training_stage != 2:

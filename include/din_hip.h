@@ -657,6 +657,28 @@ int din_adam_step_multi(const uint64_t* ptrs, const int64_t* sizes, const int32_
  * ---------------------------------------------------------------------------------------------- */
 int din_copy_rows_u8(const uint64_t* src, const uint64_t* dst, int n, int64_t bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Box-feature cache: the one launch of a frozen-backbone step (din_amd/feature_cache.py).  The trunk of the reference
+ * (infer_model.py:152-184: backbone, multi-scale fuse, RoIAlign) is, with a frozen backbone, a pure function of a frame and its boxes;
+ * its fp32 output row stays in an HBM slot and this launch lets a step skip the trunk for every frame that has one.
+ * src, dst, keep, ref_boxes: DEVICE arrays of n device addresses (keep and ref_boxes may be null: all zero).  Row i:
+ *   src[i] == 0        the row is left alone: nothing is written, flags[i] is untouched;
+ *   otherwise          row_bytes bytes go from src[i] to dst[i];
+ *   keep[i] != 0       the same bytes (the source is read once) are also written to keep[i], and the box_bytes bytes at
+ *                      boxes + i * box_bytes to keep[i] + row_bytes -- the slot's trailer: the boxes the features were computed for;
+ *   ref_boxes[i] != 0  the box_bytes bytes there are compared bytewise with boxes + i * box_bytes; on any difference flags[i] = 1 is
+ *                      written with a plain store.  0 is never written: the caller clears flags at the start of a pass.
+ * Every address in the tables, boxes, row_bytes and box_bytes are multiples of 16 (all traffic is 16-byte vectors); a row holding an
+ * address that is not, or a zero dst[i], is left alone like a row with src[i] == 0.  Sources may repeat; destinations and slots must not
+ * overlap each other, any source, or any ref_boxes row of the same launch.  One plain launch over (row, segment) items of
+ * DIN_FEAT_ROWS_SEGMENT bytes on `stream`: no allocation, no synchronisation, no atomics, capturable.  n == 0 returns DIN_OK without a
+ * launch.  DIN_E_ARG before any launch: n, row_bytes or box_bytes negative; row_bytes, box_bytes or `boxes` not a multiple of 16; a null
+ * src or dst with n > 0; a null boxes or flags with a non-null keep or ref_boxes.  Additive: the ABI version stays 9.
+ * ---------------------------------------------------------------------------------------------- */
+#define DIN_FEAT_ROWS_SEGMENT 16384
+int din_feat_rows(const uint64_t* src, const uint64_t* dst, const uint64_t* keep, const uint64_t* ref_boxes,
+                  const void* boxes, uint8_t* flags, int n, int64_t row_bytes, int box_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
