@@ -181,7 +181,8 @@ def header_symbols() -> List[str]:
 
 def build(verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into the in-tree libdin_hip.so (hipcc cross-compiles w/o a GPU)."""
-    cmd = ["make", "-C", CSRC_DIR, "-j", str(os.cpu_count() or 4)]
+    # (at most 16 jobs: on a shared host os.cpu_count() is the whole machine's, many times what one build may use)
+    cmd = ["make", "-C", CSRC_DIR, "-j", str(min(os.cpu_count() or 4, 16))]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or res.returncode != 0:
         print(res.stdout)

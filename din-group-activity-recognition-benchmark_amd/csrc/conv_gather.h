@@ -1,5 +1,6 @@
-// Shared between conv_igemm.hip and conv_gather_pipe.hip: the forward / dgrad kernel argument block and the second half of the staged
-// epilogue (LDS tile -> 16-byte coalesced NHWC stores with the fused ReLU-backward mask / accumulate / second destination).
+// Shared between the forward / data-gradient sources (conv_igemm.hip and the kernel families that live apart from it): the kernel argument
+// block, the host interface of every such family (eligibility or plan, launcher, namer), and the second half of the staged epilogue (LDS
+// tile -> 16-byte coalesced NHWC stores with the fused ReLU-backward mask / accumulate / second destination).
 #pragma once
 // Timing knock-outs (DIN_GATHER_KNOCK: drop the pixel fetches / filter fetches / MFMAs of the gather kernels -- results are WRONG) and the
 // other experiment switches of rounds 2-3 (DIN_CONV_W16, DIN_CONV_RING) exist only in builds made with -DDIN_EXPERIMENTS
@@ -11,6 +12,7 @@
 #define DIN_KNOCK(flags, bit) false
 #endif
 #include "din_common.h"
+#include <string>
 
 typedef uint32_t din_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -60,6 +62,26 @@ bool conv1x1_regw_eligible(const ConvK& k, int dtype);
 int launch_conv1x1_regw(const ConvK& k, hipStream_t st);
 struct RegwInst { int nks, ns, occ, rt; bool masked; };            // conv1x1_regw_kernel<NKS, MASKED, NS, OCC, RT>
 RegwInst conv1x1_regw_inst(const ConvK& k);
+// eligibility rules several bf16 families share: the ReLU-mask view in whole 16-byte chunks (stem, gather-pipe), and one image of the input,
+// output and mask views below 2 GiB (halo, stem: one image per buffer resource)
+inline bool mask_views_aligned8(const ConvK& k) { return !(k.flags & DIN_CONV_MASK) || (k.ldm % 8 == 0 && k.moff % 8 == 0); }
+inline bool views_below_2g(const ConvK& k) {
+    return (long long)k.H * k.W * k.ldi * 2 < 0x7fffffffll && (long long)k.OH * k.OW * k.ldo * 2 < 0x7fffffffll &&
+           (long long)k.OH * k.OW * (k.ldm > 0 ? k.ldm : 1) * 2 < 0x7fffffffll;
+}
+// host entries of conv_halo.hip: halo tiles + filter-slab ring for the mid-network 3x3 / 1x7 / 7x1 layers.  hp.bn is the filter-tile width.
+// The launcher and the namer walk DIN_CONV_HALO_TABLE: a plan without a row there is DIN_E_ARG from both.
+struct HaloPlan { int bn, th, tw, nsw, nwv, n_co_tiles; size_t lds; };             // conv_halo_kernel<bn, kh, kw, th, tw, nsw, nwv>
+bool plan_halo(int dtype, int kh, int kw, int cred, int cprod, int oh, int ow, int64_t M, HaloPlan& hp);
+int launch_conv_halo(const ConvK& k, const HaloPlan& hp, hipStream_t st);
+int append_conv_halo_name(const ConvK& k, const HaloPlan& hp, std::string& out);
+// host entries of conv_small.hip: stationary filters + halo tiles for the stem layers.  conv_small_variant reads the plan fields of k.
+// The launcher and the namer walk DIN_CONV_SMALL_TABLE: a variant without a row there is DIN_E_ARG from both.
+// conv_small_kernel<cpt, bn, nbuf, 3, 3, image ? 2 : 1, u8, waves, epi> with its dynamic LDS and persistent grid
+struct SmallVariant { int cpt, bn, nbuf, waves; bool epi, image, u8; size_t lds; int grid; };
+bool conv_small_variant(const ConvK& k, int dtype, SmallVariant& s);
+int launch_conv_small(const ConvK& k, const SmallVariant& s, hipStream_t st);
+int append_conv_small_name(const SmallVariant& s, std::string& out);
 
 __device__ __forceinline__ int64_t out_pixel(const ConvK& p, int m) {
     if (p.out_sy == 0) return m;

@@ -1,4 +1,10 @@
 // Implicit-GEMM convolution for gfx950 (MI355X): fwd / dgrad share one gather kernel; the weight gradient lives in conv_wgrad.hip.
+// This file holds the tile kernel (conv_gather_fast_kernel) with its epilogues, the generic kernel, the split-K finish, the host planning
+// (plan_gather, choose_tile, choose_gather: the ONE place a forward / data-gradient launch is given its kernel), launch_choice / run_gather,
+// the name reporters and the conv entry points.  The other kernel families sit behind conv_gather.h in files of their own:
+// conv_regw.hip, conv_stream.hip, conv_halo.hip, conv_small.hip, conv_gather_pipe.hip; filter packing and the BatchNorm folds: conv_pack.hip.
+// Every family keeps ONE X-macro table of its instantiations (here: DIN_CONV_TILE_TABLE, DIN_CONV_GENERIC_TABLE) that its launcher and its
+// namer both walk, so a chosen tuple the library does not hold is an error from the launch and from the reporter alike.
 //
 //   D[co][pix] = sum_k  Wpk[co][k] * im2col(X)[pix][k]          k = (r, s, ci)   (NHWC, ci contiguous)
 //
@@ -9,8 +15,9 @@
 //   f32x3: fp32 storage, the chunk's 4 values split into three bf16 parts each, 3 x v_mfma_f32_16x16x32_bf16 (DIN_F32_BF16X3)
 // (the k order inside a k-step is permuted identically for both operands, which a sum does not care about).
 //
-// Tile: 128 pixels x BN (128|64) filters per 256-thread workgroup (4 waves as 2x2), k-step = 8 chunks
-// (128 B per row), LDS double-buffered with an XOR swizzle (chunk ^ ((row>>1)&7)) that makes both the
+// Tiles: 128 or 256 pixels x BN (64 .. 256) filters per workgroup of 4, 8 or 16 waves (wave grid WM x WN; the rows of DIN_CONV_TILE_TABLE,
+// chosen by choose_tile); the generic kernel: 128 pixels x 64 | 128 filters on 4 waves as 2x2.  k-step = 8 chunks (128 B per row; the
+// deep-ring tiles step 4), an LDS ring of 2-4 stages with an XOR swizzle (chunk ^ ((row>>1)&7)) that makes both the
 // 8-lane ds_write_b128 groups and the 16-lane ds_read_b128 groups conflict-free.  The MFMA's i index is the
 // FILTER and j the PIXEL so that a lane ends up holding 4 consecutive output channels of one pixel
 // (16-/8-byte NHWC stores).  Epilogue fuses bias, ReLU, the ReLU-backward mask, accumulation and the
@@ -44,28 +51,8 @@ namespace {
 #define DIN_GATHER_ILV 1          // in-wave interleaved schedule of the FASTK gather loop (0: the compiler-scheduled loop, for A/B builds)
 #endif
 constexpr int BM = 128;      // pixels per workgroup tile
-constexpr int KC = 8;        // 16-byte chunks per k-step (=> 128 B per tile row)
 
 __device__ __forceinline__ int lds_slot(int row, int chunk) { return row * KC + (chunk ^ ((row >> 1) & 7)); }
-
-template <typename T> struct Mma;
-template <> struct Mma<float> {
-    __device__ static void run(const u32x4& a, const u32x4& b, f32x4& c) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[j]), c, 0, 0, 0);
-    }
-};
-// fp32 chunks multiplied as three bf16 parts (conv_shared.h).  The split is formed per fragment read: inside the unrolled fragment loops of a
-// k-step the compiler forms each fragment's parts once and reuses them across the (i, j) pairs.
-template <> struct Mma<f32x3_t> {
-    __device__ static void run(const u32x4& a, const u32x4& b, f32x4& c) { mma_f32_bf16x3(a, b, c); }
-};
-template <> struct Mma<bf16_t> {
-    __device__ static void run(const u32x4& a, const u32x4& b, f32x4& c) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
 
 // ------------------------------------------------------------------------------------------------
 // fwd / dgrad gather kernels
@@ -731,607 +718,6 @@ __global__ __launch_bounds__(64 * WM * WN, (sizeof(T) == 2 && BMT == 128 && WM *
 #endif
 }
 
-template <int V> struct IcTag { static constexpr int value = V; };
-
-// ------------------------------------------------------------------------------------------------
-// Small-channel 3x3 (stem) convolution: filters stationary in LDS + input HALO tiles, persistent workgroups.
-// For layers with 32/64 reduction channels and <= 64 produced channels over millions of pixels (Inception Conv2d_2a/2b, fwd and
-// dgrad) the implicit-GEMM kernel is bound by the L2->CU operand stream: im2col pulls every input pixel kh*kw times.  Here
-//   * the whole filter bank of the launch (<= 36 KiB) is loaded into LDS once per workgroup and stays there;
-//   * per 8x32 output tile the (8+kh-1) x (32+kw-1) input halo is brought in ONCE by LDS-DMA (1.33x the unique bytes instead of 9x),
-//     out-of-image pixels as hardware zeros; all taps are formed from LDS with a swizzle that is conflict-free at every pixel
-//     offset ((hp>>1)&3 for 64-byte pixels, hp&7 for 128-byte pixels; brute-forced against the ds_read_b128 lane groups);
-//   * workgroups are persistent (grid = 2 per CU) and walk the tiles; with 64-byte pixels the next halo is in flight while the
-//     current tile is multiplied; the epilogue is staged through the just-consumed halo buffer -> 16-byte coalesced stores with the
-//     usual fused bias / ReLU / ReLU-backward mask / accumulate.
-// bf16 only; stride 1, dilation 1; the gather geometry (ay = 1, by, cy = +-1) covers forward and (stride-1) dgrad.
-// ------------------------------------------------------------------------------------------------
-// NW: waves per workgroup (4, or 8 for the two variants whose 80 KiB of LDS allow ONE workgroup per CU -- the 64-filter forward and the
-// 64-channel dgrad of Conv2d_2b: eight waves give every SIMD two waves; each wave then owns two instead of four 16-pixel segments)
-// EPI (dgrad launches: the host picks it when DIN_CONV_MASK / DIN_CONV_ACCUM is set): the epilogue's extra operands are requested at the top
-// of the tile and held in registers through the MFMA phase; without it they are fetched inside the store loop (and cost no registers --
-// compiled into the forward variants the prefetch registers slowed Conv2d_2b's forward by a third).
-template <int CPP, int BN, int NBUF, int KH, int KW, int ST, bool U8 = false, int NW = 4, bool EPI = false>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_small_kernel(ConvK p) {
-    constexpr int NTHREADS = 64 * NW;                                  // (shadows the file-level 256)
-    static_assert(!U8 || NW == 4, "the uint8 halo loader is written for four waves");
-    static_assert(!U8 || (CPP == 1 && NBUF == 2), "uint8 frames feed the image layer only");
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef bf16_t T;
-    constexpr int TH = 8, TW = 32, NPX = TH * TW;
-    constexpr int TI = BN / 16, TJ = 16 / NW, NTAPS = KH * KW;
-    // MFMA k-slices (32 channels-of-taps each): CPP >= 4: SL slices per tap; CPP == 1 (image layer, 8 padded channels per pixel):
-    // four taps share one slice, lane group g4 carries tap 4*slice + g4 (taps >= NTAPS hit zero filter chunks of the packed bank)
-    constexpr int SL = CPP >= 4 ? CPP / 4 : 1, NSL = CPP >= 4 ? NTAPS * SL : (NTAPS + 3) / 4;
-    constexpr int CPITCH = BN * 2 + 16;
-    constexpr int HWW = (TW - 1) * ST + KW, HWH = (TH - 1) * ST + KH, HPX = HWW * HWH, HC = HPX * CPP;  // halo geometry (pixels, chunks)
-    constexpr int WBYTES = NSL * BN * 4 * 16;
-    constexpr int HBYTES = (HC * 16 + 1023) / 1024 * 1024;                                // whole 1-KiB DMA slots
-    constexpr int NSLOT = HBYTES / 1024, NTR = (NSLOT + NW - 1) / NW;
-    constexpr int NPASS = HBYTES / CPITCH >= NPX ? 1 : 2;                                  // epilogue passes through the staging buffer
-    static_assert(HBYTES / CPITCH >= NPX / NPASS, "staging does not fit the halo buffer");
-    constexpr int JN = TJ / NPASS;                                                         // pixel segments per wave per pass
-    constexpr int CPR = BN / 8;                                                            // 16-byte chunks per produced pixel
-    constexpr int NST = (NPX / NPASS) * CPR / NTHREADS * NPASS;                            // store instructions per wave per tile
-    static_assert((NPX / NPASS) * CPR % NTHREADS == 0, "store loop must be uniform");
-    constexpr unsigned OOB = 0x80000000u;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    u32x4* Wl = reinterpret_cast<u32x4*>(smem_raw);
-    auto swz = [](int row) { return CPP == 1 ? 0 : CPP == 4 ? ((row >> 1) & 3) : (row & 7); };
-
-    // ---- filters: [tap][co][chunk ^ swz(co)]  (CPP == 1: [slice][co][tap & 3]) ---------------------------------------------
-    {
-        const u32x4* __restrict__ wp = reinterpret_cast<const u32x4*>(p.w);
-        if (CPP >= 4) {
-            for (int id = tid; id < NTAPS * BN * CPP; id += NTHREADS) {
-                const int row = id / CPP, slot = id - row * CPP;
-                const int tap = row / BN, co = row - tap * BN;
-                const int cc = slot ^ swz(co);
-                Wl[id] = wp[(int64_t)co * p.wld + tap * CPP + cc];
-            }
-        } else {
-            for (int id = tid; id < NSL * BN * 4; id += NTHREADS) {
-                const int row = id >> 2, g = id & 3;
-                const int sl = row / BN, co = row - sl * BN;
-                Wl[id] = wp[(int64_t)co * p.wld + sl * 4 + g];          // sl*4+g < wld: the packed row is zero beyond the last tap
-            }
-        }
-    }
-    // ---- halo DMA plan: transfer i of this wave covers chunk ids [(wid + 4 i) * 64, +64) ------------------------------------
-    int rel[NTR];                                      // byte offset relative to the halo origin pixel (chunk already permuted)
-    short hyv[NTR], hxv[NTR];
-#pragma unroll
-    for (int i = 0; i < NTR; ++i) {
-        const int id = (wid + NW * i) * 64 + lane;
-        const int hp = id / CPP, slot = id - hp * CPP;
-        const int cc = slot ^ swz(hp);
-        const int hy = hp / HWW, hx = hp - hy * HWW;
-        rel[i] = id < HC ? (hy * p.W + hx) * p.ldi * 2 + cc * 16 : -1;
-        hyv[i] = (short)hy; hxv[i] = (short)hx;
-    }
-    const int hy0 = p.by + (p.cy < 0 ? (KH - 1) * p.cy : 0), hx0 = p.bx + (p.cx < 0 ? (KW - 1) * p.cx : 0);   // halo origin - tile origin
-    const int tiles_x = (p.OW + TW - 1) / TW, tiles_y = (p.OH + TH - 1) / TH;
-    const int tiles_img = tiles_x * tiles_y, ntiles = tiles_img * p.NB;
-    const long long img_bytes = (long long)p.H * p.W * p.ldi * 2ll;
-    const long long oimg_bytes = (long long)p.OH * p.OW * p.ldo * 2ll, mimg_bytes = (long long)p.OH * p.OW * p.ldm * 2ll;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)smem_raw;
-    const uint32_t ldsH0 = __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)WBYTES + (uint32_t)(wid * 1024));
-
-    auto issue_halo = [&](int buf, int tile) {
-        const int n = tile / tiles_img;
-        const int tr = tile - n * tiles_img;
-        const int ty = tr / tiles_x, tx = tr - ty * tiles_x;
-        const int gy0 = ty * TH * ST + hy0, gx0 = tx * TW * ST + hx0;
-        // one image per resource: 32-bit offsets always suffice; out-of-image pixels get the out-of-range offset -> zeros
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char*>(reinterpret_cast<const char*>(p.in)) + (long long)n * img_bytes, 0, (int)img_bytes, 0x00020000);
-        const int base = (gy0 * p.W + gx0) * p.ldi * 2 + p.cioff * 2;
-        const uint32_t dst = ldsH0 + (uint32_t)(buf * HBYTES);
-#pragma unroll
-        for (int i = 0; i < NTR; ++i) {
-            if (wid + NW * i < NSLOT) {                                                  // uniform: slot inside the halo buffer
-                const int gy = gy0 + hyv[i], gx = gx0 + hxv[i];
-                const bool ok = rel[i] >= 0 && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-                lds_dma16(dst + (uint32_t)(i * 1024 * NW), rs, ok ? base + rel[i] : (int)OOB, 0);
-            }
-        }
-    };
-
-    // uint8 frames: the next tile's halo bytes are fetched into registers where the DMA would be issued and written to the other halo
-    // buffer after this tile's MFMAs (nobody reads that buffer between the two barriers around them)
-    // two register sets: the bytes of tile t + 2G are requested at the top of tile t and written to LDS at the end of tile t + 1 -- a whole tile
-    // period for the loads to land (requested and consumed inside ONE tile their ~2 us were exposed every tile: 5.5 us per tile, 2.7 TB/s)
-    U8Halo<NTR> u8s[2];
-    bf16_t* u8lut = reinterpret_cast<bf16_t*>(smem_raw + WBYTES + NBUF * HBYTES);       // 512 bytes behind the halo buffers (host adds them)
-    if (U8) { u8_lut_init(u8lut, tid); __syncthreads(); }
-    auto u8_load = [&](int tile, U8Halo<NTR>& u8h) {
-        const int n = tile / tiles_img;
-        const int tr = tile - n * tiles_img;
-        const int ty = tr / tiles_x, tx = tr - ty * tiles_x;
-        u8h.template load<NSLOT>(p.u8, n, p.H, p.W, ty * TH * ST + hy0, tx * TW * ST + hx0, wid, hyv, hxv, rel);
-    };
-    const int frow = lane & 15, g4 = lane >> 4;
-    int cur = 0;
-    // persistent walk: round i covers tiles [i*G, (i+1)*G); inside a round every XCD takes a contiguous run (shared halo rows hit L2)
-    int tile = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    bool first = true;
-    if (U8) {
-        if (tile < ntiles) {
-            u8_load(tile, u8s[0]);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); u8s[0].landed();
-            u8s[0].template store<NSLOT>(smem_raw + WBYTES, u8lut, wid, lane);
-        }
-        if (tile + (int)gridDim.x < ntiles) u8_load(tile + gridDim.x, u8s[1]);
-    } else if (tile < ntiles) issue_halo(0, tile);
-    __syncthreads();                                                                   // filters visible
-    // bias once per workgroup (a load inside the tile loop is a compiler-visible wait that also drains the next halo's transfers)
-    f32x4 biasv[TI];
-#pragma unroll
-    for (int i = 0; i < TI; ++i) {
-        const int co = i * 16 + g4 * 4;
-        biasv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if ((p.flags & DIN_CONV_BIAS) && co < p.Cout) biasv[i] = *reinterpret_cast<const f32x4*>(p.bias + co);
-        asm volatile("" : "+v"(biasv[i]));                             // consumed HERE: the compiler's wait for the load stays out of the loop
-    }
-    auto tile_body = [&](auto PARC) {                                                  // PAR: which uint8 register set this tile FILLS
-        constexpr int PAR = decltype(PARC)::value;
-        // in-order completion: the halo transfers of this tile are older than the (always NST) stores of the previous tile when
-        // double-buffered, so the stores may stay in flight; single-buffered the transfers are the youngest -> drain everything
-        if (U8) {}                                                                     // (no transfers: the halo was written to LDS by the waves themselves)
-        else if (NBUF == 2 && !first) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NST) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        first = false;
-        __builtin_amdgcn_s_barrier();                                                  // halo(tile) landed; everyone left the previous tile
-        asm volatile("" ::: "memory");
-        const bool have_next = tile + (int)gridDim.x < ntiles;
-        if (U8) { if (tile + 2 * (int)gridDim.x < ntiles) u8_load(tile + 2 * gridDim.x, u8s[PAR]); }
-        else if (NBUF == 2 && have_next) issue_halo(cur ^ 1, tile + gridDim.x);
-        const u32x4* Hl = reinterpret_cast<const u32x4*>(smem_raw + WBYTES + cur * HBYTES);
-        // ---- dgrad epilogue operands (ReLU mask of the produced pixels, accumulate input): requested HERE, a whole MFMA phase before the
-        //      epilogue uses them.  Fetched inside the store loop their HBM latency (~2 us) was exposed once per tile: the Conv2d_2a dgrad
-        //      ran 1083 us inside the training step, 871 us with the early request (and 680 us with no mask at all).
-        constexpr int NIT = (NPX / NPASS) * CPR / NTHREADS;
-        const int n = tile / tiles_img;
-        const int trm = tile - n * tiles_img;
-        const int ty = trm / tiles_x, tx = trm - ty * tiles_x;
-        __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + (long long)n * oimg_bytes, 0, (int)oimg_bytes, 0x00020000);
-        __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char*>(reinterpret_cast<const char*>((p.flags & DIN_CONV_MASK) ? p.mask : p.out)) + (long long)n * mimg_bytes, 0,
-            (p.flags & DIN_CONV_MASK) ? (int)mimg_bytes : 0, 0x00020000);
-        auto out_pixel = [&](int ps, int it, int& opx, int& co) -> bool {              // pixel / channel chunk of store `it` of pass `ps`
-            const int idx = it * NTHREADS + tid;
-            const int srow = idx / CPR, c = idx - srow * CPR;
-            const int w_ = srow / (JN * 16), rem = srow - w_ * (JN * 16);
-            const int q = w_ * TJ + ps * JN + rem / 16;                                // segment of the tile
-            const int gy = ty * TH + (q >> 1), gx = tx * TW + (q & 1) * 16 + (rem & 15);
-            co = c * 8;
-            opx = gy * p.OW + gx;
-            return gy < p.OH && gx < p.OW && co < p.Cout;
-        };
-        u32x4 mkP[EPI ? NPASS : 1][EPI ? NIT : 1], oldP[EPI ? NPASS : 1][EPI ? NIT : 1];
-        if (EPI && (p.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM))) {
-#pragma unroll
-            for (int ps = 0; ps < (EPI ? NPASS : 1); ++ps)
-#pragma unroll
-                for (int it = 0; it < (EPI ? NIT : 1); ++it) {
-                    int opx, co;
-                    const bool ok = out_pixel(ps, it, opx, co);
-                    mkP[ps][it] = u32x4{0u, 0u, 0u, 0u}; oldP[ps][it] = u32x4{0u, 0u, 0u, 0u};
-                    if (p.flags & DIN_CONV_MASK)
-                        mkP[ps][it] = __builtin_amdgcn_raw_buffer_load_b128(rsM, ok ? (opx * p.ldm + p.moff + co) * 2 : (int)OOB, 0, 0);
-                    if (p.flags & DIN_CONV_ACCUM)
-                        oldP[ps][it] = __builtin_amdgcn_raw_buffer_load_b128(rsO, ok ? (opx * p.ldo + p.cooff + co) * 2 : (int)OOB, 0, 0);
-                }
-        }
-
-        f32x4 acc[TI][TJ];
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int ysgn = p.cy > 0 ? 1 : -1, xsgn = p.cx > 0 ? 1 : -1;
-        const int yb = p.cy > 0 ? 0 : KH - 1, xb = p.cx > 0 ? 0 : KW - 1;
-        if (CPP >= 4) {
-#pragma unroll
-            for (int tap = 0; tap < NTAPS; ++tap) {
-                const int r = tap / KW, s2 = tap - r * KW;
-                const int dy = yb + ysgn * r, dx = xb + xsgn * s2;
-#pragma unroll
-                for (int sl = 0; sl < SL; ++sl) {
-                    u32x4 wf[TI], xf[TJ];
-                    const int chunk = sl * 4 + g4;
-#pragma unroll
-                    for (int i = 0; i < TI; ++i) {
-                        const int co = i * 16 + frow;
-                        wf[i] = Wl[(tap * BN + co) * CPP + (chunk ^ swz(co))];
-                    }
-#pragma unroll
-                    for (int j = 0; j < TJ; ++j) {
-                        const int q = wid * TJ + j;                                     // 16-pixel segment of the tile
-                        const int hp = ((q >> 1) * ST + dy) * HWW + ((q & 1) * 16 + frow) * ST + dx;
-                        xf[j] = Hl[hp * CPP + (chunk ^ swz(hp))];
-                    }
-#pragma unroll
-                    for (int i = 0; i < TI; ++i)
-#pragma unroll
-                        for (int j = 0; j < TJ; ++j) Mma<T>::run(wf[i], xf[j], acc[i][j]);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int sl = 0; sl < NSL; ++sl) {
-                u32x4 wf[TI], xf[TJ];
-                const int tap = min(sl * 4 + g4, NTAPS - 1);                           // surplus taps: finite data x zero filter
-                const int r = tap / KW, s2 = tap - r * KW;
-                const int dy = yb + ysgn * r, dx = xb + xsgn * s2;
-#pragma unroll
-                for (int i = 0; i < TI; ++i) wf[i] = Wl[(sl * BN + i * 16 + frow) * 4 + g4];
-#pragma unroll
-                for (int j = 0; j < TJ; ++j) {
-                    const int q = wid * TJ + j;
-                    xf[j] = Hl[((q >> 1) * ST + dy) * HWW + ((q & 1) * 16 + frow) * ST + dx];
-                }
-#pragma unroll
-                for (int i = 0; i < TI; ++i)
-#pragma unroll
-                    for (int j = 0; j < TJ; ++j) Mma<T>::run(wf[i], xf[j], acc[i][j]);
-            }
-        }
-        if (U8 && have_next) {
-            // the bytes of tile + G were requested a tile ago; younger: the previous tile's stores and this tile's 3 NTR byte loads (if any)
-            if (tile + 2 * (int)gridDim.x < ntiles) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * NTR) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            u8s[PAR ^ 1].landed();
-            u8s[PAR ^ 1].template store<NSLOT>(smem_raw + WBYTES + (cur ^ 1) * HBYTES, u8lut, wid, lane);
-        }
-        __syncthreads();                                                               // all waves done reading halo(cur)
-        // ---- epilogue: stage through the consumed halo buffer, then 16-byte coalesced buffer stores (always NST per wave) -----
-        unsigned char* stg = smem_raw + WBYTES + cur * HBYTES;
-#pragma unroll
-        for (int ps = 0; ps < NPASS; ++ps) {
-#pragma unroll
-            for (int i = 0; i < TI; ++i) {
-                const f32x4 bv = biasv[i];
-                const int co = i * 16 + g4 * 4;
-#pragma unroll
-                for (int j = ps * JN; j < (ps + 1) * JN; ++j) {
-                    f32x4 v = acc[i][j] + bv;
-                    if (p.flags & DIN_CONV_RELU) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
-                    const int srow = (wid * JN + (j - ps * JN)) * 16 + frow;             // staging row of this pixel
-                    *reinterpret_cast<u32x2*>(stg + srow * CPITCH + co * 2) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                int opx, co;
-                const bool ok = out_pixel(ps, it, opx, co);
-                const int idx = it * NTHREADS + tid;
-                const int srow = idx / CPR, c = idx - srow * CPR;
-                u32x4 v = *reinterpret_cast<const u32x4*>(stg + srow * CPITCH + c * 16);
-                const int o = ok ? (opx * p.ldo + p.cooff + co) * 2 : (int)OOB;
-                if (p.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM)) {
-                    u32x4 mk = {0u, 0u, 0u, 0u}, old = {0u, 0u, 0u, 0u};
-                    if (EPI) { mk = mkP[EPI ? ps : 0][EPI ? it : 0]; old = oldP[EPI ? ps : 0][EPI ? it : 0]; }
-                    else {
-                        if (p.flags & DIN_CONV_MASK) mk = __builtin_amdgcn_raw_buffer_load_b128(rsM, ok ? (opx * p.ldm + p.moff + co) * 2 : (int)OOB, 0, 0);
-                        if (p.flags & DIN_CONV_ACCUM) old = __builtin_amdgcn_raw_buffer_load_b128(rsO, o, 0, 0);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo = __uint_as_float(v[e] << 16), hi = __uint_as_float(v[e] & 0xffff0000u);
-                        if (p.flags & DIN_CONV_MASK) {
-                            if (!(__uint_as_float(mk[e] << 16) > 0.f)) lo = 0.f;
-                            if (!(__uint_as_float(mk[e] & 0xffff0000u) > 0.f)) hi = 0.f;
-                        }
-                        if (p.flags & DIN_CONV_ACCUM) { lo += __uint_as_float(old[e] << 16); hi += __uint_as_float(old[e] & 0xffff0000u); }
-                        v[e] = pack_bf16x2(lo, hi);
-                    }
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(v, rsO, o, 0, 0);                  // out-of-range offset -> dropped, still counted
-            }
-            if (ps + 1 < NPASS) __syncthreads();
-        }
-        if (NBUF == 2) cur ^= 1;
-        else {
-            __syncthreads();                                                            // staging buffer free again
-            if (tile + (int)gridDim.x < ntiles) issue_halo(0, tile + gridDim.x);
-        }
-    };
-    if constexpr (U8) {
-        for (;;) {
-            if (tile >= ntiles) break;
-            tile_body(IcTag<0>{}); tile += gridDim.x;
-            if (tile >= ntiles) break;
-            tile_body(IcTag<1>{}); tile += gridDim.x;
-        }
-    } else {
-        for (; tile < ntiles; tile += gridDim.x) tile_body(IcTag<0>{});
-    }
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------
-// Halo-tiled convolution for the mid-network multi-tap layers (3x3, 1x7, 7x1; stride 1; bf16; fwd and dgrad).
-// The implicit-GEMM kernel streams every input pixel once per tap and the filter slab once per 128 pixels; measured, it runs at
-// (FLOP per streamed byte) x ~9.6 TB/s.  Here a workgroup owns a TH x TW = 256-pixel output tile: per 64-channel block the input
-// HALO is brought into LDS once (all taps are formed from it) and only the filter slab of one (tap, channel block) moves through
-// a small LDS-DMA ring: 2-3x fewer streamed bytes per FLOP.  Both LDS images use a 160-byte row pitch (8 data chunks + 2 pad
-// chunks the DMA leaves empty): 16 consecutive rows x one chunk are then conflict-free for ds_read_b128 at ANY row offset, so a
-// tap is nothing but an immediate offset on the fragment reads -- no per-tap address arithmetic (the first version of this kernel
-// spent 46 % of its wave cycles issuing address / bookkeeping instructions; SQ counters in profiles/r01_halo_probe.txt).
-// Persistent workgroups (one per CU) walk the (tile, filter tile) items; the next block's halo (also across items) is in flight
-// during the current block's taps, the slab ring runs NSW-1 tap steps ahead, one s_barrier per tap step, vmcnt counted by hand
-// (every wave issues the same number of transfers; surplus ones fetch nothing into pad space).  Epilogue straight from the
-// accumulators as always-issued buffer stores (bias / ReLU / ReLU-backward mask / accumulate).
-// ------------------------------------------------------------------------------------------------
-template <int BN, int KH, int KW, int TH, int TW, int NSW, int NWV_ = 8>
-__global__ __launch_bounds__(64 * NWV_, 1) void conv_halo_kernel(ConvK p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef bf16_t T;
-    // 8 waves: wave = (pixel group wp of 64 pixels, filter half wc): two waves per SIMD, so one wave's waits (barrier, vmcnt, LDS
-    // latency) hide behind the other's MFMAs -- with 4 waves (one per SIMD) the kernel ran at 20 % MFMA utilisation
-    // NWV_ = 16: pixel groups of 32 instead of 64 pixels (four waves per SIMD; the LDS budget then allows a 2-slot filter ring only)
-    // BN = 80 (Conv2d_4a's data gradient, 192 -> 80 channels): the first filter half takes 48 rows (three 16-row tiles), the second 32 (two) --
-    // a sixth fewer MFMAs than padding the bank to 96 rows; the two kinds of wave alternate on every SIMD (waves go to SIMDs round-robin)
-    constexpr int NWV = NWV_, NTAPS = KH * KW, TI = (BN + 31) / 32, TJ = 32 / NWV;
-    constexpr int WCR = BN == 80 ? 48 : BN / 2;                       // rows of the first filter half
-    constexpr int HWW = TW + KW - 1, HWH = TH + KH - 1, HPX = HWW * HWH;
-    constexpr int PCH = 10, PB = PCH * 16;                            // row pitch: 10 chunks = 160 bytes
-    constexpr int NTR_H = (HPX * PCH + 64 * NWV - 1) / (64 * NWV), HBYTES = NTR_H * 1024 * NWV;
-    constexpr int NTR_W = (BN * PCH + 64 * NWV - 1) / (64 * NWV), WBYTES = NTR_W * 1024 * NWV;
-    static_assert(TH * TW == 256 && TW % 16 == 0 && NTAPS > NSW && (BN % 32 == 0 || BN == 80), "tile shape");
-    constexpr int NST = TI * TJ;                                       // epilogue stores per wave per item
-    constexpr unsigned OOB = 0x80000000u;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int frow = lane & 15, g4 = lane >> 4;
-    const int wp = wid & (NWV / 2 - 1), wc = __builtin_amdgcn_readfirstlane(wid / (NWV / 2));
-    const int tiw = wc == 0 ? TI : (BN - WCR) / 16;                    // 16-row filter tiles of this wave (scalar)
-    const uint32_t lds_base = (uint32_t)(uintptr_t)smem_raw;
-    const uint32_t ldsWv = __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)(wid * 1024));
-
-    // ---- DMA plans ------------------------------------------------------------------------------------------------------------
-    // (the halo plan is recomputed per transfer at issue time -- once per 64-channel block; as per-lane arrays it cost ~60 VGPRs and
-    //  pushed the tap loop into AGPR spills)
-    int relW[NTR_W]; signed char wcc[NTR_W];
-#pragma unroll
-    for (int i = 0; i < NTR_W; ++i) {
-        const int id = (wid + NWV * i) * 64 + lane;
-        const int co = id / PCH, cc = id - co * PCH;
-        relW[i] = (co < BN && cc < 8) ? co * p.wld * 16 + cc * 16 : -1;  // + filter-tile row offset + (tap * cpt + 8 b) * 16
-        wcc[i] = (signed char)cc;
-    }
-    const int hy0 = p.by + (p.cy < 0 ? (KH - 1) * p.cy : 0), hx0 = p.bx + (p.cx < 0 ? (KW - 1) * p.cx : 0);
-    const int tiles_x = (p.OW + TW - 1) / TW, tiles_y = (p.OH + TH - 1) / TH;
-    const int tiles_img = tiles_x * tiles_y, nitems = tiles_img * p.NB * p.n_co_tiles;
-    const long long img_bytes = (long long)p.H * p.W * p.ldi * 2ll;
-    const long long oimg_bytes = (long long)p.OH * p.OW * p.ldo * 2ll, mimg_bytes = (long long)p.OH * p.OW * p.ldm * 2ll;
-    const int nblk = (p.cpt + 7) >> 3;                                  // 64-channel blocks
-    __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, (int)p.w_bytes, 0x00020000);
-
-    struct Item { int n, ty, tx, co_tile; };
-    auto decode_item = [&](int item) {
-        Item it;
-        it.co_tile = item % p.n_co_tiles;
-        const int tile = item / p.n_co_tiles;
-        it.n = tile / tiles_img;
-        const int tr = tile - it.n * tiles_img;
-        it.ty = tr / tiles_x; it.tx = tr - it.ty * tiles_x;
-        return it;
-    };
-    auto issue_halo = [&](int buf, const Item& it, int b) {
-        const int gy0 = it.ty * TH + hy0, gx0 = it.tx * TW + hx0;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char*>(reinterpret_cast<const char*>(p.in)) + (long long)it.n * img_bytes, 0, (int)img_bytes, 0x00020000);
-        const int base = (gy0 * p.W + gx0) * p.ldi * 2 + (p.cioff + b * 64) * 2;
-        const int nch = p.cpt - b * 8;                                  // chunks of this block that exist (>= 8: all)
-        const uint32_t dst = ldsWv + (uint32_t)(buf * HBYTES);
-#pragma unroll 2
-        for (int i = 0; i < NTR_H; ++i) {
-            const int id = (wid + NWV * i) * 64 + lane;
-            const int hp = (int)(((unsigned)id * 52429u) >> 19);         // id / 10 for id < 81920
-            const int cc = id - hp * PCH;
-            const int hy = (int)(((unsigned)hp * (65536u / HWW + 1u)) >> 16), hx = hp - hy * HWW;   // hp / HWW (hp < 1024)
-            const int gy = gy0 + hy, gx = gx0 + hx;
-            const bool ok = hp < HPX && cc < 8 && cc < nch && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-            lds_dma16(dst + (uint32_t)(i * 1024 * NWV), rs, ok ? base + (hy * p.W + hx) * p.ldi * 2 + cc * 16 : (int)OOB, 0);
-        }
-    };
-    auto issue_w = [&](int slot, int co_tile, int b, int tap) {
-        const int nch = p.cpt - b * 8;
-        const int soff = (co_tile * BN * p.wld + tap * p.cpt + b * 8) * 16;
-        const uint32_t dst = ldsWv + (uint32_t)(2 * HBYTES + slot * WBYTES);
-#pragma unroll
-        for (int i = 0; i < NTR_W; ++i) lds_dma16(dst + (uint32_t)(i * 1024 * NWV), rsW, (relW[i] >= 0 && wcc[i] < nch) ? relW[i] : (int)OOB, soff);
-    };
-
-    f32x4 acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // fragment read bases (bytes): pixel segment j of this wave at tap (0,0) of the gather direction, chunk g4; filter row frow, chunk g4
-    const int yb = p.cy > 0 ? 0 : KH - 1, xb = p.cx > 0 ? 0 : KW - 1;
-    const int tstep_y = (p.cy > 0 ? 1 : -1) * HWW * PB, tstep_x = (p.cx > 0 ? 1 : -1) * PB;     // byte step of one tap row / column
-    uint32_t xbase[TJ];
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) {
-        const int q = wp * TJ + j;
-        const int qy = TW == 32 ? (q >> 1) : q, qx = TW == 32 ? (q & 1) * 16 : 0;
-        xbase[j] = (uint32_t)(((qy + yb) * HWW + qx + frow + xb) * PB + g4 * 16);
-    }
-    const uint32_t wbase = (uint32_t)(2 * HBYTES + (wc * WCR + frow) * PB + g4 * 16);
-
-    constexpr int NBP = NWV == 16 ? 1 : 2;                             // (sixteen waves: 128 registers)
-    f32x4 biasP[NBP][TI];                                               // bias of the first NBP filter tiles (see the epilogue)
-#pragma unroll
-    for (int ct = 0; ct < NBP; ++ct)
-#pragma unroll
-        for (int i = 0; i < TI; ++i) {
-            const int co = ct * BN + wc * WCR + i * 16 + g4 * 4;
-            biasP[ct][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if ((p.flags & DIN_CONV_BIAS) && co < p.Cout) biasP[ct][i] = *reinterpret_cast<const f32x4*>(p.bias + co);
-            asm volatile("" : "+v"(biasP[ct][i]));                      // consumed here: the compiler's wait stays out of the walk
-        }
-    // ---- (item, channel block) pair walk ----------------------------------------------------------------------------------------
-    const int G = (int)gridDim.x;
-    int item = xcd_remap((int)blockIdx.x, G);
-    if (item >= nitems) return;
-    Item cur = decode_item(item);
-    int b = 0, hb = 0;
-    int item_w = item, b_w = 0, tap_w = 0;                              // (item, block, tap) of the next filter slab to issue
-    int co_w = cur.co_tile;
-    bool w_live = true;
-    auto advance_w = [&]() {
-        if (++tap_w == NTAPS) {
-            tap_w = 0;
-            if (++b_w == nblk) { b_w = 0; item_w += G; w_live = item_w < nitems; if (w_live) co_w = item_w % p.n_co_tiles; }
-        }
-    };
-    issue_halo(0, cur, 0);
-    int wslot_issue = 0;
-#pragma unroll
-    for (int s0 = 0; s0 < NSW - 1; ++s0) {
-        if (w_live) { issue_w(wslot_issue, co_w, b_w, tap_w); advance_w(); }
-        wslot_issue = wslot_issue + 1 == NSW ? 0 : wslot_issue + 1;
-    }
-    int wslot = 0;                                                      // ring slot of the current step
-    bool fresh_item = false;                                            // an epilogue's stores were issued since the last tap step
-    for (;;) {
-        int item_n = item, b_n = b + 1;
-        if (b_n == nblk) { b_n = 0; item_n = item + G; }
-        const bool has_next = item_n < nitems;
-        const Item nxt = (b_n == 0 && has_next) ? decode_item(item_n) : cur;
-        const uint32_t hoff = (uint32_t)(hb * HBYTES);
-        const bool two = p.cpt - b * 8 > 4;                             // second 32-channel slice present
-#pragma unroll
-        for (int tap = 0; tap < NTAPS; ++tap) {
-            // ---- slab of this step landed?  Younger transfers that may stay in flight (in-order completion): the NSW-2 slabs issued
-            //      after it, the halo issued at this pair's tap-0 step (taps 1 .. NSW-1), the stores of an epilogue issued since ----
-            {
-                constexpr int base_allow = (NSW - 2) * NTR_W;
-                const bool halo_tap = tap >= 1 && tap <= NSW - 1;
-                const bool store_tap = tap <= NSW - 2;
-                constexpr int a_hs = base_allow + NTR_H + NST > 63 ? 63 : base_allow + NTR_H + NST;
-                constexpr int a_s = base_allow + NST > 63 ? 63 : base_allow + NST;
-                const bool hy_ = halo_tap && has_next, st_ = store_tap && fresh_item;
-                if (!w_live) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // tail of the walk: drain
-                else if (hy_ && st_) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(a_hs) : "memory");
-                else if (hy_) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(base_allow + NTR_H) : "memory");
-                else if (st_) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(a_s) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(base_allow) : "memory");
-            }
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (w_live) { issue_w(wslot_issue, co_w, b_w, tap_w); advance_w(); }
-            wslot_issue = wslot_issue + 1 == NSW ? 0 : wslot_issue + 1;
-            if (tap == 0 && has_next) issue_halo(hb ^ 1, nxt, b_n);
-            // ---- MFMAs of (block b, tap): every fragment address = lane base + compile-time offset ------------------------------------
-            const int r = tap / KW, s2 = tap - r * KW;
-            const uint32_t xoff = hoff + (uint32_t)(r * tstep_y + s2 * tstep_x);
-            const uint32_t woff = (uint32_t)(wslot * WBYTES);
-            u32x4 wf[2][TI], xf[2][TJ];
-#pragma unroll
-            for (int i = 0; i < TI; ++i) if (i < tiw) wf[0][i] = *reinterpret_cast<const u32x4*>(smem_raw + wbase + woff + i * 16 * PB);
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) xf[0][j] = *reinterpret_cast<const u32x4*>(smem_raw + xbase[j] + xoff);
-            __builtin_amdgcn_sched_barrier(0);
-            if (two) {
-#pragma unroll
-                for (int i = 0; i < TI; ++i) if (i < tiw) wf[1][i] = *reinterpret_cast<const u32x4*>(smem_raw + wbase + woff + i * 16 * PB + 64);
-#pragma unroll
-                for (int j = 0; j < TJ; ++j) xf[1][j] = *reinterpret_cast<const u32x4*>(smem_raw + xbase[j] + xoff + 64);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-                if (i < tiw) {
-#pragma unroll
-                    for (int j = 0; j < TJ; ++j) Mma<T>::run(wf[0][i], xf[0][j], acc[i][j]);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-            if (two) {
-#pragma unroll
-                for (int i = 0; i < TI; ++i)
-                    if (i < tiw) {
-#pragma unroll
-                        for (int j = 0; j < TJ; ++j) Mma<T>::run(wf[1][i], xf[1][j], acc[i][j]);
-                    }
-            }
-            wslot = wslot + 1 == NSW ? 0 : wslot + 1;
-            if (tap == NSW - 2) fresh_item = false;
-        }
-        // ---- end of the item: epilogue straight from the accumulators ----------------------------------------------------------------
-        if (b == nblk - 1) {
-            __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + (long long)cur.n * oimg_bytes, 0, (int)oimg_bytes, 0x00020000);
-            __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<char*>(reinterpret_cast<const char*>((p.flags & DIN_CONV_MASK) ? p.mask : p.out)) + (long long)cur.n * mimg_bytes, 0,
-                (p.flags & DIN_CONV_MASK) ? (int)mimg_bytes : 0, 0x00020000);
-            // bias: preloaded before the walk for the first NBP filter tiles (a compiler-visible load here waits with vmcnt(0): it would
-            // drain the slab ring and the next halo once per item)
-            f32x4 bv[TI];
-#pragma unroll
-            for (int i = 0; i < TI; ++i) {
-                const int co = cur.co_tile * BN + wc * WCR + i * 16 + g4 * 4;
-                if (cur.co_tile < NBP) bv[i] = cur.co_tile == 0 ? biasP[0][i] : biasP[NBP - 1][i];
-                else { bv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; if ((p.flags & DIN_CONV_BIAS) && co < p.Cout) bv[i] = *reinterpret_cast<const f32x4*>(p.bias + co); }
-            }
-            // dgrad operands: ALL of the item's loads first, then all its stores (segment by segment the loads of segment j + 1 waited for the
-            // stores of segment j -- in-order completion -- i.e. TJ exposed round trips per item)
-            u32x2 mk[TJ][TI], old[TJ][TI];
-            int off[TJ][TI];
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) {
-                const int q = wp * TJ + j;
-                const int qy = TW == 32 ? (q >> 1) : q, qx = TW == 32 ? (q & 1) * 16 : 0;
-                const int gy = cur.ty * TH + qy, gx = cur.tx * TW + qx + frow;
-                const bool pok = gy < p.OH && gx < p.OW;
-                const int opx = gy * p.OW + gx;
-#pragma unroll
-                for (int i = 0; i < TI; ++i) {
-                    const int co = cur.co_tile * BN + wc * WCR + i * 16 + g4 * 4;
-                    const bool ok = pok && co < p.Cout;                      // Cout % 4 == 0 (host)
-                    off[j][i] = ok ? (opx * p.ldo + p.cooff + co) * 2 : (int)OOB;
-                    if (p.flags & DIN_CONV_MASK) mk[j][i] = __builtin_amdgcn_raw_buffer_load_b64(rsM, ok ? (opx * p.ldm + p.moff + co) * 2 : (int)OOB, 0, 0);
-                    if (p.flags & DIN_CONV_ACCUM) old[j][i] = __builtin_amdgcn_raw_buffer_load_b64(rsO, off[j][i], 0, 0);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < TJ; ++j)
-#pragma unroll
-                for (int i = 0; i < TI; ++i) {
-                    f32x4 v = acc[i][j] + bv[i];
-                    acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (p.flags & DIN_CONV_RELU) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
-                    if (p.flags & DIN_CONV_MASK) {
-                        if (!(__uint_as_float(mk[j][i][0] << 16) > 0.f)) v[0] = 0.f;
-                        if (!(__uint_as_float(mk[j][i][0] & 0xffff0000u) > 0.f)) v[1] = 0.f;
-                        if (!(__uint_as_float(mk[j][i][1] << 16) > 0.f)) v[2] = 0.f;
-                        if (!(__uint_as_float(mk[j][i][1] & 0xffff0000u) > 0.f)) v[3] = 0.f;
-                    }
-                    if (p.flags & DIN_CONV_ACCUM) {
-                        v[0] += __uint_as_float(old[j][i][0] << 16); v[1] += __uint_as_float(old[j][i][0] & 0xffff0000u);
-                        v[2] += __uint_as_float(old[j][i][1] << 16); v[3] += __uint_as_float(old[j][i][1] & 0xffff0000u);
-                    }
-                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}, rsO, off[j][i], 0, 0);
-                }
-            fresh_item = true;
-        }
-        if (!has_next) break;
-        item = item_n; b = b_n; hb ^= 1;
-        if (b == 0) cur = nxt;
-    }
-#endif
-}
-
 // split-K finish: out = epilogue(sum_s partial[s])
 template <typename T>
 __global__ void conv_splitk_finish_kernel(ConvK p, int cpad) {
@@ -1353,148 +739,6 @@ __global__ void conv_splitk_finish_kernel(ConvK p, int cpad) {
         if (p.flags & DIN_CONV_ACCUM) x += Elem<T>::ld(outp + o);
         Elem<T>::st(outp + o, x);
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight packing:  w[cout][cin][kh][kw] fp32 (* scale[cout]) -> T[rows_pad][nk*KC*EPC]
-//   transposed = 0: row = co, k = (r,s,ci)      (fwd)
-//   transposed = 1: row = ci, k = (r,s,co)      (dgrad)
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void conv_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, T* __restrict__ out,
-                                 int cout, int cin, int kh, int kw, int rows, int rows_pad, int inner, int inner_pad,
-                                 int kelems, int transposed) {
-    // inner = reduction channels per tap (cin or cout), inner_pad = padded to EPC; kelems = padded row length
-    int64_t total = (int64_t)rows_pad * kelems;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        int row = (int)(i / kelems), k = (int)(i - (int64_t)row * kelems);
-        int tap = k / inner_pad, c = k - tap * inner_pad;
-        float v = 0.f;
-        if (row < rows && tap < kh * kw && c < inner) {
-            int r = tap / kw, s = tap - r * kw;
-            int co = transposed ? c : row, ci = transposed ? row : c;
-            v = w[(((int64_t)co * cin + ci) * kh + r) * kw + s];
-            if (scale) v *= scale[co];
-        }
-        Elem<T>::st(out + i, v);
-    }
-}
-
-// 1x1 filter banks (the 26400 x 1024 embedding filter is re-packed twice per step: 108 MB in, 54 MB out per orientation): 64 x 64 tiles
-// through LDS, reads coalesced along the filter's contiguous axis (ci), writes coalesced along the packed row -- instead of one element
-// per thread with two 64-bit divisions (106 -> ~35 us per orientation).  out[row][k]: row = co (k = ci) or, transposed, row = ci (k = co).
-template <typename T>
-__global__ __launch_bounds__(256) void conv_pack_1x1_kernel(const float* __restrict__ w, const float* __restrict__ scale, T* __restrict__ out,
-                                                            int cout, int cin, int rows_pad, int kelems, int transposed) {
-    __shared__ float tile[64][65];
-    const int r0 = blockIdx.y * 64, k0 = blockIdx.x * 64;                  // tile of the packed matrix
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;                // 64 x 4
-    if (!transposed) {
-#pragma unroll 4
-        for (int rr = ty; rr < 64; rr += 4) {
-            const int co = r0 + rr, ci = k0 + tx;
-            float v = 0.f;
-            if (co < cout && ci < cin) { v = w[(int64_t)co * cin + ci]; if (scale) v *= scale[co]; }
-            if (co < rows_pad && ci < kelems) Elem<T>::st(out + (int64_t)co * kelems + ci, v);
-        }
-        return;
-    }
-    // transposed: packed row = ci, packed column = co; read w[co][ci] with ci fastest
-#pragma unroll 4
-    for (int cc = ty; cc < 64; cc += 4) {
-        const int co = k0 + cc, ci = r0 + tx;
-        float v = 0.f;
-        if (co < cout && ci < cin) { v = w[(int64_t)co * cin + ci]; if (scale) v *= scale[co]; }
-        tile[cc][tx] = v;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int rr = ty; rr < 64; rr += 4) {
-        const int ci = r0 + rr, co = k0 + tx;
-        if (ci < rows_pad && co < kelems) Elem<T>::st(out + (int64_t)ci * kelems + co, tile[tx][rr]);
-    }
-}
-
-// every filter bank of a backbone (both orientations) in one launch: workgroup b packs elements [chunk_index[b] * chunk, +chunk) of
-// bank layer_of[b]; the table lives on the device and is built once (weights, scales and packed buffers keep their addresses)
-__global__ __launch_bounds__(256) void conv_pack_multi_kernel(const din_pack_desc* __restrict__ table, const int32_t* __restrict__ layer_of,
-                                                              const int32_t* __restrict__ chunk_index, int chunk) {
-    const din_pack_desc d = table[layer_of[blockIdx.x]];
-    const float* __restrict__ w = reinterpret_cast<const float*>(d.w);
-    const float* __restrict__ scale = reinterpret_cast<const float*>(d.scale);
-    const int64_t total = (int64_t)d.rows_pad * d.kelems;
-    const int64_t i0 = (int64_t)chunk_index[blockIdx.x] * chunk;
-    int64_t i1 = i0 + chunk;
-    if (i1 > total) i1 = total;
-    const int taps = d.kh * d.kw;
-    // (banks below 2^31 elements -- every backbone bank -- take 32-bit index arithmetic: the 64-bit divisions cost more than the traffic)
-    const bool small = total < (1ll << 31);
-    for (int64_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-        int row, k;
-        if (small) { row = (int)((uint32_t)i / (uint32_t)d.kelems); k = (int)((uint32_t)i - (uint32_t)row * (uint32_t)d.kelems); }
-        else { row = (int)(i / d.kelems); k = (int)(i - (int64_t)row * d.kelems); }
-        const int tap = k / d.inner_pad, c = k - tap * d.inner_pad;
-        float v = 0.f;
-        if (row < d.rows && tap < taps && c < d.inner) {
-            const int r = tap / d.kw, s2 = tap - r * d.kw;
-            const int co = d.transposed ? c : row, ci = d.transposed ? row : c;
-            v = small ? w[(uint32_t)(((co * d.cin + ci) * d.kh + r) * d.kw + s2)] : w[(((int64_t)co * d.cin + ci) * d.kh + r) * d.kw + s2];
-            if (scale) v *= scale[co];
-        }
-        if (d.dtype == DIN_F32) reinterpret_cast<float*>(d.out)[i] = v;
-        else reinterpret_cast<bf16_t*>(d.out)[i] = f32_to_bf16(v);
-    }
-}
-
-__global__ void bn_fold_kernel(const float* gamma, const float* beta, const float* mean, const float* var, float eps,
-                               float* scale, float* shift, int c) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < c) {
-        float s = gamma[i] / sqrtf(var[i] + eps);
-        scale[i] = s;
-        shift[i] = beta[i] - mean[i] * s;
-    }
-}
-__global__ void bn_fold_bwd_kernel(const float* wdot, const float* dshift, const float* mean, const float* var, float eps,
-                                   float* dgamma, float* dbeta, int c) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < c) {
-        float rstd = 1.f / sqrtf(var[i] + eps);
-        dgamma[i] = (wdot[i] - dshift[i] * mean[i]) * rstd;
-        dbeta[i] = dshift[i];
-    }
-}
-
-// all BatchNorm layers of a backbone in one launch: ptrs[l] = {gamma, beta, mean, var}, channel l-range = [offs[l], offs[l+1])
-__device__ __forceinline__ int bn_layer_of(const int32_t* __restrict__ offs, int n, int i) {
-    int lo = 0, hi = n;                                       // offs[lo] <= i < offs[hi]
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
-}
-__global__ void bn_fold_multi_kernel(const uint64_t* __restrict__ ptrs, const int32_t* __restrict__ offs, int n, int total, float eps,
-                                     float* __restrict__ scale, float* __restrict__ shift) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int l = bn_layer_of(offs, n, i), c = i - offs[l];
-    const float* gamma = reinterpret_cast<const float*>(ptrs[4 * l + 0]);
-    const float* beta = reinterpret_cast<const float*>(ptrs[4 * l + 1]);
-    const float* mean = reinterpret_cast<const float*>(ptrs[4 * l + 2]);
-    const float* var = reinterpret_cast<const float*>(ptrs[4 * l + 3]);
-    const float s = gamma[c] / sqrtf(var[c] + eps);
-    scale[i] = s;
-    shift[i] = beta[c] - mean[c] * s;
-}
-__global__ void bn_fold_bwd_multi_kernel(const uint64_t* __restrict__ ptrs, const int32_t* __restrict__ offs, int n, int total, float eps,
-                                         const float* __restrict__ wdot, const float* __restrict__ dshift, float* __restrict__ dgamma,
-                                         float* __restrict__ dbeta) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int l = bn_layer_of(offs, n, i), c = i - offs[l];
-    const float* mean = reinterpret_cast<const float*>(ptrs[4 * l + 2]);
-    const float* var = reinterpret_cast<const float*>(ptrs[4 * l + 3]);
-    const float rstd = 1.f / sqrtf(var[c] + eps);
-    dgamma[i] = (wdot[i] - dshift[i] * mean[c]) * rstd;
-    dbeta[i] = dshift[i];
 }
 
 // ---- host-side planning ----------------------------------------------------------------------------
@@ -1592,44 +836,6 @@ int din_conv::check_desc(const din_conv_desc* d) {
 
 namespace {
 
-// halo kernel eligibility / shape.  hp.bn is the filter-tile width.
-struct HaloPlan { int bn, th, tw, nsw, nwv, n_co_tiles; size_t lds; };
-static bool plan_halo(int dtype, int kh, int kw, int cred, int cprod, int oh, int ow, int64_t M, HaloPlan& hp) {
-    const char* hv = DIN_OPT("DIN_CONV_HALO");
-    if (hv && atoi(hv) == 0) return false;
-    if (dtype != DIN_BF16 || cred < 32 || cred % 8 != 0 || cprod % 8 != 0 || cprod < 40 || M < 64 * 1024) return false;
-    const bool k33 = kh == 3 && kw == 3, k17 = kh == 1 && kw == 7, k71 = kh == 7 && kw == 1;
-    if (!(k33 || k17 || k71)) return false;
-    // filter tiles of 64 or 96 rows: fewest tiles, then least padding
-    const int t96 = (cprod + 95) / 96, t64 = (cprod + 63) / 64;
-    hp.bn = (t96 < t64 || (t96 == t64 && t96 * 96 <= t64 * 64)) ? 96 : 64;
-    hp.n_co_tiles = hp.bn == 96 ? t96 : t64;
-    const bool bn80 = k33 && cprod > 64 && cprod <= 80;   // 48 + 32 rows (16-wave kernel only, below)
-    if (hp.n_co_tiles * hp.bn * 100 > cprod * 125) return false;
-    // measured (profiles/r01_halo_probe.txt): wins 15-22 % on 3x3 layers whose filters fit ONE tile (no halo re-read per filter tile);
-    // loses against the 128x192 / 128x160 gather tiles on the wide 192-filter and 7-tap layers.  DIN_CONV_HALO=2 forces it everywhere.
-    if (!(hv && atoi(hv) == 2) && !(k33 && hp.n_co_tiles == 1)) return false;
-    hp.th = k33 ? 8 : 16; hp.tw = k33 ? 32 : 16;
-    hp.nwv = 8;
-    // padded-area waste of the tile grid must stay moderate
-    const int64_t padded = (int64_t)((oh + hp.th - 1) / hp.th * hp.th) * ((ow + hp.tw - 1) / hp.tw * hp.tw);
-    if (padded * 100 > (int64_t)oh * ow * 118) return false;
-    const int hpx = (hp.th + kh - 1) * (hp.tw + kw - 1);
-    const size_t hbytes = (size_t)((hpx * 10 + 511) / 512) * 8192, wbytes = (size_t)((hp.bn * 10 + 511) / 512) * 8192;
-    hp.nsw = 3;
-    hp.lds = 2 * hbytes + 3 * wbytes;
-    {   // sixteen waves (3x3 tiles only): transfers cover 16 KiB, the filter ring shrinks to two slots to stay inside 160 KiB
-        const char* wv = DIN_OPT("DIN_HALO_WAVES");
-        const int want = wv ? atoi(wv) : 16;
-        const size_t hb16 = (size_t)((hpx * 10 + 1023) / 1024) * 16384, wb16 = (size_t)((hp.bn * 10 + 1023) / 1024) * 16384;
-        if (want == 16 && k33 && 2 * hb16 + 2 * wb16 <= 160 * 1024) {
-            hp.nwv = 16; hp.nsw = 2; hp.lds = 2 * hb16 + 2 * wb16;
-            if (bn80) hp.bn = 80;                               // (same 16 KiB slab slots: 80 x 10 chunks <= one transfer per wave)
-        }
-    }
-    return hp.lds <= 160 * 1024;
-}
-
 template <typename T, int BMT, int BN, int WM, int WN, int KCS, int NS, bool MULTI, bool FASTK, bool XSRC, bool LANEK>
 void launch_fast(const ConvK& k, dim3 grid, hipStream_t st) {
     constexpr int LR_ = 64 * WM * WN / KCS, BNP_ = (BN + LR_ - 1) / LR_ * LR_;       // filter rows padded to whole loader passes
@@ -1650,8 +856,8 @@ void launch_fast(const ConvK& k, dim3 grid, hipStream_t st) {
 enum GatherFamily { GATHER_REGW, GATHER_STREAM, GATHER_HALO, GATHER_SMALL, GATHER_PIPE, GATHER_GENERIC, GATHER_TILE };
 // conv_gather_fast_kernel<T, BM, BN, WM, WN, KCS, NS, MULTI, FASTK, XSRC, LANEK>
 struct TileInst { int bm, bn, wm, wn, kcs, ns; bool multi, fastk, xsrc, lanek; };
-// conv_small_kernel<cpt, bn, nbuf, 3, 3, image ? 2 : 1, u8, waves, epi> with its dynamic LDS and persistent grid
-struct SmallVariant { int cpt, bn, nbuf, waves; bool epi, image, u8; size_t lds; int grid; };
+using din_gather::HaloPlan;
+using din_gather::SmallVariant;
 struct GatherChoice {
     GatherFamily family;
     GatherPlan g;               // the plan after the 256 -> 128 pixel fallbacks (bm, bn, n_px_tiles, n_co_tiles)
@@ -1765,9 +971,6 @@ GatherChoice choose_gather(const ConvK& k0, GatherPlan g, int dtype) {
     ConvK k = k0;                                          // (the eligibility rules below read the plan fields from the argument block)
     set_plan_fields(k, c);
     const bool single = !k.remap && k.nsrc == 0 && k.csplit == 0;
-    const bool mask8 = !(k.flags & DIN_CONV_MASK) || (k.ldm % 8 == 0 && k.moff % 8 == 0);
-    const bool views_2g = (long long)k.H * k.W * k.ldi * 2 < 0x7fffffffll && (long long)k.OH * k.OW * k.ldo * 2 < 0x7fffffffll &&
-                          (long long)k.OH * k.OW * (k.ldm > 0 ? k.ldm : 1) * 2 < 0x7fffffffll;
     if (fast && g.splitk == 1 && k.xsteps == 0) {
         // 1x1 layers with a 640..768-channel reduction over a large map (the Mixed_6 block entries): filters resident in registers (conv_regw.hip)
         if (din_gather::conv1x1_regw_eligible(k, dtype)) {
@@ -1779,53 +982,19 @@ GatherChoice choose_gather(const ConvK& k0, GatherPlan g, int dtype) {
         // 1x1 layers with a short reduction over a large map: persistent streaming kernel (conv_stream.hip)
         if (din_gather::conv1x1_stream_eligible(k, dtype)) { c.family = GATHER_STREAM; c.bn = din_gather::conv1x1_stream_tile(k.Cout); return c; }
     }
-    // mid-network multi-tap layers: halo tiles + filter-slab ring (conv_halo_kernel); the stem shapes keep their own kernel below
+    // mid-network multi-tap layers: halo tiles + filter-slab ring (conv_halo.hip); the stem shapes keep their own kernel below
     const bool stem_shape = k.kh == 3 && k.kw == 3 && (k.Cin == 32 || k.Cin == 64) && k.Cout <= 64 && !(k.Cin == 64 && k.Cout > 32) && (int64_t)k.M >= 256 * 1024;
     if (fast && single && g.splitk == 1 && !stem_shape && k.ay == 1 && k.ax == 1 && (k.cy == 1 || k.cy == -1) && (k.cx == 1 || k.cx == -1) && k.cy == k.cx &&
         k.out_sy == 0 && k.ldi % 8 == 0 && k.cioff % 8 == 0 && k.ldo % 4 == 0 && k.cooff % 4 == 0 &&
-        (!(k.flags & DIN_CONV_MASK) || (k.ldm % 4 == 0 && k.moff % 4 == 0)) && views_2g &&
-        plan_halo(dtype, k.kh, k.kw, k.Cin, k.Cout, k.OH, k.OW, k.M, c.halo)) {
+        (!(k.flags & DIN_CONV_MASK) || (k.ldm % 4 == 0 && k.moff % 4 == 0)) && din_gather::views_below_2g(k) &&
+        din_gather::plan_halo(dtype, k.kh, k.kw, k.Cin, k.Cout, k.OH, k.OW, k.M, c.halo)) {
         c.family = GATHER_HALO; c.bn = c.halo.bn; c.n_co_tiles = c.halo.n_co_tiles;
         return c;
     }
-    {   // stem layers: stationary filters + halo tiles (conv_small_kernel)
-        const bool common = conv_small_wanted() && dtype == DIN_BF16 && fast && single && g.splitk == 1 && k.kh == 3 && k.kw == 3 &&
-                            k.Cout <= 64 && k.Cout % 8 == 0 && k.cooff % 8 == 0 && k.ldo % 8 == 0 && k.ldi % 8 == 0 && k.cioff % 8 == 0 &&
-                            mask8 && views_2g && k.out_sy == 0 && (int64_t)k.M >= 256 * 1024;
-        // 32/64-channel 3x3 stride-1 layers (fwd and dgrad) ...
-        const bool stem = common && (g.cpt == 4 || g.cpt == 8) && g.cpt * 8 == k.Cin && k.ay == 1 && k.ax == 1 &&
-                          (k.cy == 1 || k.cy == -1) && (k.cx == 1 || k.cx == -1) && !(g.cpt == 8 && k.Cout > 32);
-        // ... and the image layer: <= 8 (zero-padded) channels per pixel, stride 2, forward only
-        const bool image = common && g.cpt == 1 && k.Cin <= 8 && k.ldi >= 8 && k.Cout <= 32 && k.ay == 2 && k.ax == 2 && k.cy == 1 && k.cx == 1 &&
-                           k.wld >= 12;
-        if (stem || image) {
-            SmallVariant& s = c.small;
-            s.cpt = g.cpt; s.bn = k.Cout <= 32 ? 32 : 64; s.image = image; s.u8 = k.u8 != nullptr;
-            const int st_ = image ? 2 : 1;
-            const int hpx = (7 * st_ + 3) * (31 * st_ + 3);
-            const int hbytes = (hpx * g.cpt * 16 + 1023) / 1024 * 1024;
-            // 128-byte pixels (the 64-channel dgrad of Conv2d_2b): one halo buffer (80 KiB) or -- DIN_CONV_SMALL_NBUF8=2 -- two (124 KiB, the next
-            // halo in flight under this tile's MFMAs like the 64-byte-pixel variants); one workgroup per CU either way
-            const bool two8 = g.cpt == 8 && opt_int(DIN_OPT("DIN_CONV_SMALL_NBUF8"), 0) == 2;
-            s.lds = (size_t)(image ? 3 * s.bn * 64 : 9 * s.bn * g.cpt * 16) + (size_t)((g.cpt == 8 && !two8) ? 1 : 2) * hbytes + (s.u8 ? 512 : 0);   // (+ the uint8 -> bf16 table)
-            // the image layer's 42 KiB workgroups fit three to a CU: 768 persistent workgroups measured 690 -> 618 us on the 96 frames
-            // (1024: no better, four do not fit); DIN_CONV_IMAGE_GRID overrides
-            const int gv = opt_int(DIN_OPT("DIN_CONV_IMAGE_GRID"), 0);
-            s.grid = image ? (gv > 0 ? gv : 768) : 512;
-            // dgrad launches with a mask / accumulate operand: the variant that requests them a tile phase early (DIN_CONV_SMALL_EPI=0: in the store loop)
-            const bool epi = (k.flags & (DIN_CONV_MASK | DIN_CONV_ACCUM)) && opt_int(DIN_OPT("DIN_CONV_SMALL_EPI"), 1) != 0;
-            // the two 80 KiB variants (one workgroup per CU) run on eight waves; DIN_CONV_SMALL_WAVES=4 restores four
-            // (64-byte pixels x 32 filters: eight waves measured slower, 706 -> 765 us)
-            const bool w8 = !image && !(g.cpt == 4 && s.bn == 32) && opt_int(DIN_OPT("DIN_CONV_SMALL_WAVES"), 8) != 4;
-            s.waves = w8 ? 8 : 4;
-            s.nbuf = (g.cpt == 8 && !(two8 && w8)) ? 1 : 2;
-            s.epi = epi && !image && ((g.cpt == 4 && s.bn == 32) || (g.cpt == 8 && w8));     // (the instantiations that exist)
-            c.family = GATHER_SMALL; c.bn = s.bn;
-            return c;
-        }
-    }
+    // stem layers: stationary filters + halo tiles (conv_small.hip)
+    if (din_gather::conv_small_variant(k, dtype, c.small)) { c.family = GATHER_SMALL; c.bn = c.small.bn; return c; }
     if (fast && !k.remap && k.nsrc == 0 && want_gather_pipe(dtype, k.M, k.Cin, k.kh * k.kw, g.bn, g.splitk, g.n_co_tiles) &&
-        g.cpt % 4 == 0 && k.Cout % 8 == 0 && k.cooff % 8 == 0 && k.ldo % 8 == 0 && mask8 &&
+        g.cpt % 4 == 0 && k.Cout % 8 == 0 && k.cooff % 8 == 0 && k.ldo % 8 == 0 && din_gather::mask_views_aligned8(k) &&
         (k.csplit == 0 || (k.csplit % 8 == 0 && k.ldo2 % 8 == 0 && k.cooff2 % 8 == 0))) {
         c.family = GATHER_PIPE;
         return c;
@@ -1836,47 +1005,87 @@ GatherChoice choose_gather(const ConvK& k0, GatherPlan g, int dtype) {
     return c;
 }
 
-// The one table from a chosen TileInst to its template instantiation: every conv_gather_fast_kernel the library holds is a row here (some
-// are reached only through an experiment switch of a -DDIN_EXPERIMENTS build).  false: no such instantiation.
+// Every conv_gather_fast_kernel the library holds, X(BM, BN, WM, WN, KCS, NS, MULTI, FASTK, XSRC, LANEK): DIN_CONV_TILE_TABLE for every operand
+// type (four waves, the general loop on eight, the multi-source forms), DIN_CONV_TILE_BF16_TABLE for bf16 alone (256-pixel tiles, the extra
+// 1x1 source of din_conv_dgrad_x, the scalar and per-lane k-walks, the three-stage ring), DIN_CONV_TILE_EXPERIMENTS_TABLE (bf16) for what only
+// an experiment switch of a -DDIN_EXPERIMENTS build reaches.  The generic kernel: X(BN), every operand type.
+#define DIN_CONV_TILE_TABLE(X)                                                                                                          \
+    X(256, 64, 4, 1, 4, 4, 0, 0, 0, 0) X(256, 64, 4, 1, 8, 2, 0, 0, 0, 0)                                                               \
+    X(128, 64, 2, 2, 8, 3, 0, 0, 0, 0) X(128, 64, 2, 2, 8, 2, 0, 0, 0, 0) X(128, 96, 2, 2, 8, 2, 0, 0, 0, 0) X(128, 128, 2, 2, 4, 4, 0, 0, 0, 0) \
+    X(128, 128, 2, 2, 8, 2, 0, 0, 0, 0) X(128, 160, 2, 2, 8, 2, 0, 0, 0, 0) X(128, 192, 2, 2, 8, 2, 0, 0, 0, 0)                         \
+    X(128, 64, 4, 2, 8, 2, 0, 0, 0, 0) X(128, 96, 4, 2, 8, 2, 0, 0, 0, 0) X(128, 128, 4, 2, 8, 2, 0, 0, 0, 0) X(128, 160, 4, 2, 8, 2, 0, 0, 0, 0) \
+    X(128, 192, 4, 2, 8, 2, 0, 0, 0, 0)                                                                                                 \
+    X(128, 64, 4, 2, 8, 2, 1, 0, 0, 0) X(128, 64, 2, 2, 8, 2, 1, 0, 0, 0) X(128, 96, 4, 2, 8, 2, 1, 0, 0, 0) X(128, 96, 2, 2, 8, 2, 1, 0, 0, 0) \
+    X(128, 128, 4, 2, 8, 2, 1, 0, 0, 0) X(128, 128, 2, 2, 8, 2, 1, 0, 0, 0) X(128, 160, 4, 2, 8, 2, 1, 0, 0, 0) X(128, 160, 2, 2, 8, 2, 1, 0, 0, 0) \
+    X(128, 192, 4, 2, 8, 2, 1, 0, 0, 0) X(128, 192, 2, 2, 8, 2, 1, 0, 0, 0)
+#define DIN_CONV_TILE_BF16_TABLE(X)                                                                                                     \
+    X(256, 256, 4, 2, 4, 4, 0, 0, 0, 0) X(256, 256, 4, 2, 8, 2, 0, 0, 0, 0) X(256, 128, 4, 2, 4, 4, 0, 0, 0, 0) X(256, 128, 4, 2, 8, 2, 0, 0, 0, 0) \
+    X(256, 96, 2, 2, 8, 2, 0, 0, 0, 0) X(256, 160, 2, 2, 8, 2, 0, 0, 0, 0) X(256, 192, 4, 2, 8, 2, 0, 0, 0, 0)                          \
+    X(256, 192, 8, 2, 8, 2, 0, 0, 0, 0) X(256, 192, 8, 2, 8, 2, 0, 1, 0, 0)                                                             \
+    X(128, 96, 4, 2, 8, 2, 0, 0, 1, 0)                                                                                                  \
+    X(128, 192, 2, 4, 8, 2, 0, 0, 0, 0) X(128, 192, 2, 4, 8, 2, 0, 1, 0, 0)                                                             \
+    X(128, 64, 4, 2, 8, 2, 0, 1, 0, 0) X(128, 128, 4, 2, 8, 2, 0, 1, 0, 0) X(128, 160, 4, 2, 8, 2, 0, 1, 0, 0) X(128, 192, 4, 2, 8, 2, 0, 1, 0, 0) \
+    X(128, 64, 4, 2, 8, 2, 0, 1, 0, 1) X(128, 128, 4, 2, 8, 2, 0, 1, 0, 1) X(128, 160, 4, 2, 8, 2, 0, 1, 0, 1) X(128, 192, 4, 2, 8, 2, 0, 1, 0, 1) \
+    X(128, 160, 4, 2, 4, 3, 0, 0, 0, 0) X(128, 192, 4, 2, 4, 3, 0, 0, 0, 0)
+#ifdef DIN_EXPERIMENTS
+#define DIN_CONV_TILE_EXPERIMENTS_TABLE(X)                                                                                              \
+    X(256, 160, 8, 2, 8, 2, 0, 0, 0, 0) X(256, 160, 8, 2, 8, 2, 0, 1, 0, 0) X(256, 128, 8, 2, 8, 2, 0, 0, 0, 0) X(256, 128, 8, 2, 8, 2, 0, 1, 0, 0) \
+    X(128, 128, 2, 2, 4, 2, 0, 1, 0, 0) X(128, 160, 2, 2, 4, 2, 0, 1, 0, 0) X(128, 192, 2, 2, 4, 2, 0, 1, 0, 0)
+#else
+#define DIN_CONV_TILE_EXPERIMENTS_TABLE(X)
+#endif
+#define DIN_CONV_GENERIC_TABLE(X) X(64) X(128)
+
+// The table row of a chosen tile / generic kernel for operand type T: launched when `k` is given, only looked up otherwise.  false: no row.
 template <typename T>
-bool launch_tile(const ConvK& k, const TileInst& t, dim3 grid, hipStream_t st) {
-#define DIN_TILE(BM_, BN_, WM_, WN_, KCS_, NS_, MULTI_, FASTK_, XSRC_, LANEK_)                                                           \
-    if (t.bm == BM_ && t.bn == BN_ && t.wm == WM_ && t.wn == WN_ && t.kcs == KCS_ && t.ns == NS_ && t.multi == MULTI_ && t.fastk == FASTK_ && \
-        t.xsrc == XSRC_ && t.lanek == LANEK_) {                                                                                         \
-        launch_fast<T, BM_, BN_, WM_, WN_, KCS_, NS_, MULTI_, FASTK_, XSRC_, LANEK_>(k, grid, st);                                         \
+bool tile_row(const TileInst& t, const ConvK* k, dim3 grid, hipStream_t st) {
+#define DIN_ROW(BM_, BN_, WM_, WN_, KCS_, NS_, MULTI_, FASTK_, XSRC_, LANEK_)                                                            \
+    if (t.bm == BM_ && t.bn == BN_ && t.wm == WM_ && t.wn == WN_ && t.kcs == KCS_ && t.ns == NS_ && t.multi == (bool)MULTI_ &&          \
+        t.fastk == (bool)FASTK_ && t.xsrc == (bool)XSRC_ && t.lanek == (bool)LANEK_) {                                                  \
+        if (k) launch_fast<T, BM_, BN_, WM_, WN_, KCS_, NS_, MULTI_, FASTK_, XSRC_, LANEK_>(*k, grid, st);                               \
         return true;                                                                                                                    \
     }
-#define DIN_TILE_PLAIN(BM_, BN_, WM_, WN_, KCS_, NS_) DIN_TILE(BM_, BN_, WM_, WN_, KCS_, NS_, false, false, false, false)
-#define DIN_TILE_WALKS(BM_, BN_, WM_, WN_, KCS_, NS_) DIN_TILE_PLAIN(BM_, BN_, WM_, WN_, KCS_, NS_) DIN_TILE(BM_, BN_, WM_, WN_, KCS_, NS_, false, true, false, false)
-#define DIN_TILE_MULTI(BN_) DIN_TILE(128, BN_, 4, 2, 8, 2, true, false, false, false) DIN_TILE(128, BN_, 2, 2, 8, 2, true, false, false, false)
-    // fp32 and bf16: four waves, and the general loop on eight
-    DIN_TILE_PLAIN(256, 64, 4, 1, 4, 4) DIN_TILE_PLAIN(256, 64, 4, 1, 8, 2)
-    DIN_TILE_PLAIN(128, 64, 2, 2, 8, 3) DIN_TILE_PLAIN(128, 64, 2, 2, 8, 2) DIN_TILE_PLAIN(128, 96, 2, 2, 8, 2) DIN_TILE_PLAIN(128, 128, 2, 2, 4, 4)
-    DIN_TILE_PLAIN(128, 128, 2, 2, 8, 2) DIN_TILE_PLAIN(128, 160, 2, 2, 8, 2) DIN_TILE_PLAIN(128, 192, 2, 2, 8, 2)
-    DIN_TILE_PLAIN(128, 64, 4, 2, 8, 2) DIN_TILE_PLAIN(128, 96, 4, 2, 8, 2) DIN_TILE_PLAIN(128, 128, 4, 2, 8, 2) DIN_TILE_PLAIN(128, 160, 4, 2, 8, 2)
-    DIN_TILE_PLAIN(128, 192, 4, 2, 8, 2)
-    DIN_TILE_MULTI(64) DIN_TILE_MULTI(96) DIN_TILE_MULTI(128) DIN_TILE_MULTI(160) DIN_TILE_MULTI(192)
+    DIN_CONV_TILE_TABLE(DIN_ROW)
     if constexpr (sizeof(T) == 2) {
-        DIN_TILE_PLAIN(256, 256, 4, 2, 4, 4) DIN_TILE_PLAIN(256, 256, 4, 2, 8, 2) DIN_TILE_PLAIN(256, 128, 4, 2, 4, 4) DIN_TILE_PLAIN(256, 128, 4, 2, 8, 2)
-        DIN_TILE_PLAIN(256, 96, 2, 2, 8, 2) DIN_TILE_PLAIN(256, 160, 2, 2, 8, 2) DIN_TILE_PLAIN(256, 192, 4, 2, 8, 2) DIN_TILE_WALKS(256, 192, 8, 2, 8, 2)
-        DIN_TILE(128, 96, 4, 2, 8, 2, false, false, true, false)                                      // + the extra 1x1 source of din_conv_dgrad_x
-        DIN_TILE_WALKS(128, 192, 2, 4, 8, 2)
-        DIN_TILE(128, 64, 4, 2, 8, 2, false, true, false, false) DIN_TILE(128, 128, 4, 2, 8, 2, false, true, false, false)
-        DIN_TILE(128, 160, 4, 2, 8, 2, false, true, false, false) DIN_TILE(128, 192, 4, 2, 8, 2, false, true, false, false)
-        DIN_TILE(128, 64, 4, 2, 8, 2, false, true, false, true) DIN_TILE(128, 128, 4, 2, 8, 2, false, true, false, true)
-        DIN_TILE(128, 160, 4, 2, 8, 2, false, true, false, true) DIN_TILE(128, 192, 4, 2, 8, 2, false, true, false, true)
-        DIN_TILE_PLAIN(128, 160, 4, 2, 4, 3) DIN_TILE_PLAIN(128, 192, 4, 2, 4, 3)
-#ifdef DIN_EXPERIMENTS
-        DIN_TILE_WALKS(256, 160, 8, 2, 8, 2) DIN_TILE_WALKS(256, 128, 8, 2, 8, 2)
-        DIN_TILE(128, 128, 2, 2, 4, 2, false, true, false, false) DIN_TILE(128, 160, 2, 2, 4, 2, false, true, false, false)
-        DIN_TILE(128, 192, 2, 2, 4, 2, false, true, false, false)
-#endif
+        DIN_CONV_TILE_BF16_TABLE(DIN_ROW)
+        DIN_CONV_TILE_EXPERIMENTS_TABLE(DIN_ROW)
     }
-#undef DIN_TILE_MULTI
-#undef DIN_TILE_WALKS
-#undef DIN_TILE_PLAIN
-#undef DIN_TILE
+#undef DIN_ROW
     return false;
+}
+template <typename T>
+bool generic_row(int bn, const ConvK* k, dim3 grid, hipStream_t st) {
+#define DIN_ROW(BN_)                                                                                                                     \
+    if (bn == BN_) {                                                                                                                     \
+        if (k) hipLaunchKernelGGL((conv_gather_generic_kernel<T, BN_>), grid, dim3(NTHREADS), 2 * (BM + 128) * KC * 16, st, *k);         \
+        return true;                                                                                                                     \
+    }
+    DIN_CONV_GENERIC_TABLE(DIN_ROW)
+#undef DIN_ROW
+    return false;
+}
+
+// a GATHER_TILE / GATHER_GENERIC choice as the reporters spell its kernel (k: the argument block with its plan fields set)
+std::string tile_kernel_name(const ConvK& k, const GatherChoice& c, int dtype) {
+    const char* T = k.mma ? "f32x3" : dtype == DIN_F32 ? "float" : "bf16";
+    const TileInst& t = c.tile;
+    char s[160];
+    if (c.family == GATHER_GENERIC) snprintf(s, sizeof s, "conv_gather_generic_kernel<%s,%d>", T, t.bn);
+    else snprintf(s, sizeof s, "conv_gather_fast_kernel<%s,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", T, t.bm, t.bn, t.wm, t.wn, t.kcs, t.ns, (int)t.multi,
+                  (int)t.fastk, (int)t.xsrc, (int)t.lanek);
+    return s;
+}
+
+// ... and its table row, launched (launch_choice) or only looked up (append_kernel_names): a tuple without a row is an error from both
+int tile_choice_row(const ConvK& k, const GatherChoice& c, int dtype, bool launch, hipStream_t st, const char* what) {
+    const dim3 grid(c.g.n_px_tiles * k.n_co_tiles, k.splitk);
+    const ConvK* kl = launch ? &k : nullptr;
+    auto row = [&](auto tag) {
+        using T = decltype(tag);
+        return c.family == GATHER_TILE ? tile_row<T>(c.tile, kl, grid, st) : generic_row<T>(c.tile.bn, kl, grid, st);
+    };
+    if (k.mma ? row(f32x3_t{}) : dtype == DIN_F32 ? row(float{}) : row(bf16_t{})) return DIN_OK;
+    DIN_FAIL(DIN_E_ARG, "%s: %s is not instantiated", what, tile_kernel_name(k, c, dtype).c_str());
 }
 
 // launches the chosen kernel on an argument block whose plan fields are set (set_plan_fields)
@@ -1888,64 +1097,19 @@ int launch_choice(ConvK& k, const GatherChoice& c, int dtype, hipStream_t st, co
     case GATHER_STREAM:
         if (din_gather::launch_conv1x1_stream(k, st)) DIN_FAIL(DIN_E_LAUNCH, "%s: conv1x1_stream launch failed", what);
         return DIN_OK;
-    case GATHER_HALO: {
-        const HaloPlan& hp = c.halo;
-        const int tiles = ((k.OH + hp.th - 1) / hp.th) * ((k.OW + hp.tw - 1) / hp.tw) * k.NB * hp.n_co_tiles;
-        auto launch = [&](auto kern) {
-            raise_lds_limit(kern, hp.lds);
-            hipLaunchKernelGGL(kern, dim3(tiles < 256 ? tiles : 256), dim3(64 * hp.nwv), hp.lds, st, k);
-        };
-        if (k.kh == 3 && k.kw == 3 && hp.nwv == 16) {
-            if (hp.bn == 64) launch(conv_halo_kernel<64, 3, 3, 8, 32, 2, 16>);
-            else if (hp.bn == 80) launch(conv_halo_kernel<80, 3, 3, 8, 32, 2, 16>);
-            else launch(conv_halo_kernel<96, 3, 3, 8, 32, 2, 16>);
-        }
-        else if (k.kh == 3 && k.kw == 3) { if (hp.bn == 64) launch(conv_halo_kernel<64, 3, 3, 8, 32, 3>); else launch(conv_halo_kernel<96, 3, 3, 8, 32, 3>); }
-        else if (k.kh == 1 && k.kw == 7) { if (hp.bn == 64) launch(conv_halo_kernel<64, 1, 7, 16, 16, 3>); else launch(conv_halo_kernel<96, 1, 7, 16, 16, 3>); }
-        else { if (hp.bn == 64) launch(conv_halo_kernel<64, 7, 1, 16, 16, 3>); else launch(conv_halo_kernel<96, 7, 1, 16, 16, 3>); }
+    case GATHER_HALO:
+        if (int e = din_gather::launch_conv_halo(k, c.halo, st)) return e;
         break;
-    }
-    case GATHER_SMALL: {
-        const SmallVariant& s = c.small;
-        auto launch = [&](auto kern) {
-            if (s.lds > 65536) raise_lds_limit(kern, s.lds);
-            hipLaunchKernelGGL(kern, dim3(s.grid), dim3(64 * s.waves), s.lds, st, k);
-        };
-        if (s.image && s.u8) launch(conv_small_kernel<1, 32, 2, 3, 3, 2, true>);
-        else if (s.image) launch(conv_small_kernel<1, 32, 2, 3, 3, 2>);
-        else if (s.cpt == 4 && s.bn == 32) { if (s.epi) launch(conv_small_kernel<4, 32, 2, 3, 3, 1, false, 4, true>); else launch(conv_small_kernel<4, 32, 2, 3, 3, 1>); }
-        else if (s.cpt == 4) { if (s.waves == 8) launch(conv_small_kernel<4, 64, 2, 3, 3, 1, false, 8>); else launch(conv_small_kernel<4, 64, 2, 3, 3, 1>); }
-        else if (s.waves == 4) launch(conv_small_kernel<8, 32, 1, 3, 3, 1>);
-        else if (s.nbuf == 2) { if (s.epi) launch(conv_small_kernel<8, 32, 2, 3, 3, 1, false, 8, true>); else launch(conv_small_kernel<8, 32, 2, 3, 3, 1, false, 8>); }
-        else { if (s.epi) launch(conv_small_kernel<8, 32, 1, 3, 3, 1, false, 8, true>); else launch(conv_small_kernel<8, 32, 1, 3, 3, 1, false, 8>); }
+    case GATHER_SMALL:
+        if (int e = din_gather::launch_conv_small(k, c.small, st)) return e;
         break;
-    }
     case GATHER_PIPE:
         if (int e = din_gather::launch_gather_pipe(k, c.g.bn, (k.M + 255) / 256, st)) return e;
         break;
-    case GATHER_GENERIC: {
-        const dim3 grid(c.g.n_px_tiles * k.n_co_tiles, k.splitk);
-        const size_t lds = 2 * (BM + 128) * KC * 16;
-        if (k.mma) {
-            if (c.tile.bn == 64) hipLaunchKernelGGL((conv_gather_generic_kernel<f32x3_t, 64>), grid, dim3(NTHREADS), lds, st, k);
-            else hipLaunchKernelGGL((conv_gather_generic_kernel<f32x3_t, 128>), grid, dim3(NTHREADS), lds, st, k);
-        } else if (dtype == DIN_F32) {
-            if (c.tile.bn == 64) hipLaunchKernelGGL((conv_gather_generic_kernel<float, 64>), grid, dim3(NTHREADS), lds, st, k);
-            else hipLaunchKernelGGL((conv_gather_generic_kernel<float, 128>), grid, dim3(NTHREADS), lds, st, k);
-        } else {
-            if (c.tile.bn == 64) hipLaunchKernelGGL((conv_gather_generic_kernel<bf16_t, 64>), grid, dim3(NTHREADS), lds, st, k);
-            else hipLaunchKernelGGL((conv_gather_generic_kernel<bf16_t, 128>), grid, dim3(NTHREADS), lds, st, k);
-        }
+    case GATHER_GENERIC:
+    case GATHER_TILE:
+        if (int e = tile_choice_row(k, c, dtype, true, st, what)) return e;
         break;
-    }
-    case GATHER_TILE: {
-        const dim3 grid(c.g.n_px_tiles * k.n_co_tiles, k.splitk);
-        const TileInst& t = c.tile;
-        if (!(k.mma ? launch_tile<f32x3_t>(k, t, grid, st) : dtype == DIN_F32 ? launch_tile<float>(k, t, grid, st) : launch_tile<bf16_t>(k, t, grid, st)))
-            DIN_FAIL(DIN_E_LAUNCH, "%s: no conv_gather_fast_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d> for dtype %d", what, t.bm, t.bn, t.wm, t.wn, t.kcs,
-                     t.ns, (int)t.multi, (int)t.fastk, (int)t.xsrc, (int)t.lanek, dtype);
-        break;
-    }
     }
     DIN_CHECK_LAUNCH(what);
     return DIN_OK;
@@ -2025,7 +1189,8 @@ static ConvK conv_k_of(const din_conv_desc* d, int which, const ParityClass* pc 
     const int esz = d->dtype == DIN_F32 ? 4 : 2;
     ConvK k{};
     k.NB = d->nb; k.kh = d->kh; k.kw = d->kw;
-    k.w_bytes = din_conv_packed_elems(d, which) * esz;
+    const PackGeom bank = pack_geom(d, which);
+    k.w_bytes = (long long)bank.rows_pad * bank.kelems * esz;
     if (which == 0) {
         k.H = d->h; k.W = d->w; k.Cin = d->cin; k.ldi = d->ldi; k.cioff = d->cioff;
         k.OH = d->oh; k.OW = d->ow; k.Cout = d->cout; k.ldo = d->ldo; k.cooff = d->cooff;
@@ -2047,14 +1212,13 @@ static ConvK conv_k_of(const din_conv_desc* d, int which, const ParityClass* pc 
         k.M = d->nb * d->h * d->w;
         return k;
     }
-    const int epc = epc_of(d->dtype);
     const bool taps = pc->khs > 0 && pc->kws > 0;
     k.kh = taps ? pc->khs : 0; k.kw = taps ? pc->kws : 1;
     k.ay = 1; k.by = (pc->py + d->ph - pc->r0c) / d->sh; k.cy = -1; k.divy = 1;
     k.ax = 1; k.bx = (pc->px + d->pw - pc->s0c) / d->sw; k.cx = -1; k.divx = 1;
     k.OH = pc->Ha; k.OW = pc->Wa; k.M = d->nb * pc->Ha * pc->Wa;
     k.out_sy = d->sh; k.out_sx = d->sw; k.out_y0 = pc->py; k.out_x0 = pc->px; k.out_H = d->h; k.out_W = d->w;
-    k.remap = 1; k.wld = (d->kh * d->kw * (pad_to(d->cout, epc) / epc) + KC - 1) / KC * KC;           // rows of the full packed bank
+    k.remap = 1; k.wld = bank.nk * KC;                                                                // rows of the full packed bank
     for (int rr = 0; rr < pc->khs; ++rr)
         for (int ss = 0; ss < pc->kws; ++ss) k.wtap[rr * pc->kws + ss] = (unsigned char)((pc->r0c + d->sh * rr) * d->kw + (pc->s0c + d->sw * ss));
     return k;
@@ -2093,51 +1257,45 @@ static int for_each_launch(const din_conv_desc* d, int which, int flags, int ldm
 }
 
 // the kernels launch_choice / run_gather launch for a choice, spelled as their instantiations: one line each, appended to `out`.
-// k: the argument block with its plan fields set (set_plan_fields)
-static void append_kernel_names(const ConvK& k, const GatherChoice& c, int dtype, std::string& out) {
-    const char* T = k.mma ? "f32x3" : dtype == DIN_F32 ? "float" : "bf16";
+// k: the argument block with its plan fields set (set_plan_fields).  The halo, stem, tile and generic families answer from the table their
+// launcher walks: a chosen tuple the library does not hold is the launcher's error here too.
+static int append_kernel_names(const ConvK& k, const GatherChoice& c, int dtype, std::string& out) {
     char line[160];
-    line[0] = 0;
     switch (c.family) {
     case GATHER_REGW: {
         const din_gather::RegwInst i = din_gather::conv1x1_regw_inst(k);
-        snprintf(line, sizeof line, "conv1x1_regw_kernel<%d,%d,%d,%d,%d>", i.nks, (int)i.masked, i.ns, i.occ, i.rt);
+        snprintf(line, sizeof line, "conv1x1_regw_kernel<%d,%d,%d,%d,%d>\n", i.nks, (int)i.masked, i.ns, i.occ, i.rt);
+        out += line;
         break;
     }
     case GATHER_STREAM: {
         const din_gather::StreamInst i = din_gather::conv1x1_stream_inst(k);
-        snprintf(line, sizeof line, "conv1x1_stream_kernel<%d,%d,%d,%d,%d>", i.bn, i.nsw, (int)i.multi, (int)i.epi, (int)i.split);
+        snprintf(line, sizeof line, "conv1x1_stream_kernel<%d,%d,%d,%d,%d>\n", i.bn, i.nsw, (int)i.multi, (int)i.epi, (int)i.split);
+        out += line;
         break;
     }
-    case GATHER_HALO: {                     // (the 8-wave forms leave the wave count to the template's default, as launch_choice spells them)
-        const HaloPlan& hp = c.halo;
-        if (hp.nwv == 16) snprintf(line, sizeof line, "conv_halo_kernel<%d,%d,%d,%d,%d,%d,16>", hp.bn, k.kh, k.kw, hp.th, hp.tw, hp.nsw);
-        else snprintf(line, sizeof line, "conv_halo_kernel<%d,%d,%d,%d,%d,%d>", hp.bn, k.kh, k.kw, hp.th, hp.tw, hp.nsw);
+    case GATHER_HALO:
+        if (int e = din_gather::append_conv_halo_name(k, c.halo, out)) return e;
+        break;
+    case GATHER_SMALL:
+        if (int e = din_gather::append_conv_small_name(c.small, out)) return e;
+        break;
+    case GATHER_PIPE: snprintf(line, sizeof line, "conv_gather_pipe_kernel<%d>\n", c.g.bn); out += line; break;
+    case GATHER_GENERIC:
+    case GATHER_TILE:
+        if (int e = tile_choice_row(k, c, dtype, false, nullptr, "conv_kernel_names")) return e;
+        out += tile_kernel_name(k, c, dtype); out += '\n';
         break;
     }
-    case GATHER_SMALL: {
-        const SmallVariant& s = c.small;
-        snprintf(line, sizeof line, "conv_small_kernel<%d,%d,%d,3,3,%d,%d,%d,%d>", s.cpt, s.bn, s.nbuf, s.image ? 2 : 1, (int)(s.image && s.u8), s.waves, (int)s.epi);
-        break;
-    }
-    case GATHER_PIPE: snprintf(line, sizeof line, "conv_gather_pipe_kernel<%d>", c.g.bn); break;
-    case GATHER_GENERIC: snprintf(line, sizeof line, "conv_gather_generic_kernel<%s,%d>", T, c.tile.bn == 64 ? 64 : 128); break;
-    case GATHER_TILE: {
-        const TileInst& t = c.tile;
-        snprintf(line, sizeof line, "conv_gather_fast_kernel<%s,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", T, t.bm, t.bn, t.wm, t.wn, t.kcs, t.ns, (int)t.multi,
-                 (int)t.fastk, (int)t.xsrc, (int)t.lanek);
-        break;
-    }
-    }
-    out += line; out += '\n';
     if (c.g.splitk > 1) { out += "conv_splitk_finish_kernel<"; out += dtype == DIN_F32 ? "float" : "bf16"; out += ">\n"; }     // (f32x3 reuses <float>)
+    return DIN_OK;
 }
 
 // one launch as append_kernel_names spells it: choose, set the plan fields, append
-static void append_launch_names(ConvK& k, const GatherPlan& g, int dtype, std::string& out) {
+static int append_launch_names(ConvK& k, const GatherPlan& g, int dtype, std::string& out) {
     const GatherChoice c = choose_gather(k, g, dtype);
     set_plan_fields(k, c);
-    append_kernel_names(k, c, dtype, out);
+    return append_kernel_names(k, c, dtype, out);
 }
 
 // the answer of a *_kernel_names entry point: at most buf_bytes bytes (NUL-terminated) written, the bytes the whole answer needs returned
@@ -2302,69 +1460,6 @@ static int run_multi_launch(ConvK& k, const GatherChoice& c, int dtype, int nsrc
 
 extern "C" {
 
-int64_t din_conv_packed_elems(const din_conv_desc* d, int transposed) {
-    if (!d) return 0;
-    const SplitDesc sd(d);
-    int epc = epc_of(d->dtype);
-    int cred = transposed ? d->cout : d->cin, cprod = transposed ? d->cin : d->cout;
-    int cpt = pad_to(cred, epc) / epc;
-    int nk = (d->kh * d->kw * cpt + KC - 1) / KC;
-    return (int64_t)pad_to(cprod, 256) * nk * KC * epc;
-}
-
-int din_conv_pack_weights(const din_conv_desc* d, const float* w, const float* scale, void* wpk, int transposed, void* stream) {
-    DIN_REQUIRE(d && w && wpk, "conv_pack: null pointer");
-    const SplitDesc sd(d);
-    int epc = epc_of(d->dtype);
-    int cred = transposed ? d->cout : d->cin, cprod = transposed ? d->cin : d->cout;
-    int inner_pad = pad_to(cred, epc);
-    int cpt = inner_pad / epc;
-    int nk = (d->kh * d->kw * cpt + KC - 1) / KC;
-    int kelems = nk * KC * epc;
-    int rows_pad = pad_to(cprod, 256);
-    int64_t total = (int64_t)rows_pad * kelems;
-    hipStream_t st = as_stream(stream);
-    if (d->kh == 1 && d->kw == 1 && total >= (1 << 20) && !(DIN_OPT("DIN_PACK_TILES") && atoi(DIN_OPT("DIN_PACK_TILES")) == 0)) {
-        // (tap-major k = channel index for a single tap; the padded tail of every row / the padded rows are written as zeros)
-        dim3 grid((kelems + 63) / 64, (rows_pad + 63) / 64);
-        if (d->dtype == DIN_F32) hipLaunchKernelGGL(conv_pack_1x1_kernel<float>, grid, dim3(256), 0, st, w, scale, (float*)wpk, d->cout, d->cin, rows_pad, kelems, transposed);
-        else hipLaunchKernelGGL(conv_pack_1x1_kernel<bf16_t>, grid, dim3(256), 0, st, w, scale, (bf16_t*)wpk, d->cout, d->cin, rows_pad, kelems, transposed);
-        DIN_CHECK_LAUNCH("conv_pack(1x1)");
-        return DIN_OK;
-    }
-    if (d->dtype == DIN_F32)
-        hipLaunchKernelGGL(conv_pack_kernel<float>, dim3(grid_1d(total, 256)), dim3(256), 0, st, w, scale, (float*)wpk,
-                           d->cout, d->cin, d->kh, d->kw, cprod, rows_pad, cred, inner_pad, kelems, transposed);
-    else
-        hipLaunchKernelGGL(conv_pack_kernel<bf16_t>, dim3(grid_1d(total, 256)), dim3(256), 0, st, w, scale, (bf16_t*)wpk,
-                           d->cout, d->cin, d->kh, d->kw, cprod, rows_pad, cred, inner_pad, kelems, transposed);
-    DIN_CHECK_LAUNCH("conv_pack");
-    return DIN_OK;
-}
-
-int din_conv_pack_desc(const din_conv_desc* d, const float* w, const float* scale, void* wpk, int transposed, din_pack_desc* out) {
-    DIN_REQUIRE(d && w && wpk && out, "conv_pack_desc: null pointer");
-    const SplitDesc sd(d);
-    const int epc = epc_of(d->dtype);
-    const int cred = transposed ? d->cout : d->cin, cprod = transposed ? d->cin : d->cout;
-    const int inner_pad = pad_to(cred, epc), cpt = inner_pad / epc;
-    const int nk = (d->kh * d->kw * cpt + KC - 1) / KC;
-    out->w = (uint64_t)(uintptr_t)w; out->scale = (uint64_t)(uintptr_t)scale; out->out = (uint64_t)(uintptr_t)wpk;
-    out->cout = d->cout; out->cin = d->cin; out->kh = d->kh; out->kw = d->kw;
-    out->rows = cprod; out->rows_pad = pad_to(cprod, 256); out->inner = cred; out->inner_pad = inner_pad; out->kelems = nk * KC * epc;
-    out->transposed = transposed; out->dtype = d->dtype;
-    return DIN_OK;
-}
-
-int din_conv_pack_multi(const din_pack_desc* table, const int32_t* layer_of, const int32_t* chunk_index, int nblocks, int chunk_elems,
-                        void* stream) {
-    DIN_REQUIRE(table && layer_of && chunk_index && nblocks >= 0 && chunk_elems > 0, "conv_pack_multi: bad argument");
-    if (nblocks == 0) return DIN_OK;
-    hipLaunchKernelGGL(conv_pack_multi_kernel, dim3(nblocks), dim3(256), 0, as_stream(stream), table, layer_of, chunk_index, chunk_elems);
-    DIN_CHECK_LAUNCH("conv_pack_multi");
-    return DIN_OK;
-}
-
 int din_conv_kernel_tile(const din_conv_desc* d, int which, int32_t* bm, int32_t* bn) {
     DIN_REQUIRE(d && bm && bn && which >= 0 && which <= 2, "conv_kernel_tile: bad argument");
     const SplitDesc sd(d);
@@ -2409,12 +1504,14 @@ int din_conv_kernel_names(const din_conv_desc* d, int which, int flags, int ldm,
         DIN_REQUIRE(!d->in_u8 && !(flags & (DIN_CONV_BIAS | DIN_CONV_RELU)), "conv_kernel_names: in_u8 / BIAS / RELU are fwd-only");
     }
     static const unsigned char raw_frames = 0;              // stands for the caller's uint8 frames: the selection only asks whether there are any
-    if (which != 2) for_each_launch(d, which, flags, ldm, moff, [&](ConvK& k, const GatherPlan& g, const char*) {
-        if (d->in_u8) k.u8 = &raw_frames;
-        k.mma = sd.split;
-        append_launch_names(k, g, d->dtype, names);
-        return 0;
-    });
+    if (which != 2) {
+        if (int e = for_each_launch(d, which, flags, ldm, moff, [&](ConvK& k, const GatherPlan& g, const char*) {
+                if (d->in_u8) k.u8 = &raw_frames;
+                k.mma = sd.split;
+                return append_launch_names(k, g, d->dtype, names);
+            }))
+            return e;
+    }
     return copy_names(names, buf, buf_bytes);
 }
 
@@ -2475,8 +1572,7 @@ int din_conv_fwd2_kernel_names(const din_conv_desc* d, int ldo2, int cooff2, int
     DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_fwd2_kernel_names: bad argument");
     std::string names;
     if (int e = for_fwd2_launch(d, sd.split, ldo2, cooff2, csplit, craw, flags, [&](ConvK& k, const GatherPlan& g) {
-            append_launch_names(k, g, d->dtype, names);
-            return 0;
+            return append_launch_names(k, g, d->dtype, names);
         }))
         return e;
     return copy_names(names, buf, buf_bytes);
@@ -2519,8 +1615,8 @@ int din_conv_dgrad_x_kernel_names(const din_conv_desc* d, const din_conv_src* x,
     DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_dgrad_x_kernel_names: bad argument");
     std::string names;
     if (int e = for_dgrad_x_launches(d, dtype0, x, ldm, moff, flags,
-            [&](ConvK& k, const GatherPlan& g, const char*) { k.mma = sd.split; append_launch_names(k, g, d->dtype, names); return 0; },
-            [&](ConvK& k, const GatherChoice& c, int sdt) { append_kernel_names(k, c, sdt, names); return 0; }))
+            [&](ConvK& k, const GatherPlan& g, const char*) { k.mma = sd.split; return append_launch_names(k, g, d->dtype, names); },
+            [&](ConvK& k, const GatherChoice& c, int sdt) { return append_kernel_names(k, c, sdt, names); }))
         return e;
     return copy_names(names, buf, buf_bytes);
 }
@@ -2539,39 +1635,9 @@ int din_conv1x1_dgrad_multi_kernel_names(int nsrc, const din_conv_src* srcs, int
     DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv1x1_dgrad_multi_kernel_names: bad argument");
     std::string names;
     if (int e = for_multi_launch(nsrc, srcs, dtype, nb, h, w, cin, ldi, cioff, ldm, moff, flags,
-                                 [&](ConvK& k, const GatherChoice& c, int sdt) { append_kernel_names(k, c, sdt, names); return 0; }))
+                                 [&](ConvK& k, const GatherChoice& c, int sdt) { return append_kernel_names(k, c, sdt, names); }))
         return e;
     return copy_names(names, buf, buf_bytes);
-}
-
-int din_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale,
-                float* shift, int c, void* stream) {
-    DIN_REQUIRE(gamma && beta && mean && var && scale && shift && c > 0, "bn_fold: bad argument");
-    hipLaunchKernelGGL(bn_fold_kernel, dim3((c + 255) / 256), dim3(256), 0, as_stream(stream), gamma, beta, mean, var, eps, scale, shift, c);
-    DIN_CHECK_LAUNCH("bn_fold");
-    return DIN_OK;
-}
-int din_bn_fold_bwd(const float* wdot, const float* dshift, const float* mean, const float* var, float eps, float* dgamma,
-                    float* dbeta, int c, void* stream) {
-    DIN_REQUIRE(wdot && dshift && mean && var && dgamma && dbeta && c > 0, "bn_fold_bwd: bad argument");
-    hipLaunchKernelGGL(bn_fold_bwd_kernel, dim3((c + 255) / 256), dim3(256), 0, as_stream(stream), wdot, dshift, mean, var, eps, dgamma, dbeta, c);
-    DIN_CHECK_LAUNCH("bn_fold_bwd");
-    return DIN_OK;
-}
-
-int din_bn_fold_multi(const uint64_t* ptrs, const int32_t* offs, int n, int total, float eps, float* scale, float* shift, void* stream) {
-    DIN_REQUIRE(ptrs && offs && scale && shift && n > 0 && total > 0, "bn_fold_multi: bad argument");
-    hipLaunchKernelGGL(bn_fold_multi_kernel, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), ptrs, offs, n, total, eps, scale, shift);
-    DIN_CHECK_LAUNCH("bn_fold_multi");
-    return DIN_OK;
-}
-int din_bn_fold_bwd_multi(const uint64_t* ptrs, const int32_t* offs, int n, int total, float eps, const float* wdot, const float* dshift,
-                          float* dgamma, float* dbeta, void* stream) {
-    DIN_REQUIRE(ptrs && offs && wdot && dshift && dgamma && dbeta && n > 0 && total > 0, "bn_fold_bwd_multi: bad argument");
-    hipLaunchKernelGGL(bn_fold_bwd_multi_kernel, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), ptrs, offs, n, total, eps, wdot,
-                       dshift, dgamma, dbeta);
-    DIN_CHECK_LAUNCH("bn_fold_bwd_multi");
-    return DIN_OK;
 }
 
 }  // extern "C"

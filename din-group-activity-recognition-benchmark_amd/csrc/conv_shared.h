@@ -1,5 +1,6 @@
-// Shared between conv_igemm.hip (forward / data gradient) and conv_wgrad.hip (weight gradient): the vector types, the workgroup size of the
-// 256-thread kernels, the uint8 image-layer halo loader of the two stem kernels, and the host helpers both planners use.
+// Shared between the forward / data-gradient sources (conv_igemm.hip, conv_halo.hip, conv_small.hip), conv_pack.hip and conv_wgrad.hip (weight
+// gradient): the vector types, the workgroup size of the 256-thread kernels, the packing granularity and the geometry of a packed filter bank,
+// the MFMA of one 16-byte chunk per storage type, the uint8 image-layer halo loader of the two stem kernels, and the host helpers the planners use.
 #pragma once
 #include "din_common.h"
 #include <stdlib.h>
@@ -12,6 +13,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 namespace {
 
 constexpr int NTHREADS = 256;
+constexpr int KC = 8;        // 16-byte chunks per k-step of a packed filter bank (=> 128 B per tile row)
 
 // ---- DIN_F32_BF16X3: fp32 operands multiplied as three bf16 parts each --------------------------------------------------------
 // x = x0 + x1 + x2 exactly, 8 + 8 + 8 significand bits: x0 = the top 16 bits of x (TRUNCATED, so the high part of a value near FLT_MAX
@@ -47,6 +49,26 @@ __device__ __forceinline__ void mma_f32_bf16x3(const u32x4& a, const u32x4& b, f
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a01), __builtin_bit_cast(bf16x8, b11), c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a01), __builtin_bit_cast(bf16x8, b00), c, 0, 0, 0);
 }
+
+// one 16-byte chunk of each operand into the MFMA, per storage type (conv_igemm.hip: the header comment)
+template <typename T> struct Mma;
+template <> struct Mma<float> {
+    __device__ static void run(const u32x4& a, const u32x4& b, f32x4& c) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[j]), c, 0, 0, 0);
+    }
+};
+// fp32 chunks multiplied as three bf16 parts.  The split is formed per fragment read: inside the unrolled fragment loops of a
+// k-step the compiler forms each fragment's parts once and reuses them across the (i, j) pairs.
+template <> struct Mma<f32x3_t> {
+    __device__ static void run(const u32x4& a, const u32x4& b, f32x4& c) { mma_f32_bf16x3(a, b, c); }
+};
+template <> struct Mma<bf16_t> {
+    __device__ static void run(const u32x4& a, const u32x4& b, f32x4& c) {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+};
 
 // ---- image layer fed from raw uint8 frames (din_conv_desc::in_u8): the halo pixels of a tile are fetched as bytes from the three colour
 //      planes, normalised exactly like utils.prep_images ((x / 255 - 0.5) * 2: three separately rounded fp32 operations, utils.py:8-19),
@@ -126,6 +148,19 @@ struct SplitDesc {
         if (d && d->dtype == DIN_F32_BF16X3) { copy = *d; copy.dtype = DIN_F32; d = &copy; split = true; }
     }
 };
+// The packed filter bank of a descriptor (dtype: the storage type), forward (transposed = 0: row = co, k = (r, s, ci)) or data-gradient
+// orientation (1: row = ci, k = (r, s, co)): cred reduction channels per tap, padded to whole chunks (inner_pad elements = cpt chunks), nk
+// k-steps of KC chunks = kelems elements per row, cprod rows padded to the widest filter tile (rows_pad).
+struct PackGeom { int cred, cprod, inner_pad, cpt, nk, kelems, rows_pad; };
+inline PackGeom pack_geom(const din_conv_desc* d, int transposed) {
+    const int epc = epc_of(d->dtype);
+    PackGeom g;
+    g.cred = transposed ? d->cout : d->cin; g.cprod = transposed ? d->cin : d->cout;
+    g.inner_pad = pad_to(g.cred, epc); g.cpt = g.inner_pad / epc;
+    g.nk = (d->kh * d->kw * g.cpt + KC - 1) / KC; g.kelems = g.nk * KC * epc;
+    g.rows_pad = pad_to(g.cprod, 256);
+    return g;
+}
 // stem layers on conv_small_kernel / conv_wgrad_small_kernel (DIN_CONV_SMALL=0: off); din_conv_accepts_u8 answers from the same switch
 inline bool conv_small_wanted() { return opt_int(DIN_OPT("DIN_CONV_SMALL"), 1) != 0; }
 

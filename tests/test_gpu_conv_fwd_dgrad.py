@@ -259,7 +259,7 @@ def bar_of(row, v, S, splitk, staged=None):
     """the per-element bar of a row for a result v whose absolute-value sum is S.  staged: the (masked) gradient g before the accumulate
     of a row marked twice=True.  Three bf16 kernels stage their output tile in LDS AS bf16 so that it leaves as 16-byte chunks of whole
     pixel rows, and add the old value to that staged element: staged_tile_store of conv_gather_fast_kernel (csrc/conv_gather.h), the last
-    block of conv1x1_stream_kernel (csrc/conv_stream.hip) and the store loop of conv_small_kernel (csrc/conv_igemm.hip), EPI or not.  Two
+    block of conv1x1_stream_kernel (csrc/conv_stream.hip) and the store loop of conv_small_kernel (csrc/conv_small.hip), EPI or not.  Two
     roundings by design: g' = bf16(g) with |g' - g| <= 2^-8 |g| (half an ulp of 8 significand bits), then bf16(g' + old) with an error of
     at most 2^-8 |g' + old| <= 2^-8 (|v| + 2^-8 |g|).  The second is the store the plain bar already holds; the first adds
     2^-8 (1 + 2^-8) |g|, and with the suite's factor 2 those rows' bar grows by 2^-7 (1 + 2^-8) |g|.  (conv_halo_kernel, the split-K finish

@@ -1,4 +1,4 @@
-"""csrc/roi_align.hip, csrc/bn.hip, the colsum kernels of conv_wgrad.hip, the bn_fold* kernels of conv_igemm.hip and the image preparation, frame-index and counter
+"""csrc/roi_align.hip, csrc/bn.hip, the colsum kernels of conv_wgrad.hip, the bn_fold* kernels of conv_pack.hip and the image preparation, frame-index and counter
 kernels of elementwise.hip, called through the C ABI and compared with float64 references written here from the definition of each
 operation, on the stored fp32 / bf16 operands.  The reference is never another kernel of this library.  Every destination is a _Buf
 (guard bands, NaN in the columns outside the view): all of that must come back bit for bit, NaN in unused source columns must reach no

@@ -263,6 +263,100 @@ def test_conv_planning_is_callable_without_gpu():
     assert rc == -1 and b"null" in lib.din_last_error_string()
 
 
+def test_every_reported_fwd_dgrad_kernel_has_a_row_in_its_launch_table():
+    """din_conv_kernel_names over the descriptors tools/conv_dispatch_table.py enumerates (both backbones, bf16 and fp32, with the misaligned
+    views; at the small test geometry and at 96 frames of 720x1280 -- the 12- and 24-frame geometries are left out to keep this test shorter
+    than tests/test_backward_trace_cpu.py), with no option and with every setting of its OPTIONS list, forward and data gradient with flags
+    0 / MASK / ACCUM / MASK | ACCUM: every call succeeds, and every line parses to a kernel family and a template tuple that is a row of the
+    X-macro table the family's launcher walks (DIN_CONV_HALO_TABLE in csrc/conv_halo.hip, DIN_CONV_SMALL_TABLE in csrc/conv_small.hip,
+    DIN_CONV_TILE_TABLE / DIN_CONV_TILE_BF16_TABLE / DIN_CONV_GENERIC_TABLE in csrc/conv_igemm.hip; the rows only a -DDIN_EXPERIMENTS build
+    holds do not count).  The register-resident, streaming and gather-pipe families keep no such table: their lines are held to their
+    spelling only."""
+    import re
+    from din_amd import _lib as L, nhwc
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import conv_dispatch_table as D
+    csrc = os.path.join(ROOT, "din-group-activity-recognition-benchmark_amd", "csrc")
+
+    def rows(name, macro):
+        with open(os.path.join(csrc, name)) as fh:
+            text = re.sub(r"//[^\n]*", "", fh.read())
+        body = re.search(r"#define " + macro + r"\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
+        return {re.sub(r"\s+", "", args) for args in re.findall(r"X\(([^()]*)\)", body)}
+
+    halo, small = rows("conv_halo.hip", "DIN_CONV_HALO_TABLE"), rows("conv_small.hip", "DIN_CONV_SMALL_TABLE")
+    tile, tile_bf16 = rows("conv_igemm.hip", "DIN_CONV_TILE_TABLE"), rows("conv_igemm.hip", "DIN_CONV_TILE_BF16_TABLE")
+    generic = rows("conv_igemm.hip", "DIN_CONV_GENERIC_TABLE")
+    assert (len(halo), len(small), len(tile), len(tile_bf16), len(generic)) == (9, 11, 24, 22, 2)
+
+    def held(line):
+        m = re.fullmatch(r"(\w+)<([\w,]+)>", line)
+        assert m, line
+        family, args = m.group(1), m.group(2)
+        if family == "conv_halo_kernel":                       # (the 8-wave forms are spelled without the wave count)
+            return (args if args.count(",") == 6 else args + ",8") in halo
+        if family == "conv_small_kernel":
+            return args in small
+        if family == "conv_gather_fast_kernel":
+            t, tup = args.split(",", 1)
+            return t in ("float", "f32x3", "bf16") and (tup in tile or (t == "bf16" and tup in tile_bf16))
+        if family == "conv_gather_generic_kernel":
+            t, tup = args.split(",", 1)
+            return t in ("float", "f32x3", "bf16") and tup in generic
+        if family == "conv_splitk_finish_kernel":
+            return args in ("float", "bf16")
+        return family in ("conv1x1_regw_kernel", "conv1x1_stream_kernel", "conv_gather_pipe_kernel")
+
+    lib = L.load()
+    cases = []
+    for backbone in ("inv3", "vgg16"):
+        for dt in (L.DIN_BF16, L.DIN_F32):
+            for nb, h, w in ((96, 720, 1280), (6, 139, 203)):
+                descs = D.descriptors(L, nhwc, backbone, nb, h, w, dt)
+                seen = set()
+                for d in descs + D.misaligned(L, nhwc, descs):
+                    key = tuple(getattr(d, f) for f in D.FIELDS)
+                    if key not in seen:
+                        seen.add(key)
+                        cases.append(d)
+    assert len(cases) >= 250, len(cases)
+    reached, calls = set(), 0
+    for opt, val in [(None, None)] + [(o, v) for o, vals in D.OPTIONS for v in vals]:
+        if opt:
+            L.set_option(opt, val)
+        try:
+            for d in cases:
+                if d.in_u8 and not lib.din_conv_accepts_u8(ctypes.byref(d)):
+                    continue                                   # (din_conv_fwd rejects it)
+                launches = [(0, 0)] + ([] if d.in_u8 else [(1, f) for f in (0, L.CONV_MASK, L.CONV_ACCUM, L.CONV_MASK | L.CONV_ACCUM)])
+                for which, flags in launches:
+                    buf = ctypes.create_string_buffer(1024)
+                    rc = lib.din_conv_kernel_names(ctypes.byref(d), which, flags, d.ldi, d.cioff, buf, len(buf))
+                    where = f"{opt}={val} which={which} flags={flags} {[getattr(d, f) for f in D.FIELDS]} dtype={d.dtype}"
+                    assert 0 < rc <= len(buf), f"{where}: {rc} {lib.din_last_error_string()}"
+                    lines = buf.value.decode().split()
+                    assert lines, where
+                    for line in lines:
+                        assert held(line), f"{where}: {line} is no row of its family's table"
+                        reached.add(line.split("<")[0])
+                    calls += 1
+        finally:
+            if opt:
+                L.set_option(opt, None)
+    assert calls >= 40000, calls
+    assert {"conv_halo_kernel", "conv_small_kernel", "conv_gather_fast_kernel", "conv_splitk_finish_kernel"} <= reached, reached
+    # no backbone layer has more than 32 taps or a dilated strided data gradient, so none reaches the generic kernel: one 7x7 layer does
+    d = L.ConvDesc()
+    d.nb, d.h, d.w, d.cin, d.oh, d.ow, d.cout = 2, 56, 56, 16, 56, 56, 72
+    d.kh = d.kw = 7
+    d.ph = d.pw = 3
+    d.sh = d.sw = d.dh = d.dw = 1
+    d.ldi, d.ldo = 16, 72
+    for d.dtype, spelled in ((L.DIN_BF16, "bf16"), (L.DIN_F32, "float"), (L.DIN_F32_BF16X3, "f32x3")):
+        lines = D.kernel_names(lib, d, 0, 0)
+        assert lines[0] == f"conv_gather_generic_kernel<{spelled},128>" and all(held(line) for line in lines), lines
+
+
 def test_state_dict_keys_match_reference_inventory():
     from din_amd.config import Config
     from din_amd.infer_model import Dynamic_volleyball

@@ -8,7 +8,8 @@ din_conv_kernel_variant report it (no GPU needed): one line per case,
 Cases: every distinct conv descriptor of the Inception-v3 trunk (up to Mixed_6e, with the channel-offset views and the fused sibling
 groups nhwc.py lays out) and of VGG16, at 12 / 24 / 96 frames of 720x1280 and at the small test geometry, both dtypes, plus one view
 per kernel family whose channel offsets are not multiples of 8; each with no option set and with every selection option of
-csrc/conv_igemm.hip (choose_gather) set alone to each value its comment documents.
+choose_gather (csrc/conv_igemm.hip) and of the family rules it calls (plan_halo in csrc/conv_halo.hip, conv_small_variant in
+csrc/conv_small.hip, the eligibility rules of csrc/conv_regw.hip and csrc/conv_stream.hip) set alone to each value its comment documents.
 
 The reporter answers from the launcher's own selection function, so two builds that print the same table launch the same kernels:
 
