@@ -167,6 +167,7 @@ SIGNATURES: Dict[str, tuple] = {
     "din_adam_step_multi": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _I, _F, _P]),
     "din_copy_rows_u8": (_I, [_P, _P, _I, _L, _P]),
     "din_feat_rows": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
+    "din_feat_rows_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
 }
 
 _lib = None

@@ -6,7 +6,9 @@ at dynamic_infer_module.py:495; 0.5 keeps that, 0.0 switches it off); frame_cach
 stay in HBM, up to that many GB per dataset, and batches are gathered from them -- din_amd/frame_cache.py; 0 = off) and num_workers (the
 DataLoader worker processes of both trainers; the reference hard-codes 4, train_net_dynamic.py:40-48; 0 = decode in the main process);
 feature_cache_gb (> 0, stage-2 trainer with a frozen backbone only: the fp32 RoIAlign output of every frame stays in HBM, up to that many
-GB per dataset, and a step skips the backbone for resident frames -- din_amd/feature_cache.py; 0 = off).
+GB per dataset, and a step skips the backbone for resident frames -- din_amd/feature_cache.py; 0 = off); feature_cache_dtype ('fp32' |
+'bf16', read only when feature_cache_gb > 0: what the slots hold.  'bf16' needs backbone_dtype = 'bf16', where the embedding GEMM
+multiplies bf16 operands anyway: the row is stored already rounded, half the bytes per frame and no cast pass, the same numbers).
 All are opt-in: at 0 the trainers behave exactly as without them."""
 from __future__ import annotations
 
@@ -28,7 +30,7 @@ _DEFAULTS = dict(
     load_backbone_stage2=False, parallel_inference=False, hierarchical_inference=False, lite_dim=None, num_DIM=1,
     load_stage2model=False, stage2model=None, temporal_pooled_first=False,
     backbone_dtype="fp32", hier_dropout_p=0.5,
-    frame_cache_gb=0, num_workers=0, feature_cache_gb=0,
+    frame_cache_gb=0, num_workers=0, feature_cache_gb=0, feature_cache_dtype="fp32",
 )
 
 

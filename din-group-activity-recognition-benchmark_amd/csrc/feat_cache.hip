@@ -12,6 +12,13 @@
 // before the first store.  The boxes (a few hundred bytes) belong to the row's item 0.  Every access lies inside [src, src + row_bytes),
 // [dst, dst + row_bytes), [keep, keep + row_bytes + box_bytes), [ref_boxes, ref_boxes + box_bytes), boxes[i] or flags[i]; all stores are
 // ordinary vector stores, no atomics: several lanes that see a difference store the same 1.
+//
+// din_feat_rows_bf16: the same launch over slots of bf16 rows (cfg.feature_cache_dtype = 'bf16': under backbone_dtype = 'bf16' the only
+// reader of feats is the embedding GEMM, which used to round the whole tensor to bf16 in a pass of its own).  Rows are row_elems bf16
+// values; a resident row is the copy above at row_bytes = 2 * row_elems.  A row the trunk just computed (src_f32[i] != 0) is row_elems
+// fp32 values at src[i]: read once, rounded once (round-to-nearest-even, the hardware conversion: pack_bf16x2), stored to dst[i] and
+// keep[i].  Items stay DIN_FEAT_ROWS_SEGMENT bytes of the DESTINATION row; a converting lane loads two 16-byte fp32 vectors per 16-byte
+// store, all eight before its first store, and every fp32 read lies inside [src, src + 4 * row_elems).
 #include "din_common.h"
 
 namespace {
@@ -27,10 +34,19 @@ constexpr int64_t SEG = DIN_FEAT_ROWS_SEGMENT;   // bytes of one row per work it
 static_assert(UNROLL == 4 && SEG == (int64_t)BLOCK * UNROLL * 16, "a segment is four 16-byte vectors per lane");
 constexpr int GRID_CAP = 256 * 16;               // workgroups: 256 CUs x 16, the rest of the items block-stride
 
+// eight fp32 values (two 16-byte vectors, lo first in memory) -> eight bf16 values (one 16-byte vector)
+__device__ __forceinline__ u32x4 round_to_bf16(u32x4 lo, u32x4 hi) {
+    return u32x4{pack_bf16x2(__uint_as_float(lo.x), __uint_as_float(lo.y)), pack_bf16x2(__uint_as_float(lo.z), __uint_as_float(lo.w)),
+                 pack_bf16x2(__uint_as_float(hi.x), __uint_as_float(hi.y)), pack_bf16x2(__uint_as_float(hi.z), __uint_as_float(hi.w))};
+}
+
+// BF16 = false: din_feat_rows (src_f32 is not read).  BF16 = true: din_feat_rows_bf16, row_bytes = 2 * row_elems.
+template <bool BF16>
 __global__ __launch_bounds__(BLOCK) void feat_rows_kernel(const uint64_t* __restrict__ src, const uint64_t* __restrict__ dst,
                                                            const uint64_t* __restrict__ keep, const uint64_t* __restrict__ ref_boxes,
-                                                           const uint8_t* __restrict__ boxes, uint8_t* __restrict__ flags,
-                                                           int64_t row_bytes, int box_bytes, int64_t segs, int64_t items) {
+                                                           const uint64_t* __restrict__ src_f32, const uint8_t* __restrict__ boxes,
+                                                           uint8_t* __restrict__ flags, int64_t row_bytes, int box_bytes, int64_t segs,
+                                                           int64_t items) {
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const int64_t row = item / segs, seg = item - row * segs;
         const uint64_t sa = src[row];
@@ -43,12 +59,22 @@ __global__ __launch_bounds__(BLOCK) void feat_rows_kernel(const uint64_t* __rest
         if (b0 < row_bytes) {
             const int64_t left = row_bytes - b0;
             const int64_t nv = (left < SEG ? left : SEG) / 16;
-            gsrc_t s = (gsrc_t)(sa + (uint64_t)b0);
             gdst_t d = (gdst_t)(da + (uint64_t)b0);
             // four named registers, not an array: the compiler moves a conditionally written private array to LDS
             const int64_t i0 = threadIdx.x, i1 = i0 + BLOCK, i2 = i1 + BLOCK, i3 = i2 + BLOCK;
             const u32x4 zero = {0, 0, 0, 0};
-            const u32x4 v0 = i0 < nv ? s[i0] : zero, v1 = i1 < nv ? s[i1] : zero, v2 = i2 < nv ? s[i2] : zero, v3 = i3 < nv ? s[i3] : zero;
+            u32x4 v0, v1, v2, v3;
+            if (BF16 && src_f32 != nullptr && src_f32[row] != 0) {       // a computed fp32 row (uniform over the workgroup)
+                gsrc_t s = (gsrc_t)(sa + 2 * (uint64_t)b0);              // destination vector i is fp32 vectors 2i and 2i + 1
+                const u32x4 a0 = i0 < nv ? s[2 * i0] : zero, c0 = i0 < nv ? s[2 * i0 + 1] : zero;
+                const u32x4 a1 = i1 < nv ? s[2 * i1] : zero, c1 = i1 < nv ? s[2 * i1 + 1] : zero;
+                const u32x4 a2 = i2 < nv ? s[2 * i2] : zero, c2 = i2 < nv ? s[2 * i2 + 1] : zero;
+                const u32x4 a3 = i3 < nv ? s[2 * i3] : zero, c3 = i3 < nv ? s[2 * i3 + 1] : zero;
+                v0 = round_to_bf16(a0, c0), v1 = round_to_bf16(a1, c1), v2 = round_to_bf16(a2, c2), v3 = round_to_bf16(a3, c3);
+            } else {
+                gsrc_t s = (gsrc_t)(sa + (uint64_t)b0);
+                v0 = i0 < nv ? s[i0] : zero, v1 = i1 < nv ? s[i1] : zero, v2 = i2 < nv ? s[i2] : zero, v3 = i3 < nv ? s[i3] : zero;
+            }
             if (i0 < nv) d[i0] = v0;
             if (i1 < nv) d[i1] = v1;
             if (i2 < nv) d[i2] = v2;
@@ -93,8 +119,28 @@ extern "C" int din_feat_rows(const uint64_t* src, const uint64_t* dst, const uin
     DIN_REQUIRE(!(keep || ref_boxes) || (boxes && flags), "feat_rows: keep / ref_boxes given without boxes and flags");
     const int64_t segs = row_bytes > 0 ? ceil_div64(row_bytes, SEG) : 1, items = segs * (int64_t)n;
     const int grid = (int)(items < GRID_CAP ? items : GRID_CAP);
-    hipLaunchKernelGGL(feat_rows_kernel, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, dst, keep, ref_boxes,
-                       static_cast<const uint8_t*>(boxes), flags, row_bytes, box_bytes, segs, items);
+    hipLaunchKernelGGL(feat_rows_kernel<false>, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, dst, keep, ref_boxes,
+                       static_cast<const uint64_t*>(nullptr), static_cast<const uint8_t*>(boxes), flags, row_bytes, box_bytes, segs, items);
     DIN_CHECK_LAUNCH("feat_rows");
+    return DIN_OK;
+}
+
+extern "C" int din_feat_rows_bf16(const uint64_t* src, const uint64_t* dst, const uint64_t* keep, const uint64_t* ref_boxes,
+                                  const uint64_t* src_f32, const void* boxes, uint8_t* flags, int n, int64_t row_elems, int box_bytes,
+                                  void* stream) {
+    DIN_REQUIRE(n >= 0 && row_elems >= 0 && box_bytes >= 0, "feat_rows_bf16: n = %d, row_elems = %lld, box_bytes = %d must not be negative",
+                n, (long long)row_elems, box_bytes);
+    DIN_REQUIRE(row_elems % 8 == 0 && box_bytes % 16 == 0,
+                "feat_rows_bf16: row_elems = %lld must be a multiple of 8 and box_bytes = %d a multiple of 16", (long long)row_elems, box_bytes);
+    DIN_REQUIRE(((uintptr_t)boxes & 15u) == 0, "feat_rows_bf16: boxes must be 16-byte aligned");
+    if (n == 0) return DIN_OK;
+    DIN_REQUIRE(src && dst, "feat_rows_bf16: null address table with n = %d", n);
+    DIN_REQUIRE(!(keep || ref_boxes) || (boxes && flags), "feat_rows_bf16: keep / ref_boxes given without boxes and flags");
+    const int64_t row_bytes = 2 * row_elems;                             // of a destination row: what the items are measured in
+    const int64_t segs = row_bytes > 0 ? ceil_div64(row_bytes, SEG) : 1, items = segs * (int64_t)n;
+    const int grid = (int)(items < GRID_CAP ? items : GRID_CAP);
+    hipLaunchKernelGGL(feat_rows_kernel<true>, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, dst, keep, ref_boxes, src_f32,
+                       static_cast<const uint8_t*>(boxes), flags, row_bytes, box_bytes, segs, items);
+    DIN_CHECK_LAUNCH("feat_rows_bf16");
     return DIN_OK;
 }

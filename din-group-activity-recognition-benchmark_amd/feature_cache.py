@@ -19,6 +19,10 @@ fc_emb_1, the head -- nothing decoded, nothing uploaded, no backbone launch.
 
 Same store as the frame cache (frame_cache.SlotStore): lazy slabs, no eviction, a full cache stops inserting and the remaining frames
 keep being decoded and computed.  Refusals and the cache's lifetime: train_net_dynamic.train_net.
+
+cfg.feature_cache_dtype = 'bf16' (with backbone_dtype = 'bf16' only): the slots hold the row already rounded to bf16, which is what
+fc_emb_1's GEMM multiplies in that mode.  Half the bytes per frame, ONE din_feat_rows_bf16 launch that rounds the computed rows on their
+way to feats and to the slots, and feats arrives as the GEMM's bf16 operand: no cast pass, the same numbers.
 """
 from __future__ import annotations
 
@@ -33,16 +37,21 @@ from .input_feed import DeviceFeed
 
 
 class FeatureCache(SlotStore):
-    """Device-resident store of fp32 box-feature rows: each slot holds `row_bytes` of features followed by the `box_bytes` of the boxes
-    they were computed for.  Filled on first use, never beyond `capacity_bytes`, no eviction."""
+    """Device-resident store of box-feature rows, fp32 or (dtype=torch.bfloat16) rounded to bf16: each slot holds `row_bytes` of
+    features in that dtype followed by the `box_bytes` of the boxes they were computed for.  Filled on first use, never beyond
+    `capacity_bytes`, no eviction."""
 
     WHAT, UNIT = "feature cache", "frames"
     FLAG_ROWS = 1 << 20                              # rows between two check() calls the flags buffer holds without an extra check
 
-    def __init__(self, device, row_bytes: int, box_bytes: int, capacity_bytes: int, chunk_frames: int = 64):
+    def __init__(self, device, row_bytes: int, box_bytes: int, capacity_bytes: int, chunk_frames: int = 64,
+                 dtype: torch.dtype = torch.float32):
         if row_bytes <= 0 or box_bytes <= 0 or row_bytes % 16 or box_bytes % 16:
             raise ValueError(f"FeatureCache: row_bytes {row_bytes} and box_bytes {box_bytes} must be positive multiples of 16")
-        self.row_bytes, self.box_bytes = int(row_bytes), int(box_bytes)
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"FeatureCache: rows are stored as torch.float32 or torch.bfloat16, not {dtype}")
+        self.row_bytes, self.box_bytes, self.dtype = int(row_bytes), int(box_bytes), dtype
+        self.row_elems = self.row_bytes // (4 if dtype == torch.float32 else 2)
         super().__init__(device, self.row_bytes + self.box_bytes, capacity_bytes, chunk_frames)
         self.flags: Optional[torch.Tensor] = None    # one uint8 per row gathered since the last check(); din_feat_rows only ever writes 1
         self._flagged: List[np.ndarray] = []         # the frame ids of those rows, in order
@@ -62,14 +71,15 @@ class FeatureCache(SlotStore):
 
     def rows(self, frame_ids, boxes: torch.Tensor, miss_pos=(), miss_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[int]]:
         """frame_ids [R] (host), boxes fp32 [R, box_bytes / 4] on the device (this step's boxes of every row), miss_pos [M] (host: which
-        of the R rows the computed rows are), miss_rows fp32 [M, row_bytes / 4] on the device -> (fp32 [R, row_bytes / 4] on the device,
+        of the R rows the computed rows are), miss_rows fp32 [M, row_elems] on the device -> (`dtype` [R, row_elems] on the device,
         the frame ids inserted by this call).  One launch on the current stream: a row comes from its slot (and its boxes are compared
         with the slot's) or from the computed row, which also goes into a free slot with its boxes while the cache has room.  A frame
-        that occurs twice is served both times from the computed row, never from the slot written by this launch."""
+        that occurs twice is served both times from the computed row, never from the slot written by this launch.  With bf16 storage
+        the computed rows still arrive as fp32 and the launch rounds them (din_feat_rows_bf16)."""
         from . import ops
         ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
         pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
-        rb, bb = self.row_bytes, self.box_bytes
+        rb, bb, ne = self.row_bytes, self.box_bytes, self.row_elems
         if not boxes.is_cuda or boxes.dtype != torch.float32 or boxes.numel() * 4 != len(ids) * bb:
             raise ValueError(f"rows: {len(ids)} rows need fp32 device boxes of {bb} bytes each, got {tuple(boxes.shape)} {boxes.dtype}")
         boxes = boxes.contiguous()
@@ -77,15 +87,15 @@ class FeatureCache(SlotStore):
             boxes = boxes.clone()
         if len(pos):
             if miss_rows is None or not miss_rows.is_cuda or miss_rows.dtype != torch.float32 or not miss_rows.is_contiguous() \
-                    or tuple(miss_rows.shape) != (len(pos), rb // 4) or miss_rows.data_ptr() % 16:
+                    or tuple(miss_rows.shape) != (len(pos), ne) or miss_rows.data_ptr() % 16:
                 raise ValueError(f"rows: {len(pos)} computed rows need a contiguous, 16-byte aligned fp32 device tensor "
-                                 f"{(len(pos), rb // 4)}, got {None if miss_rows is None else tuple(miss_rows.shape)}")
+                                 f"{(len(pos), ne)}, got {None if miss_rows is None else tuple(miss_rows.shape)}")
             if pos.min() < 0 or pos.max() >= len(ids):
                 raise ValueError("rows: miss_pos outside the batch")
         row_of = {}                                  # frame id -> address of its computed row (the first one serves all)
         for j, p in enumerate(pos):
-            row_of.setdefault(int(ids[p]), miss_rows.data_ptr() + j * rb)
-        out = torch.empty((len(ids), rb // 4), dtype=torch.float32, device=self.device)
+            row_of.setdefault(int(ids[p]), miss_rows.data_ptr() + j * ne * 4)
+        out = torch.empty((len(ids), ne), dtype=self.dtype, device=self.device)
         out_ptr = out.data_ptr()
         src, keep, ref, new_ids, fresh = [], [], [], [], set()
         for fid in ids:
@@ -107,8 +117,12 @@ class FeatureCache(SlotStore):
             ref.append(0)
         dst = [out_ptr + i * rb for i in range(len(ids))]
         flags = self._flag_rows(ids)
-        d_src, d_dst, d_keep, d_ref = self._upload(src, dst, keep, ref)
-        ops.feat_rows(d_src, d_dst, rb, d_keep, d_ref, boxes, flags, bb)
+        if self.dtype == torch.float32:
+            d_src, d_dst, d_keep, d_ref = self._upload(src, dst, keep, ref)
+            ops.feat_rows(d_src, d_dst, rb, d_keep, d_ref, boxes, flags, bb)
+        else:                                        # a row without a stored-boxes address is a computed one: fp32, to be rounded
+            d_src, d_dst, d_keep, d_ref, d_f32 = self._upload(src, dst, keep, ref, [int(r == 0) for r in ref])
+            ops.feat_rows_bf16(d_src, d_dst, ne, d_keep, d_ref, boxes, flags, bb, d_f32)
         return out, new_ids
 
     def check(self) -> None:
@@ -207,18 +221,22 @@ class FeatureLoader(CachedLoader):
         return FeatureFeed(self.loader, device, self.cache, self.dataset)
 
 
-def row_and_box_bytes(cfg) -> Tuple[int, int]:
-    """bytes of one frame's fp32 RoIAlign output [N, D, K, K] and of its fp32 boxes [N, 4]"""
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}      # cfg.feature_cache_dtype -> what the slots hold
+
+
+def row_and_box_bytes(cfg, dtype: torch.dtype = torch.float32) -> Tuple[int, int]:
+    """bytes of one frame's RoIAlign output [N, D, K, K] stored as `dtype` and of its fp32 boxes [N, 4]"""
     K = cfg.crop_size[0]
-    return cfg.num_boxes * cfg.emb_features * K * K * 4, cfg.num_boxes * 16
+    return cfg.num_boxes * cfg.emb_features * K * K * (4 if dtype == torch.float32 else 2), cfg.num_boxes * 16
 
 
 def feature_loaders(cfg, training_loader, validation_loader, training_set, validation_set, device):
     """frame_cache.build_loaders with cfg.feature_cache_gb > 0: one FeatureCache of that many GB per dataset"""
     capacity = int(float(cfg.feature_cache_gb) * 1e9)
-    rb, bb = row_and_box_bytes(cfg)
-    return (FeatureLoader(training_loader, FeatureCache(device, rb, bb, capacity), training_set),
-            FeatureLoader(validation_loader, FeatureCache(device, rb, bb, capacity), validation_set))
+    dtype = DTYPES[getattr(cfg, "feature_cache_dtype", "fp32")]
+    rb, bb = row_and_box_bytes(cfg, dtype)
+    return (FeatureLoader(training_loader, FeatureCache(device, rb, bb, capacity, dtype=dtype), training_set),
+            FeatureLoader(validation_loader, FeatureCache(device, rb, bb, capacity, dtype=dtype), validation_set))
 
 
 def refusal(cfg) -> Optional[str]:
@@ -238,4 +256,17 @@ def refusal(cfg) -> Optional[str]:
     if cfg.backbone == "inv3" and not cfg.set_bn_eval:
         return pre + ("backbone 'inv3' without set_bn_eval normalises with batch statistics, so a frame's features depend on the batch it "
                       "is in and cannot be cached")
+    dtype = getattr(cfg, "feature_cache_dtype", "fp32")
+    if dtype == "fp32":
+        return None
+    pre = f"feature_cache_dtype = {dtype!r}: "
+    if dtype not in DTYPES:
+        return pre + f"cached box features are stored as one of {sorted(DTYPES)}"
+    if cfg.backbone_dtype != "bf16":
+        return pre + (f"bf16 rows are the operand of the embedding GEMM under backbone_dtype = 'bf16' only; with backbone_dtype = "
+                      f"{cfg.backbone_dtype!r} rounding the features would change the embeddings")
+    K = cfg.crop_size[0]
+    if cfg.emb_features * K * K % 8 or cfg.num_features_boxes % 8:
+        return pre + (f"the embedding GEMM multiplies bf16 operands only when emb_features * K * K = {cfg.emb_features * K * K} and "
+                      f"num_features_boxes = {cfg.num_features_boxes} are multiples of 8")
     return None

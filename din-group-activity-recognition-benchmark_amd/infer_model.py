@@ -99,7 +99,8 @@ def _crops(model, images_flat, boxes_flat, N):
 def _cached_crops(model, refs, boxes_in, N):
     """the trunk behind the box-feature cache (feature_cache.py): the backbone and RoIAlign run, without autograd, on the M frames of
     `refs` that were decoded -- no launch when M == 0 -- and one din_feat_rows launch builds fp32 [B*T, N*D*K*K] from those rows and the
-    cache's slots, stores the new rows with their boxes and checks the boxes of the rows served from slots"""
+    cache's slots, stores the new rows with their boxes and checks the boxes of the rows served from slots.  A cache of bf16 rows
+    (cfg.feature_cache_dtype = 'bf16') returns feats as bf16, ops.linear's lowp operand: one din_feat_rows_bf16 launch, no cast pass"""
     cfg = model.cfg
     if cfg.train_backbone:
         raise ValueError("cached box features (cfg.feature_cache_gb) are the output of a frozen backbone; this model trains its backbone")

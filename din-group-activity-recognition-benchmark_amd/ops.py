@@ -150,7 +150,8 @@ class GridConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, dil: int, lowp: bool = False, split: bool = False):
         """lowp: bf16 operands / fp32 MFMA accumulation (throughput mode, used for the 26400-wide embedding GEMM when the backbone
-        already runs in bf16); x, y and all gradients stay fp32 tensors at the interface.
+        already runs in bf16); x, y and all gradients stay fp32 tensors at the interface -- except that x may arrive as the bf16 operand
+        itself (rows of the bf16 feature cache): it is then used and saved as it is, and without effective lowp it is a ValueError.
         split: fp32 storage, three-part bf16 MFMA compute (DIN_F32_BF16X3: fp32 accuracy on the bf16 matrix pipe) for the forward, the data
         gradient and the weight gradient; every tensor and buffer is what the exact fp32 call makes.  Not together with lowp."""
         if lowp and split:
@@ -165,9 +166,11 @@ class GridConvFunction(torch.autograd.Function):
         tdt = torch.bfloat16 if lowp else torch.float32
         ldo = cout if lowp else (cout + 3) // 4 * 4
         d = _desc(nb, h, w, cin, cout, kh, kw, (kh - 1) // 2 * dil, (kw - 1) // 2 * dil, dil, cin, ldo)
+        if x.dtype == torch.bfloat16 and not lowp:
+            raise ValueError(f"a bf16 x is the lowp operand itself: it needs lowp=True and cin = {cin}, cout = {cout} multiples of 8")
         if lowp:
             d.dtype = L.DIN_BF16
-            x = x.to(torch.bfloat16)
+            x = x.to(torch.bfloat16)             # (no pass over a tensor that is bf16 already, e.g. rows of the bf16 feature cache)
         elif split:
             d.dtype = L.DIN_F32_BF16X3
         st = _stream()
@@ -219,7 +222,8 @@ class GridConvFunction(torch.autograd.Function):
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], lowp: bool = False, split: bool = False) -> torch.Tensor:
     """y = x @ weight.T + bias over the last dim, on the MFMA contraction kernel (cout must be a multiple of 4).
-    lowp / split: GridConvFunction's two other numeric modes (mutually exclusive)."""
+    lowp / split: GridConvFunction's two other numeric modes (mutually exclusive).  A bf16 x is taken as lowp's operand without a cast
+    pass (ValueError unless lowp is in effect); y is fp32 either way."""
     if lowp and split:
         raise ValueError("lowp and split are mutually exclusive: bf16 storage or fp32 storage with three-part bf16 compute")
     shp = x.shape
@@ -968,6 +972,22 @@ def copy_rows_u8(src: torch.Tensor, dst: torch.Tensor, nbytes: int, n: Optional[
 FEAT_ROWS_SEGMENT = 16384        # DIN_FEAT_ROWS_SEGMENT (include/din_hip.h): bytes of one row per work item of din_feat_rows
 
 
+def _feat_rows_count(what: str, tables, boxes, flags, box_bytes: int, n: Optional[int]) -> int:
+    """the checks feat_rows and feat_rows_bf16 share: int64 device tables of at least n entries, boxes and flags that cover n rows"""
+    require_gpu(*tables, boxes, flags)
+    if any(t.dtype != torch.int64 for t in tables):
+        raise L.DinError(f"{what}: address tables are int64 device tensors")
+    rows = min(t.numel() for t in tables)
+    n = rows if n is None else n
+    if n > rows:
+        raise L.DinError(f"{what}: n = {n} rows but the tables hold {[t.numel() for t in tables]} addresses")
+    if boxes is not None and (not boxes.is_contiguous() or boxes.numel() * boxes.element_size() < n * box_bytes):
+        raise L.DinError(f"{what}: boxes must be contiguous and hold n * box_bytes = {n * box_bytes} bytes")
+    if flags is not None and (flags.dtype != torch.uint8 or not flags.is_contiguous() or flags.numel() < n):
+        raise L.DinError(f"{what}: flags is a contiguous uint8 tensor of at least n = {n} entries")
+    return n
+
+
 def feat_rows(src: torch.Tensor, dst: torch.Tensor, row_bytes: int, keep: Optional[torch.Tensor] = None,
               ref_boxes: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None,
               box_bytes: int = 0, n: Optional[int] = None) -> None:
@@ -977,17 +997,19 @@ def feat_rows(src: torch.Tensor, dst: torch.Tensor, row_bytes: int, keep: Option
     tables; boxes: a contiguous device tensor of n rows of box_bytes bytes; flags: uint8 on the device, one per row (din_feat_rows: the
     feature cache's gather + insert + box check).  Every address and both sizes are multiples of 16."""
     lib = L.load()
-    tables = [t for t in (src, dst, keep, ref_boxes) if t is not None]
-    require_gpu(*tables, boxes, flags)
-    if any(t.dtype != torch.int64 for t in tables):
-        raise L.DinError("feat_rows: address tables are int64 device tensors")
-    rows = min(t.numel() for t in tables)
-    n = rows if n is None else n
-    if n > rows:
-        raise L.DinError(f"feat_rows: n = {n} rows but the tables hold {[t.numel() for t in tables]} addresses")
-    if boxes is not None and (not boxes.is_contiguous() or boxes.numel() * boxes.element_size() < n * box_bytes):
-        raise L.DinError(f"feat_rows: boxes must be contiguous and hold n * box_bytes = {n * box_bytes} bytes")
-    if flags is not None and (flags.dtype != torch.uint8 or not flags.is_contiguous() or flags.numel() < n):
-        raise L.DinError(f"feat_rows: flags is a contiguous uint8 tensor of at least n = {n} entries")
+    n = _feat_rows_count("feat_rows", [t for t in (src, dst, keep, ref_boxes) if t is not None], boxes, flags, box_bytes, n)
     L.check(lib.din_feat_rows(_ptr(src), _ptr(dst), _ptr(keep), _ptr(ref_boxes), _ptr(boxes), _ptr(flags), n, row_bytes, box_bytes,
                               _stream()), "feat_rows")
+
+
+def feat_rows_bf16(src: torch.Tensor, dst: torch.Tensor, row_elems: int, keep: Optional[torch.Tensor] = None,
+                   ref: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None,
+                   box_bytes: int = 0, src_f32: Optional[torch.Tensor] = None, n: Optional[int] = None) -> None:
+    """feat_rows over rows of `row_elems` bf16 values (the feature cache's bf16 storage): where src_f32[i] != 0, src[i] addresses
+    `row_elems` fp32 values, which are rounded to bf16 (round-to-nearest-even) on their way to dst[i] and keep[i]; every other row is
+    feat_rows at row_bytes = 2 * row_elems.  `ref`: feat_rows's ref_boxes; src_f32: an int64 device table like the others
+    (din_feat_rows_bf16).  One launch on the current stream; every address and box_bytes are multiples of 16, row_elems of 8."""
+    lib = L.load()
+    n = _feat_rows_count("feat_rows_bf16", [t for t in (src, dst, keep, ref, src_f32) if t is not None], boxes, flags, box_bytes, n)
+    L.check(lib.din_feat_rows_bf16(_ptr(src), _ptr(dst), _ptr(keep), _ptr(ref), _ptr(src_f32), _ptr(boxes), _ptr(flags), n, row_elems,
+                                   box_bytes, _stream()), "feat_rows_bf16")

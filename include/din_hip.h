@@ -679,6 +679,27 @@ int din_copy_rows_u8(const uint64_t* src, const uint64_t* dst, int n, int64_t by
 int din_feat_rows(const uint64_t* src, const uint64_t* dst, const uint64_t* keep, const uint64_t* ref_boxes,
                   const void* boxes, uint8_t* flags, int n, int64_t row_bytes, int box_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The same launch over slots that hold bf16 rows (cfg.feature_cache_dtype = 'bf16', din_amd/feature_cache.py): with the backbone in
+ * bf16 the embedding GEMM that reads feats (infer_model.py:184) multiplies bf16 operands, so the row is stored already rounded -- half
+ * the bytes per frame, and no cast pass over feats in a cached step.  Rows are row_elems bf16 values at dst[i] and keep[i].
+ * src, dst, keep, ref_boxes, boxes, flags, box_bytes: as for din_feat_rows with row_bytes = 2 * row_elems (the trailer is at
+ * keep[i] + 2 * row_elems).  src_f32: a DEVICE array of n entries, or null: all zero.  Row i with src[i] != 0:
+ *   src_f32[i] != 0    src[i] addresses row_elems FP32 values (the row the trunk just computed): each is read once and rounded once to
+ *                      bf16, round-to-nearest-even (the gfx950 hardware conversion: NaN stays NaN), and the rounded row goes to dst[i]
+ *                      and, where keep[i] != 0, to keep[i], followed there by the boxes;
+ *   src_f32[i] == 0    src[i] addresses row_elems bf16 values (a slot): copied unchanged, exactly din_feat_rows.
+ * Every address in the tables, `boxes` and box_bytes are multiples of 16 and row_elems is a multiple of 8; a row holding an address that
+ * is not, or a zero dst[i], is left alone like a row with src[i] == 0.  Overlap rules, the (row, segment) items of
+ * DIN_FEAT_ROWS_SEGMENT bytes of the DESTINATION row (8192 values), the single plain launch on `stream` -- no allocation, no
+ * synchronisation, no atomics, capturable -- and n == 0 are din_feat_rows's.  DIN_E_ARG before any launch: n, row_elems or box_bytes
+ * negative; row_elems not a multiple of 8; box_bytes or `boxes` not a multiple of 16; a null src or dst with n > 0; a null boxes or
+ * flags with a non-null keep or ref_boxes.  Additive: the ABI version stays 9.
+ * ---------------------------------------------------------------------------------------------- */
+int din_feat_rows_bf16(const uint64_t* src, const uint64_t* dst, const uint64_t* keep, const uint64_t* ref_boxes,
+                       const uint64_t* src_f32, const void* boxes, uint8_t* flags, int n, int64_t row_elems, int box_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

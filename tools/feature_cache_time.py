@@ -15,9 +15,13 @@
    write_tree; nothing is fetched): the first cached epoch (decode + upload + trunk + insert) once, then epochs with both caches off,
    epochs fed by the frame cache (frame_cache.py: pixels resident, the trunk still runs) and later cached epochs (gather only)
    ALTERNATING, one window per epoch.
+3. With `--dtype bf16`, in place of 1 and 2: slots of fp32 rows against slots of bf16 rows (cfg.feature_cache_dtype), alternated in the
+   same windows -- the launch for computed and for resident rows, and the gather of resident rows followed by fc_emb_1's forward, where
+   the cast pass the bf16 rows spare shows (dtype_timings).
 
 One JSON line per measurement, then the GPU clock.  usage: python tools/feature_cache_time.py [--out profiles/feature_cache_time.txt]
-[--skip-feed] [--skip-kernel] [--windows 15] [--inner 5] [--rows 320] [--clips 64] [--batch 2] [--epochs 5] [--cache-gb 4]"""
+[--dtype fp32|bf16] [--skip-feed] [--skip-kernel] [--windows 15] [--inner 5] [--rows 320] [--clips 64] [--batch 2] [--epochs 5]
+[--cache-gb 4]"""
 import argparse
 import json
 import os
@@ -77,6 +81,72 @@ def kernel_timings(a, emit):
             nbytes = forms[what][1]
             gbs = {k.replace("_ms", "_GBps"): round(nbytes / (r[k] * 1e-3) / 1e9, 1) for k in ("median_ms", "min_ms", "p90_ms", "max_ms")}
             emit({"tool": "feature_cache_time", "what": f"{R} rows of {RB} B: " + what, "bytes_read_plus_written": nbytes, **r, **gbs})
+
+
+def dtype_timings(a, emit):
+    """--dtype bf16: slots of fp32 rows (din_feat_rows) against slots of bf16 rows (din_feat_rows_bf16) for the same `--rows` rows, the two
+    alternated window by window: (a) the launch alone, for computed rows (feats + slot + boxes; the bf16 form rounds on the way) and for
+    resident rows (gather + box comparison); (b) the gather of resident rows followed by fc_emb_1's forward (ops.linear, lowp: bf16
+    operands) -- the fp32 feats tensor is rounded in a pass of its own there, the bf16 one is the operand"""
+    from din_amd import ops
+    dev = torch.device("cuda")
+    R, NE = a.rows, RB // 4
+    RB16 = 2 * NE
+    g = torch.Generator(device=dev).manual_seed(0)
+    computed = torch.randn((R, NE), device=dev, generator=g)
+    boxes = torch.rand((R, BB // 4), device=dev, generator=g) * 40
+    out32, out16 = torch.empty((R, NE), device=dev), torch.empty((R, NE), device=dev, dtype=torch.bfloat16)
+    slots32 = torch.zeros(R * (RB + BB), dtype=torch.uint8, device=dev)
+    slots16 = torch.zeros(R * (RB16 + BB), dtype=torch.uint8, device=dev)
+    order = np.random.default_rng(0).permutation(R)                       # row i lives in slot order[i]
+    tab = lambda v: torch.tensor([int(x) for x in v], dtype=torch.int64, device=dev)
+    src_rows = tab(computed.data_ptr() + i * RB for i in range(R))
+    dst32, dst16 = tab(out32.data_ptr() + i * RB for i in range(R)), tab(out16.data_ptr() + i * RB16 for i in range(R))
+    slot32 = tab(slots32.data_ptr() + int(order[i]) * (RB + BB) for i in range(R))
+    slot16 = tab(slots16.data_ptr() + int(order[i]) * (RB16 + BB) for i in range(R))
+    trailer32, trailer16 = slot32 + RB, slot16 + RB16
+    zeros, ones = torch.zeros(R, dtype=torch.int64, device=dev), torch.ones(R, dtype=torch.int64, device=dev)
+    flags = torch.zeros(R, dtype=torch.uint8, device=dev)
+    K2D, NFB = 25 * 512, 1024                                             # fc_emb_1 of the VGG16 launchers: Linear(K*K*D, num_features_boxes)
+    weight = torch.randn((NFB, K2D), device=dev, generator=g) * 0.01
+    bias = torch.zeros(NFB, device=dev)
+
+    def gather32():
+        ops.feat_rows(slot32, dst32, RB, zeros, trailer32, boxes, flags, BB)
+
+    def gather16():
+        ops.feat_rows_bf16(slot16, dst16, NE, zeros, trailer16, boxes, flags, BB)
+
+    def embed32():
+        gather32()
+        return ops.linear(out32.view(R * 12, K2D), weight, bias, lowp=True)
+
+    def embed16():
+        gather16()
+        return ops.linear(out16.view(R * 12, K2D), weight, bias, lowp=True)
+
+    insert = {"computed rows, fp32 slots: din_feat_rows (feats + slot + boxes)":
+              (lambda: ops.feat_rows(src_rows, dst32, RB, slot32, zeros, boxes, flags, BB), R * (3 * RB + 2 * BB)),
+              "computed rows, bf16 slots: din_feat_rows_bf16 (round once, feats + slot + boxes)":
+              (lambda: ops.feat_rows_bf16(src_rows, dst16, NE, slot16, zeros, boxes, flags, BB, ones), R * (RB + 2 * RB16 + 2 * BB))}
+    gather = {"resident rows, fp32 slots: din_feat_rows (gather + box comparison)": (gather32, R * (2 * RB + 2 * BB)),
+              "resident rows, bf16 slots: din_feat_rows_bf16 (gather + box comparison)": (gather16, R * (2 * RB16 + 2 * BB))}
+    with torch.no_grad():
+        for forms in (insert, gather):                                    # (the inserts run first: the gathers read what they stored)
+            out32.zero_(), out16.zero_()
+            for fn, _ in forms.values():
+                fn()
+            torch.cuda.synchronize()
+            assert torch.equal(out32, computed) and torch.equal(out16, computed.to(torch.bfloat16)) and int(flags.sum()) == 0
+            for what, r in timed({k: fn for k, (fn, _) in forms.items()}, a.warmup, a.windows, a.inner).items():
+                nbytes = forms[what][1]
+                gbs = {k.replace("_ms", "_GBps"): round(nbytes / (r[k] * 1e-3) / 1e9, 1) for k in ("median_ms", "min_ms", "p90_ms", "max_ms")}
+                emit({"tool": "feature_cache_time", "what": f"{R} rows of {NE} values: " + what, "bytes_read_plus_written": nbytes, **r, **gbs})
+        assert torch.equal(embed32(), embed16())                          # the GEMM multiplies the same bf16 operands either way
+        embed = {"resident rows, fp32 slots: gather + fc_emb_1 forward (the GEMM rounds feats to bf16 in a pass of its own)": embed32,
+                 "resident rows, bf16 slots: gather + fc_emb_1 forward (feats is the bf16 operand)": embed16}
+        for what, r in timed(embed, a.warmup, a.windows, a.inner).items():
+            emit({"tool": "feature_cache_time", "what": f"{R} rows of {NE} values: " + what, "gemm": [R * 12, K2D, NFB], **r})
 
 
 def feed_timings(a, emit):
@@ -153,6 +223,7 @@ def main():
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--cache-gb", type=float, default=4.0)
+    ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--skip-feed", action="store_true")
     ap.add_argument("--out", default=None)
@@ -168,10 +239,13 @@ def main():
             with open(a.out, "w") as fh:
                 fh.write("Box-feature cache: din_feat_rows and feed rate (tools/feature_cache_time.py), one MI355X:\n" + "\n".join(lines) + "\n")
 
-    if not a.skip_kernel:
-        kernel_timings(a, emit)
-    if not a.skip_feed:
-        feed_timings(a, emit)
+    if a.dtype == "bf16":
+        dtype_timings(a, emit)
+    else:
+        if not a.skip_kernel:
+            kernel_timings(a, emit)
+        if not a.skip_feed:
+            feed_timings(a, emit)
     emit({"clock": clock()})
 
 
