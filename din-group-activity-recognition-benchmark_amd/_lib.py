@@ -94,6 +94,9 @@ SIGNATURES: Dict[str, tuple] = {
     "din_conv_dgrad_x_kernel_names": (_I, [_CD, C.POINTER(ConvSrc), _I, _I, _I, C.c_char_p, _I]),
     "din_conv1x1_wgrad_multi_workspace": (_L, [_I, C.POINTER(ConvWSrc), _I, _L, _I]),
     "din_conv1x1_wgrad_multi": (_I, [_I, C.POINTER(ConvWSrc), _I, _L, _I, _I, _I, _P, _I, _P, _L, _P]),
+    "din_conv1x1_wgrad_multi_kernel_names": (_I, [_I, C.POINTER(ConvWSrc), _I, _L, _I, C.c_char_p, _I]),
+    "din_conv_wgrad_group_kernel_names": (_I, [_I, C.POINTER(ConvWgradItem), C.c_char_p, _I]),
+    "din_conv_wgrad_group_slices": (_I, [_I, C.POINTER(ConvWgradItem), C.POINTER(C.c_int32), _I]),
     "din_conv_wgrad_group_key": (_I, [_CD]),
     "din_conv_wgrad_group_workspace": (_L, [_I, C.POINTER(ConvWgradItem)]),
     "din_conv_wgrad_group": (_I, [_I, C.POINTER(ConvWgradItem), _P, _L, _P]),

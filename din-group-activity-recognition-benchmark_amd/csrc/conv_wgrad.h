@@ -90,6 +90,7 @@ void append_wgrad_names(const din_conv_desc* d, const WgradChoice& c, std::strin
 // a tuple that is not instantiated is DIN_E_ARG
 int launch_wgrad_pipe(const WgradK& k, const PipeInst& inst, dim3 grid, dim3 block, size_t lds, hipStream_t st);
 int launch_wgrad_pipe_group(const WgradGroupK& g, int bco, bool wide, hipStream_t st);     // 16-wave instantiations only; grid = g.first[g.n] blocks
+bool wgrad_pipe_group_name(int bco, bool wide, std::string* name);     // the instantiation launch_wgrad_pipe_group launches, as rocprofv3 prints it; false: none
 size_t wgrad_pipe_lds_bytes(int bco, int bk);
 // host entries of conv_wgrad_halo.hip: the halo-tiled weight gradient of the narrow mid-network layers (dW block stationary in registers).
 // wgrad_halo_shape: the instantiation that serves (cin, cout, kh, kw) at stride 1, dilation 1, bf16 -- one table, which the launcher switches on
@@ -99,5 +100,6 @@ int launch_wgrad_halo(const WgradK& k, const HaloInst& inst, dim3 grid, dim3 blo
 // host entries of conv_wgrad_1x1.hip
 bool plan_wgrad_1x1_multi(int nsrc, const int* couts, int cin, Wg1x1K* k);
 int launch_wgrad_1x1_multi(const Wg1x1K& k, int nwg, hipStream_t st);
+bool wgrad_1x1_multi_name(int cin, std::string* name);                 // the instantiation launch_wgrad_1x1_multi launches for this input width; false: none
 
 }  // namespace din_wgrad

@@ -1,7 +1,8 @@
 // Weight gradient of the convolutions for gfx950 (MI355X): every weight-gradient kernel family that is not in a file of its own (fp32, bf16
 // two-workgroup, bf16 tail, ring, stem), the slice reduce and the column-sum (bias gradient) kernels, the one place that chooses among ALL
 // families (plan_wgrad; the pipelined, halo and 1x1-multi kernels live in conv_wgrad_pipe.hip, conv_wgrad_halo.hip and conv_wgrad_1x1.hip),
-// and the entry points din_conv_wgrad, din_conv_wgrad_group, din_conv1x1_wgrad_multi and din_colsum.
+// and the entry points din_conv_wgrad, din_conv_wgrad_group, din_conv1x1_wgrad_multi (each of the two with its host-only kernel-name reporter)
+// and din_colsum.
 //
 //   dW[co][(r,s,ci)] = sum_pix G[pix][co] * im2col(X)[pix][(r,s,ci)]
 //
@@ -1507,7 +1508,9 @@ int din_conv_wgrad(const din_conv_desc* d, const void* in, const void* dout, flo
 // ---- din_conv_wgrad_group: the weight gradients of several LAYERS in one launch of the pipelined kernel (conv_wgrad.h: WgradGroupK) -------
 // Plan: every item keeps the tile geometry plan_wgrad gives it alone; what changes is the pixel slicing.  One common slice length mps
 // (whole 32-pixel stages) is chosen so that the items' tiles x slices fill the chip's CUs ONCE: sum_g tiles_g * ceil(M_g / mps) <= CUs.
-struct WgradGroupPlan { WgradChoice wp[din_wgrad::WGRAD_GROUP_MAX]; int slices[din_wgrad::WGRAD_GROUP_MAX]; int64_t part_off[din_wgrad::WGRAD_GROUP_MAX], pace_off[din_wgrad::WGRAD_GROUP_MAX]; int mps, bco, wide; int64_t ws_bytes; };
+struct WgradGroupPlan { WgradChoice wp[din_wgrad::WGRAD_GROUP_MAX]; int slices[din_wgrad::WGRAD_GROUP_MAX]; int64_t part_off[din_wgrad::WGRAD_GROUP_MAX], pace_off[din_wgrad::WGRAD_GROUP_MAX]; int mps, bco, wide;
+                        int nsg;      // slice groups of the reduce launch's workgroups (1 / 4 / 16), from the largest slice count
+                        int64_t ws_bytes; };
 
 static int wgrad_group_key(const din_conv_desc* d, WgradChoice* out) {
     if (!d || d->dtype != DIN_BF16 || d->in_u8 || d->nb <= 0 || d->oh <= 0 || d->ow <= 0) return 0;
@@ -1561,9 +1564,11 @@ static bool plan_wgrad_group(int n, const din_conv_wgrad_item* items, WgradGroup
     if (mps >= (1ll << 30)) return false;
     gp.mps = (int)mps;
     int64_t off = 0;
+    int max_slices = 1;
     for (int g = 0; g < n; ++g) {
         const int64_t M = (int64_t)items[g].desc.nb * items[g].desc.oh * items[g].desc.ow;
         gp.slices[g] = (int)((M + mps - 1) / mps);
+        if (gp.slices[g] > max_slices) max_slices = gp.slices[g];
         gp.part_off[g] = off;
         off += ((int64_t)gp.slices[g] * gp.wp[g].cout_pad * gp.wp[g].kcols_pad * 4 + 255) / 256 * 256;
     }
@@ -1572,7 +1577,26 @@ static bool plan_wgrad_group(int n, const din_conv_wgrad_item* items, WgradGroup
         off += ((int64_t)gp.slices[g] * gp.wp[g].n_co_tiles * 8 * 4 + 255) / 256 * 256;
     }
     gp.ws_bytes = off;
+    gp.nsg = max_slices >= 64 ? 16 : max_slices >= 8 ? 4 : 1;
     return true;
+}
+
+// the lines a planned group launches: the group kernel's instantiation (a filter tile launch_wgrad_pipe_group holds no row for: DIN_E_ARG)
+// and the one reduce launch.  din_conv_wgrad_group checks here before it touches anything; din_conv_wgrad_group_kernel_names answers from here
+static int wgrad_group_lines(const WgradGroupPlan& gp, std::string* names) {
+    std::string main_kernel;
+    DIN_REQUIRE(din_wgrad::wgrad_pipe_group_name(gp.bco, gp.wide != 0, &main_kernel), "conv_wgrad_group: no group kernel for filter tile %d, wide %d", gp.bco, gp.wide);
+    if (names) { *names += main_kernel; *names += "\nconv_wgrad_reduce_group_kernel\n"; }
+    return DIN_OK;
+}
+
+static int copy_names(const std::string& names, char* buf, int buf_bytes) {
+    if (buf_bytes > 0) {
+        const size_t n = names.size() < (size_t)buf_bytes - 1 ? names.size() : (size_t)buf_bytes - 1;
+        names.copy(buf, n);
+        buf[n] = 0;
+    }
+    return (int)names.size() + 1;
 }
 
 int din_conv_wgrad_group_key(const din_conv_desc* d) { return wgrad_group_key(d, nullptr); }
@@ -1586,16 +1610,25 @@ int din_conv_wgrad_group(int n, const din_conv_wgrad_item* items, void* workspac
     DIN_REQUIRE(items && n >= 1, "conv_wgrad_group: no items");
     WgradGroupPlan gp;
     if (!plan_wgrad_group(n, items, gp)) {                          // not a group this launch serves: layer by layer
+        for (int g = 0; g < n; ++g) {                               // (the largest single-item need, checked before the first layer runs)
+            const int64_t need = din_conv_workspace_bytes(&items[g].desc, 2);
+            if (need > workspace_bytes) DIN_FAIL(DIN_E_WORKSPACE, "conv_wgrad_group: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+        }
         for (int g = 0; g < n; ++g) {
             const din_conv_wgrad_item& it = items[g];
-            const int64_t need = din_conv_workspace_bytes(&it.desc, 2);
-            if (need > workspace_bytes) DIN_FAIL(DIN_E_WORKSPACE, "conv_wgrad_group: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
             if (int e = din_conv_wgrad(&it.desc, it.in, it.dout, it.dw, it.dbias, it.scale, it.w, it.wdot, it.accumulate, workspace, workspace_bytes, stream)) return e;
         }
         return DIN_OK;
     }
     if (!workspace || workspace_bytes < gp.ws_bytes)
         DIN_FAIL(DIN_E_WORKSPACE, "conv_wgrad_group: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)gp.ws_bytes);
+    if (int e = wgrad_group_lines(gp, nullptr)) return e;
+    for (int g = 0; g < n; ++g) {                                   // every item is checked before anything is written (the memsets below)
+        const din_conv_wgrad_item& it = items[g];
+        if (int e = check_desc(&it.desc)) return e;
+        DIN_REQUIRE(it.in && it.dout && it.dw, "conv_wgrad_group: null pointer in item %d", g);
+        DIN_REQUIRE(!it.wdot || it.w, "conv_wgrad_group: wdot needs w");
+    }
     hipStream_t st = as_stream(stream);
     din_wgrad::WgradGroupK G{};
     G.n = n;
@@ -1603,9 +1636,6 @@ int din_conv_wgrad_group(int n, const din_conv_wgrad_item* items, void* workspac
     for (int g = 0; g < n; ++g) {
         const din_conv_wgrad_item& it = items[g];
         const din_conv_desc* d = &it.desc;
-        if (int e = check_desc(d)) return e;
-        DIN_REQUIRE(it.in && it.dout && it.dw, "conv_wgrad_group: null pointer in item %d", g);
-        DIN_REQUIRE(!it.wdot || it.w, "conv_wgrad_group: wdot needs w");
         const WgradChoice& wp = gp.wp[g];
         const bool prezeroed = (it.accumulate & 2) != 0;
         din_wgrad::WgradK& k = G.k[g];
@@ -1635,7 +1665,7 @@ int din_conv_wgrad_group(int n, const din_conv_wgrad_item* items, void* workspac
     DIN_CHECK_LAUNCH("conv_wgrad_group");
     WgradReduceGroupK R{};
     R.n = n;
-    int rfirst = 0, max_slices = 1;
+    int rfirst = 0;
     for (int g = 0; g < n; ++g) {
         const din_conv_wgrad_item& it = items[g];
         const din_conv_desc* d = &it.desc;
@@ -1646,13 +1676,36 @@ int din_conv_wgrad_group(int n, const din_conv_wgrad_item* items, void* workspac
         r.slices = gp.slices[g]; r.accumulate = it.accumulate & 1; r.kchunks = (d->kh * d->kw * wp.cin_pad + 255) / 256;
         R.first[g] = rfirst;
         rfirst += d->cout * r.kchunks;
-        if (gp.slices[g] > max_slices) max_slices = gp.slices[g];
     }
     for (int g = n; g <= din_wgrad::WGRAD_GROUP_MAX; ++g) R.first[g] = rfirst;
-    const int nsg = max_slices >= 64 ? 16 : max_slices >= 8 ? 4 : 1;
-    hipLaunchKernelGGL(conv_wgrad_reduce_group_kernel, dim3(rfirst), dim3(64, nsg), 0, st, R);
+    hipLaunchKernelGGL(conv_wgrad_reduce_group_kernel, dim3(rfirst), dim3(64, gp.nsg), 0, st, R);
     DIN_CHECK_LAUNCH("conv_wgrad_group reduce");
     return DIN_OK;
+}
+
+int din_conv_wgrad_group_kernel_names(int n, const din_conv_wgrad_item* items, char* buf, int buf_bytes) {
+    DIN_REQUIRE(items && n >= 1 && buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_wgrad_group_kernel_names: bad argument");
+    std::string names;
+    WgradGroupPlan gp;
+    const bool planned = plan_wgrad_group(n, items, gp);
+    for (int g = 0; g < n; ++g) {
+        const din_conv_desc* d = &items[g].desc;
+        const SplitDesc sd(d);
+        if (int e = check_desc(d)) return e;
+        if (planned) continue;                                      // not a group the launch serves: din_conv_wgrad's lines, layer by layer
+        DIN_REQUIRE(!d->in_u8 || din_conv_accepts_u8(d), "conv_wgrad_group_kernel_names: in_u8 on a layer din_conv_accepts_u8() rejects");
+        din_wgrad::append_wgrad_names(d, din_wgrad::plan_wgrad(d, sd.split), names);
+    }
+    if (planned) if (int e = wgrad_group_lines(gp, &names)) return e;
+    return copy_names(names, buf, buf_bytes);
+}
+
+int din_conv_wgrad_group_slices(int n, const din_conv_wgrad_item* items, int32_t* slices, int cap) {
+    DIN_REQUIRE(items && n >= 1 && cap >= 0 && (slices || cap == 0), "conv_wgrad_group_slices: bad argument");
+    WgradGroupPlan gp;
+    if (!plan_wgrad_group(n, items, gp)) return 0;
+    for (int g = 0; g < n && g < cap; ++g) slices[g] = gp.slices[g];
+    return gp.nsg;
 }
 
 static bool wgrad_multi_plan(int nsrc, const din_conv_wsrc* srcs, int dtype, int64_t pixels, int cin, din_wgrad::Wg1x1K* k) {
@@ -1674,22 +1727,44 @@ int64_t din_conv1x1_wgrad_multi_workspace(int nsrc, const din_conv_wsrc* srcs, i
     return (int64_t)WGRAD_HALO_GRID * k.rows_pad * cin * 4;
 }
 
+// the lines a din_conv1x1_wgrad_multi call launches: the plan (a group the kernel does not take: DIN_E_ARG), the instantiation for this input
+// width, one reduce launch per source.  The launch checks and plans here; din_conv1x1_wgrad_multi_kernel_names answers from here
+static int wgrad_multi_lines(int nsrc, const din_conv_wsrc* srcs, int dtype, int64_t pixels, int cin, din_wgrad::Wg1x1K* k, std::string* names) {
+    DIN_REQUIRE(wgrad_multi_plan(nsrc, srcs, dtype, pixels, cin, k), "conv1x1_wgrad_multi: this group does not fit the kernel "
+                "(din_conv1x1_wgrad_multi_workspace returns 0 for it: run din_conv_wgrad per layer)");
+    std::string main_kernel;
+    DIN_REQUIRE(din_wgrad::wgrad_1x1_multi_name(cin, &main_kernel), "conv1x1_wgrad_multi: Cin %d not instantiated", cin);
+    if (names) {
+        *names += main_kernel; *names += '\n';
+        for (int s = 0; s < nsrc; ++s) *names += "conv_wgrad_reduce_kernel\n";
+    }
+    return DIN_OK;
+}
+
+int din_conv1x1_wgrad_multi_kernel_names(int nsrc, const din_conv_wsrc* srcs, int dtype, int64_t pixels, int cin, char* buf, int buf_bytes) {
+    DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv1x1_wgrad_multi_kernel_names: bad argument");
+    din_wgrad::Wg1x1K k{};
+    std::string names;
+    if (int e = wgrad_multi_lines(nsrc, srcs, dtype, pixels, cin, &k, &names)) return e;
+    return copy_names(names, buf, buf_bytes);
+}
+
 int din_conv1x1_wgrad_multi(int nsrc, const din_conv_wsrc* srcs, int dtype, int64_t pixels, int cin, int ldi, int cioff, const void* in,
                             int accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
     din_wgrad::Wg1x1K k{};
     DIN_REQUIRE(in && workspace, "conv1x1_wgrad_multi: null pointer");
-    DIN_REQUIRE(wgrad_multi_plan(nsrc, srcs, dtype, pixels, cin, &k), "conv1x1_wgrad_multi: this group does not fit the kernel "
-                "(din_conv1x1_wgrad_multi_workspace returns 0 for it: run din_conv_wgrad per layer)");
+    if (int e = wgrad_multi_lines(nsrc, srcs, dtype, pixels, cin, &k, nullptr)) return e;
     DIN_REQUIRE(ldi % 8 == 0 && cioff % 8 == 0 && ldi >= cioff + cin, "conv1x1_wgrad_multi: bad input view");
     const int64_t need = (int64_t)WGRAD_HALO_GRID * k.rows_pad * cin * 4;
     if (workspace_bytes < need) DIN_FAIL(DIN_E_WORKSPACE, "conv1x1_wgrad_multi: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+    for (int s = 0; s < nsrc; ++s)                                  // every source is checked before anything is written (the memsets below)
+        DIN_REQUIRE(srcs[s].dout && srcs[s].dw && (!srcs[s].wdot || srcs[s].w), "conv1x1_wgrad_multi: null pointer in source %d", s);
     hipStream_t st = as_stream(stream);
     const bool prezeroed = (accumulate & 2) != 0;
     accumulate &= 1;
     k.x = in; k.partial = reinterpret_cast<float*>(workspace);
     k.M = (int)pixels; k.Cin = cin; k.ldi = ldi; k.cioff = cioff; k.nsrc = nsrc;
     for (int s = 0; s < nsrc; ++s) {
-        DIN_REQUIRE(srcs[s].dout && srcs[s].dw && (!srcs[s].wdot || srcs[s].w), "conv1x1_wgrad_multi: null pointer in source %d", s);
         k.src[s].g = srcs[s].dout; k.src[s].dbias = srcs[s].dbias; k.src[s].cout = srcs[s].cout; k.src[s].ld = srcs[s].ldo; k.src[s].coff = srcs[s].cooff;
         if (!prezeroed) {
             if (srcs[s].dbias && hipMemsetAsync(srcs[s].dbias, 0, sizeof(float) * srcs[s].cout, st) != hipSuccess) DIN_FAIL(DIN_E_LAUNCH, "conv1x1_wgrad_multi: memset");

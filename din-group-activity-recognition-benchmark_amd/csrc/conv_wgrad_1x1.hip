@@ -245,7 +245,7 @@ void raise_lds(K kern, size_t lds) { din_raise_lds(reinterpret_cast<const void*>
 // Deals the sources to the two classes (<= 2 sources and <= 128 rows each, every cout a multiple of 16, Cin in {192, 256, 288});
 // false: this group does not fit the kernel (the caller launches the layers one by one).
 bool plan_wgrad_1x1_multi(int nsrc, const int* couts, int cin, Wg1x1K* k) {
-    if (nsrc < 2 || nsrc > 4 || !(cin == 192 || cin == 256 || cin == 288)) return false;
+    if (nsrc < 2 || nsrc > 4 || !wgrad_1x1_multi_name(cin, nullptr)) return false;     // (an input width DIN_WGRAD_1X1_MULTI_TABLE holds)
     for (int s = 0; s < nsrc; ++s) if (couts[s] % 16 != 0 || couts[s] <= 0 || couts[s] > 128) return false;
     // greedy: largest source first into the lighter class
     int order[4] = {0, 1, 2, 3};
@@ -271,19 +271,35 @@ bool plan_wgrad_1x1_multi(int nsrc, const int* couts, int cin, Wg1x1K* k) {
     return true;
 }
 
+// the instantiations, X(Cin, CPP) = conv_wgrad_1x1_multi_kernel<CPP>: the launcher and the name (din_conv1x1_wgrad_multi_kernel_names)
+// walk this one table; an input width that is not listed is DIN_E_ARG from both
+#define DIN_WGRAD_1X1_MULTI_TABLE(X) X(192, 24) X(256, 32) X(288, 36)
+
+bool wgrad_1x1_multi_name(int cin, std::string* name) {
+#define DIN_MULTI_ROW(CIN_, CPP_)                                                   \
+    if (cin == CIN_) {                                                              \
+        static_assert(CIN_ == 8 * CPP_, "CPP: 16-byte chunks per input pixel");     \
+        if (name) *name = "conv_wgrad_1x1_multi_kernel<" #CPP_ ">";                 \
+        return true;                                                                \
+    }
+    DIN_WGRAD_1X1_MULTI_TABLE(DIN_MULTI_ROW)
+#undef DIN_MULTI_ROW
+    return false;
+}
+
 int launch_wgrad_1x1_multi(const Wg1x1K& k, int nwg, hipStream_t st) {
     dim3 grid(nwg, 2);
     const size_t lds = (size_t)NS * ((size_t)SPX * (k.Cin / 8) * 16 + k.gbytes_max);
     DIN_REQUIRE(lds <= 160 * 1024, "wgrad 1x1 multi: %zu bytes of LDS", lds);
-    auto launch = [&](auto kern) {
-        raise_lds(kern, lds);
-        hipLaunchKernelGGL(kern, grid, dim3(1024), lds, st, k);
-    };
-    if (k.Cin == 192) launch(conv_wgrad_1x1_multi_kernel<24>);
-    else if (k.Cin == 256) launch(conv_wgrad_1x1_multi_kernel<32>);
-    else if (k.Cin == 288) launch(conv_wgrad_1x1_multi_kernel<36>);
-    else DIN_FAIL(DIN_E_ARG, "wgrad 1x1 multi: Cin %d not instantiated", k.Cin);
-    return DIN_OK;
+#define DIN_MULTI_ROW(CIN_, CPP_)                                                                       \
+    if (k.Cin == CIN_) {                                                                                \
+        raise_lds(conv_wgrad_1x1_multi_kernel<CPP_>, lds);                                              \
+        hipLaunchKernelGGL(conv_wgrad_1x1_multi_kernel<CPP_>, grid, dim3(1024), lds, st, k);            \
+        return DIN_OK;                                                                                  \
+    }
+    DIN_WGRAD_1X1_MULTI_TABLE(DIN_MULTI_ROW)
+#undef DIN_MULTI_ROW
+    DIN_FAIL(DIN_E_ARG, "wgrad 1x1 multi: Cin %d not instantiated", k.Cin);
 }
 
 }  // namespace din_wgrad

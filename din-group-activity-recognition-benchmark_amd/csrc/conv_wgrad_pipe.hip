@@ -437,18 +437,34 @@ int launch_wgrad_pipe(const WgradK& k, const PipeInst& inst, dim3 grid, dim3 blo
     DIN_FAIL(DIN_E_ARG, "wgrad pipe kernel: <%d, %d, %d, %d> not instantiated", inst.bco, inst.bk, (int)inst.wide, inst.wn);
 }
 
+// the instantiations of the grouped launch, X(BCO, WIDE) = conv_wgrad_pipe_group_kernel<BCO, 256, WIDE, 8>: the launcher and the name
+// (din_conv_wgrad_group_kernel_names) walk this one table; a (filter tile, WIDE) pair that is not listed is DIN_E_ARG from both
+#define DIN_WGRAD_PIPE_GROUP_TABLE(X) X(128, true) X(128, false) X(192, true) X(192, false) X(256, true) X(256, false)
+
+bool wgrad_pipe_group_name(int bco, bool wide, std::string* name) {
+#define DIN_GROUP_ROW(BCO_, WIDE_)                                                                  \
+    if (bco == BCO_ && wide == WIDE_) {                                                             \
+        if (name) *name = "conv_wgrad_pipe_group_kernel<" #BCO_ ", 256, " #WIDE_ ", 8>";            \
+        return true;                                                                                \
+    }
+    DIN_WGRAD_PIPE_GROUP_TABLE(DIN_GROUP_ROW)
+#undef DIN_GROUP_ROW
+    return false;
+}
+
 int launch_wgrad_pipe_group(const WgradGroupK& g, int bco, bool wide, hipStream_t st) {
-    DIN_REQUIRE(g.n >= 1 && g.n <= WGRAD_GROUP_MAX && (bco == 128 || bco == 192 || bco == 256), "wgrad pipe group: %d items, tile %d", g.n, bco);
+    DIN_REQUIRE(g.n >= 1 && g.n <= WGRAD_GROUP_MAX, "wgrad pipe group: %d items", g.n);
     const size_t lds = wgrad_pipe_lds_bytes(bco, 256);
     const dim3 grid(g.first[g.n]);
-    auto launch = [&](auto kern) {
-        raise_lds(kern, lds);
-        hipLaunchKernelGGL(kern, grid, dim3(1024), lds, st, g);
-    };
-    if (bco == 128) { if (wide) launch(conv_wgrad_pipe_group_kernel<128, 256, true, 8>); else launch(conv_wgrad_pipe_group_kernel<128, 256, false, 8>); }
-    else if (bco == 192) { if (wide) launch(conv_wgrad_pipe_group_kernel<192, 256, true, 8>); else launch(conv_wgrad_pipe_group_kernel<192, 256, false, 8>); }
-    else { if (wide) launch(conv_wgrad_pipe_group_kernel<256, 256, true, 8>); else launch(conv_wgrad_pipe_group_kernel<256, 256, false, 8>); }
-    return DIN_OK;
+#define DIN_GROUP_ROW(BCO_, WIDE_)                                                                                      \
+    if (bco == BCO_ && wide == WIDE_) {                                                                                 \
+        raise_lds(conv_wgrad_pipe_group_kernel<BCO_, 256, WIDE_, 8>, lds);                                              \
+        hipLaunchKernelGGL((conv_wgrad_pipe_group_kernel<BCO_, 256, WIDE_, 8>), grid, dim3(1024), lds, st, g);          \
+        return DIN_OK;                                                                                                  \
+    }
+    DIN_WGRAD_PIPE_GROUP_TABLE(DIN_GROUP_ROW)
+#undef DIN_GROUP_ROW
+    DIN_FAIL(DIN_E_ARG, "wgrad pipe group kernel: <%d, 256, %d, 8> not instantiated", bco, (int)wide);
 }
 
 }  // namespace din_wgrad

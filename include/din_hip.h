@@ -244,6 +244,11 @@ typedef struct din_conv_wsrc {
 int64_t din_conv1x1_wgrad_multi_workspace(int nsrc, const din_conv_wsrc* srcs, int dtype, int64_t pixels, int cin);
 int din_conv1x1_wgrad_multi(int nsrc, const din_conv_wsrc* srcs, int dtype, int64_t pixels, int cin, int ldi, int cioff, const void* in,
                             int accumulate, void* workspace, int64_t workspace_bytes, void* stream);
+/* din_conv_kernel_names for din_conv1x1_wgrad_multi: "conv_wgrad_1x1_multi_kernel<CPP>" (CPP = cin / 8) and one "conv_wgrad_reduce_kernel"
+ * line per source, in launch order, spelled and returned as din_conv_kernel_names(d, 2, ...) does.  Host only: answers from the function the
+ * launch plans in and the table it launches from, reads of a din_conv_wsrc only cout, ldo and cooff.  A group the kernel does not take
+ * (din_conv1x1_wgrad_multi_workspace answers 0) is DIN_E_ARG, as from the launch. */
+int din_conv1x1_wgrad_multi_kernel_names(int nsrc, const din_conv_wsrc* srcs, int dtype, int64_t pixels, int cin, char* buf, int buf_bytes);
 
 /* The weight gradients of up to 16 LAYERS in one launch (autograd of the torch.nn.Conv2d layers of reference backbone/backbone.py:44-99 --
  * torchvision's InceptionC blocks hold ten 7-tap / 1x1 layers of equal map size each).  A weight-gradient launch of the pipelined kernel puts
@@ -268,6 +273,14 @@ typedef struct din_conv_wgrad_item {
 int din_conv_wgrad_group_key(const din_conv_desc* d);
 int64_t din_conv_wgrad_group_workspace(int n, const din_conv_wgrad_item* items);
 int din_conv_wgrad_group(int n, const din_conv_wgrad_item* items, void* workspace, int64_t workspace_bytes, void* stream);
+/* din_conv_kernel_names for din_conv_wgrad_group, host only, from the group plan the launch itself makes (of an item only desc is read):
+ * "conv_wgrad_pipe_group_kernel<BCO, 256, WIDE, 8>" and "conv_wgrad_reduce_group_kernel" for a list that runs as one launch; for a list
+ * that runs layer by layer (n = 1, n > 16, unequal or zero keys) the lines of din_conv_kernel_names(&item.desc, 2) item after item.
+ * din_conv_wgrad_group_slices: the plan's pixel slices per item (the first min(n, cap) written to slices[]); returns the slice groups of
+ * the reduce launch's workgroups (1, 4 or 16: chosen from the largest slice count), 0 for a list that runs layer by layer, or a negative
+ * DIN_E_* code. */
+int din_conv_wgrad_group_kernel_names(int n, const din_conv_wgrad_item* items, char* buf, int buf_bytes);
+int din_conv_wgrad_group_slices(int n, const din_conv_wgrad_item* items, int32_t* slices, int cap);
 
 /* out[c] = sum over rows of g[row*ld + coff + c] (fp32 result; BatchNorm shift gradient of a conv whose epilogue ran in the pool) */
 int din_colsum(const void* g, int dtype, int64_t rows, int c, int ld, int coff, float* out, void* stream);

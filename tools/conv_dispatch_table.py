@@ -29,6 +29,12 @@ din_conv_dgrad_x_kernel_names) answer, with no option set, over the launches nhw
 tensor is ReLU-masked, with and without ACCUM) -- in bf16, fp32 and fp32_bf16x3 at the four geometries, each once PER ENTRY POINT
 (fwd2 | dgrad_multi | dgrad_x, the first word of the line), with one launch that reaches it.  tests/test_gpu_conv_multi.py holds a row for every name in that file.
 
+--names --wgrad-multi prints what profiles/wgrad_multi_kernel_names.txt holds: every distinct (entry point, kernel) pair the reverse pass of
+both backbones reaches through din_conv_wgrad_group (wgrad_group) and din_conv1x1_wgrad_multi (wgrad_multi), with no option set, in bf16,
+fp32 and fp32_bf16x3 at the four geometries -- the calls are those of tools/backward_trace.py's walk (profiles/backward_launch_trace.txt), each
+handed to its entry point's reporter (din_conv_wgrad_group_kernel_names, din_conv1x1_wgrad_multi_kernel_names) -- with one launch that
+reaches it.  tests/test_gpu_wgrad_multi.py holds a row for every pair in that file.
+
 The weight gradient follows (--wgrad: only it): for the same descriptors, geometries and dtypes,
 
     <label> which=2 <option>  ->  bm bn workspace_bytes(2) group_key
@@ -235,19 +241,69 @@ def multi_names_table(L, lib, nhwc):
     return found
 
 
+def wgrad_multi_names_table(L, lib):
+    """{(entry point: wgrad_group | wgrad_multi, kernel name): label of the first launch of a backbone's reverse pass through that entry
+    point that reaches it}.  The walk is tools/backward_trace.py's (nhwc.graph_forward + graph_backward on the CPU against the recording
+    library proxy): every din_conv_wgrad_group / din_conv1x1_wgrad_multi call the pass makes is handed, arguments unchanged, to the entry
+    point's reporter"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("backward_trace", os.path.join(os.path.dirname(os.path.abspath(__file__)), "backward_trace.py"))
+    bt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bt)
+    found, buf, head = {}, C.create_string_buffer(4096), [""]
+
+    class Reporting(bt.Recorder):
+        def call(self, L_, name, args):
+            if name == "din_conv_wgrad_group":
+                n, items = args[0], args[1]
+                rc = lib.din_conv_wgrad_group_kernel_names(n, items, buf, len(buf))
+                d = items[0].desc
+                label = f"{head[0]} {n} items, the first {d.h}x{d.w} c{d.cin}>{d.cout} k{d.kh}x{d.kw} key={lib.din_conv_wgrad_group_key(C.byref(d))}"
+                entry = "wgrad_group"
+            elif name == "din_conv1x1_wgrad_multi":
+                nsrc, srcs, dtype, pixels, cin = args[:5]
+                rc = lib.din_conv1x1_wgrad_multi_kernel_names(nsrc, srcs, dtype, pixels, cin, buf, len(buf))
+                label = f"{head[0]} {pixels} pixels c{cin}>{'+'.join(str(srcs[j].cout) for j in range(nsrc))}"
+                entry = "wgrad_multi"
+            else:
+                return
+            assert 0 < rc <= len(buf), f"{name}: the reporter answered {rc} for a call the reverse pass makes"
+            for kernel in buf.value.decode().split("\n")[:-1]:
+                found.setdefault((entry, kernel), label)
+
+    saved = bt.Recorder
+    bt.Recorder = Reporting
+    try:
+        for backbone in ("inv3", "vgg16"):
+            for dtn in ("bf16", "fp32", "fp32_bf16x3"):
+                for nb, h, w in GEOMETRIES:
+                    g, dt, params = bt.backbone(backbone, dtn, h, w)
+                    head[0] = f"{backbone} {dtn} nb{nb} {h}x{w}"
+                    _lines, outcome = bt.trace(g, params, dt, nb, {}, u8=dtn == "bf16")
+                    assert outcome == "ok", f"{head[0]}: {outcome}"
+    finally:
+        bt.Recorder = saved
+    return found
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--summary", action="store_true", help="no-option decisions at 96 frames and at the small geometry, one line per descriptor")
     ap.add_argument("--names", action="store_true", help="every distinct kernel instantiation of the no-option decisions, with one launch that reaches it")
     ap.add_argument("--wgrad", action="store_true", help="the weight-gradient part only (with --names: the weight-gradient kernel names)")
     ap.add_argument("--multi", action="store_true", help="with --names: the kernels of din_conv_fwd2 / din_conv1x1_dgrad_multi / din_conv_dgrad_x")
+    ap.add_argument("--wgrad-multi", action="store_true", help="with --names: the kernels of din_conv_wgrad_group / din_conv1x1_wgrad_multi")
     args = ap.parse_args()
-    if args.multi and not args.names:
-        ap.error("--multi selects which names --names prints: use --names --multi")
+    if (args.multi or args.wgrad_multi) and not args.names:
+        ap.error("--multi / --wgrad-multi select which names --names prints: use --names --multi, --names --wgrad-multi")
     from din_amd import _lib as L, nhwc
     lib = L.load()
     for name, _ in OPTIONS + WGRAD_OPTIONS:
         L.set_option(name, None)
+    if args.names and args.wgrad_multi:
+        for (entry, name), label in sorted(wgrad_multi_names_table(L, lib).items()):
+            print(f"{entry} {name}  <-  {label}")
+        return
     if args.names and args.multi:
         for (entry, name), label in sorted(multi_names_table(L, lib, nhwc).items()):
             print(f"{entry} {name}  <-  {label}")
