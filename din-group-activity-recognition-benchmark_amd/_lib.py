@@ -132,6 +132,7 @@ SIGNATURES: Dict[str, tuple] = {
     "din_counter_add": (_I, [_P, _U64, _P]),
     "din_walk_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "din_walk_bwd": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "din_walk_bwd_kernel_name": (_I, [_I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
     "din_head_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "din_head_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "din_basenet_head_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P]),

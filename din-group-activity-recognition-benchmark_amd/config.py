@@ -9,7 +9,9 @@ feature_cache_gb (> 0, stage-2 trainer with a frozen backbone only: the fp32 RoI
 GB per dataset, and a step skips the backbone for resident frames -- din_amd/feature_cache.py; 0 = off); feature_cache_dtype ('fp32' |
 'bf16', read only when feature_cache_gb > 0: what the slots hold.  'bf16' needs backbone_dtype = 'bf16', where the embedding GEMM
 multiplies bf16 operands anyway: the row is stored already rounded, half the bytes per frame and no cast pass, the same numbers).
-All are opt-in: at 0 the trainers behave exactly as without them."""
+deterministic (stage-2 trainer, frozen backbone, one rank: the library's DIN_DETERMINISTIC option is set for the duration of train_net, so
+every gradient on that path is summed in a fixed order and two runs with one seed give the same weights bit for bit -- ops.deterministic).
+All are opt-in: at 0 / False the trainers behave exactly as without them."""
 from __future__ import annotations
 
 import os
@@ -31,6 +33,7 @@ _DEFAULTS = dict(
     load_stage2model=False, stage2model=None, temporal_pooled_first=False,
     backbone_dtype="fp32", hier_dropout_p=0.5,
     frame_cache_gb=0, num_workers=0, feature_cache_gb=0, feature_cache_dtype="fp32",
+    deterministic=False,
 )
 
 

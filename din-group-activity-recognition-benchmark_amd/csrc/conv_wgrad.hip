@@ -1094,6 +1094,28 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const T* __restrict__ g
     }
 }
 
+// DIN_DETERMINISTIC: the column sums in a fixed order, no atomics (the structure of layernorm_param_grad_ordered_kernel).  One workgroup per
+// 16-column chunk, 64 row groups: group g sums rows g, g + 64, ... in ascending order, the partial sums meet in an LDS tree of fixed shape,
+// one thread per column writes out[c] (add: adds into it once -- the accumulate-bit-1 contract of din_conv_wgrad).
+constexpr int COLSUM_ORD_COLS = 16, COLSUM_ORD_GROUPS = 64;
+template <typename T>
+__global__ __launch_bounds__(COLSUM_ORD_COLS * COLSUM_ORD_GROUPS) void colsum_ordered_kernel(const T* __restrict__ g, float* __restrict__ out, int64_t M,
+                                                                                             int cout, int ld, int coff, int add) {
+    __shared__ float part[COLSUM_ORD_GROUPS][COLSUM_ORD_COLS + 1];
+    const int cl = threadIdx.x % COLSUM_ORD_COLS, rg = threadIdx.x / COLSUM_ORD_COLS;
+    const int c = (int)blockIdx.x * COLSUM_ORD_COLS + cl;
+    float s = 0.f;
+    if (c < cout)
+        for (int64_t r = rg; r < M; r += COLSUM_ORD_GROUPS) s += Elem<T>::ld(g + r * ld + coff + c);
+    part[rg][cl] = s;
+    __syncthreads();
+    for (int h = COLSUM_ORD_GROUPS / 2; h > 0; h >>= 1) {
+        if (rg < h) part[rg][cl] += part[rg + h][cl];
+        __syncthreads();
+    }
+    if (rg == 0 && c < cout) out[c] = add ? out[c] + part[0][cl] : part[0][cl];
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 constexpr int WGRAD_SMALL_GRID = 512;
 constexpr int WGRAD_HALO_GRID = 128;       // persistent workgroups per filter-row class of conv_wgrad_halo_kernel (2 classes x 128 = one per CU)
@@ -1188,6 +1210,13 @@ int colsum_unroll(int dtype, int c, int ld, int coff) {
 
 // column sums of a pixel-major tensor view -> out[c] (fp32 atomics across row slabs): zeroed here first, or added into when `zero` is false
 int launch_colsum(int dtype, const void* g, float* out, int64_t M, int c, int ld, int coff, hipStream_t st, bool zero = true) {
+    if (din_deterministic()) {                                // fixed-order form: no memset, no atomics, whatever DIN_COLSUM_* say
+        const dim3 grid((c + COLSUM_ORD_COLS - 1) / COLSUM_ORD_COLS), block(COLSUM_ORD_COLS * COLSUM_ORD_GROUPS);
+        if (dtype == DIN_F32) hipLaunchKernelGGL(colsum_ordered_kernel<float>, grid, block, 0, st, (const float*)g, out, M, c, ld, coff, zero ? 0 : 1);
+        else hipLaunchKernelGGL(colsum_ordered_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)g, out, M, c, ld, coff, zero ? 0 : 1);
+        DIN_CHECK_LAUNCH("colsum_ordered");
+        return DIN_OK;
+    }
     if (zero && hipMemsetAsync(out, 0, sizeof(float) * c, st) != hipSuccess) DIN_FAIL(DIN_E_LAUNCH, "colsum: memset");
     const int unr = colsum_unroll(dtype, c, ld, coff);
     if (unr) {
@@ -1451,6 +1480,11 @@ int din_conv_wgrad(const din_conv_desc* d, const void* in, const void* dout, flo
     const bool prezeroed = (accumulate & 2) != 0;            // dbias / wdot were zeroed by the caller (one memset for a whole backbone)
     accumulate &= 1;
     const WgradChoice c = din_wgrad::plan_wgrad(d, sd.split);
+    // DIN_DETERMINISTIC: dW is slice partials + a fixed-order reduce already; dbias leaves the main kernel's atomic epilogue for the ordered
+    // column sum below; <w, dW> and the atomic split-K epilogue have no ordered form: refused, never run
+    const bool ordered = din_deterministic();
+    DIN_REQUIRE(!ordered || !wdot, "conv_wgrad: DIN_DETERMINISTIC: wdot (the BatchNorm-eval scale gradient) is summed with atomics; train_backbone is not covered");
+    DIN_REQUIRE(!ordered || !c.atomic, "conv_wgrad: DIN_DETERMINISTIC: DIN_WGRAD_ATOMIC selects an atomic split-K epilogue");
     if (workspace_bytes < c.ws_bytes || !workspace)
         DIN_FAIL(DIN_E_WORKSPACE, "conv_wgrad: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)c.ws_bytes);
     DIN_REQUIRE(d->dtype == DIN_F32 || (d->ldo % 8 == 0 && d->cooff % 8 == 0), "conv_wgrad: bf16 dout stride/offset must be multiples of 8");
@@ -1461,7 +1495,7 @@ int din_conv_wgrad(const din_conv_desc* d, const void* in, const void* dout, flo
 #else
     k.probe = 0;
 #endif
-    if (dbias && c.bias_fused) {
+    if (dbias && c.bias_fused && !ordered) {
         if (!prezeroed && hipMemsetAsync(dbias, 0, sizeof(float) * d->cout, st) != hipSuccess) DIN_FAIL(DIN_E_LAUNCH, "conv_wgrad: memset");
         k.dbias = dbias;
     }
@@ -1498,7 +1532,7 @@ int din_conv_wgrad(const din_conv_desc* d, const void* in, const void* dout, flo
                            d->cout, d->cin, d->kh, d->kw, c.cin_pad, c.cout_pad, c.kcols_pad, rslices, accumulate);
         DIN_CHECK_LAUNCH("conv_wgrad_reduce");
     }
-    if (dbias && !c.bias_fused) {
+    if (dbias && (!c.bias_fused || ordered)) {
         // (fp32 / bf16 tail kernels: no fused bias sum.  accumulate bit 1 adds into the caller-zeroed dbias, as the fused paths do)
         if (int e = launch_colsum(d->dtype, dout, dbias, k.M, d->cout, d->ldo, d->cooff, st, !prezeroed)) return e;
     }

@@ -25,6 +25,15 @@ din_option_slot* din_option_register(const char* name);                    // di
 #define DIN_OPT(name) ([]() -> const char* { static din_option_slot* s_ = din_option_register(name); \
                                              return s_->value.load(std::memory_order_acquire); }())
 
+// DIN_DETERMINISTIC = "1" (off by default): every entry point that sums gradients with fp32 atomics launches its fixed-order form instead, or
+// refuses with DIN_E_ARG where it has none -- never a silent fall-back (include/din_hip.h).  Read per launch, as every option.
+#include <stdlib.h>
+#include <string.h>
+static inline bool din_deterministic() {
+    const char* v = DIN_OPT("DIN_DETERMINISTIC");
+    return v && atoi(v) != 0;
+}
+
 // Dynamic-LDS limit of a kernel above 64 KiB.  hipFuncSetAttribute is a slow host call and its effect is PER DEVICE: raise once per
 // (calling thread, current device, kernel), not per launch -- and not once per process, which would leave a second device of the same
 // process at the 64 KiB default.

@@ -167,98 +167,91 @@ __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f 
 // GLOBAL_DX: the second LDS tile (dP) does not fit next to P (large T x N grids with wide / dilated kernels: 5x5 with ratio >= 2, 7x7,
 // ratio 4 at T = 10): the feature gradient then goes straight to dx with global fp32 atomics (cells outside the clip's grid are dropped
 // at the source).  Slower per position, but any grid whose forward tile fits can also be trained.
+// NO_DX (DIN_DETERMINISTIC): the same loop with the scatter compiled out -- only the offset / relation partial sums, which are plain
+// stores in a fixed order already; the feature gradient then comes from din_walk_bwd_dx_ordered_kernel below.
 constexpr int WALK_BWD_WAVES = 4;
 template <bool GLOBAL_DX>
 __global__ __launch_bounds__(WALK_BWD_WAVES * 64) void din_walk_bwd_kernel(WalkK p) {
+    constexpr bool NO_DX = false;
+#include "din_walk_bwd_body.inc"
+}
+__global__ __launch_bounds__(WALK_BWD_WAVES * 64) void din_walk_bwd_nodx_kernel(WalkK p) {
+    constexpr bool GLOBAL_DX = true, NO_DX = true;
+#include "din_walk_bwd_body.inc"
+}
+
+// DIN_DETERMINISTIC: the feature gradient in gather form -- one pass per destination cell, no floating-point atomic, every dx element
+// written exactly once with a plain store (dx needs no memset).  One workgroup per (clip, 64-channel chunk).  The corners and weights of a
+// tap (position, k) do not depend on the channel: they are tabulated in LDS once, one RECORD per tap -- its four clamped corner
+// coordinates as bytes (ly | ry << 8 | lx << 16 | rx << 24; 255 = no such corner: padding actors, and all but the first corner of the
+// plain gather), the clamped sampling position and a_k -- 16 bytes per tap, next to the clip's gz tile [t*n][64].  The waves own the
+// destination cells round-robin, lane == channel.  A wave scans the records 64 at a time (lane == record), ballots the taps with a
+// corner on its cell and walks the set bits in ascending order: the terms of a cell are summed in (position, k, corner lt-rb-lb-rt)
+// order whatever the grid, the wave schedule or the other options.  The four corners of one tap that fall on the same cell (clamped
+// coordinates coincide) carry the same weight a_k (1 - |py - cy|) (1 - |px - cx|), as in the scatter form: no de-duplication.
+constexpr int WALK_ORD_THREADS = 1024;
+constexpr int WALK_ORD_MAXDIM = 254;      // corner coordinates are bytes, 255 is the "none" mark
+__global__ __launch_bounds__(WALK_ORD_THREADS) void din_walk_bwd_dx_ordered_kernel(WalkK p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int cells = p.hp * p.wp;
-    float* tile = smem;                       // P
-    float* dtile = tile + cells * CH;         // dP (LDS mode only)
-    float* off_s = dtile + (GLOBAL_DX ? 0 : cells * CH);        // t*n*2*k2 offsets
-    float* a_s = off_s + p.t * p.n * 2 * p.k2; // t*n*k2 saved relation weights
+    const int tn = p.t * p.n, recs = tn * p.k2;
+    float* gz_s = smem;                                    // [t*n][CH]
+    float* py_s = gz_s + tn * CH;                          // [recs] clamped sampling position
+    float* px_s = py_s + recs;
+    float* ak_s = px_s + recs;                             // [recs] saved relation weight
+    uint32_t* cell_s = reinterpret_cast<uint32_t*>(ak_s + recs);       // [recs] corner bytes
     const int nchunks = (p.c + CH - 1) / CH;
-    const int ngroups = p.ngroups;
-    const int grp = blockIdx.x % ngroups, bc = blockIdx.x / ngroups;
-    const int b = bc / nchunks, chunk = bc % nchunks, c0 = chunk * CH;
+    const int b = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks, c0 = chunk * CH;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int nb = clip_n(p, b), wpc = nb + 2 * p.pl;
-    stage_tile(p, p.x, b, c0, tile);
-    stage_offsets(p, b, off_s);
-    for (int i = threadIdx.x; i < p.t * p.n * p.k2; i += (int)blockDim.x) a_s[i] = p.a[(int64_t)b * p.t * p.n * p.k2 + i];
-    if (!GLOBAL_DX)
-        for (int i = threadIdx.x; i < cells * CH; i += (int)blockDim.x) dtile[i] = 0.f;
-    __syncthreads();
     const bool cok = c0 + lane < p.c;
-    // feature-gradient scatter of one corner: LDS tile, or dx itself when the tile does not fit
-    auto scatter = [&](int cy, int cx, float v) {
-        if (!GLOBAL_DX) { atomicAdd(&dtile[(cy * p.wp + cx) * CH + lane], v); return; }
-        const int tt2 = cy - p.pt, nn2 = cx - p.pl;
-        if (cok && tt2 >= 0 && tt2 < p.t && nn2 >= 0 && nn2 < nb && v != 0.f)
-            atomicAdd(&p.dx[((int64_t)(b * p.t + tt2) * p.n + nn2) * p.c + c0 + lane], v);
-    };
-    // per-chunk partial sums, plain stores (each (chunk, position, k) is written exactly once): scratch[chunk][ d_off [b,t,n,2k2] | d_a [b,t,n,k2] ];
-    // din_walk_bwd_finish_kernel adds the chunks in a fixed order
-    float* d_off = p.scratch + (int64_t)chunk * p.b * p.t * p.n * 3 * p.k2;
-    float* d_a = d_off + (int64_t)p.b * p.t * p.n * 2 * p.k2;
-    for (int pos = grp * WALK_BWD_WAVES + w; pos < p.t * p.n; pos += ngroups * WALK_BWD_WAVES)
-    if (pos % p.n >= nb) {                                // padding actor: no gradient (the finish kernel sums every chunk's slot)
-        const int64_t gpos = (int64_t)b * p.t * p.n + pos;
-        for (int j = lane; j < 3 * p.k2; j += 64) {
-            if (j < 2 * p.k2) d_off[gpos * 2 * p.k2 + j] = 0.f; else d_a[gpos * p.k2 + (j - 2 * p.k2)] = 0.f;
-        }
-    } else {
-        int tt = pos / p.n, nn = pos - tt * p.n;
-        const int64_t gpos = (int64_t)b * p.t * p.n + pos;
-        const float* pr = off_s + pos * 2 * p.k2;
-        const float g = cok ? p.gz[gpos * p.c + c0 + lane] : 0.f;
-        for (int k = 0; k < p.k2; ++k) {
-            const float ak = a_s[pos * p.k2 + k];
-            if (p.plain) {
-                const int r = k / p.kw, s2 = k - r * p.kw;
-                const int cy = p.pt + tt + p.ky0 + r * p.ratio, cx = p.pl + nn + p.kx0 + s2 * p.ratio;
-                const float sk = tile[(cy * p.wp + cx) * CH + lane];
-                scatter(cy, cx, ak * g);
-                const float d_s = wave_sum(g * sk);
-                if (lane == 0) { d_off[gpos * 2 * p.k2 + k] = 0.f; d_off[gpos * 2 * p.k2 + p.k2 + k] = 0.f; d_a[gpos * p.k2 + k] = d_s; }
-                continue;
-            }
-            Corner c = corners(p, wpc, tt, nn, k, pr[k], pr[p.k2 + k]);
-            float wy_l = coef(c.py, c.ly), wy_r = coef(c.py, c.ry), wx_l = coef(c.px, c.lx), wx_r = coef(c.px, c.rx);
-            const int i_lt = (c.ly * p.wp + c.lx) * CH + lane, i_rb = (c.ry * p.wp + c.rx) * CH + lane;
-            const int i_lb = (c.ry * p.wp + c.lx) * CH + lane, i_rt = (c.ly * p.wp + c.rx) * CH + lane;
-            float v_lt = tile[i_lt], v_rb = tile[i_rb], v_lb = tile[i_lb], v_rt = tile[i_rt];
-            float sk = v_lt * (wy_l * wx_l) + v_rb * (wy_r * wx_r) + v_lb * (wy_r * wx_l) + v_rt * (wy_l * wx_r);
-            // feature gradient: scatter-add a_k * w_corner * gz into the padded tile (LDS atomics; waves may collide)
-            const float ag = ak * g;
-            scatter(c.ly, c.lx, ag * (wy_l * wx_l));
-            scatter(c.ry, c.rx, ag * (wy_r * wx_r));
-            scatter(c.ry, c.lx, ag * (wy_r * wx_l));
-            scatter(c.ly, c.rx, ag * (wy_l * wx_r));
-            // per-corner <gz, P_corner> and <gz, S_k> over this channel chunk
-            float d_s = wave_sum(g * sk);
-            float d_lt = wave_sum(g * v_lt), d_rb = wave_sum(g * v_rb), d_lb = wave_sum(g * v_lb), d_rt = wave_sum(g * v_rt);
-            if (lane == 0) {
-                // d/d py of (1-|py-cy|) = -sign(py-cy); clamp passes gradient on the closed interval (Q8, Q9)
-                const float my = (c.py0 >= 0.f && c.py0 <= (float)(p.phy >= 0 ? p.phy : (p.ihy >= 0 ? p.ihy : p.hp - 1))) ? 1.f : 0.f;
-                const float mx = (c.px0 >= 0.f && c.px0 <= (float)(p.phx >= 0 ? p.phx : (p.ihx >= 0 ? p.ihx : wpc - 1))) ? 1.f : 0.f;
-                const float sy_l = -sgn(c.py - (float)c.ly), sy_r = -sgn(c.py - (float)c.ry);
-                const float sx_l = -sgn(c.px - (float)c.lx), sx_r = -sgn(c.px - (float)c.rx);
-                float doy = d_lt * sy_l * wx_l + d_rb * sy_r * wx_r + d_lb * sy_r * wx_l + d_rt * sy_l * wx_r;
-                float dox = d_lt * wy_l * sx_l + d_rb * wy_r * sx_r + d_lb * wy_r * sx_l + d_rt * wy_l * sx_r;
-                d_off[gpos * 2 * p.k2 + k] = my * ak * doy;
-                d_off[gpos * 2 * p.k2 + p.k2 + k] = mx * ak * dox;
-                d_a[gpos * p.k2 + k] = d_s;
+    for (int pos = w; pos < tn; pos += WALK_ORD_THREADS / 64)
+        gz_s[pos * CH + lane] = cok ? p.gz[((int64_t)b * tn + pos) * p.c + c0 + lane] : 0.f;
+    for (int r = threadIdx.x; r < recs; r += WALK_ORD_THREADS) {
+        const int pos = r / p.k2, k = r - pos * p.k2;
+        const int tt = pos / p.n, nn = pos - tt * p.n;
+        uint32_t word = 0xFFFFFFFFu;
+        float py = 0.f, px = 0.f;
+        if (nn < nb) {                                     // (padding actors of a shorter clip scatter nothing)
+            if (p.plain) {                                 // the lattice point itself, weight a_k: one corner, coefficients 1 - |0|
+                const int rr = k / p.kw, s = k - rr * p.kw;
+                const int cy = p.pt + tt + p.ky0 + rr * p.ratio, cx = p.pl + nn + p.kx0 + s * p.ratio;
+                word = (uint32_t)cy | 0xFF00u | ((uint32_t)cx << 16) | 0xFF000000u;
+                py = (float)cy; px = (float)cx;
+            } else {
+                const float* pr = p.pred + ((int64_t)b * tn + pos) * p.cp;
+                const Corner c = corners(p, wpc, tt, nn, k, pr[k], pr[p.k2 + k]);
+                word = (uint32_t)c.ly | ((uint32_t)c.ry << 8) | ((uint32_t)c.lx << 16) | ((uint32_t)c.rx << 24);
+                py = c.py; px = c.px;
             }
         }
+        cell_s[r] = word; py_s[r] = py; px_s[r] = px;
+        ak_s[r] = p.a[(int64_t)b * recs + r];
     }
-    if (GLOBAL_DX) return;
     __syncthreads();
-    // un-pad and add this group's share: dx[b,t,n,c] += dP[pt+t][pl+n][c]
-    for (int q = w; q < p.t * p.n; q += WALK_BWD_WAVES) {
-        int tt = q / p.n, nn = q - tt * p.n;
-        if (nn >= nb) continue;                            // cells beyond the clip's grid are zero padding: their gradient is dropped
-        const float v = dtile[((p.pt + tt) * p.wp + p.pl + nn) * CH + lane];
-        if (cok && v != 0.f) atomicAdd(&p.dx[((int64_t)b * p.t * p.n + q) * p.c + c0 + lane], v);
+    for (int q = w; q < tn; q += WALK_ORD_THREADS / 64) {
+        const int tt = q / p.n, nn = q - tt * p.n;
+        float acc = 0.f;
+        if (nn < nb) {                                     // cells beyond the clip's grid are zero padding: they keep 0
+            const uint32_t cy = (uint32_t)(p.pt + tt), cx = (uint32_t)(p.pl + nn);
+            for (int base = 0; base < recs; base += 64) {
+                const uint32_t mine = base + lane < recs ? cell_s[base + lane] : 0xFFFFFFFFu;
+                const bool hit = ((mine & 255u) == cy || ((mine >> 8) & 255u) == cy) && (((mine >> 16) & 255u) == cx || (mine >> 24) == cx);
+                unsigned long long todo = __ballot(hit);
+                while (todo) {
+                    const int r = base + __ffsll((long long)todo) - 1;
+                    todo &= todo - 1;
+                    const uint32_t wd = cell_s[r];         // (wave-uniform address: an LDS broadcast)
+                    const bool yl = (wd & 255u) == cy, yr = ((wd >> 8) & 255u) == cy, xl = ((wd >> 16) & 255u) == cx, xr = (wd >> 24) == cx;
+                    const float wgt = ak_s[r] * (coef(py_s[r], (int)cy) * coef(px_s[r], (int)cx));
+                    const float v = wgt * gz_s[(r / p.k2) * CH + lane];
+                    if (yl && xl) acc += v;                // lt, rb, lb, rt: the scatter form's order
+                    if (yr && xr) acc += v;
+                    if (yr && xl) acc += v;
+                    if (yl && xr) acc += v;
+                }
+            }
+        }
+        if (cok) p.dx[((int64_t)b * tn + q) * p.c + c0 + lane] = acc;
     }
 }
 
@@ -318,6 +311,35 @@ int fill(WalkK& p, int cp, int b, int t, int n, int c, int kh, int kw, int ratio
     return DIN_OK;
 }
 
+// The feature-gradient kernel of a din_walk_bwd call under the current options, decided HERE once: din_walk_bwd launches from it and
+// din_walk_bwd_kernel_name spells it.  lds: dynamic LDS of din_walk_bwd_kernel<> / din_walk_bwd_nodx_kernel; lds_dx: of the ordered kernel.
+enum { WALK_DX_LDS = 0, WALK_DX_GLOBAL = 1, WALK_DX_ORDERED = 2 };
+struct WalkBwdChoice { int form; size_t lds, lds_dx; };
+int choose_walk_bwd(const WalkK& p, WalkBwdChoice& ch) {
+    const size_t tile_b = (size_t)p.hp * p.wp * CH * sizeof(float), tab_b = (size_t)p.t * p.n * 3 * p.k2 * sizeof(float);
+    if (din_deterministic()) {
+        // no atomic form under the option, whatever DIN_WALK_BWD_GLOBAL says: the offset / relation sums from the scatter-free loop, dx from
+        // the ordered kernel (gz tile + 16 bytes per tap)
+        ch.form = WALK_DX_ORDERED;
+        ch.lds = tile_b + tab_b;
+        ch.lds_dx = ((size_t)p.t * p.n * CH + (size_t)p.t * p.n * p.k2 * 4) * sizeof(float);
+        DIN_REQUIRE(p.hp <= WALK_ORD_MAXDIM && p.wp <= WALK_ORD_MAXDIM,
+                    "din_walk_bwd: DIN_DETERMINISTIC: padded grid %d x %d exceeds %d cells a side", p.hp, p.wp, WALK_ORD_MAXDIM);
+        DIN_REQUIRE(ch.lds <= 160 * 1024 && ch.lds_dx <= 160 * 1024,
+                    "din_walk_bwd: DIN_DETERMINISTIC: T x N grid too large for the ordered feature gradient (%zu / %zu bytes of LDS)", ch.lds, ch.lds_dx);
+        return DIN_OK;
+    }
+    // feature gradient scattered straight into dx (fp32 L2 atomics): measured 320 -> 118 us on 32 clips x 36 positions against the LDS dP tile,
+    // whose ds_add_f32 traffic alone cost 230 us (a knock-out of the LDS atomics: 95 us).  DIN_WALK_BWD_GLOBAL=0 keeps the LDS tile when it fits.
+    const char* gx = DIN_OPT("DIN_WALK_BWD_GLOBAL");
+    const bool global_dx = 2 * tile_b + tab_b > 160 * 1024 || !(gx && atoi(gx) == 0);
+    ch.form = global_dx ? WALK_DX_GLOBAL : WALK_DX_LDS;
+    ch.lds = (global_dx ? 1 : 2) * tile_b + tab_b;
+    ch.lds_dx = 0;
+    DIN_REQUIRE(ch.lds <= 160 * 1024, "din_walk_bwd: T x N grid too large for one LDS tile (%zu bytes)", ch.lds);
+    return DIN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -348,21 +370,23 @@ int din_walk_bwd(const float* x, const float* pred, int cp, const float* a, cons
     p.x = x; p.pred = pred; p.a = const_cast<float*>(a); p.gz = gz; p.dx = dx; p.scratch = scratch;
     hipStream_t st = as_stream(stream);
     int64_t positions = (int64_t)b * t * n;
-    const size_t tile_b = (size_t)p.hp * p.wp * CH * sizeof(float), tab_b = (size_t)t * n * 3 * p.k2 * sizeof(float);
-    // feature gradient scattered straight into dx (fp32 L2 atomics): measured 320 -> 118 us on 32 clips x 36 positions against the LDS dP tile,
-    // whose ds_add_f32 traffic alone cost 230 us (a knock-out of the LDS atomics: 95 us).  DIN_WALK_BWD_GLOBAL=0 keeps the LDS tile when it fits.
-    const char* gx = DIN_OPT("DIN_WALK_BWD_GLOBAL");
-    const bool global_dx = 2 * tile_b + tab_b > 160 * 1024 || !(gx && atoi(gx) == 0);
-    const size_t lds = (global_dx ? 1 : 2) * tile_b + tab_b;
-    DIN_REQUIRE(lds <= 160 * 1024, "din_walk_bwd: T x N grid too large for one LDS tile (%zu bytes)", lds);
-    auto raise = [&](const void* fn) -> int {
-        if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            DIN_FAIL(DIN_E_LAUNCH, "din_walk_bwd: cannot raise the dynamic LDS limit to %zu bytes", lds);
+    WalkBwdChoice ch{};
+    if (int e = choose_walk_bwd(p, ch)) return e;
+    const bool ordered = ch.form == WALK_DX_ORDERED, global_dx = ch.form == WALK_DX_GLOBAL;
+    const size_t lds = ch.lds;
+    auto raise = [&](const void* fn, size_t bytes) -> int {
+        if (bytes > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+            DIN_FAIL(DIN_E_LAUNCH, "din_walk_bwd: cannot raise the dynamic LDS limit to %zu bytes", bytes);
         return DIN_OK;
     };
-    if (int e = raise(global_dx ? reinterpret_cast<const void*>(din_walk_bwd_kernel<true>) : reinterpret_cast<const void*>(din_walk_bwd_kernel<false>))) return e;
-    if (hipMemsetAsync(dx, 0, sizeof(float) * positions * c, st) != hipSuccess) DIN_FAIL(DIN_E_LAUNCH, "din_walk_bwd: memset");
+    if (int e = raise(ordered ? reinterpret_cast<const void*>(din_walk_bwd_nodx_kernel)
+                      : global_dx ? reinterpret_cast<const void*>(din_walk_bwd_kernel<true>) : reinterpret_cast<const void*>(din_walk_bwd_kernel<false>), lds)) return e;
     int nchunks = (c + CH - 1) / CH;
+    if (ordered) {
+        if (int e = raise(reinterpret_cast<const void*>(din_walk_bwd_dx_ordered_kernel), ch.lds_dx)) return e;
+        hipLaunchKernelGGL(din_walk_bwd_dx_ordered_kernel, dim3(b * nchunks), dim3(WALK_ORD_THREADS), ch.lds_dx, st, p);
+        DIN_CHECK_LAUNCH("din_walk_bwd_dx_ordered");
+    } else if (hipMemsetAsync(dx, 0, sizeof(float) * positions * c, st) != hipSuccess) DIN_FAIL(DIN_E_LAUNCH, "din_walk_bwd: memset");
     // every workgroup stages the clip's whole padded tile: as few position groups as still fill the chip (~4 workgroups per CU); one wave per
     // position (the round-1 launch) cost 298 us on 32 clips x 36 positions, almost all of it re-staging.  DIN_WALK_BWD_GROUPS overrides.
     const int full = (t * n + WALK_BWD_WAVES - 1) / WALK_BWD_WAVES;
@@ -370,13 +394,26 @@ int din_walk_bwd(const float* x, const float* pred, int cp, const float* a, cons
     { const char* gv = DIN_OPT("DIN_WALK_BWD_GROUPS"); if (gv && atoi(gv) > 0) ngroups = atoi(gv); }
     if (ngroups > full) ngroups = full;
     p.ngroups = ngroups;
-    if (global_dx) hipLaunchKernelGGL(din_walk_bwd_kernel<true>, dim3(b * nchunks * ngroups), dim3(WALK_BWD_WAVES * 64), lds, st, p);
+    if (ordered) hipLaunchKernelGGL(din_walk_bwd_nodx_kernel, dim3(b * nchunks * ngroups), dim3(WALK_BWD_WAVES * 64), lds, st, p);
+    else if (global_dx) hipLaunchKernelGGL(din_walk_bwd_kernel<true>, dim3(b * nchunks * ngroups), dim3(WALK_BWD_WAVES * 64), lds, st, p);
     else hipLaunchKernelGGL(din_walk_bwd_kernel<false>, dim3(b * nchunks * ngroups), dim3(WALK_BWD_WAVES * 64), lds, st, p);
     DIN_CHECK_LAUNCH("din_walk_bwd");
     const int fin_threads = (3 * p.k2 + 63) / 64 * 64;
     hipLaunchKernelGGL(din_walk_bwd_finish_kernel, dim3((unsigned)positions), dim3(fin_threads), 0, st, scratch, a, dpred,
                        positions, p.k2, cp, scale_factor, nchunks);
     DIN_CHECK_LAUNCH("din_walk_bwd_finish");
+    return DIN_OK;
+}
+
+int din_walk_bwd_kernel_name(int b, int t, int n, int c, int kh, int kw, int ratio, char* buf, int buf_bytes) {
+    DIN_REQUIRE(buf && buf_bytes > 0, "din_walk_bwd_kernel_name: no buffer");
+    WalkK p{};
+    if (int e = fill(p, 3 * kh * kw, b, t, n, c, kh, kw, ratio, 1, 0, nullptr, nullptr)) return e;
+    WalkBwdChoice ch{};
+    if (int e = choose_walk_bwd(p, ch)) return e;
+    const char* name = ch.form == WALK_DX_ORDERED ? "din_walk_bwd_dx_ordered_kernel" : ch.form == WALK_DX_GLOBAL ? "din_walk_bwd_kernel<true>" : "din_walk_bwd_kernel<false>";
+    DIN_REQUIRE((int)strlen(name) < buf_bytes, "din_walk_bwd_kernel_name: buffer of %d bytes too small", buf_bytes);
+    strcpy(buf, name);
     return DIN_OK;
 }
 

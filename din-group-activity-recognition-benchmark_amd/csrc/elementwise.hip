@@ -82,6 +82,30 @@ __global__ void dot_kernel(const float* __restrict__ x, const float* __restrict_
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) atomicAdd(out + idx, s);
 }
+// DIN_DETERMINISTIC: one workgroup; thread i sums elements i, i + 1024, ... (four accumulators, joined in a fixed order), the wave
+// butterfly, then thread 0 adds the sixteen wave sums in order and adds the total into out[idx] once
+constexpr int DOT_ORD_THREADS = 1024;
+__global__ __launch_bounds__(DOT_ORD_THREADS) void dot_ordered_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out,
+                                                                      int idx, int64_t n) {
+    __shared__ float part[DOT_ORD_THREADS / 64];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int64_t i = threadIdx.x;
+    for (; i + 3 * DOT_ORD_THREADS < n; i += 4 * DOT_ORD_THREADS) {
+        s0 += x[i] * y[i];
+        s1 += x[i + DOT_ORD_THREADS] * y[i + DOT_ORD_THREADS];
+        s2 += x[i + 2 * DOT_ORD_THREADS] * y[i + 2 * DOT_ORD_THREADS];
+        s3 += x[i + 3 * DOT_ORD_THREADS] * y[i + 3 * DOT_ORD_THREADS];
+    }
+    for (; i < n; i += DOT_ORD_THREADS) s0 += x[i] * y[i];
+    const float s = wave_sum((s0 + s1) + (s2 + s3));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tot = 0.f;
+        for (int q = 0; q < DOT_ORD_THREADS / 64; ++q) tot += part[q];
+        out[idx] += tot;
+    }
+}
 __global__ void grad_cast_mask_kernel(const float* __restrict__ g, const void* __restrict__ y, void* __restrict__ out, int dtype,
                                       int64_t pixels, int c, int ldy, int yoff, int ldo, int ooff, int use_mask) {
     const int c4 = c >> 2;
@@ -254,6 +278,11 @@ int din_scale_by_param(const float* x, const float* scalar, int idx, float* out,
 int din_dot_accum(const float* x, const float* y, float* out, int idx, int64_t n, void* stream) {
     DIN_REQUIRE(x && y && out && n >= 0 && idx >= 0, "dot_accum: bad argument");
     if (n == 0) return DIN_OK;
+    if (din_deterministic()) {
+        hipLaunchKernelGGL(dot_ordered_kernel, dim3(1), dim3(DOT_ORD_THREADS), 0, as_stream(stream), x, y, out, idx, n);
+        DIN_CHECK_LAUNCH("dot_accum");
+        return DIN_OK;
+    }
     hipLaunchKernelGGL(dot_kernel, dim3(grid_1d(n, 256, 512)), dim3(256), 0, as_stream(stream), x, y, out, idx, n);
     DIN_CHECK_LAUNCH("dot_accum");
     return DIN_OK;

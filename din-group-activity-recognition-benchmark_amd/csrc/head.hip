@@ -78,6 +78,47 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(const float* __r
     if (threadIdx.x < a) atomicAdd(dbias + threadIdx.x, dscores[bi * a + threadIdx.x] * inv_t);
 }
 
+// DIN_DETERMINISTIC: head_bwd_kernel's ds alone (same arithmetic, same order over j) ...
+__global__ __launch_bounds__(HEAD_THREADS) void head_bwd_ds_kernel(const float* __restrict__ dscores, const float* __restrict__ w,
+                                                                   const int32_t* __restrict__ argmax, int b, int t, int n, int c, int a,
+                                                                   float* __restrict__ ds) {
+    const int bi = blockIdx.x / t, ti = blockIdx.x % t;
+    const float inv_t = 1.f / (float)t;
+    float* dsb = ds + ((int64_t)(bi * t + ti) * n) * c;
+    for (int ch = threadIdx.x; ch < c; ch += HEAD_THREADS) {
+        int am = argmax[(int64_t)(bi * t + ti) * c + ch];
+        float g = 0.f;
+        for (int j = 0; j < a; ++j) g += dscores[bi * a + j] * inv_t * w[(int64_t)j * c + ch];
+        for (int i = 0; i < n; ++i) dsb[(int64_t)i * c + ch] = (i == am) ? g : 0.f;
+    }
+}
+
+// ... and dw / dbias: one thread per dw[j, ch] (and per dbias[j], the last a threads) walks the b*t frames in ascending order and adds its
+// sum into the caller's buffer once -- the same terms as the atomic form, no atomics
+__global__ __launch_bounds__(HEAD_THREADS) void head_param_grad_ordered_kernel(const float* __restrict__ dscores, const float* __restrict__ s,
+                                                                               const int32_t* __restrict__ argmax, int b, int t, int n, int c,
+                                                                               int a, float* __restrict__ dw, float* __restrict__ dbias) {
+    const int64_t i = (int64_t)blockIdx.x * HEAD_THREADS + threadIdx.x;
+    const float inv_t = 1.f / (float)t;
+    if (i < (int64_t)a * c) {
+        const int j = (int)(i / c), ch = (int)(i - (int64_t)j * c);
+        float acc = 0.f;
+#pragma unroll 8
+        for (int f = 0; f < b * t; ++f) {                  // (independent loads of several frames in flight; the adds stay in frame order)
+            const int am = argmax[(int64_t)f * c + ch];
+            const float pooled = s[((int64_t)f * n + am) * c + ch];
+            const float dsc = dscores[(f / t) * a + j] * inv_t;
+            acc += dsc * pooled;
+        }
+        dw[i] += acc;
+    } else if (i < (int64_t)a * c + a) {
+        const int j = (int)(i - (int64_t)a * c);
+        float acc = 0.f;
+        for (int f = 0; f < b * t; ++f) acc += dscores[(f / t) * a + j] * inv_t;
+        dbias[j] += acc;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -101,6 +142,15 @@ int din_head_bwd(const float* dscores, const float* s, const float* w, const int
                  int a, float* ds, float* dw, float* dbias, void* stream) {
     DIN_REQUIRE(dscores && s && w && argmax && ds && dw && dbias, "head_bwd: null pointer");
     DIN_REQUIRE(b > 0 && t > 0 && n > 0 && c > 0 && a > 0 && a <= MAX_ACT, "head_bwd: bad shape");
+    if (din_deterministic()) {
+        hipLaunchKernelGGL(head_bwd_ds_kernel, dim3(b * t), dim3(HEAD_THREADS), 0, as_stream(stream), dscores, w, argmax, b, t, n, c, a, ds);
+        DIN_CHECK_LAUNCH("head_bwd");
+        const int64_t threads = (int64_t)a * c + a;
+        hipLaunchKernelGGL(head_param_grad_ordered_kernel, dim3((unsigned)ceil_div64(threads, HEAD_THREADS)), dim3(HEAD_THREADS), 0, as_stream(stream),
+                           dscores, s, argmax, b, t, n, c, a, dw, dbias);
+        DIN_CHECK_LAUNCH("head_param_grad_ordered");
+        return DIN_OK;
+    }
     hipLaunchKernelGGL(head_bwd_kernel, dim3(b * t), dim3(HEAD_THREADS), 0, as_stream(stream), dscores, s, w, argmax, b, t, n, c, a, ds, dw, dbias);
     DIN_CHECK_LAUNCH("head_bwd");
     return DIN_OK;

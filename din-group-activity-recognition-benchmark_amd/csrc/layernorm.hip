@@ -200,6 +200,37 @@ __global__ void layernorm_param_grad_kernel(const float* __restrict__ dy, const 
     atomicAdd(dbeta + col, b);
 }
 
+// DIN_DETERMINISTIC: dgamma / dbeta of ANY row count as a fixed-order column reduction, no atomics.  One workgroup per 16-column chunk
+// (64-byte row segments), 64 row groups: group g sums rows g, g + 64, ... in ascending order, the 64 partial sums then meet in an LDS
+// tree whose shape does not depend on anything but its size, and one thread per column adds the total into the caller's buffer once.
+constexpr int LNP_COLS = 16, LNP_GROUPS = 64;
+__global__ __launch_bounds__(LNP_COLS * LNP_GROUPS) void layernorm_param_grad_ordered_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ y,
+    const float* __restrict__ stats, float* __restrict__ dgamma, float* __restrict__ dbeta, int64_t rows, int64_t len, int relu,
+    float drop_p, uint64_t seed, const uint64_t* __restrict__ seed_off) {
+    __shared__ float pa[LNP_GROUPS][LNP_COLS + 1], pb[LNP_GROUPS][LNP_COLS + 1];
+    seed = fold_seed(seed, seed_off);
+    const int cl = threadIdx.x % LNP_COLS, rg = threadIdx.x / LNP_COLS;
+    const int64_t col = (int64_t)blockIdx.x * LNP_COLS + cl;
+    float a = 0.f, b = 0.f;
+    if (col < len)
+        for (int64_t r = rg; r < rows; r += LNP_GROUPS) {
+            int64_t i = r * len + col;
+            float xh = (x[i] + (res ? res[i] : 0.f) - stats[r * 2]) * stats[r * 2 + 1];
+            float g = dy[i] * keep_scale(seed, i, drop_p);
+            if (relu && !(y[i] > 0.f)) g = 0.f;
+            a += g * xh;
+            b += g;
+        }
+    pa[rg][cl] = a; pb[rg][cl] = b;
+    __syncthreads();
+    for (int s = LNP_GROUPS / 2; s > 0; s >>= 1) {
+        if (rg < s) { pa[rg][cl] += pa[rg + s][cl]; pb[rg][cl] += pb[rg + s][cl]; }
+        __syncthreads();
+    }
+    if (rg == 0 && col < len) { dgamma[col] += pa[0][cl]; dbeta[col] += pb[0][cl]; }
+}
+
 }  // namespace
 
 extern "C" {
@@ -223,11 +254,16 @@ int din_layernorm_bwd(const float* dy, const float* x, const float* res, const f
     if (rows == 0) return DIN_OK;
     // few long rows (per-clip LN): per-element atomics from the row kernel are cheap (rows adds per address);
     // many short rows (nl_emb_1): dedicated column-reduction kernel
-    const int atomic_params = rows <= 8 ? 1 : 0;
+    const bool ordered = din_deterministic();                 // dgamma / dbeta from the fixed-order column reduction, for every row count
+    const int atomic_params = rows <= 8 && !ordered ? 1 : 0;
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)rows), dim3(LN_THREADS), 0, as_stream(stream), dy, x, res, gamma, y, stats, dx,
                        dgamma, dbeta, len, relu, drop_p, seed, seed_offset, atomic_params);
     DIN_CHECK_LAUNCH("layernorm_bwd");
-    if (!atomic_params) {
+    if (ordered) {
+        hipLaunchKernelGGL(layernorm_param_grad_ordered_kernel, dim3((unsigned)ceil_div64(len, LNP_COLS)), dim3(LNP_COLS * LNP_GROUPS), 0,
+                           as_stream(stream), dy, x, res, y, stats, dgamma, dbeta, rows, len, relu, drop_p, seed, seed_offset);
+        DIN_CHECK_LAUNCH("layernorm_param_grad_ordered");
+    } else if (!atomic_params) {
         int64_t rpb = 32;
         dim3 grid((unsigned)ceil_div64(len, 256), (unsigned)ceil_div64(rows, rpb));
         hipLaunchKernelGGL(layernorm_param_grad_kernel, grid, dim3(256), 0, as_stream(stream), dy, x, res, y, stats, dgamma, dbeta, rows, len,

@@ -5,6 +5,7 @@ the autograd tape only.  All tensors here are fp32 (the tail of the path is alwa
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional, Tuple
 
@@ -17,6 +18,37 @@ from .nhwc import _ptr, _stream, din_dtype, require_gpu, workspace
 # Device-side per-step part of every dropout seed (int64 [1]) or None.  A training step captured in a HIP graph (din_amd.graph_step) bakes
 # the host-computed seeds into the launches; the kernels add *SEED_OFFSET, which the captured step advances once per replay.
 SEED_OFFSET: Optional[torch.Tensor] = None
+
+
+DETERMINISTIC_OPTION = "DIN_DETERMINISTIC"
+
+
+@contextlib.contextmanager
+def deterministic(on: bool = True):
+    """Inside the block every gradient sum of the frozen-backbone stage-2 path (walk dx, LayerNorm dgamma / dbeta, head dw / dbias,
+    dot_accum, the bias gradient of linear / GridConvFunction) runs its fixed-order kernel: same inputs, same bits, whatever the wave
+    schedule (include/din_hip.h: DIN_DETERMINISTIC).  on=False switches the option off inside the block.  Options are process-wide: the
+    previous value is put back on exit, also when the block raises.  What has no ordered form (a trained backbone's BatchNorm-scale
+    gradient, for one) raises DinError under the option instead of running atomics."""
+    before = L.get_option(DETERMINISTIC_OPTION)
+    L.set_option(DETERMINISTIC_OPTION, 1 if on else None)
+    try:
+        yield
+    finally:
+        L.set_option(DETERMINISTIC_OPTION, before)
+
+
+def deterministic_refusal(cfg, world: int) -> Optional[str]:
+    """why cfg.deterministic cannot be honoured, or None (train_net_dynamic.train_net raises ValueError with it)"""
+    if not getattr(cfg, "deterministic", False):
+        return None
+    if cfg.train_backbone:
+        return ("deterministic = True: train_backbone is set, and the backbone's bias / BatchNorm-scale gradients and the RoIAlign backward "
+                "still sum with atomics; the mode covers the frozen backbone")
+    if world > 1:
+        return (f"deterministic = True: {world} ranks, and the order in which the gradient all-reduce sums the ranks is RCCL's; the mode "
+                f"covers one rank")
+    return None
 
 
 # ------------------------------------------------------------------------------------------------

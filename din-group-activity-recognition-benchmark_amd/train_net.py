@@ -163,7 +163,8 @@ def build_model(cfg):
 
 def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     """Reference train_net (:28-138), stage 1.  Launch one process per GPU with torchrun; a single process works too.  max_steps bounds
-    the number of epochs (smoke runs)."""
+    the number of epochs (smoke runs).  cfg.deterministic is ignored here: stage 1 trains the backbone, whose bias / BatchNorm-scale
+    gradients and RoIAlign backward have no fixed-order form (the stage-2 trainer's deterministic mode covers the frozen backbone)."""
     model = build_model(cfg)                                           # (refuses stage 2 before touching the device)
     if getattr(cfg, "result_path", None) is None:
         cfg.init_config()

@@ -26,7 +26,7 @@ import torch
 import torch.nn.functional as F
 import torch.utils.data as data
 
-from . import parallel
+from . import ops, parallel
 from . import feature_cache, frame_cache
 from .input_feed import DeviceFeed  # noqa: F401  (re-exported: `from train_net import *` launchers)
 from .infer_model import (ARG_volleyball, AT_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, Dynamic_volleyball,
@@ -198,10 +198,20 @@ def _mask_counters(model):
 
 def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     """Reference train_net (:27-157).  Launch one process per GPU with torchrun; a single process works too.  max_steps bounds the number
-    of epochs (smoke runs)."""
-    why_not = feature_cache.refusal(cfg)                               # cfg.feature_cache_gb > 0 where cached features would be wrong
+    of epochs (smoke runs).  cfg.deterministic: the whole call runs under ops.deterministic() (frozen backbone, one rank; the option is
+    back at its previous value when the call returns or raises)."""
+    # cfg.deterministic where a sum's order is not ours (first: its answer is the same whatever the caches and workers are set to), then
+    # cfg.feature_cache_gb > 0 where cached features would be wrong -- both before any process group or loader exists
+    why_not = ops.deterministic_refusal(cfg, int(os.environ.get("WORLD_SIZE", "1"))) or feature_cache.refusal(cfg)
     if why_not:
         raise ValueError(why_not)
+    if getattr(cfg, "deterministic", False):
+        with ops.deterministic():
+            return _train_net(cfg, training_set, validation_set, max_steps)
+    return _train_net(cfg, training_set, validation_set, max_steps)
+
+
+def _train_net(cfg, training_set, validation_set, max_steps):
     rank, local_rank, world = parallel.init_from_env()
     np.random.seed(cfg.train_random_seed)
     torch.manual_seed(cfg.train_random_seed)

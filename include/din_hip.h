@@ -479,6 +479,18 @@ int din_walk_fwd(const float* x, const float* pred, int cp, int b, int t, int n,
 int din_walk_bwd(const float* x, const float* pred, int cp, const float* a, const float* gz,
                  int b, int t, int n, int c, int kh, int kw, int ratio, int scale_factor, int plain, const int32_t* clamp,
                  const int32_t* n_per_clip, float* dx, float* dpred, float* scratch, void* stream);
+/* host-only, launches nothing: the name of the kernel that forms the FEATURE gradient dx of a din_walk_bwd call of this shape under the
+ * current options, from the decision code the launcher itself switches on: "din_walk_bwd_kernel<true>" (scatter into dx with fp32
+ * atomics, the shipped choice), "din_walk_bwd_kernel<false>" (LDS tile, DIN_WALK_BWD_GLOBAL = 0 where two tiles fit) or, under
+ * DIN_DETERMINISTIC, "din_walk_bwd_dx_ordered_kernel" (gather form: the terms of a destination cell -- the transposed torch.gather of
+ * dynamic_infer_module.py:229-258 -- summed in (position, tap, corner) order, no atomics).  DIN_E_ARG where the launch would refuse.
+ *
+ * DIN_DETERMINISTIC = "1" (din_set_option; unset by default, and then nothing changes): din_walk_bwd, din_layernorm_bwd (dgamma /
+ * dbeta), din_head_bwd (dw / dbias), din_dot_accum, din_colsum and the dbias of din_conv_wgrad produce results that are a pure function
+ * of their arguments: no floating-point atomic, no sum whose order depends on scheduling, grid heuristics or other options.  A call that
+ * has no such form under the option returns DIN_E_ARG naming it (a walk grid whose ordered kernel does not fit 160 KB of LDS;
+ * din_conv_wgrad with wdot): never a silent fall-back.  The reference has no counterpart (it relies on cuDNN / ATen's defaults). */
+int din_walk_bwd_kernel_name(int b, int t, int n, int c, int kh, int kw, int ratio, char* buf, int buf_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Row H  head (infer_model.py:224-232): max over actors -> fc_activities -> mean over frames.
