@@ -169,7 +169,10 @@ SIGNATURES: Dict[str, tuple] = {
     "din_act_dropout_bwd": (_I, [_P, _P, _P, _L, _I, _F, _U64, _P, _P]),
     "din_adam_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P]),
     "din_adam_step_multi": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _I, _F, _P]),
-    "din_copy_rows_u8": (_I, [_P, _P, _I, _L, _P]),
+    "din_grad_sqnorm_multi": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "din_grad_norm_finish": (_I, [_P, _I, _F, _F, _P, _P]),
+    "din_adam_step_multi_clip": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _I, _F, _P, _P]),
+    "din_copy_rows_u8":(_I, [_P, _P, _I, _L, _P]),
     "din_feat_rows": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
     "din_feat_rows_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
 }

@@ -11,7 +11,11 @@ GB per dataset, and a step skips the backbone for resident frames -- din_amd/fea
 multiplies bf16 operands anyway: the row is stored already rounded, half the bytes per frame and no cast pass, the same numbers).
 deterministic (stage-2 trainer, frozen backbone, one rank: the library's DIN_DETERMINISTIC option is set for the duration of train_net, so
 every gradient on that path is summed in a fixed order and two runs with one seed give the same weights bit for bit -- ops.deterministic).
-All are opt-in: at 0 / False the trainers behave exactly as without them."""
+max_grad_norm (both trainers; None = off): the global L2 norm of the gradient is clipped to it inside the fused Adam step --
+torch.nn.utils.clip_grad_norm_ semantics, what the reference tried and left commented out at train_net_dynamic.py:222-223 -- and a step
+whose norm is not finite is skipped (din_amd/optim.py); float('inf') measures and guards without ever clipping; anything else is a
+positive finite number.
+All are opt-in: at 0 / False / None the trainers behave exactly as without them."""
 from __future__ import annotations
 
 import os
@@ -34,6 +38,7 @@ _DEFAULTS = dict(
     backbone_dtype="fp32", hier_dropout_p=0.5,
     frame_cache_gb=0, num_workers=0, feature_cache_gb=0, feature_cache_dtype="fp32",
     deterministic=False,
+    max_grad_norm=None,
 )
 
 

@@ -2,6 +2,7 @@
 // All tensors are NHWC with (pixel stride, channel offset); one thread handles a 4-channel group of one
 // pixel so that every access is an 8-/16-byte coalesced vector along the channel axis.
 #include "din_common.h"
+#include <cmath>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -184,11 +185,11 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 }
 
 // multi-tensor form: one launch for the whole parameter list.  ptrs[t] = {p, g, m, v} of tensor t; workgroup b updates elements
-// [chunk_index[b] * chunk, +chunk) of tensor chunk_tensor[b]
-__global__ __launch_bounds__(256) void adam_multi_kernel(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
-                                                         const int32_t* __restrict__ chunk_tensor, const int32_t* __restrict__ chunk_index,
-                                                         int chunk, float lr, float b1, float b2, float eps, float wd, float bc1,
-                                                         float bc2_sqrt, float gscale) {
+// [chunk_index[b] * chunk, +chunk) of tensor chunk_tensor[b].  adam_multi_chunk is the whole update of one workgroup: the plain and the
+// clipped launch both call it, so the two cannot drift -- they differ only in the factor they hand in as gscale.
+__device__ __forceinline__ void adam_multi_chunk(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
+                                                 const int32_t* __restrict__ chunk_tensor, const int32_t* __restrict__ chunk_index, int chunk,
+                                                 float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
     const int t = chunk_tensor[blockIdx.x];
     float* __restrict__ p = reinterpret_cast<float*>(ptrs[4 * t + 0]);
     const float* __restrict__ g = reinterpret_cast<const float*>(ptrs[4 * t + 1]);
@@ -208,6 +209,101 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const uint64_t* __restr
         float denom = sqrtf(vi) / bc2_sqrt + eps;
         p[i] = pi - (lr / bc1) * (mi / denom);
     }
+}
+__global__ __launch_bounds__(256) void adam_multi_kernel(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
+                                                         const int32_t* __restrict__ chunk_tensor, const int32_t* __restrict__ chunk_index,
+                                                         int chunk, float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                         float bc2_sqrt, float gscale) {
+    adam_multi_chunk(ptrs, sizes, chunk_tensor, chunk_index, chunk, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+}
+// the same launch behind a global-norm clip: state[0] = the step's gradient norm, state[1] = its clip coefficient (grad_norm_finish_kernel).
+// A norm that is not finite skips the step: no store at all.  Otherwise g is multiplied by ONE factor, gscale * coef, formed once; with
+// coef == 1.0f that product is gscale itself and every stored bit is adam_multi_kernel's.
+__global__ __launch_bounds__(256) void adam_multi_clip_kernel(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
+                                                              const int32_t* __restrict__ chunk_tensor, const int32_t* __restrict__ chunk_index,
+                                                              int chunk, float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                              float bc2_sqrt, float gscale, const float* __restrict__ state) {
+    const float norm = state[0], coef = state[1];
+    if (!(fabsf(norm) <= 3.402823466e+38f)) return;             // Inf or NaN (a comparison with NaN is false)
+    adam_multi_chunk(ptrs, sizes, chunk_tensor, chunk_index, chunk, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale * coef);
+}
+
+// ---- global gradient norm: sum of squares of every gradient of the tables above, in fp64 and in a fixed order -------------------------
+// One workgroup per chunk.  Element j of the chunk belongs to 4-element group j / 4, group q to thread q % 256: a thread adds the
+// squares of its groups in ascending order, each element widened to double BEFORE it is squared (1e25 and 1e-30 both square to
+// fp64 normals; in fp32 the first overflows and the second vanishes), then a fixed LDS tree joins the 256 threads.  The assignment depends on
+// the element's index only, never on the address: a chunk that starts on a 16-byte boundary reads its groups as 16-byte vectors, any other
+// start (a gradient view at an odd 4-byte offset of a bucket) reads the same groups as four dwords, and both add in the same order -- the
+// partial is a pure function of the values, the tables and the chunk length.  No atomics; the gradient is only read.
+constexpr int SQN_THREADS = 256;
+__device__ __forceinline__ double block_tree_sum(double acc, double* sh) {
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int s = SQN_THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+__global__ __launch_bounds__(SQN_THREADS) void grad_sqnorm_multi_kernel(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
+                                                                        const int32_t* __restrict__ chunk_tensor,
+                                                                        const int32_t* __restrict__ chunk_index, int chunk,
+                                                                        double* __restrict__ partials) {
+    __shared__ double sh[SQN_THREADS];
+    const int t = chunk_tensor[blockIdx.x];
+    const float* __restrict__ g = reinterpret_cast<const float*>(ptrs[4 * t + 1]);
+    const int64_t n = sizes[t];
+    const int64_t i0 = (int64_t)chunk_index[blockIdx.x] * chunk;
+    int64_t len = n - i0;
+    if (len > chunk) len = chunk;
+    if (len < 0) len = 0;
+    const float* __restrict__ gc = g + i0;
+    const int64_t nfull = len >> 2;                              // whole 4-element groups
+    double acc = 0.0;
+    if ((reinterpret_cast<uintptr_t>(gc) & 15) == 0) {
+        const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(gc);
+#pragma unroll 8
+        for (int64_t q = threadIdx.x; q < nfull; q += SQN_THREADS) {
+            const f32x4 x = g4[q];
+            acc += (double)x[0] * (double)x[0];
+            acc += (double)x[1] * (double)x[1];
+            acc += (double)x[2] * (double)x[2];
+            acc += (double)x[3] * (double)x[3];
+        }
+    } else {
+#pragma unroll 4
+        for (int64_t q = threadIdx.x; q < nfull; q += SQN_THREADS) {
+            const float x0 = gc[4 * q], x1 = gc[4 * q + 1], x2 = gc[4 * q + 2], x3 = gc[4 * q + 3];
+            acc += (double)x0 * (double)x0;
+            acc += (double)x1 * (double)x1;
+            acc += (double)x2 * (double)x2;
+            acc += (double)x3 * (double)x3;
+        }
+    }
+    if ((int64_t)threadIdx.x == nfull % SQN_THREADS)             // the ragged last group (len % 4 elements) goes to the thread whose turn it is
+        for (int64_t j = nfull << 2; j < len; ++j) acc += (double)gc[j] * (double)gc[j];
+    const double total = block_tree_sum(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+// One workgroup: adds the n partials (thread t takes t, t + 256, ... in ascending order, then the same tree), forms the norm of the
+// averaged gradient and the clip coefficient, and keeps the running statistics.  state: float[8], see include/din_hip.h.
+__global__ __launch_bounds__(SQN_THREADS) void grad_norm_finish_kernel(const double* __restrict__ partials, int n, float gscale, float max_norm,
+                                                                       float* __restrict__ state) {
+    __shared__ double sh[SQN_THREADS];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += SQN_THREADS) acc += partials[i];
+    const double total = block_tree_sum(acc, sh);
+    if (threadIdx.x != 0) return;
+    const float norm = (float)((double)gscale * sqrt(total));   // one rounding
+    const bool finite = fabsf(norm) <= 3.402823466e+38f;
+    const float coef = finite ? fminf(1.f, max_norm / (norm + 1e-6f)) : 0.f;
+    float sum = state[2], mx = state[3], steps = state[4], skipped = state[5], clipped = state[6];
+    if (finite) { sum += norm; mx = fmaxf(mx, norm); } else skipped += 1.f;
+    if (finite && coef < 1.f) clipped += 1.f;
+    steps += 1.f;
+    state[0] = norm; state[1] = coef; state[2] = sum; state[3] = mx;
+    state[4] = steps; state[5] = skipped; state[6] = clipped; state[7] = 0.f;
 }
 
 __global__ void counter_add_kernel(uint64_t* counter, uint64_t delta) { *counter = (*counter + delta) & 0x7FFFFFFFFFFFFFFFull; }
@@ -330,6 +426,43 @@ int din_adam_step_multi(const uint64_t* ptrs, const int64_t* sizes, const int32_
     hipLaunchKernelGGL(adam_multi_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), ptrs, sizes, chunk_tensor, chunk_index, chunk_elems,
                        lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale);
     DIN_CHECK_LAUNCH("adam_step_multi");
+    return DIN_OK;
+}
+
+int din_grad_sqnorm_multi(const uint64_t* ptrs, const int64_t* sizes, const int32_t* chunk_tensor, const int32_t* chunk_index, int nchunks,
+                          int chunk_elems, double* partials, void* stream) {
+    DIN_REQUIRE(ptrs && sizes && chunk_tensor && chunk_index && partials && nchunks >= 0 && chunk_elems > 0, "grad_sqnorm_multi: bad argument");
+    DIN_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7) == 0, "grad_sqnorm_multi: partials must be 8-byte aligned");
+    if (nchunks == 0) return DIN_OK;
+    hipLaunchKernelGGL(grad_sqnorm_multi_kernel, dim3(nchunks), dim3(SQN_THREADS), 0, as_stream(stream), ptrs, sizes, chunk_tensor, chunk_index,
+                       chunk_elems, partials);
+    DIN_CHECK_LAUNCH("grad_sqnorm_multi");
+    return DIN_OK;
+}
+
+int din_grad_norm_finish(const double* partials, int n, float grad_scale, float max_norm, float* state, void* stream) {
+    DIN_REQUIRE(state && n >= 0 && (partials || n == 0), "grad_norm_finish: bad argument");
+    DIN_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7) == 0, "grad_norm_finish: partials must be 8-byte aligned");
+    DIN_REQUIRE((reinterpret_cast<uintptr_t>(state) & 3) == 0, "grad_norm_finish: state must be 4-byte aligned");
+    DIN_REQUIRE(max_norm > 0.f, "grad_norm_finish: max_norm must be positive (infinity: measure and guard only)");   // (false for NaN)
+    DIN_REQUIRE(std::isfinite(grad_scale), "grad_norm_finish: grad_scale must be finite");
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(SQN_THREADS), 0, as_stream(stream), partials, n, grad_scale, max_norm, state);
+    DIN_CHECK_LAUNCH("grad_norm_finish");
+    return DIN_OK;
+}
+
+int din_adam_step_multi_clip(const uint64_t* ptrs, const int64_t* sizes, const int32_t* chunk_tensor, const int32_t* chunk_index, int nchunks,
+                             int chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                             const float* state, void* stream) {
+    DIN_REQUIRE(ptrs && sizes && chunk_tensor && chunk_index && state && nchunks >= 0 && chunk_elems > 0 && step >= 1,
+                "adam_step_multi_clip: bad argument");
+    DIN_REQUIRE((reinterpret_cast<uintptr_t>(state) & 3) == 0, "adam_step_multi_clip: state must be 4-byte aligned");
+    DIN_REQUIRE(std::isfinite(grad_scale), "adam_step_multi_clip: grad_scale must be finite");
+    if (nchunks == 0) return DIN_OK;
+    float bc1 = 1.f - powf(beta1, (float)step), bc2 = sqrtf(1.f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(adam_multi_clip_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), ptrs, sizes, chunk_tensor, chunk_index,
+                       chunk_elems, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, state);
+    DIN_CHECK_LAUNCH("adam_step_multi_clip");
     return DIN_OK;
 }
 

@@ -6,6 +6,9 @@ own format, so the `'optimizer'` entry of a reference stage-2 checkpoint (train_
 and a checkpoint written here loads into torch.optim.Adam."""
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 
 import ctypes as C
@@ -17,13 +20,41 @@ CHUNK = 8192          # elements per workgroup of the multi-tensor launch
 RING = 4              # pinned staging tables per parameter group (the host may run this many optimizer steps ahead of the GPU)
 
 
+def grad_norm_refusal(value):
+    """why `value` cannot be cfg.max_grad_norm / FusedAdam(max_grad_norm=...), or None.  None switches clipping off, float('inf') measures
+    and guards without ever clipping; any other value is a positive finite number (both trainers raise ValueError with this before a
+    loader exists)."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        return f"max_grad_norm = {value!r}: not a number (None = off, float('inf') = measure and guard only, else a positive number)"
+    if math.isnan(value) or value <= 0:
+        return f"max_grad_norm = {value!r}: must be a positive number (None = off, float('inf') = measure and guard only)"
+    return None
+
+
 class FusedAdam:
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    """max_grad_norm (None = off: nothing below changes): torch.nn.utils.clip_grad_norm_(params, max_grad_norm) folded into the step.  The
+    squared norm of every live gradient is reduced in fp64 by one multi-tensor launch over the tables the Adam launch already keeps
+    (din_grad_sqnorm_multi), one small launch forms norm = grad_scale * sqrt(total) and coef = min(1, max / (norm + 1e-6)) on the device
+    (din_grad_norm_finish), and the Adam launch multiplies the gradient by grad_scale * coef instead of grad_scale
+    (din_adam_step_multi_clip): no write pass over the gradients, no host read.  A step whose norm is not finite is SKIPPED: weights and
+    moments keep their bits; the per-parameter step count behind the bias correction still advances (it is host state, and reading the
+    flag back would be the synchronisation this design avoids).  grad_stats() reads the running statistics, one device read."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+        why_not = grad_norm_refusal(max_grad_norm)
+        if why_not:
+            raise ValueError(why_not)
         self.params = [p for p in params]
         self.param_groups = [dict(params=self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
         self.state = {}         # param -> (exp_avg, exp_avg_sq)
         self.steps = {}         # param -> number of updates it received (bias correction is per parameter, as in torch)
         self._tables = {}       # group identity -> [key, pinned ring, ptrs_dev, sizes_dev, chunk_tensor_dev, chunk_index_dev, nchunks, events, turn, last grad ptrs]
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)    # (not part of state_dict(): torch.optim.Adam's format)
+        self._gstate = None     # device float32 [8]: din_grad_norm_finish's state (norm, coef, running statistics)
+        self._partials = None   # device float64 [chunks of the live set]: one squared-norm partial per workgroup
+        self._host_stats = [0.0, 0.0, 0, 0, 0]     # norm sum, norm max, steps, skipped, clipped of the non-fused path
 
     @property
     def step_count(self) -> int:
@@ -48,6 +79,10 @@ class FusedAdam:
             self.steps[p] = self.steps.get(p, 0) + 1
         fused = all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in live)
         if not fused:
+            if self.max_grad_norm is not None:
+                grad_scale = self._clip_scale_slow(live, grad_scale)
+                if grad_scale is None:
+                    return
             for p in live:
                 st = self.state[p]
                 ops.adam_step(p.data, p.grad.contiguous(), st[0], st[1], g["lr"], g["betas"][0], g["betas"][1], g["eps"],
@@ -59,10 +94,78 @@ class FusedAdam:
         for p in live:
             groups.setdefault(self.steps[p], []).append(p)
         self._keep = []
+        if self.max_grad_norm is not None:
+            self._step_clipped(groups, g, grad_scale)
+            return
         for step, plist in groups.items():
             self._launch(plist, step, g, grad_scale)
 
+    def _clip_scale_slow(self, live, grad_scale):
+        """the non-fused path (non-contiguous or non-fp32 parameters; slow on purpose): the same norm, coefficient and skip rule formed by
+        torch ops and decided by ONE read-back.  Returns the factor ops.adam_step multiplies the gradients by, or None to skip the step."""
+        total = torch.zeros((), dtype=torch.float64, device=live[0].device)
+        for p in live:
+            total += p.grad.double().pow(2).sum()
+        with np.errstate(over="ignore"):
+            norm = np.float32(float(grad_scale) * math.sqrt(float(total.item())))       # (the one read-back; sqrt(nan) is nan)
+        hs = self._host_stats
+        hs[2] += 1
+        if not np.isfinite(norm):
+            hs[3] += 1
+            return None
+        with np.errstate(over="ignore"):
+            coef = min(np.float32(1.0), np.float32(self.max_grad_norm) / (norm + np.float32(1e-6)))
+        hs[0], hs[1], hs[4] = hs[0] + float(norm), max(hs[1], float(norm)), hs[4] + int(coef < 1)
+        return float(np.float32(grad_scale) * np.float32(coef))
+
+    def _step_clipped(self, groups, g, grad_scale):
+        """squared norm of every group -> one global norm and coefficient on the device -> the clipped Adam launch of every group"""
+        lib, dev = L.load(), next(iter(groups.values()))[0].device
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        tables = [(step, self._table(plist)) for step, plist in groups.items()]
+        total = sum(tb[6] for _, tb in tables)
+        if self._gstate is None:
+            self._gstate = torch.zeros(8, dtype=torch.float32, device=dev)
+        if self._partials is None or self._partials.numel() != total:              # (only when the live set changes)
+            self._partials = torch.empty(max(total, 1), dtype=torch.float64, device=dev)[:total]
+        first = 0
+        for _, tb in tables:
+            L.check(lib.din_grad_sqnorm_multi(C.c_void_p(tb[2].data_ptr()), C.c_void_p(tb[3].data_ptr()), C.c_void_p(tb[4].data_ptr()),
+                                              C.c_void_p(tb[5].data_ptr()), tb[6], CHUNK,
+                                              C.c_void_p(self._partials.data_ptr() + 8 * first), stream), "grad_sqnorm_multi")
+            first += tb[6]
+        L.check(lib.din_grad_norm_finish(C.c_void_p(self._partials.data_ptr()), total, grad_scale, self.max_grad_norm,
+                                         C.c_void_p(self._gstate.data_ptr()), stream), "grad_norm_finish")
+        for step, tb in tables:
+            L.check(lib.din_adam_step_multi_clip(C.c_void_p(tb[2].data_ptr()), C.c_void_p(tb[3].data_ptr()), C.c_void_p(tb[4].data_ptr()),
+                                                 C.c_void_p(tb[5].data_ptr()), tb[6], CHUNK, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                                                 g["weight_decay"], step, grad_scale, C.c_void_p(self._gstate.data_ptr()), stream),
+                    "adam_step_multi_clip")
+
+    def grad_stats(self, reset: bool = True):
+        """{"steps", "skipped", "clipped", "norm_mean", "norm_max"} of the steps since the last reset: ONE device -> host read (a
+        synchronisation: call it once per pass, like the meters).  norm_mean is taken over the steps whose norm was finite (0.0 when there
+        was none).  reset=True zeroes the running statistics."""
+        hs = self._host_stats
+        s = [0.0] * 8 if self._gstate is None else [float(x) for x in self._gstate.cpu()]
+        total, nmax = s[2] + hs[0], max(s[3], hs[1])
+        steps, skipped, clipped = int(s[4]) + hs[2], int(s[5]) + hs[3], int(s[6]) + hs[4]
+        if reset:
+            if self._gstate is not None:
+                self._gstate[2:7].zero_()
+            self._host_stats = [0.0, 0.0, 0, 0, 0]
+        finite = steps - skipped
+        return {"steps": steps, "skipped": skipped, "clipped": clipped, "norm_mean": total / finite if finite else 0.0, "norm_max": nmax}
+
     def _launch(self, live, step, g, grad_scale):
+        _, _, ptrs_dev, sizes_dev, ct_dev, ci_dev, nchunks, _, _, _ = self._table(live)
+        L.check(L.load().din_adam_step_multi(C.c_void_p(ptrs_dev.data_ptr()), C.c_void_p(sizes_dev.data_ptr()),
+                                             C.c_void_p(ct_dev.data_ptr()), C.c_void_p(ci_dev.data_ptr()), nchunks, CHUNK,
+                                             g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], step,
+                                             grad_scale, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "adam_step_multi")
+
+    def _table(self, live):
+        """the device tables of one group with this step's gradient addresses in place (uploaded on the current stream when they moved)"""
         dev = live[0].device
         key = tuple(id(p) for p in live)
         slot = key                                               # table cache slot: the group's identity (two step-count groups of equal size
@@ -100,11 +203,8 @@ class FusedAdam:
             copied[turn] = torch.cuda.Event()
             copied[turn].record()
             tb[8], tb[9] = (turn + 1) % RING, gptrs
-        L.check(L.load().din_adam_step_multi(C.c_void_p(ptrs_dev.data_ptr()), C.c_void_p(sizes_dev.data_ptr()),
-                                             C.c_void_p(ct_dev.data_ptr()), C.c_void_p(ci_dev.data_ptr()), nchunks, CHUNK,
-                                             g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], step,
-                                             grad_scale, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "adam_step_multi")
         self._keep.append(grads)      # the launch reads these asynchronously
+        return tb
 
     # ---- checkpoint format of torch.optim.Adam (state by parameter index; 'step' as a float32 scalar tensor) ----------------------
     def state_dict(self):

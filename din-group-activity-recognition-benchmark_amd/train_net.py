@@ -33,8 +33,8 @@ from .base_model import Basenet_collective, Basenet_volleyball
 from .config import Config  # noqa: F401  (the reference's launchers do `from train_net import *` and then `Config('volleyball')`)
 from . import frame_cache
 from .input_feed import DeviceFeed  # noqa: F401  (re-exported: `from train_net import *` launchers)
-from .optim import FusedAdam
-from .train_net_dynamic import SyntheticCollective, SyntheticVolleyball, adjust_lr, set_bn_eval
+from .optim import FusedAdam, grad_norm_refusal
+from .train_net_dynamic import SyntheticCollective, SyntheticVolleyball, add_grad_stats, adjust_lr, grad_stats_line, set_bn_eval
 from .utils import Timer, print_log
 
 
@@ -121,7 +121,7 @@ def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets,
         else:
             optimizer.step()
         meters.add(actions_scores.detach(), actions_in, activities_scores.detach(), activities_in, total_loss, batch_size)
-    return meters.info(epoch)
+    return add_grad_stats(meters.info(epoch), optimizer)
 
 
 def _test_pass(data_loader, model, device, epoch, cfg, collective):
@@ -164,7 +164,11 @@ def build_model(cfg):
 def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     """Reference train_net (:28-138), stage 1.  Launch one process per GPU with torchrun; a single process works too.  max_steps bounds
     the number of epochs (smoke runs).  cfg.deterministic is ignored here: stage 1 trains the backbone, whose bias / BatchNorm-scale
-    gradients and RoIAlign backward have no fixed-order form (the stage-2 trainer's deterministic mode covers the frozen backbone)."""
+    gradients and RoIAlign backward have no fixed-order form (the stage-2 trainer's deterministic mode covers the frozen backbone).
+    cfg.max_grad_norm: see din_amd/optim.py (FusedAdam)."""
+    why_not = grad_norm_refusal(getattr(cfg, "max_grad_norm", None))       # (before anything else: it needs no device and no loader)
+    if why_not:
+        raise ValueError(why_not)
     model = build_model(cfg)                                           # (refuses stage 2 before touching the device)
     if getattr(cfg, "result_path", None) is None:
         cfg.init_config()
@@ -199,7 +203,7 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     if cfg.set_bn_eval:
         model.apply(set_bn_eval)
     params = [p for p in model.parameters() if p.requires_grad]
-    optimizer = FusedAdam(params, lr=cfg.train_learning_rate, weight_decay=cfg.weight_decay)
+    optimizer = FusedAdam(params, lr=cfg.train_learning_rate, weight_decay=cfg.weight_decay, max_grad_norm=getattr(cfg, "max_grad_norm", None))
     buckets = parallel.GradBuckets(params) if world > 1 else None
     train = train_collective if collective else train_volleyball
     test = test_collective if collective else test_volleyball
@@ -216,6 +220,8 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
         if rank == 0:
             print_log(log_path, "Train epoch %d: loss %.5f activities acc %.2f%% actions acc %.2f%%"
                       % (epoch, info["loss"], info["activities_acc"], info["actions_acc"]))
+            if "grad_norm_mean" in info:
+                print_log(log_path, grad_stats_line(epoch, info))
         if epoch % cfg.test_interval_epoch == 0:
             tinfo = test(validation_loader, model, device, epoch, cfg)
             if tinfo["activities_acc"] > best_result["activities_acc"]:

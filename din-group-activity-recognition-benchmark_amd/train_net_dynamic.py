@@ -31,7 +31,7 @@ from . import feature_cache, frame_cache
 from .input_feed import DeviceFeed  # noqa: F401  (re-exported: `from train_net import *` launchers)
 from .infer_model import (ARG_volleyball, AT_volleyball, Dynamic_collective, Dynamic_TCE_volleyball, Dynamic_volleyball,
                           PCTDM_volleyball)
-from .optim import FusedAdam
+from .optim import FusedAdam, grad_norm_refusal
 from .utils import AverageMeter, Timer, print_log
 
 
@@ -146,7 +146,20 @@ def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets,
             optimizer.step()
         meters.add(activities_scores.detach(), activities_in, total_loss)
     frame_cache.end_pass(feed)                                         # (the feature cache's box check; nothing for the other feeds)
-    return meters.info(epoch)
+    return add_grad_stats(meters.info(epoch), optimizer)
+
+
+def add_grad_stats(info, optimizer):
+    """with cfg.max_grad_norm set: the pass's gradient-norm statistics join its info (one device read per pass, like the meters)"""
+    if getattr(optimizer, "max_grad_norm", None) is not None:
+        st = optimizer.grad_stats()
+        info.update(grad_norm_mean=st["norm_mean"], grad_norm_max=st["norm_max"], skipped_steps=st["skipped"], clipped_steps=st["clipped"])
+    return info
+
+
+def grad_stats_line(epoch, info):
+    return ("Train epoch %d: grad norm mean %.4g max %.4g, %d steps clipped, %d skipped (non-finite norm)"
+            % (epoch, info["grad_norm_mean"], info["grad_norm_max"], info["clipped_steps"], info["skipped_steps"]))
 
 
 def _test_pass(data_loader, model, device, epoch, cfg, collective):
@@ -199,7 +212,10 @@ def _mask_counters(model):
 def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     """Reference train_net (:27-157).  Launch one process per GPU with torchrun; a single process works too.  max_steps bounds the number
     of epochs (smoke runs).  cfg.deterministic: the whole call runs under ops.deterministic() (frozen backbone, one rank; the option is
-    back at its previous value when the call returns or raises)."""
+    back at its previous value when the call returns or raises).  cfg.max_grad_norm: see din_amd/optim.py (FusedAdam)."""
+    why_not = grad_norm_refusal(getattr(cfg, "max_grad_norm", None))       # (before anything else: it needs no device and no loader)
+    if why_not:
+        raise ValueError(why_not)
     # cfg.deterministic where a sum's order is not ours (first: its answer is the same whatever the caches and workers are set to), then
     # cfg.feature_cache_gb > 0 where cached features would be wrong -- both before any process group or loader exists
     why_not = ops.deterministic_refusal(cfg, int(os.environ.get("WORLD_SIZE", "1"))) or feature_cache.refusal(cfg)
@@ -261,7 +277,7 @@ def _train_net(cfg, training_set, validation_set, max_steps):
     if cfg.set_bn_eval:
         model.apply(set_bn_eval)
     params = [p for p in model.parameters() if p.requires_grad]
-    optimizer = FusedAdam(params, lr=cfg.train_learning_rate, weight_decay=cfg.weight_decay)
+    optimizer = FusedAdam(params, lr=cfg.train_learning_rate, weight_decay=cfg.weight_decay, max_grad_norm=getattr(cfg, "max_grad_norm", None))
     start_epoch = 1
     if resume is not None and getattr(cfg, "resume_optimizer", True) and "optimizer" in resume:
         # (the reference reloads only the weights; resuming the moments, the epoch and the dropout-mask counters too is the extension
@@ -289,6 +305,8 @@ def _train_net(cfg, training_set, validation_set, max_steps):
         info = train(training_loader, model, device, optimizer, epoch, cfg, buckets)
         if rank == 0:
             print_log(log_path, "Train epoch %d: loss %.5f acc %.2f%%" % (epoch, info["loss"], info["activities_acc"]))
+            if "grad_norm_mean" in info:
+                print_log(log_path, grad_stats_line(epoch, info))
         if epoch % cfg.test_interval_epoch == 0:
             tinfo = test(validation_loader, model, device, epoch, cfg)
             if tinfo["activities_acc"] > best_result["activities_acc"]:

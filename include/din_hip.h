@@ -670,6 +670,41 @@ int din_adam_step_multi(const uint64_t* ptrs, const int64_t* sizes, const int32_
                         int step, float grad_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Global gradient-norm clipping inside the fused Adam step (din_amd/optim.py: FusedAdam(max_grad_norm=...)).  The semantics are
+ * torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) followed by torch.optim.Adam.step() -- what the reference's trainer
+ * tried and left commented out (train_net_dynamic.py:222-223) -- plus one addition: a step whose norm is not finite is skipped.
+ * Three launches on one stream, over the tables of din_adam_step_multi unchanged: no allocation, no synchronisation, no atomics,
+ * capturable; every sum has a fixed order, so each result is a pure function of the gradient values, the tables and chunk_elems, with
+ * or without the DIN_DETERMINISTIC option.  Additive: the ABI version stays 9.
+ *
+ * din_grad_sqnorm_multi: workgroup b writes partials[b] = sum of g[i]^2 over elements [chunk_index[b]*chunk_elems, +chunk_elems) of
+ *   tensor chunk_tensor[b], g = column 1 of ptrs [nt][4].  Every element is widened to double before it is squared and the sum is
+ *   kept in double (a gradient of magnitude 1e25 has a finite fp32 norm while its square overflows fp32).  g may start at any 4-byte
+ *   offset: a chunk on a 16-byte boundary is read as 16-byte vectors, any other as dwords, in the same order of addition.  partials
+ *   holds nchunks doubles.  nchunks == 0 returns DIN_OK without a launch.
+ * din_grad_norm_finish: one workgroup adds partials[0..n) in a fixed order (the ranges of several din_grad_sqnorm_multi launches laid
+ *   end to end give ONE global norm) and one thread writes state, float[8], with plain stores:
+ *     [0] norm = (float)(grad_scale * sqrt(total))       -- grad_scale: the 1 / world factor the optimizer applies, so this is the
+ *                                                            norm of the AVERAGED gradient; one rounding
+ *     [1] coef = min(1, max_norm / (norm + 1e-6)) in fp32 -- torch's formula; 0 when norm is not finite (the step is skipped)
+ *     [2] running sum of the finite norms    [3] running maximum of the finite norms    [4] steps measured
+ *     [5] steps skipped (norm not finite)    [6] steps clipped (coef < 1)               [7] 0
+ *   [2..6] are read, updated and written back: the caller zeroes state once and whenever it wants the running part to restart.
+ *   max_norm = +infinity measures and guards without ever clipping.  n == 0 gives norm = 0, coef = 1.
+ * din_adam_step_multi_clip: din_adam_step_multi with `state` as written above.  state[0] not finite: nothing is stored -- p, exp_avg
+ *   and exp_avg_sq of every tensor keep their bits.  Otherwise g is multiplied by ONE factor, grad_scale * state[1], formed once in fp32
+ *   (weight decay is added after it, as in torch); with state[1] == 1 every stored bit is din_adam_step_multi's.
+ * DIN_E_ARG, with nothing read or written: a null table, partials (n > 0) or state; a negative count; chunk_elems <= 0; step < 1;
+ *   partials not 8-byte aligned; state not 4-byte aligned; max_norm <= 0 or NaN; grad_scale not finite.
+ * ---------------------------------------------------------------------------------------------- */
+int din_grad_sqnorm_multi(const uint64_t* ptrs, const int64_t* sizes, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                          int nchunks, int chunk_elems, double* partials, void* stream);
+int din_grad_norm_finish(const double* partials, int n, float grad_scale, float max_norm, float* state, void* stream);
+int din_adam_step_multi_clip(const uint64_t* ptrs, const int64_t* sizes, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                             int nchunks, int chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay,
+                             int step, float grad_scale, const float* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Frame cache: n byte-row copies in one launch (din_amd/frame_cache.py).  Replaces, from the second epoch on, what the reference does
  * for every frame of every epoch: decode + resize + stack on the host (volleyball.py:223-275) and a blocking upload of the batch
  * (train_net_dynamic.py:174) -- decoded uint8 frames stay in HBM slots and a batch is gathered from them.
