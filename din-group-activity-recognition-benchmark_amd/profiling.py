@@ -125,7 +125,8 @@ class hbm_survey:
 
 class LaunchTimer:
     """Brackets one conv launch with HIP events when profiling.PROFILE is a list; names the kernel the launch resolves to exactly as rocprofv3
-    prints it (forward / data gradient: din_conv_kernel_tile / din_conv_kernel_variant; weight gradient: din_conv_kernel_names).  With
+    prints it (forward / data gradient: din_conv_kernel_tile / din_conv_kernel_variant, or din_conv_rf_kernel_names for a launch nhwc routed to
+    the filter-stationary halo kernel; weight gradient: din_conv_kernel_names).  With
     PROFILE_ONLY set, launches of other kernels are left alone, so a timed step that only needs the dominant kernel's launch times pays for
     ~20 event pairs instead of ~190."""
     def __init__(self, kind, d, name=""):
@@ -146,8 +147,16 @@ class LaunchTimer:
             if self.name.startswith("group:"):                         # din_conv_wgrad_group: the grouped form of the items' sixteen-wave pipe instantiation
                 return main.replace("conv_wgrad_pipe_kernel<", "conv_wgrad_pipe_group_kernel<")
             return main
-        bm, bn = C.c_int32(0), C.c_int32(0)
         which = {"fwd": 0, "dgrad": 1}[self.kind]
+        rf = getattr(d, "rf", None)
+        if rf is not None:
+            # the launch goes through din_conv_rf_fwd / din_conv_rf_dgrad (nhwc sets d.rf = (flags, ldm, moff)): their own reporter names it
+            buf = C.create_string_buffer(256)
+            rc = L.load().din_conv_rf_kernel_names(C.byref(d), which, rf[0], rf[1], rf[2], buf, len(buf))
+            if rc < 0:
+                L.check(rc, "din_conv_rf_kernel_names")
+            return buf.value.decode().split("\n")[0]
+        bm, bn = C.c_int32(0), C.c_int32(0)
         L.load().din_conv_kernel_tile(C.byref(d), which, C.byref(bm), C.byref(bn))
         tn = {L.DIN_BF16: "unsigned short", L.DIN_F32_BF16X3: "f32x3_t"}.get(d.dtype, "float")      # (as the demangler spells the element tag)
         if bm.value == 4 and not (self.kind == "dgrad" and "+" in self.name):

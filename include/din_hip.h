@@ -182,6 +182,22 @@ int din_conv_fwd(const din_conv_desc* d, const void* in, const void* wpk, const 
 int din_conv_dgrad(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din,
                    const void* mask, int ldm, int moff, int flags,
                    void* workspace, int64_t workspace_bytes, void* stream);
+/* The filter-stationary halo kernel (csrc/conv_halo_rf.hip) for the narrow 3x3 layers: bf16, 3x3, stride 1, dilation 1, reduction and
+ * produced channels in 40..96 at multiples of 8; forward (BIAS / RELU) and data gradient (MASK / ACCUM; the mask view at multiples of 8).
+ * It is NOT reachable through din_conv_fwd / din_conv_dgrad: the caller asks din_conv_rf_eligible once per launch (host only, reads no
+ * pointer: 1 = din_conv_rf_fwd / din_conv_rf_dgrad serve this launch and the planner wants it there, 0 = call din_conv_fwd / din_conv_dgrad)
+ * and then calls the matching entry, which takes the argument list of din_conv_fwd / din_conv_dgrad (the workspace is not used) and
+ * computes the same result.  A launch that is not eligible is DIN_E_ARG from the entries and the reporter, never another kernel.
+ * Options: DIN_CONV_HALO_RF = 0 off, unset the planner's rule (a floor on the pixels of the launch, profiles/halo_rf_layers.txt), 2 every
+ * eligible shape; DIN_CONV_HALO = 0 switches it off as well.  din_conv_rf_kernel_names answers like din_conv_kernel_names, with the kernel
+ * spelled as rocprofv3 prints it ("conv_halo_rf_kernel<3, 3, true>": 16-row filter tiles per wave, 32-channel steps per tap, data gradient). */
+int din_conv_rf_eligible(const din_conv_desc* d, int which /*0 fwd,1 dgrad*/, int flags, int ldm, int moff);
+int din_conv_rf_fwd(const din_conv_desc* d, const void* in, const void* wpk, const float* bias, void* out,
+                    int flags, void* workspace, int64_t workspace_bytes, void* stream);
+int din_conv_rf_dgrad(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din,
+                      const void* mask, int ldm, int moff, int flags,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int din_conv_rf_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes);
 /* Fused dgrad of up to four 1x1 / stride-1 convolutions that read the SAME tensor (the branch-entry convs of torchvision's
  * InceptionA/C blocks, backbone.py:61-77): din = sum_b dout_b . W_b^T computed as ONE contraction over the concatenated
  * channels, so the (write-bound) gradient tensor is written once instead of once per branch with read-modify-write.

@@ -14,7 +14,8 @@ LAYERS = {  # name: (nb, h, w, cin, cout, k, s, p)
     "vgg_conv4_2": (12, 90, 160, 512, 512, 3, 1, 1),
     "vgg_conv5_2": (12, 45, 80, 512, 512, 3, 1, 1),
     "inc_5b_1x1": (96, 87, 157, 192, 64, 1, 1, 0),
-    "inc_5d_3x3": (96, 87, 157, 96, 96, 3, 1, 1),
+    "inc_5d_3x3": (96, 87, 157, 96, 96, 3, 1, 1),              # Mixed_5b / 5c / 5d branch3x3dbl_3
+    "inc_5b_3x3dbl_2": (96, 87, 157, 64, 96, 3, 1, 1),         # Mixed_5b / 5c / 5d / 6a branch3x3dbl_2
     "inc_6b_1x1": (96, 43, 78, 768, 192, 1, 1, 0),
     "inc_6c_1x7": (96, 43, 78, 160, 160, (1, 7), 1, (0, 3)),
     "inc_2b_3x3": (96, 357, 637, 32, 64, 3, 1, 1),
@@ -66,10 +67,15 @@ def main():
     ap.add_argument("--no-dbias", action="store_true", help="wgrad without the bias gradient (what do its per-workgroup atomics cost?)")
     ap.add_argument("--const", action="store_true", help="constant operands (low toggle rate): shows how much the clock sags on random data")
     ap.add_argument("--relu", action="store_true", help="half of the activations / gradients zero, as behind a ReLU (what the mid-network layers see)")
+    ap.add_argument("--frames", type=int, default=0, help="frames (nb) instead of the layer's own count")
+    ap.add_argument("--rf-ab", type=int, default=0, metavar="ROUNDS",
+                    help="fwd / dgrad: time DIN_CONV_HALO_RF=0 (the kernel din_conv_fwd / din_conv_dgrad choose) against =2 (conv_halo_rf_kernel "
+                         "wherever eligible) in alternating rounds of --iters launches in THIS process; one line per form with the median round")
     a = ap.parse_args()
     lib = L.load()
     torch.manual_seed(0)                                  # (same operands in every process: the checksums of an A/B pair are comparable)
     nb, h, w, cin, cout, k, s, p = LAYERS[a.layer]
+    nb = a.frames or nb
     k = (k, k) if isinstance(k, int) else k
     p = (p, p) if isinstance(p, int) else p
     oh = (h + 2 * p[0] - k[0]) // s + 1
@@ -98,13 +104,48 @@ def main():
     which = {"fwd": 0, "dgrad": 1, "wgrad": 2}[a.which]
     wsb = lib.din_conv_workspace_bytes(C.byref(d), which)
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device="cuda")
+    def routed():
+        """the entry points of a forward / data-gradient launch as nhwc picks them: the filter-stationary halo kernel where the library says so"""
+        if a.which == "fwd" and lib.din_conv_rf_eligible(C.byref(d), 0, 3, 0, 0):
+            return lib.din_conv_rf_fwd, lib.din_conv_dgrad
+        if a.which == "dgrad" and lib.din_conv_rf_eligible(C.byref(d), 1, a.flags, cin, 0):
+            return lib.din_conv_fwd, lib.din_conv_rf_dgrad
+        return lib.din_conv_fwd, lib.din_conv_dgrad
+    entry = list(routed())
     def run():
         if a.which == "fwd":
-            L.check(lib.din_conv_fwd(C.byref(d), x.data_ptr(), wpk.data_ptr(), bias.data_ptr(), y.data_ptr(), 3, ws.data_ptr(), wsb, None))
+            L.check(entry[0](C.byref(d), x.data_ptr(), wpk.data_ptr(), bias.data_ptr(), y.data_ptr(), 3, ws.data_ptr(), wsb, None))
         elif a.which == "dgrad":
-            L.check(lib.din_conv_dgrad(C.byref(d), gy.data_ptr(), wpt.data_ptr(), dx.data_ptr(), x.data_ptr(), cin, 0, a.flags, ws.data_ptr(), wsb, None))
+            L.check(entry[1](C.byref(d), gy.data_ptr(), wpt.data_ptr(), dx.data_ptr(), x.data_ptr(), cin, 0, a.flags, ws.data_ptr(), wsb, None))
         else:
             L.check(lib.din_conv_wgrad(C.byref(d), x.data_ptr(), gy.data_ptr(), dw.data_ptr(), None if a.no_dbias else bias.data_ptr(), None, None, None, 0, ws.data_ptr(), wsb, None))
+    fl = 2.0 * nb * oh * ow * cout * cin * k[0] * k[1]
+    if a.rf_ab and a.which != "wgrad":
+        out = {"fwd": y, "dgrad": dx}[a.which]
+        times, names, sums = {"0": [], "2": []}, {}, {}
+        for rnd in range(a.rf_ab + 1):                     # (round 0 warms up)
+            for mode in ("0", "2"):
+                L.set_option("DIN_CONV_HALO_RF", mode)
+                entry[:] = routed()
+                names[mode] = "conv_halo_rf_kernel" if lib.din_conv_rf_eligible(C.byref(d), which, 3 if which == 0 else a.flags, 0 if which == 0 else cin, 0) else "din_conv_" + a.which
+                run()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.iters):
+                    run()
+                e1.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    times[mode].append(e0.elapsed_time(e1) / a.iters)
+                sums[mode] = out.float().abs().sum().item()
+        L.set_option("DIN_CONV_HALO_RF", None)
+        for mode in ("0", "2"):
+            t = sorted(times[mode])
+            med = t[len(t) // 2]
+            print(f"{a.layer:16s} nb={nb:3d} {a.which:5s} flags={3 if which == 0 else a.flags:2d} DIN_CONV_HALO_RF={mode} {names[mode]:20s} median {med*1e3:8.1f} us "
+                  f"(min {t[0]*1e3:.1f}, max {t[-1]*1e3:.1f}; {len(t)} rounds x {a.iters})  {fl/med/1e9:7.1f} TFLOP/s  |out|_1 = {sums[mode]:.6e}", flush=True)
+        return
     for _ in range(3):
         run()
     torch.cuda.synchronize()
@@ -115,7 +156,6 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / a.iters
-    fl = 2.0 * nb * oh * ow * cout * cin * k[0] * k[1]
     chk = {"fwd": y, "dgrad": dx, "wgrad": dw}[a.which].float().abs().sum().item()
     print(f"{a.layer:14s} {a.dtype} {a.which:5s} {ms*1e3:9.1f} us  {fl/ms/1e9:8.1f} TFLOP/s  (M={nb*oh*ow}, K={cin*k[0]*k[1]}, N={cout})  |out|_1 = {chk:.6e}", flush=True)
 
