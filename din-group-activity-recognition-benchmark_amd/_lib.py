@@ -91,6 +91,10 @@ SIGNATURES: Dict[str, tuple] = {
     "din_conv_rf_fwd": (_I, [_CD, _P, _P, _P, _P, _I, _P, _L, _P]),
     "din_conv_rf_dgrad": (_I, [_CD, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P]),
     "din_conv_rf_kernel_names": (_I, [_CD, _I, _I, _I, _I, C.c_char_p, _I]),
+    "din_conv_rf5_eligible": (_I, [_CD, _I, _I, _I, _I]),
+    "din_conv_rf5_fwd": (_I, [_CD, _P, _P, _P, _P, _I, _P, _L, _P]),
+    "din_conv_rf5_dgrad": (_I, [_CD, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P]),
+    "din_conv_rf5_kernel_names": (_I, [_CD, _I, _I, _I, _I, C.c_char_p, _I]),
     "din_conv1x1_dgrad_multi": (_I, [_I, C.POINTER(ConvSrc), _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P]),
     "din_conv1x1_dgrad_multi_kernel_names": (_I, [_I, C.POINTER(ConvSrc), _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
     "din_conv_dgrad_x_fused": (_I, [_CD]),

@@ -26,9 +26,9 @@
 // epilogue.  It needs the mask view in whole 16-byte chunks (din_conv_rf_eligible).  Accumulate operands are requested one, two or four pixel
 // fragments at a time before their stores (compiler-visible loads: nothing is in flight at that point; the planner keeps ACCUM launches on
 // the old kernels).  The forward's bias sits in LDS behind the halo buffers.
-// What the 5x5 48 -> 64 layers of the same blocks would need: their 48-channel taps are 6 chunks, so a 32-channel step straddles taps and a
-// lane's fragment offset is no longer one immediate per (tap, step): a per-lane k-walk (two base registers per lane) and 25 x 2 x TI filter
-// fragments per wave (200 registers at TI = 2).  Conv2d_4a (80 -> 192) does not fit the register file.
+// The 5x5 48 -> 64 layers of the same blocks have a kernel family of their own, conv_halo_rf5_kernel (conv_halo_rf5.hip): their 48-channel
+// taps are 6 chunks, so a 32-channel step straddles taps, and the reduction is walked densely over (tap, chunk) there.  Conv2d_4a
+// (80 -> 192) does not fit the register file.
 #include "din_common.h"
 #include "conv_wgrad.h"
 #include "conv_gather.h"

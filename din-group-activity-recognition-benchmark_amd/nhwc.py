@@ -461,14 +461,17 @@ def _bn_train_forward(lib, raw: torch.Tensor, dt: int, rows: int, cout: int, gam
 
 
 def _conv_fwd_launch(lib, d, src, wpk, bias, dst, flags: int, st, dev, name: str) -> None:
-    """one forward conv launch: on the filter-stationary halo kernel where the library says so (din_conv_rf_eligible, asked once per op),
-    through din_conv_fwd otherwise; d.rf tells the launch timer which of the two reporters names the kernel"""
+    """one forward conv launch: on a filter-stationary halo kernel where the library says so (din_conv_rf_eligible for the 3x3 family,
+    din_conv_rf5_eligible for the 5x5 one, each asked once per op), through din_conv_fwd otherwise; d.rf / d.rf5 tell the launch timer which
+    of the three reporters names the kernel"""
     ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(d), 0), dev)
     rf = bool(lib.din_conv_rf_eligible(C.byref(d), 0, flags, 0, 0))
+    rf5 = not rf and bool(lib.din_conv_rf5_eligible(C.byref(d), 0, flags, 0, 0))     # (the 5x5 family: 3x3 and 5x5 exclude each other)
     d.rf = (flags, 0, 0) if rf else None
+    d.rf5 = (flags, 0, 0) if rf5 else None
+    fn = lib.din_conv_rf_fwd if rf else lib.din_conv_rf5_fwd if rf5 else lib.din_conv_fwd
     with _timed("fwd", d, name):
-        L.check((lib.din_conv_rf_fwd if rf else lib.din_conv_fwd)(C.byref(d), _ptr(src), _ptr(wpk), _ptr(bias), _ptr(dst), flags, _ptr(ws), wsb, st),
-                "conv_fwd " + name)
+        L.check(fn(C.byref(d), _ptr(src), _ptr(wpk), _ptr(bias), _ptr(dst), flags, _ptr(ws), wsb, st), "conv_fwd " + name)
 
 
 def graph_forward(g: Graph, image_buf: torch.Tensor, params: Sequence[torch.Tensor], dt: int, save_for_backward: bool = True,
@@ -633,6 +636,7 @@ class BackwardPlan:
     partitioned: set                                # tensors whose gradient is first WRITTEN range by range by its readers (see _partitioned)
     first_writer: Dict[int, int]                    # tensor id -> the first op in program order that writes it (its gradient is dead after it)
     rf_dgrad: set = field(default_factory=set)      # op indices whose own data-gradient launch runs the filter-stationary halo kernel (din_conv_rf_dgrad)
+    rf5_dgrad: set = field(default_factory=set)     # the same for the 5x5 family (din_conv_rf5_dgrad)
 
 
 def _partitioned(readers: List[Tuple[int, int]], writers: Sequence[Tuple[int, int]]) -> bool:
@@ -749,18 +753,19 @@ def plan_backward(g: Graph, nb: int, dt: int, bn_train: bool, side_ok: bool, u8:
     # 3x3 / stride-1 convs whose data gradient the library wants on the filter-stationary halo kernel: asked once per op, here, with the
     # launch's gradient view and ReLU-mask view (without ACCUM: whether the launch accumulates is known when the pass reaches it, and
     # _BackwardPass.dgrad asks again for one that does)
-    rf_dgrad = set()
+    # (the 5x5 family, din_conv_rf5_eligible, is asked the same way into a set of its own)
+    rf_dgrad, rf5_dgrad = set(), set()
     for oi, op in enumerate(g.ops):
-        if op.kind == "conv" and op.k == (3, 3) and op.s == (1, 1) and op.pooled is None and op.src.tid != g.input_tid:
+        if op.kind == "conv" and op.k in ((3, 3), (5, 5)) and op.s == (1, 1) and op.pooled is None and op.src.tid != g.input_tid:
             d = _conv_desc(g, op, nb, dt)
             if op.bn and bn_train:
                 d.ldo, d.cooff = op.dst.c, 0                       # (the gradient operand is the contiguous dy of bn_train_backward)
             masked = g.tensors[op.src.tid].relu_masked
-            if lib.din_conv_rf_eligible(C.byref(d), 1, L.CONV_MASK if masked else 0, g.tensors[op.src.tid].c if masked else 0,
-                                        op.src.coff if masked else 0):
-                rf_dgrad.add(oi)
+            ask, into = (lib.din_conv_rf_eligible, rf_dgrad) if op.k == (3, 3) else (lib.din_conv_rf5_eligible, rf5_dgrad)
+            if ask(C.byref(d), 1, L.CONV_MASK if masked else 0, g.tensors[op.src.tid].c if masked else 0, op.src.coff if masked else 0):
+                into.add(oi)
     return BackwardPlan(offsets, bn_index, bn_train, side, bool(u8), groups, member_of, x_host, siblings, multi_w, group_on, group_max,
-                        group_bytes, partitioned, first_writer, rf_dgrad)
+                        group_bytes, partitioned, first_writer, rf_dgrad, rf5_dgrad)
 
 
 class _Pending(NamedTuple):
@@ -1059,14 +1064,17 @@ class _BackwardPass:
                 L.check(self.lib.din_conv_dgrad_x(C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc), self.mask_of(op.src), ts.c, op.src.coff, flags,
                                                   C.byref(xs), _ptr(ws), wsb, self.st), "conv_dgrad_x " + op.name)
         else:
-            rf = oi in self.plan.rf_dgrad
+            rf, rf5 = oi in self.plan.rf_dgrad, oi in self.plan.rf5_dgrad
             if rf and acc:                                           # (the plan asked without ACCUM: an accumulating launch gets its own answer)
                 rf = bool(self.lib.din_conv_rf_eligible(C.byref(d), 1, flags, ts.c, op.src.coff))
+            if rf5 and acc:
+                rf5 = bool(self.lib.din_conv_rf5_eligible(C.byref(d), 1, flags, ts.c, op.src.coff))
             d.rf = (flags, ts.c, op.src.coff) if rf else None        # (the launch timer names the kernel from the matching reporter)
+            d.rf5 = (flags, ts.c, op.src.coff) if rf5 else None
+            fn = self.lib.din_conv_rf_dgrad if rf else self.lib.din_conv_rf5_dgrad if rf5 else self.lib.din_conv_dgrad
             with _timed("dgrad", d, op.name):
-                L.check((self.lib.din_conv_rf_dgrad if rf else self.lib.din_conv_dgrad)(
-                    C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc), self.mask_of(op.src), ts.c, op.src.coff, flags, _ptr(ws), wsb, self.st),
-                    "conv_dgrad " + op.name)
+                L.check(fn(C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc), self.mask_of(op.src), ts.c, op.src.coff, flags, _ptr(ws), wsb, self.st),
+                        "conv_dgrad " + op.name)
 
     # ---- the steps of the loop, one op at a time
     def skip(self, oi: int) -> None:

@@ -125,8 +125,8 @@ class hbm_survey:
 
 class LaunchTimer:
     """Brackets one conv launch with HIP events when profiling.PROFILE is a list; names the kernel the launch resolves to exactly as rocprofv3
-    prints it (forward / data gradient: din_conv_kernel_tile / din_conv_kernel_variant, or din_conv_rf_kernel_names for a launch nhwc routed to
-    the filter-stationary halo kernel; weight gradient: din_conv_kernel_names).  With
+    prints it (forward / data gradient: din_conv_kernel_tile / din_conv_kernel_variant, or din_conv_rf_kernel_names / din_conv_rf5_kernel_names for a launch nhwc
+    routed to a filter-stationary halo kernel; weight gradient: din_conv_kernel_names).  With
     PROFILE_ONLY set, launches of other kernels are left alone, so a timed step that only needs the dominant kernel's launch times pays for
     ~20 event pairs instead of ~190."""
     def __init__(self, kind, d, name=""):
@@ -155,6 +155,13 @@ class LaunchTimer:
             rc = L.load().din_conv_rf_kernel_names(C.byref(d), which, rf[0], rf[1], rf[2], buf, len(buf))
             if rc < 0:
                 L.check(rc, "din_conv_rf_kernel_names")
+            return buf.value.decode().split("\n")[0]
+        rf5 = getattr(d, "rf5", None)
+        if rf5 is not None:                                            # (the 5x5 family: din_conv_rf5_fwd / _dgrad, named by din_conv_rf5_kernel_names)
+            buf = C.create_string_buffer(256)
+            rc = L.load().din_conv_rf5_kernel_names(C.byref(d), which, rf5[0], rf5[1], rf5[2], buf, len(buf))
+            if rc < 0:
+                L.check(rc, "din_conv_rf5_kernel_names")
             return buf.value.decode().split("\n")[0]
         bm, bn = C.c_int32(0), C.c_int32(0)
         L.load().din_conv_kernel_tile(C.byref(d), which, C.byref(bm), C.byref(bn))

@@ -198,6 +198,20 @@ int din_conv_rf_dgrad(const din_conv_desc* d, const void* dout, const void* wpk_
                       const void* mask, int ldm, int moff, int flags,
                       void* workspace, int64_t workspace_bytes, void* stream);
 int din_conv_rf_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes);
+/* The same for the narrow 5x5 layers (csrc/conv_halo_rf5.hip): bf16, 5x5, stride 1, dilation 1, oh = h + 2 ph - 4, reduction and produced
+ * channels in 40..64 at multiples of 8; forward (BIAS / RELU) and data gradient (MASK / ACCUM; the mask view at multiples of 8).  One
+ * corner is not served: a MASKED data gradient with 56 or 64 reduction channels AND more than 48 produced channels (halo buffers and mask
+ * regions would exceed the LDS).  A family of its own, not reached through din_conv_rf_*: the caller asks din_conv_rf5_eligible and calls
+ * din_conv_rf5_fwd / din_conv_rf5_dgrad, which take the argument lists of their rf counterparts.  Options: DIN_CONV_HALO_RF5 = 0 off, unset
+ * the planner's rule (a floor on the pixels of the launch, profiles/halo_rf5_layers.txt; no ACCUM), 2 every eligible shape; DIN_CONV_HALO = 0
+ * switches it off as well.  Kernel names: "conv_halo_rf5_kernel<6, false>" (16-byte chunks per tap of the reduction, data gradient). */
+int din_conv_rf5_eligible(const din_conv_desc* d, int which /*0 fwd,1 dgrad*/, int flags, int ldm, int moff);
+int din_conv_rf5_fwd(const din_conv_desc* d, const void* in, const void* wpk, const float* bias, void* out,
+                     int flags, void* workspace, int64_t workspace_bytes, void* stream);
+int din_conv_rf5_dgrad(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din,
+                       const void* mask, int ldm, int moff, int flags,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int din_conv_rf5_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes);
 /* Fused dgrad of up to four 1x1 / stride-1 convolutions that read the SAME tensor (the branch-entry convs of torchvision's
  * InceptionA/C blocks, backbone.py:61-77): din = sum_b dout_b . W_b^T computed as ONE contraction over the concatenated
  * channels, so the (write-bound) gradient tensor is written once instead of once per branch with read-modify-write.

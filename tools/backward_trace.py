@@ -2,7 +2,7 @@
 """The launch sequence of the backbone's reverse pass (nhwc.graph_backward), recorded with no GPU: profiles/backward_launch_trace.txt.
 
 libdin_hip.so is loaded as usual, but nhwc sees it through a proxy: the planning queries (workspace sizes, group keys, packed sizes and
-descriptors, kernel reporters, din_conv_accepts_u8, din_conv_dgrad_x_fused, din_conv_rf_eligible, din_bn_parts, the option and error calls) reach the library,
+descriptors, kernel reporters, din_conv_accepts_u8, din_conv_dgrad_x_fused, din_conv_rf_eligible, din_conv_rf5_eligible, din_bn_parts, the option and error calls) reach the library,
 every entry point that would launch is recorded and answered with 0.  Tensors live on the CPU (torch.empty never touches its pages, so
 production shapes cost nothing); the stream queries are stubbed.  What is recorded is the complete host behaviour of the pass:
 
@@ -52,7 +52,7 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 QUERIES = ("din_conv_packed_elems", "din_conv_pack_desc", "din_conv_accepts_u8", "din_conv_dgrad_x_fused", "din_conv_rf_eligible",
-           "din_conv_rf_kernel_names", "din_bn_parts", "din_set_option", "din_get_option", "din_last_error_string", "din_abi_version",
+           "din_conv_rf_kernel_names", "din_conv_rf5_eligible", "din_conv_rf5_kernel_names", "din_bn_parts", "din_set_option", "din_get_option", "din_last_error_string", "din_abi_version",
            "din_build_arch")
 STREAM = 0x57
 

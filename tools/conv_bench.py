@@ -71,6 +71,8 @@ def main():
     ap.add_argument("--rf-ab", type=int, default=0, metavar="ROUNDS",
                     help="fwd / dgrad: time DIN_CONV_HALO_RF=0 (the kernel din_conv_fwd / din_conv_dgrad choose) against =2 (conv_halo_rf_kernel "
                          "wherever eligible) in alternating rounds of --iters launches in THIS process; one line per form with the median round")
+    ap.add_argument("--rf5-ab", type=int, default=0, metavar="ROUNDS",
+                    help="the same A/B for the 5x5 family: DIN_CONV_HALO_RF5=0 against =2 (conv_halo_rf5_kernel wherever eligible)")
     a = ap.parse_args()
     lib = L.load()
     torch.manual_seed(0)                                  # (same operands in every process: the checksums of an A/B pair are comparable)
@@ -110,6 +112,10 @@ def main():
             return lib.din_conv_rf_fwd, lib.din_conv_dgrad
         if a.which == "dgrad" and lib.din_conv_rf_eligible(C.byref(d), 1, a.flags, cin, 0):
             return lib.din_conv_fwd, lib.din_conv_rf_dgrad
+        if a.which == "fwd" and lib.din_conv_rf5_eligible(C.byref(d), 0, 3, 0, 0):
+            return lib.din_conv_rf5_fwd, lib.din_conv_dgrad
+        if a.which == "dgrad" and lib.din_conv_rf5_eligible(C.byref(d), 1, a.flags, cin, 0):
+            return lib.din_conv_fwd, lib.din_conv_rf5_dgrad
         return lib.din_conv_fwd, lib.din_conv_dgrad
     entry = list(routed())
     def run():
@@ -120,14 +126,17 @@ def main():
         else:
             L.check(lib.din_conv_wgrad(C.byref(d), x.data_ptr(), gy.data_ptr(), dw.data_ptr(), None if a.no_dbias else bias.data_ptr(), None, None, None, 0, ws.data_ptr(), wsb, None))
     fl = 2.0 * nb * oh * ow * cout * cin * k[0] * k[1]
-    if a.rf_ab and a.which != "wgrad":
+    if (a.rf_ab or a.rf5_ab) and a.which != "wgrad":
+        # the family under test: its option, its eligibility call, its kernel
+        opt, ask, kern, rounds = (("DIN_CONV_HALO_RF5", lib.din_conv_rf5_eligible, "conv_halo_rf5_kernel", a.rf5_ab) if a.rf5_ab else
+                                  ("DIN_CONV_HALO_RF", lib.din_conv_rf_eligible, "conv_halo_rf_kernel", a.rf_ab))
         out = {"fwd": y, "dgrad": dx}[a.which]
         times, names, sums = {"0": [], "2": []}, {}, {}
-        for rnd in range(a.rf_ab + 1):                     # (round 0 warms up)
+        for rnd in range(rounds + 1):                      # (round 0 warms up)
             for mode in ("0", "2"):
-                L.set_option("DIN_CONV_HALO_RF", mode)
+                L.set_option(opt, mode)
                 entry[:] = routed()
-                names[mode] = "conv_halo_rf_kernel" if lib.din_conv_rf_eligible(C.byref(d), which, 3 if which == 0 else a.flags, 0 if which == 0 else cin, 0) else "din_conv_" + a.which
+                names[mode] = kern if ask(C.byref(d), which, 3 if which == 0 else a.flags, 0 if which == 0 else cin, 0) else "din_conv_" + a.which
                 run()
                 torch.cuda.synchronize()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -139,11 +148,11 @@ def main():
                 if rnd:
                     times[mode].append(e0.elapsed_time(e1) / a.iters)
                 sums[mode] = out.float().abs().sum().item()
-        L.set_option("DIN_CONV_HALO_RF", None)
+        L.set_option(opt, None)
         for mode in ("0", "2"):
             t = sorted(times[mode])
             med = t[len(t) // 2]
-            print(f"{a.layer:16s} nb={nb:3d} {a.which:5s} flags={3 if which == 0 else a.flags:2d} DIN_CONV_HALO_RF={mode} {names[mode]:20s} median {med*1e3:8.1f} us "
+            print(f"{a.layer:16s} nb={nb:3d} {a.which:5s} flags={3 if which == 0 else a.flags:2d} {opt}={mode} {names[mode]:20s} median {med*1e3:8.1f} us "
                   f"(min {t[0]*1e3:.1f}, max {t[-1]*1e3:.1f}; {len(t)} rounds x {a.iters})  {fl/med/1e9:7.1f} TFLOP/s  |out|_1 = {sums[mode]:.6e}", flush=True)
         return
     for _ in range(3):

@@ -9,7 +9,9 @@ alike.  A window is `--inner` steps between two device synchronisations after `-
 windows, per step, in ms.  A difference is reported next to the spread of the windows (max - min of each form): inside it, it is noise.
 One JSON line per measurement.  The figures are one run on a shared machine.
 
-usage: python tools/halo_rf_time.py [--windows 9] [--inner 3] [--warmup 2] [--clips 32,4] [--out FILE]"""
+--option DIN_CONV_HALO_RF5 toggles the 5x5 family instead (conv_halo_rf5_kernel, csrc/conv_halo_rf5.hip), everything else the same.
+
+usage: python tools/halo_rf_time.py [--option DIN_CONV_HALO_RF] [--windows 9] [--inner 3] [--warmup 2] [--clips 32,4] [--out FILE]"""
 import argparse
 import json
 import os
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--clips", default="32,4")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--option", default="DIN_CONV_HALO_RF", choices=["DIN_CONV_HALO_RF", "DIN_CONV_HALO_RF5"], help="the kernel family toggled")
     a = ap.parse_args()
     import bench
     from din_amd import _lib as L
@@ -68,7 +71,7 @@ def main():
         times = {k: [] for k in forms}
         for it in range(a.warmup + a.windows):
             for k, v in forms.items():
-                L.set_option("DIN_CONV_HALO_RF", v)
+                L.set_option(a.option, v)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(a.inner):
@@ -76,12 +79,12 @@ def main():
                 torch.cuda.synchronize()
                 if it >= a.warmup:
                     times[k].append((time.perf_counter() - t0) * 1e3 / a.inner)
-        L.set_option("DIN_CONV_HALO_RF", None)
+        L.set_option(a.option, None)
         r = {}
         for k, t in times.items():
             t.sort()
             r[k] = {"median_ms": round(t[len(t) // 2], 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4), "windows": a.windows, "steps_per_window": a.inner}
-            emit({"tool": "halo_rf_time", "what": "training step", "clips": clips, "DIN_CONV_HALO_RF": k, **r[k],
+            emit({"tool": "halo_rf_time", "what": "training step", "clips": clips, a.option: k, **r[k],
                   "clips_per_s": round(clips / r[k]["median_ms"] * 1e3, 1)})
         spread = max(r[k]["max_ms"] - r[k]["min_ms"] for k in r)
         d = r["unset"]["median_ms"] - r["off"]["median_ms"]
