@@ -17,7 +17,7 @@
 // ring.  With one wave per SIMD nothing hides a wait and a wave issues one instruction per four clocks: next to a 16-clock MFMA that is a
 // budget of three other instructions.  So (as conv1x1_regw_kernel) the fragment reads are inline asm with a rolling window of three or four
 // reads ahead of the MFMAs and hand-counted lgkmcnt; the MFMAs are inline asm too, which fixes the register file of every filter fragment
-// (rf_mfma); and the transfers of the next halo are issued one behind every second or fourth fragment of a block's first half from a
+// (rf::mfma); and the transfers of the next halo are issued one behind every second or fourth fragment of a block's first half from a
 // per-lane plan made once (11 instructions per transfer), so that they sit between the MFMAs and have landed at the hand-over (vmcnt(0):
 // nothing else is in flight there but stores a whole block old).
 // MFMA row 4 g + e of row tile i is channel (class base) + 4 TI g + 4 i + e: a lane of the result holds 4 TI consecutive channels of a pixel.
@@ -28,59 +28,27 @@
 // the old kernels).  The forward's bias sits in LDS behind the halo buffers.
 // The 5x5 48 -> 64 layers of the same blocks have a kernel family of their own, conv_halo_rf5_kernel (conv_halo_rf5.hip): their 48-channel
 // taps are 6 chunks, so a 32-channel step straddles taps, and the reduction is walked densely over (tap, chunk) there.  Conv2d_4a
-// (80 -> 192) does not fit the register file.
+// (80 -> 192) does not fit the register file.  What the two families share -- the inline-asm primitives (rf::read, rf::mfma, rf::wait,
+// rf::pin), the work items, the epilogue's mask / accumulate pieces, the planner's checks and the bodies of the entry points -- is in
+// conv_halo_rf.h (namespace din_rf, rf:: below).
 #include "din_common.h"
 #include "conv_wgrad.h"
 #include "conv_gather.h"
 #include "conv_shared.h"
-#include <stdlib.h>
-#include <type_traits>
+#include "conv_halo_rf.h"
 
 using din_wgrad::lds_dma16;
 using din_gather::ConvK;
+namespace rf = din_rf;
 
 namespace {
 
-constexpr int RF_TH = 8, RF_TW = 32, RF_HWW = RF_TW + 2, RF_HWH = RF_TH + 2, RF_HPX = RF_HWW * RF_HWH;
+constexpr int RF_HWW = rf::TW + 2, RF_HWH = rf::TH + 2, RF_HPX = RF_HWW * RF_HWH;
 constexpr int RF_PCH = 10, RF_PB = RF_PCH * 16;                                  // row pitch: 10 chunks = 160 bytes (conv_halo.hip)
 constexpr int RF_NTR_H = (RF_HPX * RF_PCH + 255) / 256;                          // halo transfers per wave and block (14)
 constexpr int RF_HB = RF_NTR_H * 4096;                                           // bytes of one halo buffer
-constexpr unsigned RF_OOB = 0x80000000u;
 // dynamic LDS: two halo buffers, then the four waves' mask regions (masked data gradient) or their bias values (forward)
 constexpr size_t rf_lds(int ti, bool dg, bool mask) { return (size_t)2 * RF_HB + (dg ? (mask ? (size_t)4 * 4 * ti * 1024 : 0) : 1024); }
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void rf_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rf_static_for<I + 1, N>(f);
-    }
-}
-template <int OFF>
-__device__ __forceinline__ void rf_read(u32x4& dst, uint32_t addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <bool ACC>
-__device__ __forceinline__ void rf_pin(u32x4& x) {               // the value lives in an accumulation (ACC) or an architectural register from here on
-    if constexpr (ACC) asm volatile("" : "+a"(x));
-    else asm volatile("" : "+v"(x));
-}
-// c (+)= a x b.  Inline asm, with the register file of every operand chosen here (ACC: the filter fragment sits in an accumulation
-// register): through the builtin the allocator keeps every fragment it can in architectural registers and copies the others there in
-// front of their MFMA (904 v_accvgpr_read per tile in the first build of the 96 -> 96 form).  FIRST: the tile's first k-step, C = 0.
-template <bool ACC, bool FIRST>
-__device__ __forceinline__ void rf_mfma(f32x4& c, const u32x4& a, const u32x4& b) {
-    if constexpr (FIRST) {
-        if constexpr (ACC) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(c) : "a"(a), "v"(b));
-        else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(c) : "v"(a), "v"(b));
-    } else {
-        if constexpr (ACC) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
-        else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-    }
-}
-template <int N>
-__device__ __forceinline__ void rf_wait(u32x4& x) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "n"(N)); }
 
 // byte offset of pixel fragment j (row j >> 1 of the wave's four, columns (j & 1) * 16 ..) at tap (r, s), 32-channel step kk of the block,
 // from the lane's base; the data gradient walks the taps backwards from the far corner of the halo
@@ -115,7 +83,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
     const int W_ = p.W, H_ = p.H, ldi = p.ldi, OH = p.OH, OW = p.OW, Cout = p.Cout, ldo = p.ldo, cooff = p.cooff, cpt = p.cpt, flags = p.flags;
     const int ldm = p.ldm, moff = p.moff, cioff2 = p.cioff * 2;
     const int hy0 = p.by - (DG ? 2 : 0), hx0 = p.bx - (DG ? 2 : 0);
-    const int tiles_x = (OW + RF_TW - 1) / RF_TW, tiles_y = (OH + RF_TH - 1) / RF_TH;
+    const int tiles_x = (OW + rf::TW - 1) / rf::TW, tiles_y = (OH + rf::TH - 1) / rf::TH;
     const int tiles_img = tiles_x * tiles_y, nitems = tiles_img * p.NB;
     const long long img_bytes = (long long)H_ * W_ * ldi * 2ll;
     const long long oimg_bytes = (long long)OH * OW * ldo * 2ll, mimg_bytes = (long long)OH * OW * ldm * 2ll;
@@ -124,14 +92,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
     const char* const maskp = reinterpret_cast<const char*>(p.mask);
     const bool masked = (flags & DIN_CONV_MASK) != 0;
 
-    struct Item { int n, ty, tx; };
-    auto decode_item = [&](int item) {
-        Item it;
-        it.n = item / tiles_img;
-        const int tr = item - it.n * tiles_img;
-        it.ty = tr / tiles_x; it.tx = tr - it.ty * tiles_x;
-        return it;
-    };
+    using rf::Item;
     // ---- halo transfers.  Halo chunk id = (wid + 4 i) * 64 + lane of transfer i, lane-linear in LDS (conv_halo.hip).  What a lane fetches in
     // transfer i never changes, so its plan is made once: rel[i] = byte offset of (halo pixel, chunk) from the halo's first pixel, pk = its
     // halo column and chunk (16 bits per transfer; chunk 15: a pad chunk or past the halo, never fetched).  Per transfer that leaves the column
@@ -157,8 +118,8 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
     auto halo_blk = [&](const Item& it, int b) __attribute__((always_inline)) {
         HaloBlk h;
         h.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(inp) + (long long)it.n * img_bytes, 0, (int)img_bytes, 0x00020000);
-        h.gx0 = it.tx * RF_TW + hx0;
-        h.base = ((it.ty * RF_TH + hy0) * W_ + h.gx0) * ldi * 2 + cioff2 + b * 128;
+        h.gx0 = it.tx * rf::TW + hx0;
+        h.base = ((it.ty * rf::TH + hy0) * W_ + h.gx0) * ldi * 2 + cioff2 + b * 128;
         h.nch = cpt - b * 8;                                                      // (>= 8: all)
         return h;
     };
@@ -167,7 +128,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
         const int hx = (int)__builtin_amdgcn_ubfe(pk[i >> 1], 16 * (i & 1), 6), cc = (int)__builtin_amdgcn_ubfe(pk[i >> 1], 16 * (i & 1) + 8, 4);
         const bool ok = (unsigned)(h.gx0 + hx) < (unsigned)W_ && cc < h.nch;
         int voff = rel[i] + h.base;
-        voff = ok ? voff : (int)RF_OOB;
+        voff = ok ? voff : (int)rf::OOB;
         lds_dma16(ldsWv + (uint32_t)(buf * RF_HB + i * 4096), h.rs, voff, 0);
     };
     // transfer i of the wave's own mask region: chunk id = i * 64 + lane = (pixel pl of the wave's 128, chunk c of its 2 TI)
@@ -176,16 +137,16 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
         asm volatile("" : "+v"(ln));
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(maskp) + (long long)it.n * mimg_bytes, 0, (int)mimg_bytes, 0x00020000);
         const unsigned id = (unsigned)(i * 64 + ln), pl = id / (unsigned)(2 * TI), c = id - pl * (unsigned)(2 * TI);
-        const int gy = it.ty * RF_TH + 4 * wp + (int)(pl >> 5), gx = it.tx * RF_TW + (int)(pl & 31u);
+        const int gy = it.ty * rf::TH + 4 * wp + (int)(pl >> 5), gx = it.tx * rf::TW + (int)(pl & 31u);
         const int co = cbase + (int)c * 8;
         const bool ok = gy < OH && gx < OW && co < Cout;
-        lds_dma16(ldsMk + (uint32_t)(i * 1024), rs, ok ? ((gy * OW + gx) * ldm + moff + co) * 2 : (int)RF_OOB, 0);
+        lds_dma16(ldsMk + (uint32_t)(i * 1024), rs, ok ? ((gy * OW + gx) * ldm + moff + co) * 2 : (int)rf::OOB, 0);
     };
 
     const int G = (int)gridDim.x;
     int item = xcd_remap((int)blockIdx.x, G);
     if (item >= nitems) return;
-    Item cur = decode_item(item);
+    Item cur = rf::decode_item(item, tiles_img, tiles_x);
     {
         const HaloBlk h0 = halo_blk(cur, 0);
 #pragma unroll
@@ -205,12 +166,12 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
                 for (int i = 0; i < TI; ++i) {
                     const int chan = cbase + (frow >> 2) * 4 * TI + i * 4 + (frow & 3);
                     const bool real = chan < Cout && ks * 4 + g4 < cpt;
-                    Wf[tap][ks][i] = __builtin_amdgcn_raw_buffer_load_b128(rsW, real ? chan * wld16 + g4 * 16 : (int)RF_OOB, (tap * cpt + ks * 4) * 16, 0);
+                    Wf[tap][ks][i] = __builtin_amdgcn_raw_buffer_load_b128(rsW, real ? chan * wld16 + g4 * 16 : (int)rf::OOB, (tap * cpt + ks * 4) * 16, 0);
                 }
-        // where they live is decided HERE (rf_mfma): the first NA fragments in accumulation registers, the others in architectural ones
-        rf_static_for<0, 9 * NKS * TI>([&](auto N_) __attribute__((always_inline)) {
+        // where they live is decided HERE (rf::mfma): the first NA fragments in accumulation registers, the others in architectural ones
+        rf::static_for<0, 9 * NKS * TI>([&](auto N_) __attribute__((always_inline)) {
             constexpr int n = decltype(N_)::value, tap = n / (NKS * TI), ks = (n / TI) % NKS, i = n % TI;
-            rf_pin<(n < NA)>(Wf[tap][ks][i]);
+            rf::pin<(n < NA)>(Wf[tap][ks][i]);
         });
     }
     // forward: the wave's 16 TI bias values behind the halo buffers (in registers they would push filters out; read from global memory in
@@ -221,7 +182,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
             *reinterpret_cast<float*>(smem_raw + 2 * RF_HB + wid * 256 + lane * 4) = ((flags & DIN_CONV_BIAS) && co < Cout) ? p.bias[co] : 0.f;
         }
     }
-    f32x4 acc[TI][8];                                                             // (the first k-step of a tile writes them: rf_mfma<.., FIRST>)
+    f32x4 acc[TI][8];                                                             // (the first k-step of a tile writes them: rf::mfma<.., FIRST>)
 
     // lane base of the fragment reads: first row of the wave's pixel half, pixel column frow, chunk g4
     const uint32_t xb0 = lds_base + (uint32_t)((4 * wp * RF_HWW + frow) * RF_PB + g4 * 16);
@@ -241,12 +202,12 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
 #pragma unroll
             for (int jj = 0; jj < EB; ++jj) {
                 const int j = jb + jj;
-                const int gy = it.ty * RF_TH + 4 * wp + (j >> 1), gx = it.tx * RF_TW + (j & 1) * 16 + frow_e;
-                pxo[jj] = (gy < OH && gx < OW) ? ((gy * OW + gx) * ldo + cooff) * 2 : (int)RF_OOB;
+                const int gy = it.ty * rf::TH + 4 * wp + (j >> 1), gx = it.tx * rf::TW + (j & 1) * 16 + frow_e;
+                pxo[jj] = (gy < OH && gx < OW) ? ((gy * OW + gx) * ldo + cooff) * 2 : (int)rf::OOB;
 #pragma unroll
                 for (int i = 0; i < TI; ++i) {
                     const int co = cbase + g4_e * 4 * TI + i * 4;
-                    if (DG && (flags & DIN_CONV_ACCUM)) old[DG ? jj : 0][i] = __builtin_amdgcn_raw_buffer_load_b64(rsO, co < Cout ? pxo[jj] + co * 2 : (int)RF_OOB, 0, 0);
+                    if (DG && (flags & DIN_CONV_ACCUM)) old[DG ? jj : 0][i] = __builtin_amdgcn_raw_buffer_load_b64(rsO, rf::piece_off(pxo[jj], co, Cout), 0, 0);
                 }
             }
 #pragma unroll
@@ -264,17 +225,10 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
                     }
                     if (DG && masked) {
                         const u32x2 mk = *reinterpret_cast<const u32x2*>(smem_raw + 2 * RF_HB + wid * MBW + pl * (2 * TI * 16) + g4_e * 8 * TI + i * 8);
-                        if (!(__uint_as_float(mk[0] << 16) > 0.f)) v[0] = 0.f;
-                        if (!(__uint_as_float(mk[0] & 0xffff0000u) > 0.f)) v[1] = 0.f;
-                        if (!(__uint_as_float(mk[1] << 16) > 0.f)) v[2] = 0.f;
-                        if (!(__uint_as_float(mk[1] & 0xffff0000u) > 0.f)) v[3] = 0.f;
+                        rf::mask4(v, mk);
                     }
-                    if (DG && (flags & DIN_CONV_ACCUM)) {
-                        v[0] += __uint_as_float(old[DG ? jj : 0][i][0] << 16); v[1] += __uint_as_float(old[DG ? jj : 0][i][0] & 0xffff0000u);
-                        v[2] += __uint_as_float(old[DG ? jj : 0][i][1] << 16); v[3] += __uint_as_float(old[DG ? jj : 0][i][1] & 0xffff0000u);
-                    }
-                    // (out of range: pxo has bit 31 set and stays >= 2^31 as an unsigned offset; Cout % 8 == 0: a piece is whole or absent)
-                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}, rsO, co < Cout ? pxo[jj] + co * 2 : (int)RF_OOB, 0, 0);
+                    if (DG && (flags & DIN_CONV_ACCUM)) v = rf::accum4(v, old[DG ? jj : 0][i]);
+                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}, rsO, rf::piece_off(pxo[jj], co, Cout), 0, 0);
                 }
             }
             asm volatile("" ::: "memory");                                       // one batch at a time: the operands of both would push filters out
@@ -288,8 +242,8 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
     for (;;) {
         const int item_n = item + G;
         const bool has_next_item = item_n < nitems;
-        const Item nxt = has_next_item ? decode_item(item_n) : cur;
-        rf_static_for<0, NBLK>([&](auto B_) __attribute__((always_inline)) {
+        const Item nxt = has_next_item ? rf::decode_item(item_n, tiles_img, tiles_x) : cur;
+        rf::static_for<0, NBLK>([&](auto B_) __attribute__((always_inline)) {
             constexpr int b = decltype(B_)::value;
             constexpr int KB = b == NBLK - 1 ? NKS - 2 * b : 2;                  // 32-channel steps of this block per tap
             constexpr int NSTEP = 9 * KB, NF = NSTEP * 8;                        // steps = (tap, kk); fragments
@@ -299,21 +253,21 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf_kernel(ConvK p) {
             const bool hn = !last_blk || has_next_item;                           // a next (item, block) exists: its halo goes into buffer hb ^ 1
             const HaloBlk hnx = halo_blk(last_blk ? nxt : cur, last_blk ? 0 : b + 1);
             const uint32_t xa = xb0 + (uint32_t)(hb * RF_HB);
-            rf_static_for<0, D>([&](auto F_) __attribute__((always_inline)) {
+            rf::static_for<0, D>([&](auto F_) __attribute__((always_inline)) {
                 constexpr int f = decltype(F_)::value;
-                rf_read<rf_frag_off<DG>((f >> 3) / KB, (f >> 3) % KB, f & 7)>(xf[f], xa);
+                rf::read<rf_frag_off<DG>((f >> 3) / KB, (f >> 3) % KB, f & 7)>(xf[f], xa);
             });
-            rf_static_for<0, NF>([&](auto F_) __attribute__((always_inline)) {
+            rf::static_for<0, NF>([&](auto F_) __attribute__((always_inline)) {
                 constexpr int f = decltype(F_)::value;
                 constexpr int step = f >> 3, j = f & 7, tap = step / KB, kk = step % KB, ks = 2 * b + kk;
-                rf_wait<(NF - 1 - f < D - 1 ? NF - 1 - f : D - 1)>(xf[f % D]);
-                rf_static_for<0, TI>([&](auto I_) __attribute__((always_inline)) {
+                rf::wait<(NF - 1 - f < D - 1 ? NF - 1 - f : D - 1)>(xf[f % D]);
+                rf::static_for<0, TI>([&](auto I_) __attribute__((always_inline)) {
                     constexpr int i = decltype(I_)::value;
-                    rf_mfma<((tap * NKS + ks) * TI + i < NA), (b == 0 && step == 0)>(acc[i][j], Wf[tap][ks][i], xf[f % D]);
+                    rf::mfma<((tap * NKS + ks) * TI + i < NA), (b == 0 && step == 0)>(acc[i][j], Wf[tap][ks][i], xf[f % D]);
                 });
                 if constexpr (f + D < NF) {
                     constexpr int nf = f + D;
-                    rf_read<rf_frag_off<DG>((nf >> 3) / KB, (nf >> 3) % KB, nf & 7)>(xf[f % D], xa);
+                    rf::read<rf_frag_off<DG>((nf >> 3) / KB, (nf >> 3) % KB, nf & 7)>(xf[f % D], xa);
                 }
                 if constexpr (f % SP == 0) {                                      // one transfer after the MFMAs of every SP-th fragment
                     constexpr int t = f / SP;
@@ -354,7 +308,7 @@ std::string rf_kernel_name(const RfInst& r) {
 int rf_row(const RfInst& r, const ConvK* k, hipStream_t st) {
     auto go = [&](auto kern) {
         if (!k) return DIN_OK;
-        const int tiles = ((k->OH + RF_TH - 1) / RF_TH) * ((k->OW + RF_TW - 1) / RF_TW) * k->NB;
+        const int tiles = ((k->OH + rf::TH - 1) / rf::TH) * ((k->OW + rf::TW - 1) / rf::TW) * k->NB;
         const size_t lds = rf_lds(r.ti, r.dg, (k->flags & DIN_CONV_MASK) != 0);
         raise_lds_limit(kern, rf_lds(r.ti, r.dg, true));
         hipLaunchKernelGGL(kern, dim3(tiles < 256 ? tiles : 256), dim3(256), lds, st, *k);
@@ -367,14 +321,9 @@ int rf_row(const RfInst& r, const ConvK* k, hipStream_t st) {
     DIN_FAIL(DIN_E_ARG, "conv_halo_rf: %s is not instantiated", rf_kernel_name(r).c_str());
 }
 
-// Eligibility, geometry and instantiation of the launch `which` (0 forward, 1 data gradient) of a descriptor: bf16, 3x3, stride 1,
-// dilation 1, reduction and produced channels in 40 .. 96 and multiples of 8, views as conv_halo_kernel takes them except the mask view
-// (whole 16-byte chunks: it travels by LDS-DMA).  Options: DIN_CONV_HALO=0 and DIN_CONV_HALO_RF=0 switch the kernel off, DIN_CONV_HALO_RF=2
-// forces it on every eligible shape; unset, the planner's rule holds (rf_wanted: a floor on the pixels of the launch, no ACCUM).  Reads no pointer.
+// the planner's rule (option unset): a floor on the pixels of the launch, no ACCUM
 bool rf_wanted(int which, int flags, int cred, int cprod, int oh, int ow, int64_t M) {
-    // padded-area waste of the 8 x 32 tile grid must stay moderate (plan_halo's rule)
-    const int64_t padded = (int64_t)((oh + RF_TH - 1) / RF_TH * RF_TH) * ((ow + RF_TW - 1) / RF_TW * RF_TW);
-    if (padded * 100 > (int64_t)oh * ow * 118) return false;
+    if (!rf::tile_waste_ok(oh, ow)) return false;
     // <= 64 -> <= 64 channels (VGG's conv1_2): the stem kernel's shape (conv_small.hip), never measured against this one
     if (cred <= 64 && cprod <= 64) return false;
     // accumulate operands are requested one or two pixel fragments at a time (the filters leave no registers for more): several exposed
@@ -387,101 +336,47 @@ bool rf_wanted(int which, int flags, int cred, int cprod, int oh, int ow, int64_
     return M >= floor;
 }
 
+// Eligibility, geometry and instantiation of the launch `which` (0 forward, 1 data gradient) of a descriptor: what rf::plan_common asks of
+// a 3x3 with 40 .. 96 channels.  Options: DIN_CONV_HALO=0 and DIN_CONV_HALO_RF=0 switch the kernel off, DIN_CONV_HALO_RF=2 forces it on
+// every eligible shape; unset, the planner's rule holds (rf_wanted).  Reads no pointer.
 bool rf_plan(const din_conv_desc* d, int which, int flags, int ldm, int moff, ConvK& k, RfInst& r) {
-    if (!d || (which != 0 && which != 1) || d->dtype != DIN_BF16 || d->in_u8) return false;
-    if (d->nb <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->cout <= 0) return false;
-    if (d->kh != 3 || d->kw != 3 || d->sh != 1 || d->sw != 1 || d->dh != 1 || d->dw != 1) return false;
-    if (d->oh != d->h + 2 * d->ph - 2 || d->ow != d->w + 2 * d->pw - 2 || d->oh <= 0 || d->ow <= 0) return false;
-    if ((int64_t)d->nb * d->h * d->w >= (1ll << 31) || (int64_t)d->nb * d->oh * d->ow >= (1ll << 31)) return false;
-    const int cred = which ? d->cout : d->cin, cprod = which ? d->cin : d->cout;
-    if (cred % 8 != 0 || cprod % 8 != 0 || cred < 40 || cred > 96 || cprod < 40 || cprod > 96) return false;
-    if (d->ldi % 8 != 0 || d->cioff % 8 != 0 || d->ldi < d->cioff + d->cin || d->ldo % 4 != 0 || d->cooff % 4 != 0 || d->ldo < d->cooff + d->cout) return false;
-    if (which == 0 && (flags & ~(DIN_CONV_BIAS | DIN_CONV_RELU))) return false;
-    if (which == 1) {
-        if (flags & ~(DIN_CONV_MASK | DIN_CONV_ACCUM)) return false;
-        if (d->ldo % 8 != 0 || d->cooff % 8 != 0) return false;                  // the gradient operand is read in whole chunks
-        if ((flags & DIN_CONV_MASK) && (ldm % 8 != 0 || moff % 8 != 0 || moff < 0 || ldm < moff + cprod)) return false;
-    }
-    const char* hv = DIN_OPT("DIN_CONV_HALO");
-    if (hv && atoi(hv) == 0) return false;
+    if (!rf::plan_common(d, which, flags, ldm, moff, 3, 96, k)) return false;
     const char* rv = DIN_OPT("DIN_CONV_HALO_RF");
     const int mode = rv ? atoi(rv) : 1;
-    if (mode == 0) return false;
-    k = ConvK{};
-    k.NB = d->nb; k.kh = 3; k.kw = 3;
-    const PackGeom bank = pack_geom(d, which);
-    k.w_bytes = (long long)bank.rows_pad * bank.kelems * 2;
-    k.ay = k.ax = 1; k.divy = k.divx = 1;
-    if (which == 0) {
-        k.H = d->h; k.W = d->w; k.Cin = d->cin; k.ldi = d->ldi; k.cioff = d->cioff;
-        k.OH = d->oh; k.OW = d->ow; k.Cout = d->cout; k.ldo = d->ldo; k.cooff = d->cooff;
-        k.by = -d->ph; k.bx = -d->pw; k.cy = k.cx = 1;
-    } else {
-        k.H = d->oh; k.W = d->ow; k.Cin = d->cout; k.ldi = d->ldo; k.cioff = d->cooff;
-        k.OH = d->h; k.OW = d->w; k.Cout = d->cin; k.ldo = d->ldi; k.cooff = d->cioff;
-        k.by = d->ph; k.bx = d->pw; k.cy = k.cx = -1;
-    }
-    k.M = k.NB * k.OH * k.OW;
-    k.in_bytes = (long long)k.NB * k.H * k.W * k.ldi * 2;
-    k.cpt = bank.cpt; k.Q = 9 * bank.cpt; k.nk = bank.nk; k.wld = bank.nk * KC;
-    k.flags = flags; k.ldm = (flags & DIN_CONV_MASK) ? ldm : 0; k.moff = (flags & DIN_CONV_MASK) ? moff : 0;
-    k.splitk = 1; k.ks_per_split = k.nk; k.n_co_tiles = 1;
-    if (!din_gather::views_below_2g(k)) return false;
-    if (mode != 2 && !rf_wanted(which, flags, cred, cprod, k.OH, k.OW, k.M)) return false;
+    const int cred = k.Cin, cprod = k.Cout;
+    if (mode == 0 || (mode != 2 && !rf_wanted(which, flags, cred, cprod, k.OH, k.OW, k.M))) return false;
     r.ti = cprod <= 64 ? 2 : 3; r.nks = cred <= 64 ? 2 : 3; r.dg = which == 1;
     return true;
 }
+
+struct Rf3 {
+    typedef RfInst Inst;
+    static constexpr auto plan = rf_plan;
+    static constexpr auto row = rf_row;
+    static constexpr auto name = rf_kernel_name;
+    static constexpr const char* prefix = "conv_rf";
+};
 
 }  // namespace
 
 extern "C" {
 
-int din_conv_rf_eligible(const din_conv_desc* d, int which, int flags, int ldm, int moff) {
-    ConvK k; RfInst r;
-    return rf_plan(d, which, flags, ldm, moff, k, r) && rf_row(r, nullptr, nullptr) == DIN_OK ? 1 : 0;
-}
+int din_conv_rf_eligible(const din_conv_desc* d, int which, int flags, int ldm, int moff) { return rf::eligible<Rf3>(d, which, flags, ldm, moff); }
 
+// (workspace: the argument list of din_conv_fwd / din_conv_dgrad; this kernel never splits its reduction)
 int din_conv_rf_fwd(const din_conv_desc* d, const void* in, const void* wpk, const float* bias, void* out, int flags,
-                    void* workspace, int64_t workspace_bytes, void* stream) {
-    (void)workspace; (void)workspace_bytes;                                      // (the argument list of din_conv_fwd: this kernel never splits its reduction)
-    if (int e = din_conv::check_desc(d)) return e;
-    DIN_REQUIRE(in && wpk && out, "conv_rf_fwd: null pointer");
-    DIN_REQUIRE(!(flags & DIN_CONV_BIAS) || bias, "conv_rf_fwd: BIAS flag without bias");
-    ConvK k; RfInst r;
-    DIN_REQUIRE(rf_plan(d, 0, flags, 0, 0, k, r), "conv_rf_fwd: not eligible (ask din_conv_rf_eligible)");
-    k.in = in; k.w = wpk; k.out = out; k.bias = bias;
-    if (int e = rf_row(r, &k, as_stream(stream))) return e;
-    DIN_CHECK_LAUNCH("conv_rf_fwd");
-    return DIN_OK;
+                    void* /*workspace*/, int64_t /*workspace_bytes*/, void* stream) {
+    return rf::fwd<Rf3>(d, in, wpk, bias, out, flags, stream);
 }
 
 int din_conv_rf_dgrad(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din_, const void* mask, int ldm, int moff, int flags,
-                      void* workspace, int64_t workspace_bytes, void* stream) {
-    (void)workspace; (void)workspace_bytes;
-    if (int e = din_conv::check_desc(d)) return e;
-    DIN_REQUIRE(dout && wpk_t && din_, "conv_rf_dgrad: null pointer");
-    DIN_REQUIRE(!(flags & DIN_CONV_MASK) || mask, "conv_rf_dgrad: MASK flag without mask");
-    ConvK k; RfInst r;
-    DIN_REQUIRE(rf_plan(d, 1, flags, ldm, moff, k, r), "conv_rf_dgrad: not eligible (ask din_conv_rf_eligible)");
-    k.in = dout; k.w = wpk_t; k.out = din_; k.mask = mask;
-    if (int e = rf_row(r, &k, as_stream(stream))) return e;
-    DIN_CHECK_LAUNCH("conv_rf_dgrad");
-    return DIN_OK;
+                      void* /*workspace*/, int64_t /*workspace_bytes*/, void* stream) {
+    return rf::dgrad<Rf3>(d, dout, wpk_t, din_, mask, ldm, moff, flags, stream);
 }
 
 int din_conv_rf_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes) {
-    if (int e = din_conv::check_desc(d)) return e;
-    DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_rf_kernel_names: bad argument");
-    ConvK k; RfInst r;
-    DIN_REQUIRE(rf_plan(d, which, flags, ldm, moff, k, r), "conv_rf_kernel_names: not eligible (ask din_conv_rf_eligible)");
-    if (int e = rf_row(r, nullptr, nullptr)) return e;
-    const std::string names = rf_kernel_name(r) + "\n";
-    if (buf_bytes > 0) {
-        const size_t n = names.size() < (size_t)buf_bytes - 1 ? names.size() : (size_t)buf_bytes - 1;
-        memcpy(buf, names.data(), n);
-        buf[n] = 0;
-    }
-    return (int)names.size() + 1;
+    return rf::kernel_names<Rf3>(d, which, flags, ldm, moff, buf, buf_bytes);
 }
 
 }  // extern "C"
+

@@ -7,7 +7,7 @@
 // image is the halo of ONE tile and all its channels -- (8 + 4) x (32 + 4) = 432 pixels, filled by LDS-DMA with out-of-image rows as
 // out-of-range buffer offsets, double-buffered across items -- so the only barrier is one hand-over per tile.  Fragment reads and MFMAs are
 // inline asm with a rolling window of reads and hand-counted lgkmcnt, the next halo's transfers sit between the MFMAs of the tile's first
-// half, the bias sits in LDS behind the halo buffers (all as there).
+// half, the bias sits in LDS behind the halo buffers (all as there; the code the two share is conv_halo_rf.h, rf:: below).
 //
 // What is new: THE REDUCTION IS WALKED DENSELY.  A tap has CPT = 5..8 chunks of 8 channels (40..64 reduction channels), so a 32-channel
 // MFMA step (4 chunks, one per lane group g4) does not end where a tap ends.  Padding every tap to 64 channels would cost 50 steps for the
@@ -43,17 +43,16 @@
 #include "conv_wgrad.h"
 #include "conv_gather.h"
 #include "conv_shared.h"
-#include <stdlib.h>
-#include <type_traits>
+#include "conv_halo_rf.h"
 
 using din_wgrad::lds_dma16;
 using din_gather::ConvK;
+namespace rf = din_rf;
 
 namespace {
 
-constexpr int R5_TH = 8, R5_TW = 32, R5_HWW = R5_TW + 4, R5_HWH = R5_TH + 4, R5_HPX = R5_HWW * R5_HWH;
+constexpr int R5_HWW = rf::TW + 4, R5_HWH = rf::TH + 4, R5_HPX = R5_HWW * R5_HWH;
 constexpr int R5_TI = 2;                                                          // 16-row filter tiles per wave: two classes, <= 64 produced channels
-constexpr unsigned R5_OOB = 0x80000000u;
 constexpr int r5_pch(int cpt) { return cpt <= 6 ? 6 : 10; }                       // pitch in chunks (header: bank conflicts)
 constexpr int r5_nwt(int cpt) { return (R5_HPX * r5_pch(cpt) + 63) / 64; }        // 1 KB wave-transfers of one halo
 constexpr int r5_hb(int cpt) { return r5_nwt(cpt) * 1024; }                       // bytes of one halo buffer
@@ -64,37 +63,6 @@ constexpr size_t r5_lds(int cpt, bool dg, bool mask, int cprod) {
     return (size_t)2 * r5_hb(cpt) + (dg ? (mask ? (size_t)2 * 2048 * (4 + r5_n1(cprod)) : 0) : 1024);
 }
 constexpr size_t R5_LDS_MAX = 160 * 1024;
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void r5_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        r5_static_for<I + 1, N>(f);
-    }
-}
-template <int OFF>
-__device__ __forceinline__ void r5_read(u32x4& dst, uint32_t addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <bool ACC>
-__device__ __forceinline__ void r5_pin(u32x4& x) {               // the value lives in an accumulation (ACC) or an architectural register from here on
-    if constexpr (ACC) asm volatile("" : "+a"(x));
-    else asm volatile("" : "+v"(x));
-}
-// c (+)= a x b with the register file of every operand chosen here (conv_halo_rf.hip, rf_mfma).  FIRST: the tile's first step, C = 0.
-template <bool ACC, bool FIRST>
-__device__ __forceinline__ void r5_mfma(f32x4& c, const u32x4& a, const u32x4& b) {
-    if constexpr (FIRST) {
-        if constexpr (ACC) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(c) : "a"(a), "v"(b));
-        else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(c) : "v"(a), "v"(b));
-    } else {
-        if constexpr (ACC) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
-        else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-    }
-}
-template <int N>
-__device__ __forceinline__ void r5_wait(u32x4& x) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "n"(N)); }
 
 // ---- the dense walk.  Chunk q = tap * CPT + c of the reduction; step ks covers chunks 4 ks .. 4 ks + 3, one per lane group.
 // byte offset of chunk q of pixel fragment j (row j >> 1 of the wave's four, columns (j & 1) * 16 ..) from the lane's base
@@ -160,7 +128,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
     const int W_ = p.W, H_ = p.H, ldi = p.ldi, OH = p.OH, OW = p.OW, Cout = p.Cout, ldo = p.ldo, cooff = p.cooff, flags = p.flags;
     const int ldm = p.ldm, moff = p.moff, cioff2 = p.cioff * 2;
     const int hy0 = p.by - (DG ? 4 : 0), hx0 = p.bx - (DG ? 4 : 0);
-    const int tiles_x = (OW + R5_TW - 1) / R5_TW, tiles_y = (OH + R5_TH - 1) / R5_TH;
+    const int tiles_x = (OW + rf::TW - 1) / rf::TW, tiles_y = (OH + rf::TH - 1) / rf::TH;
     const int tiles_img = tiles_x * tiles_y, nitems = tiles_img * p.NB;
     const long long img_bytes = (long long)H_ * W_ * ldi * 2ll;
     const long long oimg_bytes = (long long)OH * OW * ldo * 2ll, mimg_bytes = (long long)OH * OW * ldm * 2ll;
@@ -169,14 +137,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
     const char* const maskp = reinterpret_cast<const char*>(p.mask);
     const bool masked = DG && (flags & DIN_CONV_MASK) != 0;
 
-    struct Item { int n, ty, tx; };
-    auto decode_item = [&](int item) {
-        Item it;
-        it.n = item / tiles_img;
-        const int tr = item - it.n * tiles_img;
-        it.ty = tr / tiles_x; it.tx = tr - it.ty * tiles_x;
-        return it;
-    };
+    using rf::Item;
     // ---- halo transfers.  Halo chunk id = (wid + 4 i) * 64 + lane of transfer i, lane-linear in LDS.  What a lane fetches in transfer i
     // never changes: pk keeps its halo column (6 bits), chunk (4 bits; 15: a pad chunk or past the halo, never fetched) and halo row (4
     // bits), 16 bits per transfer.  Rows outside the image need no test: the buffer resource covers ONE image and the whole offset sits in
@@ -198,8 +159,8 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
     auto halo_blk = [&](const Item& it) __attribute__((always_inline)) {
         HaloBlk h;
         h.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(inp) + (long long)it.n * img_bytes, 0, (int)img_bytes, 0x00020000);
-        h.gx0 = it.tx * R5_TW + hx0;
-        h.base = ((it.ty * R5_TH + hy0) * W_ + h.gx0) * ldi * 2 + cioff2;
+        h.gx0 = it.tx * rf::TW + hx0;
+        h.base = ((it.ty * rf::TH + hy0) * W_ + h.gx0) * ldi * 2 + cioff2;
         return h;
     };
     auto halo_one = [&](int buf, const HaloBlk& h, int i) __attribute__((always_inline)) {
@@ -209,7 +170,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
         const int hy = (int)__builtin_amdgcn_ubfe(pk[i >> 1], 16 * (i & 1) + 10, 4);
         const bool ok = (unsigned)(h.gx0 + hx) < (unsigned)W_ && cc < CPT;
         int voff = ((hy * W_ + hx) * ldi + cc * 8) * 2 + h.base;
-        voff = ok ? voff : (int)R5_OOB;
+        voff = ok ? voff : (int)rf::OOB;
         // (readfirstlane: under scalar-register pressure the allocator keeps such a uniform sum in a vector register, which m0 cannot take)
         lds_dma16(__builtin_amdgcn_readfirstlane(ldsWv + (uint32_t)(buf * HB + i * 4096)), h.rs, voff, 0);
     };
@@ -220,16 +181,16 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
         asm volatile("" : "+v"(ln));
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(maskp) + (long long)it.n * mimg_bytes, 0, (int)mimg_bytes, 0x00020000);
         const unsigned id = (unsigned)(i * 64 + ln), pl = id / (unsigned)mch, c = id - pl * (unsigned)mch;
-        const int gy = it.ty * R5_TH + 4 * wp + (int)(pl >> 5), gx = it.tx * R5_TW + (int)(pl & 31u);
+        const int gy = it.ty * rf::TH + 4 * wp + (int)(pl >> 5), gx = it.tx * rf::TW + (int)(pl & 31u);
         const int co = cbase + (int)c * 8;
         const bool ok = gy < OH && gx < OW && co < Cout;
-        lds_dma16(__builtin_amdgcn_readfirstlane(ldsMk + (uint32_t)(i * 1024)), rs, ok ? ((gy * OW + gx) * ldm + moff + co) * 2 : (int)R5_OOB, 0);
+        lds_dma16(__builtin_amdgcn_readfirstlane(ldsMk + (uint32_t)(i * 1024)), rs, ok ? ((gy * OW + gx) * ldm + moff + co) * 2 : (int)rf::OOB, 0);
     };
 
     const int G = (int)gridDim.x;
     int item = xcd_remap((int)blockIdx.x, G);
     if (item >= nitems) return;
-    Item cur = decode_item(item);
+    Item cur = rf::decode_item(item, tiles_img, tiles_x);
     {
         const HaloBlk h0 = halo_blk(cur);
 #pragma unroll
@@ -248,12 +209,12 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
             for (int i = 0; i < TI; ++i) {
                 const int chan = cbase + (frow >> 2) * 4 * TI + i * 4 + (frow & 3);
                 const bool real = chan < Cout && ks * 4 + g4 < Q;
-                Wf[ks][i] = __builtin_amdgcn_raw_buffer_load_b128(rsW, real ? chan * wld16 + g4 * 16 : (int)R5_OOB, ks * 64, 0);
+                Wf[ks][i] = __builtin_amdgcn_raw_buffer_load_b128(rsW, real ? chan * wld16 + g4 * 16 : (int)rf::OOB, ks * 64, 0);
             }
-        // where they live is decided HERE (r5_mfma): the first NA fragments in accumulation registers, the others in architectural ones
-        r5_static_for<0, NSTEP * TI>([&](auto N_) __attribute__((always_inline)) {
+        // where they live is decided HERE (rf::mfma): the first NA fragments in accumulation registers, the others in architectural ones
+        rf::static_for<0, NSTEP * TI>([&](auto N_) __attribute__((always_inline)) {
             constexpr int n = decltype(N_)::value;
-            r5_pin<(n < NA)>(Wf[n / TI][n % TI]);
+            rf::pin<(n < NA)>(Wf[n / TI][n % TI]);
         });
     }
     // forward: the wave's 16 TI bias values behind the halo buffers
@@ -263,7 +224,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
             *reinterpret_cast<float*>(smem_raw + 2 * HB + wid * 256 + lane * 4) = ((flags & DIN_CONV_BIAS) && co < Cout) ? p.bias[co] : 0.f;
         }
     }
-    f32x4 acc[TI][8];                                                             // (the first step of a tile writes them: r5_mfma<.., FIRST>)
+    f32x4 acc[TI][8];                                                             // (the first step of a tile writes them: rf::mfma<.., FIRST>)
 
     // lane base of the fragment reads: first row of the wave's pixel half, pixel column frow, chunk g4
     const uint32_t xb0 = lds_base + (uint32_t)((4 * wp * R5_HWW + frow) * PB + g4 * 16);
@@ -277,14 +238,14 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
         __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(outp + (long long)it.n * oimg_bytes, 0, (int)oimg_bytes, 0x00020000);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int gy = it.ty * R5_TH + 4 * wp + (j >> 1), gx = it.tx * R5_TW + (j & 1) * 16 + frow_e;
-            const int pxo = (gy < OH && gx < OW) ? ((gy * OW + gx) * ldo + cooff) * 2 : (int)R5_OOB;   // byte offset of the fragment's pixel, or out of range
+            const int gy = it.ty * rf::TH + 4 * wp + (j >> 1), gx = it.tx * rf::TW + (j & 1) * 16 + frow_e;
+            const int pxo = (gy < OH && gx < OW) ? ((gy * OW + gx) * ldo + cooff) * 2 : (int)rf::OOB;   // byte offset of the fragment's pixel, or out of range
             [[maybe_unused]] u32x2 old[TI];                                       // (BIAS / RELU are forward flags, MASK / ACCUM data-gradient flags: host)
             if constexpr (DG) {
 #pragma unroll
                 for (int i = 0; i < TI; ++i) {
                     const int co = cbase + g4_e * 4 * TI + i * 4;
-                    if (flags & DIN_CONV_ACCUM) old[i] = __builtin_amdgcn_raw_buffer_load_b64(rsO, co < Cout ? pxo + co * 2 : (int)R5_OOB, 0, 0);
+                    if (flags & DIN_CONV_ACCUM) old[i] = __builtin_amdgcn_raw_buffer_load_b64(rsO, rf::piece_off(pxo, co, Cout), 0, 0);
                 }
             }
             const int pl = (j >> 1) * 32 + (j & 1) * 16 + frow_e;
@@ -303,18 +264,11 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
                         // (a lane group past the class's real channels stores nothing: it reads the region's last chunk, not past it)
                         const int gm = g4_e < mch ? g4_e : mch - 1;
                         const u32x2 mk = *reinterpret_cast<const u32x2*>(smem_raw + (ldsMk - lds_base) + (pl * mch + gm) * 16 + i * 8);
-                        if (!(__uint_as_float(mk[0] << 16) > 0.f)) v[0] = 0.f;
-                        if (!(__uint_as_float(mk[0] & 0xffff0000u) > 0.f)) v[1] = 0.f;
-                        if (!(__uint_as_float(mk[1] << 16) > 0.f)) v[2] = 0.f;
-                        if (!(__uint_as_float(mk[1] & 0xffff0000u) > 0.f)) v[3] = 0.f;
+                        rf::mask4(v, mk);
                     }
-                    if (flags & DIN_CONV_ACCUM) {
-                        v[0] += __uint_as_float(old[i][0] << 16); v[1] += __uint_as_float(old[i][0] & 0xffff0000u);
-                        v[2] += __uint_as_float(old[i][1] << 16); v[3] += __uint_as_float(old[i][1] & 0xffff0000u);
-                    }
+                    if (flags & DIN_CONV_ACCUM) v = rf::accum4(v, old[i]);
                 }
-                // (out of range: pxo has bit 31 set and stays >= 2^31 as an unsigned offset; Cout % 8 == 0: a piece is whole or absent)
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}, rsO, co < Cout ? pxo + co * 2 : (int)R5_OOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}, rsO, rf::piece_off(pxo, co, Cout), 0, 0);
             }
             asm volatile("" ::: "memory");                                       // one fragment at a time: the filters leave no registers for more
         }
@@ -327,7 +281,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
     for (;;) {
         const int item_n = item + G;
         const bool hn = item_n < nitems;                                          // a next item exists: its halo goes into buffer hb ^ 1
-        const Item nxt = hn ? decode_item(item_n) : cur;
+        const Item nxt = hn ? rf::decode_item(item_n, tiles_img, tiles_x) : cur;
         const HaloBlk hnx = halo_blk(nxt);
         const uint32_t xa = xb0 + (uint32_t)(hb * HB);
         // the read address of a step: xa, or for a step that straddles two taps xa + K in the lane groups >= SP of the step (made where
@@ -343,23 +297,23 @@ __global__ __launch_bounds__(256, 1) void conv_halo_rf5_kernel(ConvK p) {
                 xs[s & 1] = xa;
             }
         };
-        r5_static_for<0, D>([&](auto F_) __attribute__((always_inline)) {
+        rf::static_for<0, D>([&](auto F_) __attribute__((always_inline)) {
             constexpr int f = decltype(F_)::value;
             static_assert(D <= 8 && r5_sp<CPT, DG>(0) == 4, "the first reads belong to step 0, a whole-tap step");
-            r5_read<r5_off<CPT, DG>(0, f & 7)>(xf[f], xa);
+            rf::read<r5_off<CPT, DG>(0, f & 7)>(xf[f], xa);
         });
-        r5_static_for<0, NF>([&](auto F_) __attribute__((always_inline)) {
+        rf::static_for<0, NF>([&](auto F_) __attribute__((always_inline)) {
             constexpr int f = decltype(F_)::value;
             constexpr int ks = f >> 3, j = f & 7;
-            r5_wait<(NF - 1 - f < D - 1 ? NF - 1 - f : D - 1)>(xf[f % D]);
-            r5_static_for<0, TI>([&](auto I_) __attribute__((always_inline)) {
+            rf::wait<(NF - 1 - f < D - 1 ? NF - 1 - f : D - 1)>(xf[f % D]);
+            rf::static_for<0, TI>([&](auto I_) __attribute__((always_inline)) {
                 constexpr int i = decltype(I_)::value;
-                r5_mfma<(ks * TI + i < NA), (ks == 0)>(acc[i][j], Wf[ks][i], xf[f % D]);
+                rf::mfma<(ks * TI + i < NA), (ks == 0)>(acc[i][j], Wf[ks][i], xf[f % D]);
             });
             if constexpr (f + D < NF) {
                 constexpr int nf = f + D, ns = nf >> 3;
                 if constexpr ((nf & 7) == 0) step_addr(std::integral_constant<int, ns>{});
-                r5_read<r5_off<CPT, DG>(4 * ns, nf & 7)>(xf[f % D], xs[ns & 1]);
+                rf::read<r5_off<CPT, DG>(4 * ns, nf & 7)>(xf[f % D], xs[ns & 1]);
             }
             if constexpr (f % SP == 0) {                                          // one transfer after the MFMAs of every SP-th fragment
                 constexpr int t = f / SP;
@@ -397,7 +351,7 @@ std::string rf5_kernel_name(const Rf5Inst& r) {
 int rf5_row(const Rf5Inst& r, const ConvK* k, hipStream_t st) {
     auto go = [&](auto kern) {
         if (!k) return DIN_OK;
-        const int tiles = ((k->OH + R5_TH - 1) / R5_TH) * ((k->OW + R5_TW - 1) / R5_TW) * k->NB;
+        const int tiles = ((k->OH + rf::TH - 1) / rf::TH) * ((k->OW + rf::TW - 1) / rf::TW) * k->NB;
         const size_t lds = r5_lds(r.cpt, r.dg, (k->flags & DIN_CONV_MASK) != 0, k->Cout);
         DIN_REQUIRE(lds <= R5_LDS_MAX, "conv_halo_rf5: %zu bytes of LDS", lds);
         raise_lds_limit(kern, lds);
@@ -413,9 +367,7 @@ int rf5_row(const Rf5Inst& r, const ConvK* k, hipStream_t st) {
 
 // the planner's rule (option unset)
 bool rf5_wanted(int which, int flags, int oh, int ow, int64_t M) {
-    // padded-area waste of the 8 x 32 tile grid must stay moderate (plan_halo's rule)
-    const int64_t padded = (int64_t)((oh + R5_TH - 1) / R5_TH * R5_TH) * ((ow + R5_TW - 1) / R5_TW * R5_TW);
-    if (padded * 100 > (int64_t)oh * ow * 118) return false;
+    if (!rf::tile_waste_ok(oh, ow)) return false;
     // accumulate operands are requested one pixel fragment at a time (the filters leave no registers for more): exposed memory round
     // trips per tile, not measured against the old kernels -- no backbone layer asks for it
     if (flags & DIN_CONV_ACCUM) return false;
@@ -426,108 +378,48 @@ bool rf5_wanted(int which, int flags, int oh, int ow, int64_t M) {
     return M >= (which == 0 ? 160 * 1024 : 1280 * 1024);
 }
 
-// Eligibility, geometry and instantiation of the launch `which` (0 forward, 1 data gradient) of a descriptor: bf16, 5x5, stride 1,
-// dilation 1, reduction and produced channels in 40 .. 64 and multiples of 8, views as conv_halo_rf_kernel takes them (the mask view in
-// whole 16-byte chunks: it travels by LDS-DMA), and the launch's LDS within 160 KB -- a MASKED data gradient with 56 or 64 reduction
-// channels (160-byte pitch: 136 KB of halo buffers) has room for the mask of <= 48 produced channels only.  Options: DIN_CONV_HALO=0 and
-// DIN_CONV_HALO_RF5=0 switch the kernel off, DIN_CONV_HALO_RF5=2 forces it on every eligible shape; unset, the planner's rule holds
-// (rf5_wanted).  Reads no pointer.
+// Eligibility, geometry and instantiation of the launch `which` (0 forward, 1 data gradient) of a descriptor: what rf::plan_common asks of
+// a 5x5 with 40 .. 64 channels, and the launch's LDS within 160 KB -- a MASKED data gradient with 56 or 64 reduction channels (160-byte
+// pitch: 136 KB of halo buffers) has room for the mask of <= 48 produced channels only.  Options: DIN_CONV_HALO=0 and DIN_CONV_HALO_RF5=0
+// switch the kernel off, DIN_CONV_HALO_RF5=2 forces it on every eligible shape; unset, the planner's rule holds (rf5_wanted).  Reads no
+// pointer.
 bool rf5_plan(const din_conv_desc* d, int which, int flags, int ldm, int moff, ConvK& k, Rf5Inst& r) {
-    if (!d || (which != 0 && which != 1) || d->dtype != DIN_BF16 || d->in_u8) return false;
-    if (d->nb <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->cout <= 0) return false;
-    if (d->kh != 5 || d->kw != 5 || d->sh != 1 || d->sw != 1 || d->dh != 1 || d->dw != 1) return false;
-    if (d->oh != d->h + 2 * d->ph - 4 || d->ow != d->w + 2 * d->pw - 4 || d->oh <= 0 || d->ow <= 0) return false;
-    if ((int64_t)d->nb * d->h * d->w >= (1ll << 31) || (int64_t)d->nb * d->oh * d->ow >= (1ll << 31)) return false;
-    const int cred = which ? d->cout : d->cin, cprod = which ? d->cin : d->cout;
-    if (cred % 8 != 0 || cprod % 8 != 0 || cred < 40 || cred > 64 || cprod < 40 || cprod > 64) return false;
-    if (d->ldi % 8 != 0 || d->cioff % 8 != 0 || d->ldi < d->cioff + d->cin || d->ldo % 4 != 0 || d->cooff % 4 != 0 || d->ldo < d->cooff + d->cout) return false;
-    if (which == 0 && (flags & ~(DIN_CONV_BIAS | DIN_CONV_RELU))) return false;
-    if (which == 1) {
-        if (flags & ~(DIN_CONV_MASK | DIN_CONV_ACCUM)) return false;
-        if (d->ldo % 8 != 0 || d->cooff % 8 != 0) return false;                  // the gradient operand is read in whole chunks
-        if ((flags & DIN_CONV_MASK) && (ldm % 8 != 0 || moff % 8 != 0 || moff < 0 || ldm < moff + cprod)) return false;
-    }
-    if (r5_lds(cred / 8, which == 1, (flags & DIN_CONV_MASK) != 0, cprod) > R5_LDS_MAX) return false;
-    const char* hv = DIN_OPT("DIN_CONV_HALO");
-    if (hv && atoi(hv) == 0) return false;
+    if (!rf::plan_common(d, which, flags, ldm, moff, 5, 64, k)) return false;
+    if (r5_lds(k.cpt, which == 1, (flags & DIN_CONV_MASK) != 0, k.Cout) > R5_LDS_MAX) return false;
     const char* rv = DIN_OPT("DIN_CONV_HALO_RF5");
     const int mode = rv ? atoi(rv) : 1;
-    if (mode == 0) return false;
-    k = ConvK{};
-    k.NB = d->nb; k.kh = 5; k.kw = 5;
-    const PackGeom bank = pack_geom(d, which);
-    k.w_bytes = (long long)bank.rows_pad * bank.kelems * 2;
-    k.ay = k.ax = 1; k.divy = k.divx = 1;
-    if (which == 0) {
-        k.H = d->h; k.W = d->w; k.Cin = d->cin; k.ldi = d->ldi; k.cioff = d->cioff;
-        k.OH = d->oh; k.OW = d->ow; k.Cout = d->cout; k.ldo = d->ldo; k.cooff = d->cooff;
-        k.by = -d->ph; k.bx = -d->pw; k.cy = k.cx = 1;
-    } else {
-        k.H = d->oh; k.W = d->ow; k.Cin = d->cout; k.ldi = d->ldo; k.cioff = d->cooff;
-        k.OH = d->h; k.OW = d->w; k.Cout = d->cin; k.ldo = d->ldi; k.cooff = d->cioff;
-        k.by = d->ph; k.bx = d->pw; k.cy = k.cx = -1;
-    }
-    k.M = k.NB * k.OH * k.OW;
-    k.in_bytes = (long long)k.NB * k.H * k.W * k.ldi * 2;
-    k.cpt = bank.cpt; k.Q = 25 * bank.cpt; k.nk = bank.nk; k.wld = bank.nk * KC;
-    k.flags = flags; k.ldm = (flags & DIN_CONV_MASK) ? ldm : 0; k.moff = (flags & DIN_CONV_MASK) ? moff : 0;
-    k.splitk = 1; k.ks_per_split = k.nk; k.n_co_tiles = 1;
-    if (!din_gather::views_below_2g(k)) return false;
-    if (mode != 2 && !rf5_wanted(which, flags, k.OH, k.OW, k.M)) return false;
-    r.cpt = bank.cpt; r.dg = which == 1;
+    if (mode == 0 || (mode != 2 && !rf5_wanted(which, flags, k.OH, k.OW, k.M))) return false;
+    r.cpt = k.cpt; r.dg = which == 1;
     return true;
 }
+
+struct Rf5 {
+    typedef Rf5Inst Inst;
+    static constexpr auto plan = rf5_plan;
+    static constexpr auto row = rf5_row;
+    static constexpr auto name = rf5_kernel_name;
+    static constexpr const char* prefix = "conv_rf5";
+};
 
 }  // namespace
 
 extern "C" {
 
-int din_conv_rf5_eligible(const din_conv_desc* d, int which, int flags, int ldm, int moff) {
-    ConvK k; Rf5Inst r;
-    return rf5_plan(d, which, flags, ldm, moff, k, r) && rf5_row(r, nullptr, nullptr) == DIN_OK ? 1 : 0;
-}
+int din_conv_rf5_eligible(const din_conv_desc* d, int which, int flags, int ldm, int moff) { return rf::eligible<Rf5>(d, which, flags, ldm, moff); }
 
+// (workspace: the argument list of din_conv_fwd / din_conv_dgrad; this kernel never splits its reduction)
 int din_conv_rf5_fwd(const din_conv_desc* d, const void* in, const void* wpk, const float* bias, void* out, int flags,
-                     void* workspace, int64_t workspace_bytes, void* stream) {
-    (void)workspace; (void)workspace_bytes;                                      // (the argument list of din_conv_fwd: this kernel never splits its reduction)
-    if (int e = din_conv::check_desc(d)) return e;
-    DIN_REQUIRE(in && wpk && out, "conv_rf5_fwd: null pointer");
-    DIN_REQUIRE(!(flags & DIN_CONV_BIAS) || bias, "conv_rf5_fwd: BIAS flag without bias");
-    ConvK k; Rf5Inst r;
-    DIN_REQUIRE(rf5_plan(d, 0, flags, 0, 0, k, r), "conv_rf5_fwd: not eligible (ask din_conv_rf5_eligible)");
-    k.in = in; k.w = wpk; k.out = out; k.bias = bias;
-    if (int e = rf5_row(r, &k, as_stream(stream))) return e;
-    DIN_CHECK_LAUNCH("conv_rf5_fwd");
-    return DIN_OK;
+                     void* /*workspace*/, int64_t /*workspace_bytes*/, void* stream) {
+    return rf::fwd<Rf5>(d, in, wpk, bias, out, flags, stream);
 }
 
 int din_conv_rf5_dgrad(const din_conv_desc* d, const void* dout, const void* wpk_t, void* din_, const void* mask, int ldm, int moff, int flags,
-                       void* workspace, int64_t workspace_bytes, void* stream) {
-    (void)workspace; (void)workspace_bytes;
-    if (int e = din_conv::check_desc(d)) return e;
-    DIN_REQUIRE(dout && wpk_t && din_, "conv_rf5_dgrad: null pointer");
-    DIN_REQUIRE(!(flags & DIN_CONV_MASK) || mask, "conv_rf5_dgrad: MASK flag without mask");
-    ConvK k; Rf5Inst r;
-    DIN_REQUIRE(rf5_plan(d, 1, flags, ldm, moff, k, r), "conv_rf5_dgrad: not eligible (ask din_conv_rf5_eligible)");
-    k.in = dout; k.w = wpk_t; k.out = din_; k.mask = mask;
-    if (int e = rf5_row(r, &k, as_stream(stream))) return e;
-    DIN_CHECK_LAUNCH("conv_rf5_dgrad");
-    return DIN_OK;
+                       void* /*workspace*/, int64_t /*workspace_bytes*/, void* stream) {
+    return rf::dgrad<Rf5>(d, dout, wpk_t, din_, mask, ldm, moff, flags, stream);
 }
 
 int din_conv_rf5_kernel_names(const din_conv_desc* d, int which, int flags, int ldm, int moff, char* buf, int buf_bytes) {
-    if (int e = din_conv::check_desc(d)) return e;
-    DIN_REQUIRE(buf_bytes >= 0 && (buf || buf_bytes == 0), "conv_rf5_kernel_names: bad argument");
-    ConvK k; Rf5Inst r;
-    DIN_REQUIRE(rf5_plan(d, which, flags, ldm, moff, k, r), "conv_rf5_kernel_names: not eligible (ask din_conv_rf5_eligible)");
-    if (int e = rf5_row(r, nullptr, nullptr)) return e;
-    const std::string names = rf5_kernel_name(r) + "\n";
-    if (buf_bytes > 0) {
-        const size_t n = names.size() < (size_t)buf_bytes - 1 ? names.size() : (size_t)buf_bytes - 1;
-        memcpy(buf, names.data(), n);
-        buf[n] = 0;
-    }
-    return (int)names.size() + 1;
+    return rf::kernel_names<Rf5>(d, which, flags, ldm, moff, buf, buf_bytes);
 }
 
 }  // extern "C"

@@ -1298,16 +1298,6 @@ static int append_launch_names(ConvK& k, const GatherPlan& g, int dtype, std::st
     return append_kernel_names(k, c, dtype, out);
 }
 
-// the answer of a *_kernel_names entry point: at most buf_bytes bytes (NUL-terminated) written, the bytes the whole answer needs returned
-static int copy_names(const std::string& names, char* buf, int buf_bytes) {
-    if (buf_bytes > 0) {
-        const size_t n = names.size() < (size_t)buf_bytes - 1 ? names.size() : (size_t)buf_bytes - 1;
-        memcpy(buf, names.data(), n);
-        buf[n] = 0;
-    }
-    return (int)names.size() + 1;
-}
-
 // The launch din_conv_fwd2 makes for a checked descriptor (dtype normalised, split: it was DIN_F32_BF16X3): every argument check that reads
 // no pointer, then f(argument block without pointers, plan).  din_conv_fwd2 binds its pointers and launches from here;
 // din_conv_fwd2_kernel_names names the kernel from here.

@@ -1624,15 +1624,6 @@ static int wgrad_group_lines(const WgradGroupPlan& gp, std::string* names) {
     return DIN_OK;
 }
 
-static int copy_names(const std::string& names, char* buf, int buf_bytes) {
-    if (buf_bytes > 0) {
-        const size_t n = names.size() < (size_t)buf_bytes - 1 ? names.size() : (size_t)buf_bytes - 1;
-        names.copy(buf, n);
-        buf[n] = 0;
-    }
-    return (int)names.size() + 1;
-}
-
 int din_conv_wgrad_group_key(const din_conv_desc* d) { return wgrad_group_key(d, nullptr); }
 
 int64_t din_conv_wgrad_group_workspace(int n, const din_conv_wgrad_item* items) {

@@ -460,16 +460,20 @@ def _bn_train_forward(lib, raw: torch.Tensor, dt: int, rows: int, cout: int, gam
     return bmean, rstd
 
 
+# the filter-stationary halo kernel families (csrc/conv_halo_rf.h), one row each: kernel size, the four entry points, the BackwardPlan set it fills
+RfFamily = NamedTuple("RfFamily", [("k", Tuple[int, int]), ("eligible", str), ("fwd", str), ("dgrad", str), ("names", str), ("plan_set", str)])
+RF_FAMILIES = (RfFamily((3, 3), "din_conv_rf_eligible", "din_conv_rf_fwd", "din_conv_rf_dgrad", "din_conv_rf_kernel_names", "rf_dgrad"),
+               RfFamily((5, 5), "din_conv_rf5_eligible", "din_conv_rf5_fwd", "din_conv_rf5_dgrad", "din_conv_rf5_kernel_names", "rf5_dgrad"))
+
+
 def _conv_fwd_launch(lib, d, src, wpk, bias, dst, flags: int, st, dev, name: str) -> None:
-    """one forward conv launch: on a filter-stationary halo kernel where the library says so (din_conv_rf_eligible for the 3x3 family,
-    din_conv_rf5_eligible for the 5x5 one, each asked once per op), through din_conv_fwd otherwise; d.rf / d.rf5 tell the launch timer which
-    of the three reporters names the kernel"""
+    """one forward conv launch: on a filter-stationary halo kernel where the library says so (the families of RF_FAMILIES are asked in turn,
+    once per op; their kernel sizes exclude each other), through din_conv_fwd otherwise; d.rf = (reporter, flags, ldm, moff) tells the
+    launch timer which reporter names the kernel"""
     ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(d), 0), dev)
-    rf = bool(lib.din_conv_rf_eligible(C.byref(d), 0, flags, 0, 0))
-    rf5 = not rf and bool(lib.din_conv_rf5_eligible(C.byref(d), 0, flags, 0, 0))     # (the 5x5 family: 3x3 and 5x5 exclude each other)
-    d.rf = (flags, 0, 0) if rf else None
-    d.rf5 = (flags, 0, 0) if rf5 else None
-    fn = lib.din_conv_rf_fwd if rf else lib.din_conv_rf5_fwd if rf5 else lib.din_conv_fwd
+    fam = next((f for f in RF_FAMILIES if getattr(lib, f.eligible)(C.byref(d), 0, flags, 0, 0)), None)
+    d.rf = (fam.names, flags, 0, 0) if fam else None
+    fn = getattr(lib, fam.fwd if fam else "din_conv_fwd")
     with _timed("fwd", d, name):
         L.check(fn(C.byref(d), _ptr(src), _ptr(wpk), _ptr(bias), _ptr(dst), flags, _ptr(ws), wsb, st), "conv_fwd " + name)
 
@@ -750,22 +754,21 @@ def plan_backward(g: Graph, nb: int, dt: int, bn_train: bool, side_ok: bool, u8:
     group_on = switch("GROUP_WGRAD") and bf16 and not side
     group_max = max(2, min(16, int(L.get_option("DIN_GROUP_WGRAD_MAX") or GROUP_WGRAD_MAX))) if group_on else 0
     group_bytes = int(L.get_option("DIN_GROUP_WGRAD_MB") or GROUP_WGRAD_MB) << 20 if group_on else 0
-    # 3x3 / stride-1 convs whose data gradient the library wants on the filter-stationary halo kernel: asked once per op, here, with the
-    # launch's gradient view and ReLU-mask view (without ACCUM: whether the launch accumulates is known when the pass reaches it, and
-    # _BackwardPass.dgrad asks again for one that does)
-    # (the 5x5 family, din_conv_rf5_eligible, is asked the same way into a set of its own)
-    rf_dgrad, rf5_dgrad = set(), set()
+    # stride-1 convs whose data gradient the library wants on a filter-stationary halo kernel (RF_FAMILIES, each into the plan set of its
+    # own): asked once per op, here, with the launch's gradient view and ReLU-mask view (without ACCUM: whether the launch accumulates is
+    # known when the pass reaches it, and _BackwardPass.dgrad asks again for one that does)
+    rf_sets = {f.plan_set: set() for f in RF_FAMILIES}
     for oi, op in enumerate(g.ops):
-        if op.kind == "conv" and op.k in ((3, 3), (5, 5)) and op.s == (1, 1) and op.pooled is None and op.src.tid != g.input_tid:
+        fam = next((f for f in RF_FAMILIES if op.kind == "conv" and f.k == op.k), None)
+        if fam and op.s == (1, 1) and op.pooled is None and op.src.tid != g.input_tid:
             d = _conv_desc(g, op, nb, dt)
             if op.bn and bn_train:
                 d.ldo, d.cooff = op.dst.c, 0                       # (the gradient operand is the contiguous dy of bn_train_backward)
             masked = g.tensors[op.src.tid].relu_masked
-            ask, into = (lib.din_conv_rf_eligible, rf_dgrad) if op.k == (3, 3) else (lib.din_conv_rf5_eligible, rf5_dgrad)
-            if ask(C.byref(d), 1, L.CONV_MASK if masked else 0, g.tensors[op.src.tid].c if masked else 0, op.src.coff if masked else 0):
-                into.add(oi)
+            if getattr(lib, fam.eligible)(C.byref(d), 1, L.CONV_MASK if masked else 0, g.tensors[op.src.tid].c if masked else 0, op.src.coff if masked else 0):
+                rf_sets[fam.plan_set].add(oi)
     return BackwardPlan(offsets, bn_index, bn_train, side, bool(u8), groups, member_of, x_host, siblings, multi_w, group_on, group_max,
-                        group_bytes, partitioned, first_writer, rf_dgrad, rf5_dgrad)
+                        group_bytes, partitioned, first_writer, **rf_sets)
 
 
 class _Pending(NamedTuple):
@@ -1064,14 +1067,11 @@ class _BackwardPass:
                 L.check(self.lib.din_conv_dgrad_x(C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc), self.mask_of(op.src), ts.c, op.src.coff, flags,
                                                   C.byref(xs), _ptr(ws), wsb, self.st), "conv_dgrad_x " + op.name)
         else:
-            rf, rf5 = oi in self.plan.rf_dgrad, oi in self.plan.rf5_dgrad
-            if rf and acc:                                           # (the plan asked without ACCUM: an accumulating launch gets its own answer)
-                rf = bool(self.lib.din_conv_rf_eligible(C.byref(d), 1, flags, ts.c, op.src.coff))
-            if rf5 and acc:
-                rf5 = bool(self.lib.din_conv_rf5_eligible(C.byref(d), 1, flags, ts.c, op.src.coff))
-            d.rf = (flags, ts.c, op.src.coff) if rf else None        # (the launch timer names the kernel from the matching reporter)
-            d.rf5 = (flags, ts.c, op.src.coff) if rf5 else None
-            fn = self.lib.din_conv_rf_dgrad if rf else self.lib.din_conv_rf5_dgrad if rf5 else self.lib.din_conv_dgrad
+            fam = next((f for f in RF_FAMILIES if oi in getattr(self.plan, f.plan_set)), None)
+            if fam and acc and not getattr(self.lib, fam.eligible)(C.byref(d), 1, flags, ts.c, op.src.coff):
+                fam = None                                           # (the plan asked without ACCUM: an accumulating launch gets its own answer)
+            d.rf = (fam.names, flags, ts.c, op.src.coff) if fam else None       # (the launch timer names the kernel from this reporter)
+            fn = getattr(self.lib, fam.dgrad if fam else "din_conv_dgrad")
             with _timed("dgrad", d, op.name):
                 L.check(fn(C.byref(d), _ptr(gout), _ptr(wpt), _ptr(gsrc), self.mask_of(op.src), ts.c, op.src.coff, flags, _ptr(ws), wsb, self.st),
                         "conv_dgrad " + op.name)

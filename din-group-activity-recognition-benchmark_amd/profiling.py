@@ -150,18 +150,11 @@ class LaunchTimer:
         which = {"fwd": 0, "dgrad": 1}[self.kind]
         rf = getattr(d, "rf", None)
         if rf is not None:
-            # the launch goes through din_conv_rf_fwd / din_conv_rf_dgrad (nhwc sets d.rf = (flags, ldm, moff)): their own reporter names it
+            # the launch goes through a family of nhwc.RF_FAMILIES (nhwc sets d.rf = (reporter, flags, ldm, moff)): its own reporter names it
             buf = C.create_string_buffer(256)
-            rc = L.load().din_conv_rf_kernel_names(C.byref(d), which, rf[0], rf[1], rf[2], buf, len(buf))
+            rc = getattr(L.load(), rf[0])(C.byref(d), which, rf[1], rf[2], rf[3], buf, len(buf))
             if rc < 0:
-                L.check(rc, "din_conv_rf_kernel_names")
-            return buf.value.decode().split("\n")[0]
-        rf5 = getattr(d, "rf5", None)
-        if rf5 is not None:                                            # (the 5x5 family: din_conv_rf5_fwd / _dgrad, named by din_conv_rf5_kernel_names)
-            buf = C.create_string_buffer(256)
-            rc = L.load().din_conv_rf5_kernel_names(C.byref(d), which, rf5[0], rf5[1], rf5[2], buf, len(buf))
-            if rc < 0:
-                L.check(rc, "din_conv_rf5_kernel_names")
+                L.check(rc, rf[0])
             return buf.value.decode().split("\n")[0]
         bm, bn = C.c_int32(0), C.c_int32(0)
         L.load().din_conv_kernel_tile(C.byref(d), which, C.byref(bm), C.byref(bn))

@@ -6,6 +6,7 @@ import torch
 import os as _os
 _os.environ.setdefault("DIN_OPTIONS_FROM_ENV", "1")   # tuning tool: DIN_* variables of this process become library options (din_set_option) at load
 from din_amd import _lib as L
+from din_amd.nhwc import RF_FAMILIES
 
 LAYERS = {  # name: (nb, h, w, cin, cout, k, s, p)
     "vgg_conv1_2": (12, 720, 1280, 64, 64, 3, 1, 1),
@@ -108,14 +109,11 @@ def main():
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device="cuda")
     def routed():
         """the entry points of a forward / data-gradient launch as nhwc picks them: the filter-stationary halo kernel where the library says so"""
-        if a.which == "fwd" and lib.din_conv_rf_eligible(C.byref(d), 0, 3, 0, 0):
-            return lib.din_conv_rf_fwd, lib.din_conv_dgrad
-        if a.which == "dgrad" and lib.din_conv_rf_eligible(C.byref(d), 1, a.flags, cin, 0):
-            return lib.din_conv_fwd, lib.din_conv_rf_dgrad
-        if a.which == "fwd" and lib.din_conv_rf5_eligible(C.byref(d), 0, 3, 0, 0):
-            return lib.din_conv_rf5_fwd, lib.din_conv_dgrad
-        if a.which == "dgrad" and lib.din_conv_rf5_eligible(C.byref(d), 1, a.flags, cin, 0):
-            return lib.din_conv_fwd, lib.din_conv_rf5_dgrad
+        for fam in RF_FAMILIES:
+            if a.which == "fwd" and getattr(lib, fam.eligible)(C.byref(d), 0, 3, 0, 0):
+                return getattr(lib, fam.fwd), lib.din_conv_dgrad
+            if a.which == "dgrad" and getattr(lib, fam.eligible)(C.byref(d), 1, a.flags, cin, 0):
+                return lib.din_conv_fwd, getattr(lib, fam.dgrad)
         return lib.din_conv_fwd, lib.din_conv_dgrad
     entry = list(routed())
     def run():
