@@ -180,6 +180,8 @@ SIGNATURES: Dict[str, tuple] = {
     "din_grad_sqnorm_multi": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "din_grad_norm_finish": (_I, [_P, _I, _F, _F, _P, _P]),
     "din_adam_step_multi_clip": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _I, _F, _P, _P]),
+    "din_adam_state_advance": (_I, [_P, _P, _F, _F, _P]),
+    "din_adam_step_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P]),
     "din_copy_rows_u8":(_I, [_P, _P, _I, _L, _P]),
     "din_feat_rows": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
     "din_feat_rows_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),

@@ -185,8 +185,9 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 }
 
 // multi-tensor form: one launch for the whole parameter list.  ptrs[t] = {p, g, m, v} of tensor t; workgroup b updates elements
-// [chunk_index[b] * chunk, +chunk) of tensor chunk_tensor[b].  adam_multi_chunk is the whole update of one workgroup: the plain and the
-// clipped launch both call it, so the two cannot drift -- they differ only in the factor they hand in as gscale.
+// [chunk_index[b] * chunk, +chunk) of tensor chunk_tensor[b].  adam_multi_chunk is the whole update of one workgroup: the plain, the
+// clipped and the device-state launch all call it, so they cannot drift -- they differ only in the factor they hand in as gscale and in
+// where lr and the bias corrections come from.
 __device__ __forceinline__ void adam_multi_chunk(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
                                                  const int32_t* __restrict__ chunk_tensor, const int32_t* __restrict__ chunk_index, int chunk,
                                                  float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
@@ -226,6 +227,32 @@ __global__ __launch_bounds__(256) void adam_multi_clip_kernel(const uint64_t* __
     const float norm = state[0], coef = state[1];
     if (!(fabsf(norm) <= 3.402823466e+38f)) return;             // Inf or NaN (a comparison with NaN is false)
     adam_multi_chunk(ptrs, sizes, chunk_tensor, chunk_index, chunk, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale * coef);
+}
+// ---- Adam whose step count and learning rate live on the device (a captured launch bakes every host argument) --------------------------
+// ostate: double[4] = {step, lr, beta1^step, beta2^step}, see include/din_hip.h.  adam_state_advance_kernel counts one step -- unless
+// the clip state says the step is skipped, in which case the record keeps its bits -- and adam_multi_dev_kernel is adam_multi_kernel /
+// adam_multi_clip_kernel with lr and both bias corrections formed from the record: 1 - beta^step in fp64, rounded once to fp32.
+__global__ __launch_bounds__(64) void adam_state_advance_kernel(double* __restrict__ ostate, const float* __restrict__ clip, float b1, float b2) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (clip && !(fabsf(clip[0]) <= 3.402823466e+38f)) return;
+    const double step = ostate[0], p1 = ostate[2], p2 = ostate[3];
+    ostate[0] = step + 1.0;
+    ostate[2] = p1 * (double)b1;
+    ostate[3] = p2 * (double)b2;
+}
+__global__ __launch_bounds__(256) void adam_multi_dev_kernel(const uint64_t* __restrict__ ptrs, const int64_t* __restrict__ sizes,
+                                                             const int32_t* __restrict__ chunk_tensor, const int32_t* __restrict__ chunk_index,
+                                                             int chunk, float b1, float b2, float eps, float wd, float gscale,
+                                                             const double* __restrict__ ostate, const float* __restrict__ clip) {
+    float factor = gscale;
+    if (clip) {
+        const float norm = clip[0], coef = clip[1];
+        if (!(fabsf(norm) <= 3.402823466e+38f)) return;
+        factor = gscale * coef;
+    }
+    const float lr = (float)ostate[1];
+    const float bc1 = (float)(1.0 - ostate[2]), bc2_sqrt = (float)sqrt(1.0 - ostate[3]);
+    adam_multi_chunk(ptrs, sizes, chunk_tensor, chunk_index, chunk, lr, b1, b2, eps, wd, bc1, bc2_sqrt, factor);
 }
 
 // ---- global gradient norm: sum of squares of every gradient of the tables above, in fp64 and in a fixed order -------------------------
@@ -463,6 +490,30 @@ int din_adam_step_multi_clip(const uint64_t* ptrs, const int64_t* sizes, const i
     hipLaunchKernelGGL(adam_multi_clip_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), ptrs, sizes, chunk_tensor, chunk_index,
                        chunk_elems, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, state);
     DIN_CHECK_LAUNCH("adam_step_multi_clip");
+    return DIN_OK;
+}
+
+int din_adam_state_advance(double* ostate, const float* clip_state, float beta1, float beta2, void* stream) {
+    DIN_REQUIRE(ostate, "adam_state_advance: bad argument");
+    DIN_REQUIRE((reinterpret_cast<uintptr_t>(ostate) & 7) == 0, "adam_state_advance: ostate must be 8-byte aligned");
+    DIN_REQUIRE((reinterpret_cast<uintptr_t>(clip_state) & 3) == 0, "adam_state_advance: clip_state must be 4-byte aligned");
+    DIN_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "adam_state_advance: betas must lie in [0, 1)");   // (false for NaN)
+    hipLaunchKernelGGL(adam_state_advance_kernel, dim3(1), dim3(64), 0, as_stream(stream), ostate, clip_state, beta1, beta2);
+    DIN_CHECK_LAUNCH("adam_state_advance");
+    return DIN_OK;
+}
+
+int din_adam_step_multi_dev(const uint64_t* ptrs, const int64_t* sizes, const int32_t* chunk_tensor, const int32_t* chunk_index, int nchunks,
+                            int chunk_elems, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                            const double* ostate, const float* clip_state, void* stream) {
+    DIN_REQUIRE(ptrs && sizes && chunk_tensor && chunk_index && ostate && nchunks >= 0 && chunk_elems > 0, "adam_step_multi_dev: bad argument");
+    DIN_REQUIRE((reinterpret_cast<uintptr_t>(ostate) & 7) == 0, "adam_step_multi_dev: ostate must be 8-byte aligned");
+    DIN_REQUIRE((reinterpret_cast<uintptr_t>(clip_state) & 3) == 0, "adam_step_multi_dev: clip_state must be 4-byte aligned");
+    DIN_REQUIRE(std::isfinite(grad_scale), "adam_step_multi_dev: grad_scale must be finite");
+    if (nchunks == 0) return DIN_OK;
+    hipLaunchKernelGGL(adam_multi_dev_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), ptrs, sizes, chunk_tensor, chunk_index,
+                       chunk_elems, beta1, beta2, eps, weight_decay, grad_scale, ostate, clip_state);
+    DIN_CHECK_LAUNCH("adam_step_multi_dev");
     return DIN_OK;
 }
 

@@ -33,6 +33,17 @@ def grad_norm_refusal(value):
     return None
 
 
+class _DevState:
+    """the device record of one step-count group of FusedAdam(capturable=True): float64 [4] = {steps taken, lr, beta1^steps, beta2^steps}
+    (include/din_hip.h: din_adam_state_advance).  Initialised from the host, the powers in double from the fp32 betas the launches
+    receive; `lr` is the host's copy of field 1 (FusedAdam.sync_lr)."""
+
+    def __init__(self, device, step, lr, betas):
+        b1, b2 = (float(np.float32(b)) for b in betas)
+        self.lr = float(lr)
+        self.dev = torch.tensor([float(step), self.lr, b1 ** step, b2 ** step], dtype=torch.float64).to(device)
+
+
 class FusedAdam:
     """max_grad_norm (None = off: nothing below changes): torch.nn.utils.clip_grad_norm_(params, max_grad_norm) folded into the step.  The
     squared norm of every live gradient is reduced in fp64 by one multi-tensor launch over the tables the Adam launch already keeps
@@ -40,13 +51,31 @@ class FusedAdam:
     (din_grad_norm_finish), and the Adam launch multiplies the gradient by grad_scale * coef instead of grad_scale
     (din_adam_step_multi_clip): no write pass over the gradients, no host read.  A step whose norm is not finite is SKIPPED: weights and
     moments keep their bits; the per-parameter step count behind the bias correction still advances (it is host state, and reading the
-    flag back would be the synchronisation this design avoids).  grad_stats() reads the running statistics, one device read."""
+    flag back would be the synchronisation this design avoids).  grad_stats() reads the running statistics, one device read.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+    capturable (False = off: nothing above changes): the step count, the learning rate and both beta powers live in a small device record
+    per step-count group (_DevState) instead of on the host.  step() launches din_adam_state_advance + din_adam_step_multi_dev per group
+    (behind the two norm launches when max_grad_norm is set), reads nothing back and bakes no per-step host value into a launch: the two
+    launches replay from a HIP graph as consecutive steps.  param_groups[0]['lr'] stays the interface: a changed value reaches the record
+    by a small eager copy (sync_lr) before the next step.  A SKIPPED step does not count in this mode: the record keeps its bits and the
+    next step's bias correction is that of the un-advanced count.  state_dict() reads 'step' from the device (one read).  Every parameter
+    must be a contiguous fp32 device tensor (ValueError naming the parameter otherwise).  step() itself refuses to run inside a stream
+    capture: its address-table upload reads a slot of the rotating pinned RING, which a graph would go on reading after the slot moved
+    on (capturing the whole training step is not part of this class yet)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, capturable=False):
         why_not = grad_norm_refusal(max_grad_norm)
         if why_not:
             raise ValueError(why_not)
         self.params = [p for p in params]
+        self.capturable = bool(capturable)
+        if self.capturable:
+            for i, p in enumerate(self.params):
+                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                    raise ValueError(f"FusedAdam(capturable=True): parameter {i} (shape {tuple(p.shape)}, {p.dtype}, {p.device}, "
+                                     f"{'contiguous' if p.is_contiguous() else 'not contiguous'}) is not a contiguous fp32 device tensor; "
+                                     f"the non-fused path reads the host-side step count and cannot be captured")
+        self._records = {}      # capturable: param -> _DevState of its step-count group (shared by the group's parameters)
         self.param_groups = [dict(params=self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
         self.state = {}         # param -> (exp_avg, exp_avg_sq)
         self.steps = {}         # param -> number of updates it received (bias correction is per parameter, as in torch)
@@ -58,6 +87,8 @@ class FusedAdam:
 
     @property
     def step_count(self) -> int:
+        if self.capturable:                                      # (one device read)
+            return max(self._device_steps().values(), default=0)
         return max(self.steps.values(), default=0)
 
     def zero_grad(self, set_to_none: bool = True):
@@ -72,6 +103,9 @@ class FusedAdam:
         g = self.param_groups[0]
         live = [p for p in self.params if p.grad is not None]
         if not live:
+            return
+        if self.capturable:
+            self._step_capturable(live, g, grad_scale)
             return
         for p in live:
             if p not in self.state:
@@ -120,27 +154,83 @@ class FusedAdam:
 
     def _step_clipped(self, groups, g, grad_scale):
         """squared norm of every group -> one global norm and coefficient on the device -> the clipped Adam launch of every group"""
-        lib, dev = L.load(), next(iter(groups.values()))[0].device
+        lib = L.load()
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         tables = [(step, self._table(plist)) for step, plist in groups.items()]
-        total = sum(tb[6] for _, tb in tables)
+        self._measure_norm([tb for _, tb in tables], grad_scale, stream)
+        for step, tb in tables:
+            L.check(lib.din_adam_step_multi_clip(C.c_void_p(tb[2].data_ptr()), C.c_void_p(tb[3].data_ptr()), C.c_void_p(tb[4].data_ptr()),
+                                                 C.c_void_p(tb[5].data_ptr()), tb[6], CHUNK, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                                                 g["weight_decay"], step, grad_scale, C.c_void_p(self._gstate.data_ptr()), stream),
+                    "adam_step_multi_clip")
+
+    def _measure_norm(self, tables, grad_scale, stream):
+        """din_grad_sqnorm_multi over every table, then ONE din_grad_norm_finish: self._gstate holds the step's norm and coefficient"""
+        lib, dev = L.load(), tables[0][2].device
+        total = sum(tb[6] for tb in tables)
         if self._gstate is None:
             self._gstate = torch.zeros(8, dtype=torch.float32, device=dev)
         if self._partials is None or self._partials.numel() != total:              # (only when the live set changes)
             self._partials = torch.empty(max(total, 1), dtype=torch.float64, device=dev)[:total]
         first = 0
-        for _, tb in tables:
+        for tb in tables:
             L.check(lib.din_grad_sqnorm_multi(C.c_void_p(tb[2].data_ptr()), C.c_void_p(tb[3].data_ptr()), C.c_void_p(tb[4].data_ptr()),
                                               C.c_void_p(tb[5].data_ptr()), tb[6], CHUNK,
                                               C.c_void_p(self._partials.data_ptr() + 8 * first), stream), "grad_sqnorm_multi")
             first += tb[6]
         L.check(lib.din_grad_norm_finish(C.c_void_p(self._partials.data_ptr()), total, grad_scale, self.max_grad_norm,
                                          C.c_void_p(self._gstate.data_ptr()), stream), "grad_norm_finish")
-        for step, tb in tables:
-            L.check(lib.din_adam_step_multi_clip(C.c_void_p(tb[2].data_ptr()), C.c_void_p(tb[3].data_ptr()), C.c_void_p(tb[4].data_ptr()),
-                                                 C.c_void_p(tb[5].data_ptr()), tb[6], CHUNK, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                                                 g["weight_decay"], step, grad_scale, C.c_void_p(self._gstate.data_ptr()), stream),
-                    "adam_step_multi_clip")
+
+    # ---- capturable=True: step count, learning rate and beta powers on the device ------------------------------------------------------
+    def _step_capturable(self, live, g, grad_scale):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdam.step() inside a stream capture: the gradient address table is uploaded from a rotating pinned "
+                               "buffer a graph must not keep reading; capture din_adam_state_advance / din_adam_step_multi_dev over "
+                               "tables of your own instead")
+        fresh = [p for p in live if p not in self._records]
+        if fresh:
+            rec = _DevState(fresh[0].device, 0, g["lr"], g["betas"])       # (parameters that start together share one record)
+            for p in fresh:
+                self._records[p] = rec
+                if p not in self.state:
+                    self.state[p] = (torch.zeros_like(p, dtype=torch.float32), torch.zeros_like(p, dtype=torch.float32))
+        self.sync_lr()
+        groups = {}
+        for p in live:
+            groups.setdefault(id(self._records[p]), []).append(p)
+        self._keep = []
+        lib = L.load()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        tables = [(self._records[plist[0]], self._table(plist)) for plist in groups.values()]
+        clip = None
+        if self.max_grad_norm is not None:
+            self._measure_norm([tb for _, tb in tables], grad_scale, stream)
+            clip = C.c_void_p(self._gstate.data_ptr())
+        b1, b2 = g["betas"]
+        for rec, tb in tables:
+            ostate = C.c_void_p(rec.dev.data_ptr())
+            L.check(lib.din_adam_state_advance(ostate, clip, b1, b2, stream), "adam_state_advance")
+            L.check(lib.din_adam_step_multi_dev(C.c_void_p(tb[2].data_ptr()), C.c_void_p(tb[3].data_ptr()), C.c_void_p(tb[4].data_ptr()),
+                                                C.c_void_p(tb[5].data_ptr()), tb[6], CHUNK, b1, b2, g["eps"], g["weight_decay"], grad_scale,
+                                                ostate, clip, stream), "adam_step_multi_dev")
+
+    def sync_lr(self):
+        """param_groups[0]['lr'] -> every device record whose copy differs: one small eager copy per record (none when nothing changed);
+        step() calls it before its launches"""
+        lr = float(self.param_groups[0]["lr"])
+        for rec in {id(r): r for r in self._records.values()}.values():
+            if rec.lr != lr:
+                rec.dev[1:2].copy_(torch.tensor([lr], dtype=torch.float64))
+                rec.lr = lr
+
+    def _device_steps(self):
+        """param -> steps taken, read from the device records: ONE device -> host read"""
+        recs = list({id(r): r for r in self._records.values()}.values())
+        if not recs:
+            return {}
+        host = torch.stack([r.dev for r in recs]).cpu()
+        step_of = {id(r): int(round(float(host[i, 0]))) for i, r in enumerate(recs)}
+        return {p: step_of[id(r)] for p, r in self._records.items()}
 
     def grad_stats(self, reset: bool = True):
         """{"steps", "skipped", "clipped", "norm_mean", "norm_max"} of the steps since the last reset: ONE device -> host read (a
@@ -209,10 +299,11 @@ class FusedAdam:
     # ---- checkpoint format of torch.optim.Adam (state by parameter index; 'step' as a float32 scalar tensor) ----------------------
     def state_dict(self):
         state = {}
+        steps = self._device_steps() if self.capturable else self.steps
         for i, p in enumerate(self.params):
             if p in self.state:
                 m, v = self.state[p]
-                state[i] = {"step": torch.tensor(float(self.steps.get(p, 0))), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
+                state[i] = {"step": torch.tensor(float(steps.get(p, 0))), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
         g = self.param_groups[0]
         group = dict(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"], amsgrad=False, maximize=False,
                      foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False,
@@ -230,7 +321,7 @@ class FusedAdam:
             if k in groups[0]:
                 g[k] = tuple(groups[0][k]) if k == "betas" else groups[0][k]
         index_of = {pid: i for i, pid in enumerate(groups[0]["params"])}
-        self.state, self.steps, self._tables = {}, {}, {}
+        self.state, self.steps, self._tables, self._records = {}, {}, {}, {}
         for pid, st in sd["state"].items():
             p = self.params[index_of[int(pid)]]
             if tuple(st["exp_avg"].shape) != tuple(p.shape):
@@ -238,3 +329,10 @@ class FusedAdam:
             self.state[p] = (st["exp_avg"].to(device=p.device, dtype=torch.float32).clone().contiguous(),
                              st["exp_avg_sq"].to(device=p.device, dtype=torch.float32).clone().contiguous())
             self.steps[p] = int(round(float(st["step"])))
+        if self.capturable:                                      # one record per distinct step count, the powers computed in double
+            by_step = {}
+            for p, step in self.steps.items():
+                if step not in by_step:
+                    by_step[step] = _DevState(p.device, step, g["lr"], g["betas"])
+                self._records[p] = by_step[step]
+            self.steps = {}

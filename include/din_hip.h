@@ -735,6 +735,30 @@ int din_adam_step_multi_clip(const uint64_t* ptrs, const int64_t* sizes, const i
                              int step, float grad_scale, const float* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Adam with device-resident state (din_amd/optim.py: FusedAdam(capturable=True)).  din_adam_step_multi and din_adam_step_multi_clip
+ * take the learning rate and the step count as host arguments and form the bias corrections on the host: a launch captured in a HIP
+ * graph would replay step 1's forever.  Here both live in a small device record, so the optimizer of the reference's step
+ * (train_net_dynamic.py:104,224: torch.optim.Adam, optimizer.step()) can be part of a captured training step.  Additive: ABI 9 stays.
+ *   ostate: double[4], 8-byte aligned = { [0] steps taken, [1] learning rate, [2] beta1^steps, [3] beta2^steps }.  The caller
+ *   initialises it ({0, lr, 1, 1} for a fresh optimizer; a resumed one uploads the powers computed in double) and may overwrite [1]
+ *   between launches (an ordinary copy on the same stream).
+ * din_adam_state_advance: replaces the host's `step += 1` (torch.optim.Adam's state['step']).  One workgroup, one thread: [0] += 1,
+ *   [2] *= beta1, [3] *= beta2, in fp64.  With a clip_state (din_grad_norm_finish's float[8]) whose norm [0] is not finite nothing is
+ *   written: a skipped step does not count, and the next step's bias correction is that of the un-advanced count.
+ * din_adam_step_multi_dev: din_adam_step_multi with lr = (float)ostate[1], and the bias corrections (float)(1 - ostate[2]) and
+ *   (float)sqrt(1 - ostate[3]) formed in fp64 and rounded once.  clip_state == NULL: the gradient is multiplied by grad_scale.
+ *   Otherwise as din_adam_step_multi_clip: ONE factor grad_scale * clip_state[1], and no store at all when clip_state[0] is not
+ *   finite.  The update loop is the one the two other launches run.  Launch it AFTER din_adam_state_advance (steps taken >= 1).
+ * Both: plain vector stores, no atomics, no allocation, no synchronisation, capturable.  DIN_E_ARG, with nothing read or written: a
+ *   null table or ostate; ostate not 8-byte aligned; clip_state not 4-byte aligned; a negative count; chunk_elems <= 0; a beta of the
+ *   advance outside [0, 1); grad_scale not finite.
+ * ---------------------------------------------------------------------------------------------- */
+int din_adam_state_advance(double* ostate, const float* clip_state, float beta1, float beta2, void* stream);
+int din_adam_step_multi_dev(const uint64_t* ptrs, const int64_t* sizes, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                            int nchunks, int chunk_elems, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                            const double* ostate, const float* clip_state, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Frame cache: n byte-row copies in one launch (din_amd/frame_cache.py).  Replaces, from the second epoch on, what the reference does
  * for every frame of every epoch: decode + resize + stack on the host (volleyball.py:223-275) and a blocking upload of the batch
  * (train_net_dynamic.py:174) -- decoded uint8 frames stay in HBM slots and a batch is gathered from them.
