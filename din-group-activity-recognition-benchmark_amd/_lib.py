@@ -183,6 +183,8 @@ SIGNATURES: Dict[str, tuple] = {
     "din_adam_state_advance": (_I, [_P, _P, _F, _F, _P]),
     "din_adam_step_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P]),
     "din_copy_rows_u8":(_I, [_P, _P, _I, _L, _P]),
+    "din_copy_rows_u8_flip": (_I, [_P, _P, _P, _I, _L, _L, _P]),
+    "din_flip_clip_labels": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P]),
     "din_feat_rows": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
     "din_feat_rows_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
 }

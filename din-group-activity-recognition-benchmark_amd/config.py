@@ -15,6 +15,9 @@ max_grad_norm (both trainers; None = off): the global L2 norm of the gradient is
 torch.nn.utils.clip_grad_norm_ semantics, what the reference tried and left commented out at train_net_dynamic.py:222-223 -- and a step
 whose norm is not finite is skipped (din_amd/optim.py); float('inf') measures and guards without ever clipping; anything else is a
 positive finite number.
+flip_prob (both trainers, training passes only; 0.0 = off): every clip of a training batch is mirrored left-right with this probability --
+all its frames inside the batch's gather launch, its boxes, and for volleyball the team side of its activity label
+(din_amd/frame_cache.py: FlipPlan); refused together with feature_cache_gb > 0.
 All are opt-in: at 0 / False / None the trainers behave exactly as without them."""
 from __future__ import annotations
 
@@ -39,6 +42,7 @@ _DEFAULTS = dict(
     frame_cache_gb=0, num_workers=0, feature_cache_gb=0, feature_cache_dtype="fp32",
     deterministic=False,
     max_grad_norm=None,
+    flip_prob=0.0,
 )
 
 

@@ -217,7 +217,9 @@ class FeatureLoader(CachedLoader):
     """a DataLoader of a `frame_ids=True` dataset together with the feature cache of that dataset: what the stage-2 trainer's passes
     receive in place of the loader when cfg.feature_cache_gb > 0"""
 
-    def feed(self, device) -> FeatureFeed:
+    def feed(self, device, flip=None) -> FeatureFeed:
+        if flip is not None:                         # (train_net refuses the combination first: frame_cache.flip_refusal)
+            raise ValueError("flip augmentation cannot be fed from the feature cache: its rows belong to the unmirrored frames")
         return FeatureFeed(self.loader, device, self.cache, self.dataset)
 
 

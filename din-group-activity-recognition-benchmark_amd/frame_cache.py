@@ -17,6 +17,9 @@ No eviction: an epoch touches every frame once in random order, so least-recentl
 full cache stops inserting and the remaining frames keep coming from the loader.  Each rank owns its caches; DistributedSampler
 reshuffles clips across ranks every epoch, so a rank's hit rate grows over several epochs instead of reaching 100 % in the second
 (rank-stable sharding would change the sampling and is not done here).
+
+Flip augmentation (cfg.flip_prob, training passes only) lives here too, because a clip is mirrored where its batch is built: the gather
+becomes din_copy_rows_u8_flip for a batch with a drawn clip (FlipPlan, CachedFeed; FlippedFeed for loaders without a cache).
 """
 from __future__ import annotations
 
@@ -101,41 +104,16 @@ class SlotTable:
         return {"hits": self.hits, "misses": self.misses, "inserted": self.inserted, "bytes": self.bytes}
 
 
-class SlotStore:
-    """Device side of a SlotTable: the lazily allocated slabs, slot addresses and the rotating pinned buffers the address tables of a
-    launch travel in.  FrameCache (uint8 frames) and feature_cache.FeatureCache (fp32 box features) are the two stores."""
+class TableUpload:
+    """the rotating pinned buffers the int64 tables of a launch (addresses, flip flags) travel in"""
 
     TABLE_SLOTS = 4                                  # pinned address-table buffers in rotation (one batch uses one)
-    WHAT, UNIT = "frame cache", "frames"             # the words of the freeze log line
 
-    def __init__(self, device, slot_bytes: int, capacity_bytes: int, chunk_frames: int = 64):
+    def __init__(self, device):
         self.device = torch.device(device)
-        self.table = SlotTable(slot_bytes, capacity_bytes, chunk_frames)
-        self.slabs: List[torch.Tensor] = []
         self._pinned: List[Optional[torch.Tensor]] = [None] * self.TABLE_SLOTS
         self._sent: List[Optional[torch.cuda.Event]] = [None] * self.TABLE_SLOTS
         self._turn = 0
-
-    hits = property(lambda self: self.table.hits)
-    misses = property(lambda self: self.table.misses)
-    inserted = property(lambda self: self.table.inserted)
-    bytes = property(lambda self: self.table.bytes)
-
-    def _grow(self, n_slots: int) -> bool:
-        try:
-            self.slabs.append(torch.empty(n_slots * self.table.stride, dtype=torch.uint8, device=self.device))
-            return True
-        except RuntimeError as e:                    # (torch.cuda.OutOfMemoryError is one)
-            log.warning("%s frozen at %d %s (%.2f GB): a slab of %d %s could not be allocated: %s", self.WHAT,
-                        self.table.allocated, self.UNIT, self.table.bytes / 1e9, n_slots, self.UNIT, str(e).splitlines()[0])
-            return False
-
-    def slot_address(self, slot: int) -> int:
-        slab, off = self.table.locate(slot)
-        return self.slabs[slab].data_ptr() + off
-
-    def resident(self, fid: int) -> bool:
-        return int(fid) in self.table.slot_of
 
     def _upload(self, *tables: Sequence[int]) -> List[torch.Tensor]:
         """int64 address tables -> device, in ONE asynchronous copy on the current stream out of a pinned buffer that is reused only after
@@ -159,6 +137,39 @@ class SlotStore:
         return [dev[a:a + n] for a, n in views]
 
 
+class SlotStore(TableUpload):
+    """Device side of a SlotTable: the lazily allocated slabs, slot addresses and the rotating pinned buffers the address tables of a
+    launch travel in.  FrameCache (uint8 frames) and feature_cache.FeatureCache (fp32 box features) are the two stores."""
+
+    WHAT, UNIT = "frame cache", "frames"             # the words of the freeze log line
+
+    def __init__(self, device, slot_bytes: int, capacity_bytes: int, chunk_frames: int = 64):
+        super().__init__(device)
+        self.table = SlotTable(slot_bytes, capacity_bytes, chunk_frames)
+        self.slabs: List[torch.Tensor] = []
+
+    hits = property(lambda self: self.table.hits)
+    misses = property(lambda self: self.table.misses)
+    inserted = property(lambda self: self.table.inserted)
+    bytes = property(lambda self: self.table.bytes)
+
+    def _grow(self, n_slots: int) -> bool:
+        try:
+            self.slabs.append(torch.empty(n_slots * self.table.stride, dtype=torch.uint8, device=self.device))
+            return True
+        except RuntimeError as e:                    # (torch.cuda.OutOfMemoryError is one)
+            log.warning("%s frozen at %d %s (%.2f GB): a slab of %d %s could not be allocated: %s", self.WHAT,
+                        self.table.allocated, self.UNIT, self.table.bytes / 1e9, n_slots, self.UNIT, str(e).splitlines()[0])
+            return False
+
+    def slot_address(self, slot: int) -> int:
+        slab, off = self.table.locate(slot)
+        return self.slabs[slab].data_ptr() + off
+
+    def resident(self, fid: int) -> bool:
+        return int(fid) in self.table.slot_of
+
+
 class FrameCache(SlotStore):
     """Device-resident uint8 frame store with fixed-size slots, filled on first use, never beyond `capacity_bytes`, no eviction."""
 
@@ -166,15 +177,24 @@ class FrameCache(SlotStore):
         self.frame_shape = tuple(int(v) for v in frame_shape)
         self.frame_bytes = int(np.prod(self.frame_shape))
         super().__init__(device, self.frame_bytes, capacity_bytes, chunk_frames)
+        self.flip_flags: Optional[torch.Tensor] = None      # the device flags (int64 [R]) of the last build_batch, None when it mirrored nothing
 
-    def build_batch(self, frame_ids, miss_pos=(), miss_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[int]]:
+    def build_batch(self, frame_ids, miss_pos=(), miss_rows: Optional[torch.Tensor] = None,
+                    flip_rows=None) -> Tuple[torch.Tensor, List[int]]:
         """frame_ids [R] (host), miss_pos [M] (host: which of the R rows the uploaded frames are), miss_rows uint8 [M, *frame_shape] on
         the device -> (uint8 [R, *frame_shape] on the device, the frame ids inserted by this call).  On the current stream: one launch
         that copies the new frames into free slots, then one launch that gathers all R rows (slot, or uploaded row where the cache has
-        no room)."""
+        no room).  flip_rows [R] (host, bool; flip augmentation): the rows the gather mirrors left-right on their way out -- the slots
+        always hold the frame as decoded.  Where any is set the gather is din_copy_rows_u8_flip, its flags travel with the address
+        tables and stay in `self.flip_flags` for the labels' launch; otherwise the two launches are the ones described above."""
         from . import ops
         ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
         pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
+        flags = None if flip_rows is None else np.asarray(flip_rows).reshape(-1) != 0
+        if flags is not None and len(flags) != len(ids):
+            raise ValueError(f"build_batch: {len(flags)} flip flags for {len(ids)} rows")
+        if flags is not None and not flags.any():
+            flags = None
         if len(pos):
             if miss_rows is None or not miss_rows.is_cuda or miss_rows.dtype != torch.uint8 or not miss_rows.is_contiguous() \
                     or tuple(miss_rows.shape) != (len(pos),) + self.frame_shape:
@@ -205,9 +225,16 @@ class FrameCache(SlotStore):
             else:
                 raise KeyError(f"frame {fid} is neither resident nor among the uploaded frames of this batch")
         dst = [out_ptr + i * fb for i in range(len(ids))]
-        d_ins_src, d_ins_dst, d_src, d_dst = self._upload(ins_src, ins_dst, src, dst)
-        ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)                 # (no launch when nothing is new)
-        ops.copy_rows_u8(d_src, d_dst, fb)
+        self.flip_flags = None
+        if flags is None:
+            d_ins_src, d_ins_dst, d_src, d_dst = self._upload(ins_src, ins_dst, src, dst)
+            ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)             # (no launch when nothing is new)
+            ops.copy_rows_u8(d_src, d_dst, fb)
+            return out, new_ids
+        d_ins_src, d_ins_dst, d_src, d_dst, self.flip_flags = self._upload(ins_src, ins_dst, src, dst, flags.astype(np.int64))
+        ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)                 # (the insert stays plain: a slot is never mirrored)
+        width = self.frame_shape[-1]
+        ops.copy_rows_u8_flip(d_src, d_dst, self.flip_flags, fb // width, width)
         return out, new_ids
 
     def insert(self, frame_ids, rows: torch.Tensor) -> List[int]:
@@ -265,8 +292,8 @@ class CachedFeed:
     device.  Only the frames the workers decoded are uploaded (DeviceFeed overlaps that with the previous step); the batch is built on
     the compute stream by `cache.build_batch`, and `dataset.resident` is marked for what went in."""
 
-    def __init__(self, loader: Iterable, device, cache: FrameCache, dataset):
-        self.loader, self.device, self.cache, self.dataset = loader, torch.device(device), cache, dataset
+    def __init__(self, loader: Iterable, device, cache: FrameCache, dataset, flip: Optional["EpochFlips"] = None):
+        self.loader, self.device, self.cache, self.dataset, self.flip = loader, torch.device(device), cache, dataset, flip
         self._kept: collections.deque = collections.deque()
         self._feed = DeviceFeed(_HostSide(loader, self._kept), self.device)
 
@@ -274,9 +301,13 @@ class CachedFeed:
         self._kept.clear()
         for miss_rows, *labels in self._feed:
             shape, ids, pos = self._kept.popleft()
-            images, new_ids = self.cache.build_batch(ids, pos, miss_rows)
+            # flip augmentation: one draw per clip, repeated over its T rows; a batch without a flagged clip is built exactly as without it
+            rows = None if self.flip is None else self.flip.rows(shape[0], shape[1])
+            images, new_ids = self.cache.build_batch(ids, pos, miss_rows, flip_rows=rows)
             if new_ids:
                 self.dataset.resident[torch.as_tensor(new_ids, dtype=torch.int64)] = 1
+            if rows is not None:
+                self.flip.mirror_labels(labels, self.cache.flip_flags)
             yield (images.view(shape + self.cache.frame_shape), *labels)
 
     def __len__(self):
@@ -290,8 +321,8 @@ class CachedLoader:
     def __init__(self, loader, cache: FrameCache, dataset):
         self.loader, self.cache, self.dataset = loader, cache, dataset
 
-    def feed(self, device) -> CachedFeed:
-        return CachedFeed(self.loader, device, self.cache, self.dataset)
+    def feed(self, device, flip: Optional["EpochFlips"] = None) -> CachedFeed:
+        return CachedFeed(self.loader, device, self.cache, self.dataset, flip)
 
     def __iter__(self):
         return iter(self.loader)
@@ -300,9 +331,123 @@ class CachedLoader:
         return len(self.loader)
 
 
-def feed_for(loader, device):
-    """the device feed of a pass: CachedFeed for a CachedLoader, input_feed.DeviceFeed for anything else"""
-    return loader.feed(device) if isinstance(loader, CachedLoader) else DeviceFeed(loader, device)
+# ---- flip augmentation (cfg.flip_prob) ----------------------------------------------------------------------------------------------------
+# In a training pass every clip is mirrored left-right with probability cfg.flip_prob, as a whole: all T frames inside the launch that
+# builds the batch (din_copy_rows_u8_flip: the same bytes read and written as the plain gather, no host work), its boxes
+# (x -> out_size[1] - x) and, for volleyball, the team side of its activity label (din_flip_clip_labels, one launch).  Actions have no
+# side and the collective activities neither.  Evaluation passes never flip.
+class EpochFlips:
+    """the flips of one training pass of one rank: `draw` is called once per batch, in batch order"""
+
+    def __init__(self, plan: "FlipPlan", epoch: int):
+        self.prob, self.label_map, self.width = plan.prob, plan.label_map, plan.width
+        self._rng = np.random.default_rng([plan.seed, plan.rank, int(epoch)])
+        self._device_map: Optional[torch.Tensor] = None
+        self.flipped = 0                                # clips mirrored so far (a host count: the info's `flipped_clips`)
+
+    def draw(self, num_clips: int) -> np.ndarray:
+        """bool [num_clips]: which clips of the next batch are mirrored"""
+        flags = self._rng.random(int(num_clips)) < self.prob
+        self.flipped += int(flags.sum())
+        return flags
+
+    def rows(self, num_clips: int, num_frames: int) -> Optional[np.ndarray]:
+        """the next batch's draw repeated over the T rows of every clip (bool [B * T]), or None when no clip is flagged"""
+        flags = self.draw(num_clips)
+        return np.repeat(flags, int(num_frames)) if flags.any() else None
+
+    def mirror_labels(self, labels, flags: torch.Tensor) -> None:
+        """labels = [boxes [B, T, N, 4], actions, activities [B, T]] (+ [bboxes_num [B, T]], collective) on the device, flags int64 [B * T]
+        on the device: the flagged clips' boxes and activities, in place, one launch"""
+        from . import ops
+        if self.label_map is not None and self._device_map is None:
+            self._device_map = torch.tensor(self.label_map, dtype=torch.int64, device=flags.device)
+        ops.flip_clip_labels(labels[0], labels[2], flags, labels[3] if len(labels) > 3 else None, self._device_map, self.width)
+
+
+class FlipPlan:
+    """which clips a run mirrors.  The draws of epoch e come from np.random.default_rng([seed, rank, e]): a resumed run repeats the flips
+    of an epoch, ranks differ from each other, and a deterministic run stays reproducible.  label_map: the activity label of a mirrored
+    clip (volleyball.FLIP_ACTIVITIES; None: labels have no side); width: the feature map's, which the boxes are mirrored in."""
+
+    def __init__(self, prob: float, seed: int, rank: int, label_map: Optional[Sequence[int]] = None, width: float = 0.0):
+        self.prob, self.seed, self.rank = float(prob), int(seed) & (2 ** 63 - 1), int(rank)
+        self.label_map, self.width = (None if label_map is None else list(label_map)), float(width)
+
+    def epoch(self, e: int) -> EpochFlips:
+        return EpochFlips(self, e)
+
+
+def flip_refusal(cfg) -> Optional[str]:
+    """why cfg.flip_prob cannot be honoured, or None (both trainers' train_net raise ValueError with it)"""
+    p = getattr(cfg, "flip_prob", 0.0)
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:
+        return f"flip_prob = {p!r}: the probability of mirroring a clip is a real number in [0, 1]"
+    if p == 0:
+        return None
+    pre = f"flip_prob = {p}: "
+    if wants_features(cfg):
+        return pre + f"feature_cache_gb = {cfg.feature_cache_gb} caches the box features of the unmirrored frame; they cannot serve a mirrored one"
+    if cfg.dataset_name == "volleyball":
+        from .volleyball import ACTIVITIES
+        if cfg.num_activities != len(ACTIVITIES):
+            return pre + (f"a mirrored volleyball clip swaps the team side of its label among the {len(ACTIVITIES)} activities of "
+                          f"volleyball.ACTIVITIES; num_activities is {cfg.num_activities}")
+    return None
+
+
+def flip_plan(cfg, epoch: int, rank: int) -> Optional[EpochFlips]:
+    """the flips of training epoch `epoch` on rank `rank`, or None with cfg.flip_prob == 0 (nothing changes then)"""
+    p = getattr(cfg, "flip_prob", 0.0)
+    if not p:
+        return None
+    label_map = None
+    if cfg.dataset_name == "volleyball":
+        from .volleyball import FLIP_ACTIVITIES as label_map
+    return FlipPlan(p, cfg.train_random_seed, rank, label_map, cfg.out_size[1]).epoch(epoch)
+
+
+class FlippedFeed:
+    """DeviceFeed's iteration contract with flip augmentation over a plain loader (no frame cache): the batch is uploaded as it is and
+    its flagged clips are mirrored on the device, one din_copy_rows_u8_flip launch into a new tensor plus the labels' launch.  A batch
+    without a flagged clip is handed on untouched."""
+
+    def __init__(self, loader: Iterable, device, flip: EpochFlips):
+        self.loader, self.device, self.flip = loader, torch.device(device), flip
+        self._feed = DeviceFeed(loader, self.device)
+        self._tables = TableUpload(self.device)
+
+    def __iter__(self) -> Iterator:
+        from . import ops
+        for batch in self._feed:
+            images, *labels = batch
+            if images.dtype != torch.uint8 or images.dim() < 3 or not images.is_contiguous():
+                raise ValueError(f"flip_prob mirrors contiguous uint8 [B, T, ..., W] frames on the device; the loader gave {images.dtype} "
+                                 f"{tuple(images.shape)}")
+            num_clips, num_frames = images.shape[0], images.shape[1]
+            rows = self.flip.rows(num_clips, num_frames)
+            if rows is None:
+                yield batch
+                continue
+            out = torch.empty_like(images)
+            width, fb = images.shape[-1], images[0, 0].numel()
+            src = [images.data_ptr() + i * fb for i in range(len(rows))]
+            dst = [out.data_ptr() + i * fb for i in range(len(rows))]
+            d_src, d_dst, d_flags = self._tables._upload(src, dst, rows.astype(np.int64))
+            ops.copy_rows_u8_flip(d_src, d_dst, d_flags, fb // width, width)
+            self.flip.mirror_labels(labels, d_flags)
+            yield [out, *labels]
+
+    def __len__(self):
+        return len(self.loader)
+
+
+def feed_for(loader, device, flip: Optional[EpochFlips] = None):
+    """the device feed of a pass: CachedFeed for a CachedLoader, input_feed.DeviceFeed for anything else; with the flips of a training
+    pass (`flip_plan`), the CachedFeed mirrors inside its gather and a plain loader goes through FlippedFeed"""
+    if flip is None:
+        return loader.feed(device) if isinstance(loader, CachedLoader) else DeviceFeed(loader, device)
+    return loader.feed(device, flip) if isinstance(loader, CachedLoader) else FlippedFeed(loader, device, flip)
 
 
 def end_pass(feed) -> None:

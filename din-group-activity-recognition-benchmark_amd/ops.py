@@ -1001,7 +1001,54 @@ def copy_rows_u8(src: torch.Tensor, dst: torch.Tensor, nbytes: int, n: Optional[
     L.check(lib.din_copy_rows_u8(_ptr(src), _ptr(dst), n, nbytes, _stream()), "copy_rows_u8")
 
 
-FEAT_ROWS_SEGMENT = 16384        # DIN_FEAT_ROWS_SEGMENT (include/din_hip.h): bytes of one row per work item of din_feat_rows
+def copy_rows_u8_flip(src: torch.Tensor, dst: torch.Tensor, flip: Optional[torch.Tensor], lines: int, width: int,
+                      n: Optional[int] = None) -> None:
+    """copy_rows_u8 over rows of `lines` lines of `width` bytes, with the rows whose flag is set mirrored left-right: where flip[i] != 0,
+    dst[i][l * width + x] = src[i][l * width + width - 1 - x].  flip: an int64 device tensor like the tables, or None (no row is
+    mirrored).  A mirrored row must not be written over its source (din_copy_rows_u8_flip: the flip augmentation's gather)."""
+    lib = L.load()
+    require_gpu(src, dst, *(() if flip is None else (flip,)))
+    if src.dtype != torch.int64 or dst.dtype != torch.int64 or (flip is not None and flip.dtype != torch.int64):
+        raise L.DinError("copy_rows_u8_flip: address tables and flags are int64 device tensors")
+    held = [t.numel() for t in (src, dst, flip) if t is not None]
+    n = min(held) if n is None else n
+    if n > min(held):
+        raise L.DinError(f"copy_rows_u8_flip: n = {n} rows but the tables and flags hold {held} entries")
+    if flip is not None and not flip.is_contiguous():
+        raise L.DinError("copy_rows_u8_flip: flags must be contiguous")
+    L.check(lib.din_copy_rows_u8_flip(_ptr(src), _ptr(dst), _ptr(flip), n, lines, width, _stream()), "copy_rows_u8_flip")
+
+
+def flip_clip_labels(boxes: Optional[torch.Tensor], activities: Optional[torch.Tensor], flip: torch.Tensor,
+                     n_valid: Optional[torch.Tensor], label_map: Optional[torch.Tensor], width: float) -> None:
+    """the labels of mirrored clips, in place, one launch on the current stream.  flip: int64 device flags, one per frame (row) of the
+    batch.  boxes: fp32 [..., n, 4] (x1, y1, x2, y2) in feature px with `rows` frames in all: in a flagged row the first n_valid[row]
+    boxes (all n without n_valid, an int32 tensor of one count per row) become (width - x2, y1, width - x1, y2).  activities: int64, one
+    per row: a flagged row's label a becomes label_map[a] (an int64 device tensor) when 0 <= a < len(label_map); without a map the
+    labels stay.  Either half may be None (din_flip_clip_labels)."""
+    lib = L.load()
+    require_gpu(*(t for t in (boxes, activities, flip, n_valid, label_map) if t is not None))
+    rows = flip.numel()
+    if flip.dtype != torch.int64 or not flip.is_contiguous():
+        raise L.DinError("flip_clip_labels: flags are a contiguous int64 device tensor")
+    n = 0
+    if boxes is not None:
+        if boxes.dtype != torch.float32 or not boxes.is_contiguous() or boxes.dim() < 2 or boxes.shape[-1] != 4 \
+                or boxes.numel() != rows * boxes.shape[-2] * 4:
+            raise L.DinError(f"flip_clip_labels: boxes must be contiguous fp32 [..., n, 4] over {rows} rows, got {tuple(boxes.shape)}")
+        n = boxes.shape[-2]
+    if activities is not None and (activities.dtype != torch.int64 or not activities.is_contiguous() or activities.numel() != rows):
+        raise L.DinError(f"flip_clip_labels: activities must be contiguous int64 with {rows} entries")
+    if n_valid is not None and (n_valid.dtype != torch.int32 or not n_valid.is_contiguous() or n_valid.numel() != rows):
+        raise L.DinError(f"flip_clip_labels: n_valid must be contiguous int32 with {rows} entries")
+    if label_map is not None and (label_map.dtype != torch.int64 or not label_map.is_contiguous()):
+        raise L.DinError("flip_clip_labels: label_map is a contiguous int64 device tensor")
+    classes = 0 if label_map is None else label_map.numel()
+    L.check(lib.din_flip_clip_labels(_ptr(boxes), _ptr(activities), _ptr(flip), _ptr(n_valid), _ptr(label_map), rows, n, float(width),
+                                     classes, _stream()), "flip_clip_labels")
+
+
+FEAT_ROWS_SEGMENT = 16384       # DIN_FEAT_ROWS_SEGMENT (include/din_hip.h): bytes of one row per work item of din_feat_rows
 
 
 def _feat_rows_count(what: str, tables, boxes, flags, box_bytes: int, n: Optional[int]) -> int:

@@ -38,6 +38,11 @@ def init_from_env(backend: Optional[str] = None) -> tuple:
     return rank, local, world
 
 
+def current_rank() -> int:
+    """this process's rank: 0 without a process group"""
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
 def shard_range(total: int, rank: int, world: int) -> range:
     """Clips [r*B/G, (r+1)*B/G) of a global batch; remainder clips go to the lowest ranks."""
     base, rem = divmod(total, world)

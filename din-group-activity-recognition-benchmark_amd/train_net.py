@@ -34,7 +34,7 @@ from .config import Config  # noqa: F401  (the reference's launchers do `from tr
 from . import frame_cache
 from .input_feed import DeviceFeed  # noqa: F401  (re-exported: `from train_net import *` launchers)
 from .optim import FusedAdam, grad_norm_refusal
-from .train_net_dynamic import SyntheticCollective, SyntheticVolleyball, add_grad_stats, adjust_lr, grad_stats_line, set_bn_eval
+from .train_net_dynamic import SyntheticCollective, SyntheticVolleyball, add_flip_stats, add_grad_stats, adjust_lr, grad_stats_line, set_bn_eval
 from .utils import Timer, print_log
 
 
@@ -104,7 +104,8 @@ def _losses(actions_scores, activities_scores, actions_in, activities_in, batch_
 
 def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets, collective, max_batches=None):
     meters = _Meters(cfg, device)
-    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device)):
+    flip = frame_cache.flip_plan(cfg, epoch, parallel.current_rank())      # None unless cfg.flip_prob > 0
+    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device, flip)):
         if max_batches is not None and bi >= max_batches:
             break
         model.train()
@@ -121,7 +122,7 @@ def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets,
         else:
             optimizer.step()
         meters.add(actions_scores.detach(), actions_in, activities_scores.detach(), activities_in, total_loss, batch_size)
-    return add_grad_stats(meters.info(epoch), optimizer)
+    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), flip)
 
 
 def _test_pass(data_loader, model, device, epoch, cfg, collective):
@@ -167,6 +168,9 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     gradients and RoIAlign backward have no fixed-order form (the stage-2 trainer's deterministic mode covers the frozen backbone).
     cfg.max_grad_norm: see din_amd/optim.py (FusedAdam)."""
     why_not = grad_norm_refusal(getattr(cfg, "max_grad_norm", None))       # (before anything else: it needs no device and no loader)
+    if why_not:
+        raise ValueError(why_not)
+    why_not = frame_cache.flip_refusal(cfg)                            # (cfg.flip_prob: no device and no loader either)
     if why_not:
         raise ValueError(why_not)
     model = build_model(cfg)                                           # (refuses stage 2 before touching the device)

@@ -32,6 +32,16 @@ _ACTIVITY_ID = {n: i for i, n in enumerate(ACTIVITIES)}
 _ACTION_ID = {n: i for i, n in enumerate(ACTIONS)}
 
 
+def _other_side(names):
+    """index of the same activity on the other team's side: the leading 'r' / 'l' swapped ('-' and '_' after it are one separator: the
+    reference's list spells 'r_spike' but 'l-spike')"""
+    key = {(n[0], n[1:].replace("-", "_")): i for i, n in enumerate(names)}
+    return [key[({"r": "l", "l": "r"}[n[0]], n[1:].replace("-", "_"))] for n in names]
+
+
+FLIP_ACTIVITIES = _other_side(ACTIVITIES)       # label of a clip mirrored left-right (cfg.flip_prob): [4, 5, 6, 7, 0, 1, 2, 3]
+
+
 def volley_read_annotations(path: str) -> Dict[int, dict]:
     """one sequence's annotations.txt: `<fid>.jpg <activity> {x y w h <action>}*` per line -> {fid: {file_name, group_activity,
     actions [n], bboxes int [n, 4] as (y1, x1, y2, x2) in source pixels}} (volleyball.py:31-66)"""

@@ -772,6 +772,37 @@ int din_adam_step_multi_dev(const uint64_t* ptrs, const int64_t* sizes, const in
 int din_copy_rows_u8(const uint64_t* src, const uint64_t* dst, int n, int64_t bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Flip augmentation (cfg.flip_prob, din_amd/frame_cache.py): the same gather with some rows mirrored left-right on their way.
+ * Row i is `lines` lines of `width` bytes (a uint8 [3, H, W] frame: lines = 3 * H, width = W).  src, dst: as for din_copy_rows_u8;
+ * src[i] == 0 leaves row i alone.  flip: a DEVICE array of n int64 flags (int64 so that they travel in the buffer of the address
+ * tables), or null: all zero.
+ *   flip[i] == 0   row i is copied exactly as din_copy_rows_u8 copies lines * width bytes;
+ *   flip[i] != 0   dst[i][l * width + x] = src[i][l * width + width - 1 - x] for every line l and column x.
+ * Any width, any alignment; where width is a multiple of 16 and both addresses of a row are 16-byte aligned (every real frame) a mirrored
+ * row moves as 16-byte vectors whose bytes are reversed in registers, otherwise byte by byte.  Every access lies inside the two ranges
+ * of its row.  Sources may repeat; destinations must not overlap each other or any source -- a mirrored row in particular must NOT be
+ * written over its own source (the copy is not an in-place reversal).  One plain launch over (row, whole-line segment) items on
+ * `stream`: no allocation, no synchronisation.  n == 0 or lines * width == 0 returns DIN_OK without a launch; a negative n, lines or
+ * width, or a null src or dst with n > 0, returns DIN_E_ARG before any launch.  Additive: the ABI version stays 9.
+ * ---------------------------------------------------------------------------------------------- */
+int din_copy_rows_u8_flip(const uint64_t* src, const uint64_t* dst, const int64_t* flip,
+                          int n, int64_t lines, int64_t width, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The labels of the mirrored clips, in place, one launch for a batch.  rows = B * T frames; flip: the int64 flags of
+ * din_copy_rows_u8_flip, one per row.  boxes: fp32 [rows, n, 4] in feature px (x1, y1, x2, y2), or null.  For a flagged row r and box
+ * j < (n_valid ? n_valid[r] : n): (x1, y1, x2, y2) -> (width - x2, y1, width - x1, y2), each new coordinate ONE fp32 subtraction (RoIAlign
+ * samples continuous coordinates with pixel centres at +0.5, so column x of a map `width` wide mirrors to width - x).  Boxes at
+ * j >= n_valid[r] (the zero padding of the collective set) and unflagged rows are untouched.  activities: int64 [rows], or null.  For a
+ * flagged row, a = label_map[a] where label_map (DEVICE int64 [classes]) is non-null and 0 <= a < classes; otherwise a is unchanged.
+ * No allocation, no synchronisation.  rows == 0, or nothing to do (no boxes or n == 0, and no activities or no label_map), returns
+ * DIN_OK without a launch; a negative rows, n or classes, or null flags where there is work, returns DIN_E_ARG before any launch.
+ * Additive: the ABI version stays 9.
+ * ---------------------------------------------------------------------------------------------- */
+int din_flip_clip_labels(float* boxes, int64_t* activities, const int64_t* flip, const int32_t* n_valid,
+                         const int64_t* label_map, int rows, int n, float width, int classes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Box-feature cache: the one launch of a frozen-backbone step (din_amd/feature_cache.py).  The trunk of the reference
  * (infer_model.py:152-184: backbone, multi-scale fuse, RoIAlign) is, with a frozen backbone, a pure function of a frame and its boxes;
  * its fp32 output row stays in an HBM slot and this launch lets a step skip the trunk for every frame that has one.
