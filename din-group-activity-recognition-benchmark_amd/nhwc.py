@@ -333,18 +333,29 @@ class _BnTables:
         self.n, self.total = len(off_list) - 1, off_list[-1]
 
 
-def _bn_tables(g: "Graph", params: Sequence[torch.Tensor], dev) -> Optional[_BnTables]:
-    rows, off_list, pos = [], [0], 0
-    for op in g.ops:
+def param_layout(g: "Graph") -> Tuple[List[int], Dict[int, int]]:
+    """Where the parameters of each op sit in `params` (the order of Graph.param_names): (op index -> index of its weight, -1 for an op
+    that is no conv; conv + BatchNorm op index -> its slot in the graph's BatchNorm tables).  Behind a weight come gamma, beta, running
+    mean and running variance (conv + BatchNorm) or the bias, if the conv has one."""
+    offsets, bn_index, pos = [], {}, 0
+    for oi, op in enumerate(g.ops):
         if op.kind != "conv":
+            offsets.append(-1)
             continue
+        offsets.append(pos)
         if op.bn:
-            gamma, beta, mean, var = params[pos + 1:pos + 5]
-            rows.append([gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), var.data_ptr()])
-            off_list.append(off_list[-1] + gamma.numel())
-            pos += 5
-        else:
-            pos += 2 if op.bias else 1
+            bn_index[oi] = len(bn_index)
+        pos += 5 if op.bn else (2 if op.bias else 1)
+    return offsets, bn_index
+
+
+def _bn_tables(g: "Graph", params: Sequence[torch.Tensor], dev) -> Optional[_BnTables]:
+    offsets, bn_index = param_layout(g)
+    rows, off_list = [], [0]
+    for oi in bn_index:
+        gamma, beta, mean, var = params[offsets[oi] + 1:offsets[oi] + 5]
+        rows.append([gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), var.data_ptr()])
+        off_list.append(off_list[-1] + gamma.numel())
     if not rows:
         return None
     key = tuple(r[0] for r in rows)
@@ -377,7 +388,7 @@ def _pack_cache(g: Graph, params: Sequence[torch.Tensor], dt: int, dev, with_tra
     pc.bn_shift = torch.empty(bn.total, dtype=torch.float32, device=dev) if bn is not None else None
     pc.wpk, pc.wpt = {}, {}
     descs, layer_of, chunk_index = [], [], []
-    pos, bn_i = 0, 0
+    offsets, bn_index = param_layout(g)
     src_of: Dict[int, tuple] = {}
     pc.wfused = {}
     for oi, op in enumerate(g.ops):
@@ -385,15 +396,8 @@ def _pack_cache(g: Graph, params: Sequence[torch.Tensor], dt: int, dev, with_tra
             continue
         cin = g.cin_image if op.src.tid == g.input_tid else op.src.c
         d = _conv_desc(g, op, 1, dt, cin)
-        w = params[pos]
-        scale_ptr = None
-        if op.bn:
-            o0 = bn.off_list[bn_i]
-            scale_ptr = C.c_void_p(pc.bn_scale.data_ptr() + 4 * o0)
-            bn_i += 1
-            pos += 5
-        else:
-            pos += 2 if op.bias else 1
+        w = params[offsets[oi]]
+        scale_ptr = C.c_void_p(pc.bn_scale.data_ptr() + 4 * bn.off_list[bn_index[oi]]) if op.bn else None
         src_of[oi] = (w, scale_ptr)
         for transposed in ((0, 1) if (with_transposed and op.src.tid != g.input_tid) else (0,)):
             n_el = lib.din_conv_packed_elems(C.byref(d), transposed)
@@ -466,156 +470,251 @@ RF_FAMILIES = (RfFamily((3, 3), "din_conv_rf_eligible", "din_conv_rf_fwd", "din_
                RfFamily((5, 5), "din_conv_rf5_eligible", "din_conv_rf5_fwd", "din_conv_rf5_dgrad", "din_conv_rf5_kernel_names", "rf5_dgrad"))
 
 
-def _conv_fwd_launch(lib, d, src, wpk, bias, dst, flags: int, st, dev, name: str) -> None:
-    """one forward conv launch: on a filter-stationary halo kernel where the library says so (the families of RF_FAMILIES are asked in turn,
-    once per op; their kernel sizes exclude each other), through din_conv_fwd otherwise; d.rf = (reporter, flags, ldm, moff) tells the
-    launch timer which reporter names the kernel"""
-    ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(d), 0), dev)
-    fam = next((f for f in RF_FAMILIES if getattr(lib, f.eligible)(C.byref(d), 0, flags, 0, 0)), None)
-    d.rf = (fam.names, flags, 0, 0) if fam else None
-    fn = getattr(lib, fam.fwd if fam else "din_conv_fwd")
-    with _timed("fwd", d, name):
-        L.check(fn(C.byref(d), _ptr(src), _ptr(wpk), _ptr(bias), _ptr(dst), flags, _ptr(ws), wsb, st), "conv_fwd " + name)
+# ------------------------------------------------------------------------------------------------
+# the two passes, each in three parts: a plan decides (plan_forward / plan_backward: no tensor, no stream, no launch; the only readers
+# of the switches and options, and where the library is asked which route or kernel family a launch takes), a pass object does
+# (_ForwardPass / _BackwardPass: the buffers, the caches and one method per step), and graph_forward / graph_backward is the loop over the ops.
+# profiles/forward_launch_trace.txt and profiles/backward_launch_trace.txt (tools/backward_trace.py, tests/test_forward_trace_cpu.py,
+# tests/test_backward_trace_cpu.py) pin every launch, allocation order and hook of both.
+# ------------------------------------------------------------------------------------------------
+class FwdGroup(NamedTuple):
+    """a sibling group that runs as ONE two-destination launch over the members' concatenated filter bank (din_conv_fwd2)"""
+    members: Tuple[int, ...]    # op indices, the lead first: it writes its own view, the others the adjacent views of one tensor
+    ctot: int                   # output channels of all members ...
+    craw: int                   # ... and of those in front of the commuted-pool members, which leave their raw conv output in `mid` (0: no such member)
+    v2: View                    # where the second destination starts (group_view of the second member)
+    name: str                   # the members' names, as the launch timer sees the launch
+
+
+@dataclass
+class FwdStep:
+    """One op's turn in the forward pass.  route is the _ForwardPass method that runs it:
+      bn_train  conv -> raw output (-> commuted pool) -> batch statistics -> normalise + ReLU into dst
+      member    a sibling launch already produced this conv's output; pd: its commuted pool + shift + ReLU is still to run
+      lead      the first conv of a sibling group: one din_conv_fwd2 launch for all of `group`
+      pooled    conv1x1 into a temporary, then the commuted average pool with the conv's shift + ReLU as its epilogue
+      conv      one conv launch with its epilogue
+      maxpool (amax: and its winning-tap map is kept for backward) | avgpool | bilinear
+    Only `conv` and `pooled` can run a filter-stationary halo kernel (rf): bn_train and lead have no such entry point and are not asked."""
+    route: str
+    d: Optional[L.ConvDesc] = None          # conv routes: the descriptor of the conv launch, ready (lead: cout = group.ctot; bn_train: raw output)
+    pd: Optional[L.PoolDesc] = None         # the pool's descriptor / the commuted pool's
+    flags: int = 0                          # CONV_BIAS | CONV_RELU of the epilogue, on whichever launch writes dst (pooled: the pool's; the conv gets 0)
+    rf: Optional[RfFamily] = None           # the family of RF_FAMILIES whose forward entry point runs the conv; None: din_conv_fwd
+    ws_bytes: int = 0                       # split-K workspace of the conv launch
+    w: int = -1                             # conv: index of its weight in params (param_layout)
+    bn: int = -1                            # conv + BatchNorm: its slot in the graph's BatchNorm tables
+    group: Optional[FwdGroup] = None
+    amax: bool = False
+
+
+@dataclass
+class ForwardPlan:
+    """What one forward pass of a graph will launch: a function of the graph, the frame count, the dtype, the BatchNorm mode, whether the
+    frames are uint8, whether a reverse pass follows, the FUSE_FWD_SIBLINGS switch and the library's planning queries (plan_forward)."""
+    steps: List[FwdStep]                    # one per op
+    bn_train: bool                          # batch-statistics BatchNorm (and the graph has BatchNorm layers)
+    bn_off: List[int]                       # BatchNorm slot -> first channel in the flat scale / shift arrays (one more entry: their length)
+    save_for_backward: bool
+
+
+def plan_forward(g: Graph, nb: int, dt: int, bn_train: bool, u8: bool, save_for_backward: bool) -> ForwardPlan:
+    """Decide the forward pass of g on nb frames.  u8: the image layer reads raw uint8 frames [nb,3,h,w].  The only place of the pass that
+    reads FUSE_FWD_SIBLINGS and asks the library (din_conv_workspace_bytes, the `eligible` entries of RF_FAMILIES: once per conv on the
+    conv / pooled routes, in turn -- their kernel sizes exclude each other); built on every call (options change between passes)."""
+    lib = L.load()
+    offsets, bn_index = param_layout(g)
+    bn_off = [0]
+    for oi in bn_index:
+        bn_off.append(bn_off[-1] + g.ops[oi].dst.c)
+    bn_train = bool(bn_train) and bool(bn_index)
+    group_of = {grp[0]: grp for grp in g.fwd_groups} if (switch("FUSE_FWD_SIBLINGS") and not bn_train) else {}
+    fused_done = set()                                     # members whose output a group launch produces
+    steps: List[FwdStep] = []
+    for oi, op in enumerate(g.ops):
+        if op.kind == "maxpool":
+            # the winning-tap map is saved when the pooled tensor is a ReLU output: backward then never re-reads the input
+            steps.append(FwdStep("maxpool", pd=_pool_desc(g, op, nb, dt),
+                                 amax=bool(save_for_backward) and g.tensors[op.src.tid].relu_masked and op.src.tid != g.input_tid))
+            continue
+        if op.kind in ("avgpool", "bilinear"):
+            steps.append(FwdStep(op.kind, pd=_pool_desc(g, op, nb, dt)))
+            continue
+        if op.kind != "conv":
+            raise L.DinError("unknown op " + op.kind)
+        cin = g.cin_image if op.src.tid == g.input_tid else op.src.c
+        d = _conv_desc(g, op, nb, dt, cin)
+        if op.src.tid == g.input_tid and u8:
+            d.in_u8, d.ldi, d.cioff = 1, 8, 0                      # raw uint8 frames [nb,3,h,w]: the image layer normalises on load
+        w, k = offsets[oi], bn_index.get(oi, -1)
+        relu = L.CONV_RELU if op.relu else 0
+        if op.bn and bn_train:
+            # conv -> raw [nb,oh,ow,cout] (-> commuted pool: also linear, so avgpool(conv(x)) == conv(avgpool(x)) holds before the
+            # normalisation) -> batch statistics -> normalise + ReLU into dst's view
+            dR, pd = _conv_desc(g, op, nb, dt, cin), None
+            dR.in_u8, dR.ldi, dR.cioff = d.in_u8, d.ldi, d.cioff      # (uint8 frames feed the image layer in this mode too)
+            dR.ldo, dR.cooff = op.dst.c, 0
+            if op.pooled is not None:
+                dR.oh, dR.ow = g.tensors[op.src.tid].h, g.tensors[op.src.tid].w
+                _, pd = _pooled_descs(g, op, nb, dt)
+                pd.ldo, pd.cooff = op.dst.c, 0
+            steps.append(FwdStep("bn_train", dR, pd, ws_bytes=lib.din_conv_workspace_bytes(C.byref(dR), 0), w=w, bn=k))
+            continue
+        if oi in fused_done:
+            pd = None
+            if op.pooled is not None:                   # the group launch leaves the raw conv output in `mid`: pool + shift + ReLU into dst
+                _, pd = _pooled_descs(g, op, nb, dt)
+                pd.ldi, pd.cioff = g.tensors[op.mid.tid].c, op.mid.coff
+            steps.append(FwdStep("member", None, pd, L.CONV_BIAS | relu, w=w, bn=k))
+            continue
+        if oi in group_of and op.bn:
+            # sibling convs of one source: ONE launch over the concatenated filter bank.  A shape that would run split-K, or members whose
+            # BatchNorm slots are not adjacent (one shift array serves the launch), fall through to separate launches.
+            grp = group_of[oi]
+            rest = [g.ops[i] for i in grp[1:]]
+            ctot = op.dst.c + sum(o.dst.c for o in rest)
+            craw = ctot - sum(o.dst.c for o in rest if o.pooled is not None)
+            dF = _conv_desc(g, op, nb, dt, cin)
+            dF.cout = ctot
+            if lib.din_conv_workspace_bytes(C.byref(dF), 0) == 0 and bn_off[k + len(grp)] - bn_off[k] == ctot:
+                group = FwdGroup(tuple(grp), ctot, craw if craw < ctot else 0, group_view(rest[0]), "+".join(g.ops[i].name for i in grp))
+                steps.append(FwdStep("lead", dF, None, L.CONV_BIAS | relu, w=w, bn=k, group=group))
+                fused_done.update(grp[1:])
+                continue
+        flags = (L.CONV_BIAS if (op.bn or op.bias) else 0) | relu
+        pd = None
+        if op.pooled is not None:
+            d, pd = _pooled_descs(g, op, nb, dt)
+        conv_flags = 0 if pd is not None else flags
+        ws_bytes = lib.din_conv_workspace_bytes(C.byref(d), 0)
+        fam = next((f for f in RF_FAMILIES if getattr(lib, f.eligible)(C.byref(d), 0, conv_flags, 0, 0)), None)
+        d.rf = (fam.names, conv_flags, 0, 0) if fam else None     # (reporter, flags, ldm, moff): tells the launch timer which reporter names the kernel
+        steps.append(FwdStep("pooled" if pd is not None else "conv", d, pd, flags, fam, ws_bytes, w, k))
+    return ForwardPlan(steps, bn_train, bn_off, bool(save_for_backward))
+
+
+class _ForwardPass:
+    """The state of one forward pass -- the buffers, what backward needs of each op (aux), the BatchNorm tables and the pack cache -- and
+    one method per route of FwdStep, called as route(op index, op, its step, source buffer, destination buffer).  Everything here does;
+    which route an op takes, on which kernel family and with which descriptors was decided by plan_forward."""
+
+    def __init__(self, g: Graph, plan: ForwardPlan, image_buf: torch.Tensor, params: Sequence[torch.Tensor], dt: int):
+        self.g, self.plan, self.params, self.dt, self.lib = g, plan, params, dt, L.load()
+        self.nb, self.dev, self.tdt = image_buf.shape[0], image_buf.device, torch_dtype(dt)
+        self.bufs: List[Optional[torch.Tensor]] = [None] * len(g.tensors)
+        self.bufs[g.input_tid] = image_buf
+        self.aux: list = []
+        self.st = _stream()
+        self.bn = _bn_tables(g, params, self.dev)
+        self.pc = _pack_cache(g, params, dt, self.dev, plan.save_for_backward, self.bn)
+        if self.bn is not None and self.bn.off_list != plan.bn_off:
+            raise L.DinError("graph_forward: a BatchNorm layer's parameters do not have its conv's output channels")
+
+    def fold_and_pack(self) -> None:
+        lib, bn, pc = self.lib, self.bn, self.pc
+        if self.plan.bn_train:
+            pc.bn_scale.fill_(1.0)                                # filters are packed unscaled: the normalisation happens after the conv
+        elif bn is not None:
+            # every BatchNorm layer of the graph folded in ONE launch into flat scale / shift arrays (views per layer: shift_scale)
+            L.check(lib.din_bn_fold_multi(_ptr(bn.ptrs), _ptr(bn.offs), bn.n, bn.total, BN_EPS, _ptr(pc.bn_scale), _ptr(pc.bn_shift), self.st), "bn_fold_multi")
+        # ... and every filter bank (forward and, when training, dgrad orientation) repacked with the folded scale in ONE launch
+        L.check(lib.din_conv_pack_multi(_ptr(pc.table), _ptr(pc.layer_of), _ptr(pc.chunk_index), pc.nblocks, PACK_CHUNK, self.st), "conv_pack_multi")
+
+    def empty(self, *shape, dtype=None) -> torch.Tensor:
+        return torch.empty(shape, dtype=dtype or self.tdt, device=self.dev)
+
+    def buffer(self, tid: int) -> torch.Tensor:
+        if self.bufs[tid] is None:
+            t = self.g.tensors[tid]
+            self.bufs[tid] = self.empty(self.nb, t.h, t.w, t.c)
+        return self.bufs[tid]
+
+    def shift_scale(self, op: Op, s: FwdStep):
+        """(what the epilogue adds: the folded BatchNorm shift or the conv's own bias; the folded BatchNorm scale, kept for backward)"""
+        if s.bn < 0:
+            return (self.params[s.w + 1] if op.bias else None), None
+        o0, o1 = self.plan.bn_off[s.bn], self.plan.bn_off[s.bn + 1]
+        return self.pc.bn_shift[o0:o1], self.pc.bn_scale[o0:o1]
+
+    def conv_launch(self, oi: int, s: FwdStep, src, bias, dst, flags: int) -> None:
+        """the conv launch of the bn_train / pooled / conv routes, through the planned family's entry point"""
+        name = self.g.ops[oi].name
+        ws, wsb = workspace(s.ws_bytes, self.dev)
+        fn = getattr(self.lib, s.rf.fwd if s.rf else "din_conv_fwd")
+        with _timed("fwd", s.d, name):
+            L.check(fn(C.byref(s.d), _ptr(src), _ptr(self.pc.wpk[oi]), _ptr(bias), _ptr(dst), flags, _ptr(ws), wsb, self.st), "conv_fwd " + name)
+
+    def bn_train(self, oi, op, s, src, dst) -> None:
+        pd, td = s.pd, self.g.tensors[op.dst.tid]
+        raw = self.empty(self.nb, s.d.oh, s.d.ow, s.d.cout)
+        self.conv_launch(oi, s, src, None, raw, 0)
+        if pd is not None:
+            pooled_raw = self.empty(self.nb, pd.oh, pd.ow, pd.c)
+            L.check(self.lib.din_avgpool_fwd(C.byref(pd), _ptr(raw), _ptr(pooled_raw), None, 0, self.st), "avgpool_fwd(raw)")
+            raw = pooled_raw
+        gamma, beta, mean, var = self.params[s.w + 1:s.w + 5]
+        bmean, rstd = _bn_train_forward(self.lib, raw, self.dt, self.nb * td.h * td.w, op.dst.c, gamma, beta, mean, var, op.relu, dst, td.c, op.dst.coff, self.st)
+        self.aux.append((None, raw if self.plan.save_for_backward else None, bmean, rstd))
+
+    def member(self, oi, op, s, src, dst) -> None:
+        shift, scale = self.shift_scale(op, s)
+        if s.pd is not None:
+            L.check(self.lib.din_avgpool_fwd(C.byref(s.pd), _ptr(self.bufs[op.mid.tid]), _ptr(dst), _ptr(shift), s.flags, self.st), "avgpool_fwd(epilogue)")
+        self.aux.append((scale,))
+
+    def lead(self, oi, op, s, src, dst) -> None:
+        grp, o0 = s.group, self.plan.bn_off[s.bn]          # (one shift array for all members: their BatchNorm slots are adjacent)
+        second = self.buffer(grp.v2.tid)
+        with _timed("fwd", s.d, grp.name):
+            L.check(self.lib.din_conv_fwd2(C.byref(s.d), _ptr(src), _ptr(self.pc.wfused[oi]), _ptr(self.pc.bn_shift[o0:o0 + grp.ctot]), _ptr(dst), _ptr(second),
+                                           self.g.tensors[grp.v2.tid].c, grp.v2.coff, op.dst.c, grp.craw, s.flags, None, 0, self.st), "conv_fwd2 " + op.name)
+        self.aux.append((self.shift_scale(op, s)[1],))
+
+    def pooled(self, oi, op, s, src, dst) -> None:
+        shift, scale = self.shift_scale(op, s)
+        tmp = self.empty(self.nb, s.pd.h, s.pd.w, s.pd.c)
+        self.conv_launch(oi, s, src, None, tmp, 0)
+        L.check(self.lib.din_avgpool_fwd(C.byref(s.pd), _ptr(tmp), _ptr(dst), _ptr(shift), s.flags, self.st), "avgpool_fwd(epilogue)")
+        self.aux.append((scale,))
+
+    def conv(self, oi, op, s, src, dst) -> None:
+        shift, scale = self.shift_scale(op, s)
+        self.conv_launch(oi, s, src, shift, dst, s.flags)
+        self.aux.append((scale,))
+
+    def maxpool(self, oi, op, s, src, dst) -> None:
+        amax = self.empty(self.nb, s.pd.oh, s.pd.ow, s.pd.c, dtype=torch.uint8) if s.amax else None
+        L.check(self.lib.din_maxpool_fwd(C.byref(s.pd), _ptr(src), _ptr(dst), _ptr(amax), self.st), "maxpool_fwd")
+        self.aux.append((amax,))
+
+    def avgpool(self, oi, op, s, src, dst) -> None:
+        L.check(self.lib.din_avgpool_fwd(C.byref(s.pd), _ptr(src), _ptr(dst), None, 0, self.st), "avgpool_fwd")
+        self.aux.append(())
+
+    def bilinear(self, oi, op, s, src, dst) -> None:
+        L.check(self.lib.din_bilinear_fwd(C.byref(s.pd), _ptr(src), _ptr(dst), self.st), "bilinear_fwd")
+        self.aux.append(())
 
 
 def graph_forward(g: Graph, image_buf: torch.Tensor, params: Sequence[torch.Tensor], dt: int, save_for_backward: bool = True,
                   bn_train: bool = False):
-    """Run the graph.  image_buf: NHWC [nb,h,w,cpad] of dtype dt.  Returns (bufs, aux) for backward.
+    """Run the graph.  image_buf: NHWC [nb,h,w,cpad] of dtype dt (or the raw uint8 frames [nb,3,h,w] where _accepts_u8_frames).  Returns
+    (bufs, aux) for backward: bufs indexed by tensor id, aux one tuple per op.
     bn_train: BatchNorm layers normalise with the statistics of this batch and update their running statistics (the reference's stage-2
     default for Inception-v3: model.train() without set_bn_eval, train_net_dynamic.py:98-100,170-172).  Each BasicConv2d then runs as
     conv (unscaled filters, raw output kept for backward) -> statistics -> normalise + ReLU into the consumer's view; the folded-BN
     fusions (sibling launches, shift in the conv / pool epilogue) do not apply."""
-    lib = L.load()
-    nb = image_buf.shape[0]
-    dev = image_buf.device
-    tdt = torch_dtype(dt)
-    bufs: List[Optional[torch.Tensor]] = [None] * len(g.tensors)
-    bufs[g.input_tid] = image_buf
-    it = iter(params)
-    aux = []
-    st = _stream()
-    bn = _bn_tables(g, params, dev)
-    pc = _pack_cache(g, params, dt, dev, save_for_backward, bn)
-    bn_train = bool(bn_train) and bn is not None
-    if bn_train:
-        bn_scale, bn_shift = pc.bn_scale, pc.bn_shift
-        bn_scale.fill_(1.0)                                   # filters are packed unscaled: the normalisation happens after the conv
-    elif bn is not None:
-        # every BatchNorm layer of the graph folded in ONE launch into flat scale / shift arrays (views per layer below)
-        bn_scale, bn_shift = pc.bn_scale, pc.bn_shift
-        L.check(lib.din_bn_fold_multi(_ptr(bn.ptrs), _ptr(bn.offs), bn.n, bn.total, BN_EPS, _ptr(bn_scale), _ptr(bn_shift), st), "bn_fold_multi")
-    # ... and every filter bank (forward and, when training, dgrad orientation) repacked with the folded scale in ONE launch
-    L.check(lib.din_conv_pack_multi(_ptr(pc.table), _ptr(pc.layer_of), _ptr(pc.chunk_index), pc.nblocks, PACK_CHUNK, st), "conv_pack_multi")
-    bn_i = 0
-    group_of = {grp[0]: grp for grp in g.fwd_groups} if (switch("FUSE_FWD_SIBLINGS") and not bn_train) else {}
-    fused_done = set()                                     # members whose output the group launch already produced
-    for oi, op in enumerate(g.ops):
-        td = g.tensors[op.dst.tid]
-        if bufs[op.dst.tid] is None:
-            bufs[op.dst.tid] = torch.empty((nb, td.h, td.w, td.c), dtype=tdt, device=dev)
-        src, dst = bufs[op.src.tid], bufs[op.dst.tid]
-        if op.kind == "conv":
-            cin = g.cin_image if op.src.tid == g.input_tid else op.src.c
-            d = _conv_desc(g, op, nb, dt, cin)
-            if op.src.tid == g.input_tid and src.dtype == torch.uint8:
-                d.in_u8, d.ldi, d.cioff = 1, 8, 0                      # raw uint8 frames [nb,3,h,w]: the image layer normalises on load
-            w = next(it)
-            scale = shift = None
-            if op.bn:
-                gamma, beta, mean, var = next(it), next(it), next(it), next(it)
-                o0, o1 = bn.off_list[bn_i], bn.off_list[bn_i + 1]
-                bn_i += 1
-                scale, shift = bn_scale[o0:o1], bn_shift[o0:o1]
-                bias = shift
-            else:
-                bias = next(it) if op.bias else None
-            if op.bn and bn_train:
-                # conv -> raw [nb,oh,ow,cout] (-> commuted pool: also linear, so avgpool(conv(x)) == conv(avgpool(x)) holds before the
-                # normalisation) -> batch statistics -> normalise + ReLU into dst's view
-                dR = _conv_desc(g, op, nb, dt, cin)
-                dR.in_u8, dR.ldi, dR.cioff = d.in_u8, d.ldi, d.cioff      # (uint8 frames feed the image layer in this mode too)
-                dR.ldo, dR.cooff = op.dst.c, 0
-                raw = torch.empty((nb, g.tensors[op.src.tid].h if op.pooled is not None else td.h,
-                                   g.tensors[op.src.tid].w if op.pooled is not None else td.w, op.dst.c), dtype=tdt, device=dev)
-                if op.pooled is not None:
-                    dR.oh, dR.ow = raw.shape[1], raw.shape[2]
-                ws, wsb = workspace(lib.din_conv_workspace_bytes(C.byref(dR), 0), dev)
-                with _timed("fwd", dR, op.name):
-                    L.check(lib.din_conv_fwd(C.byref(dR), _ptr(src), _ptr(pc.wpk[oi]), None, _ptr(raw), 0, _ptr(ws), wsb, st), "conv_fwd " + op.name)
-                if op.pooled is not None:
-                    _, pd = _pooled_descs(g, op, nb, dt)
-                    pd.ldo, pd.cooff = op.dst.c, 0
-                    pooled_raw = torch.empty((nb, td.h, td.w, op.dst.c), dtype=tdt, device=dev)
-                    L.check(lib.din_avgpool_fwd(C.byref(pd), _ptr(raw), _ptr(pooled_raw), None, 0, st), "avgpool_fwd(raw)")
-                    raw = pooled_raw
-                bmean, rstd = _bn_train_forward(lib, raw, dt, nb * td.h * td.w, op.dst.c, gamma, beta, mean, var, op.relu, dst, td.c,
-                                                op.dst.coff, st)
-                aux.append((None, raw if save_for_backward else None, bmean, rstd))
-                continue
-            if oi in fused_done:
-                if op.pooled is not None:                   # the group launch left the raw conv output in `mid`: pool + shift + ReLU into dst
-                    _, pd = _pooled_descs(g, op, nb, dt)
-                    pd.ldi, pd.cioff = g.tensors[op.mid.tid].c, op.mid.coff
-                    L.check(lib.din_avgpool_fwd(C.byref(pd), _ptr(bufs[op.mid.tid]), _ptr(dst), _ptr(bias),
-                                                L.CONV_BIAS | (L.CONV_RELU if op.relu else 0), st), "avgpool_fwd(epilogue)")
-                aux.append((scale,))
-                continue
-            if oi in group_of and op.bn:
-                # sibling convs of one source: ONE launch over the concatenated filter bank, first member into its own view, the others into
-                # the adjacent views of their shared tensor (din_conv_fwd2).  Shapes that would run split-K fall through to separate launches.
-                grp = group_of[oi]
-                rest = [g.ops[i] for i in grp[1:]]
-                ctot = op.dst.c + sum(o.dst.c for o in rest)
-                craw = ctot - sum(o.dst.c for o in rest if o.pooled is not None)
-                dF = _conv_desc(g, op, nb, dt, cin)
-                dF.cout = ctot
-                v2 = group_view(rest[0])
-                t2 = v2.tid
-                td2 = g.tensors[t2]
-                if lib.din_conv_workspace_bytes(C.byref(dF), 0) == 0 and bn.off_list[bn_i - 1 + len(grp)] - o0 == ctot:
-                    if bufs[t2] is None:
-                        bufs[t2] = torch.empty((nb, td2.h, td2.w, td2.c), dtype=tdt, device=dev)
-                    flags = L.CONV_BIAS | (L.CONV_RELU if op.relu else 0)
-                    with _timed("fwd", dF, "+".join(g.ops[i].name for i in grp)):
-                        L.check(lib.din_conv_fwd2(C.byref(dF), _ptr(src), _ptr(pc.wfused[oi]), _ptr(bn_shift[o0:o0 + ctot]), _ptr(dst),
-                                                  _ptr(bufs[t2]), td2.c, v2.coff, op.dst.c, craw if craw < ctot else 0, flags, None, 0, st),
-                                "conv_fwd2 " + op.name)
-                    fused_done.update(grp[1:])
-                    aux.append((scale,))
-                    continue
-            wpk = pc.wpk[oi]
-            flags = (L.CONV_BIAS if bias is not None else 0) | (L.CONV_RELU if op.relu else 0)
-            if op.pooled is not None:
-                d, pd = _pooled_descs(g, op, nb, dt)
-                tmp = torch.empty((nb, pd.h, pd.w, pd.c), dtype=tdt, device=dev)
-                _conv_fwd_launch(lib, d, src, wpk, None, tmp, 0, st, dev, op.name)
-                L.check(lib.din_avgpool_fwd(C.byref(pd), _ptr(tmp), _ptr(dst), _ptr(bias), flags, st), "avgpool_fwd(epilogue)")
-            else:
-                _conv_fwd_launch(lib, d, src, wpk, bias, dst, flags, st, dev, op.name)
-            aux.append((scale,))
-        elif op.kind == "maxpool":
-            d = _pool_desc(g, op, nb, dt)
-            # save the winning-tap map when the pooled tensor is a ReLU output: backward then never re-reads the input
-            amax = None
-            if save_for_backward and g.tensors[op.src.tid].relu_masked and op.src.tid != g.input_tid:
-                amax = torch.empty((nb, td.h, td.w, op.src.c), dtype=torch.uint8, device=dev)
-            L.check(lib.din_maxpool_fwd(C.byref(d), _ptr(src), _ptr(dst), _ptr(amax), st), "maxpool_fwd")
-            aux.append((amax,))
-        elif op.kind in ("avgpool", "bilinear"):
-            d = _pool_desc(g, op, nb, dt)
-            if op.kind == "avgpool":
-                L.check(lib.din_avgpool_fwd(C.byref(d), _ptr(src), _ptr(dst), None, 0, st), "avgpool_fwd")
-            else:
-                L.check(lib.din_bilinear_fwd(C.byref(d), _ptr(src), _ptr(dst), st), "bilinear_fwd")
-            aux.append(())
-        else:
-            raise L.DinError("unknown op " + op.kind)
-    return bufs, aux
+    plan = plan_forward(g, image_buf.shape[0], dt, bn_train, image_buf.dtype == torch.uint8, save_for_backward)
+    fp = _ForwardPass(g, plan, image_buf, params, dt)
+    fp.fold_and_pack()
+    for oi, (op, step) in enumerate(zip(g.ops, plan.steps)):
+        dst = fp.buffer(op.dst.tid)
+        getattr(fp, step.route)(oi, op, step, fp.bufs[op.src.tid], dst)
+    return fp.bufs, fp.aux
 
 
 # ------------------------------------------------------------------------------------------------
-# reverse pass: plan_backward decides (no tensor, no stream), _BackwardPass does, graph_backward is the loop over the ops.
-# profiles/backward_launch_trace.txt (tools/backward_trace.py, tests/test_backward_trace_cpu.py) pins every launch and hook of it.
+# reverse pass
 # ------------------------------------------------------------------------------------------------
 ViewKey = Tuple[int, int, int]                 # (tensor id, channel offset, channels)
 
@@ -670,18 +769,11 @@ def plan_backward(g: Graph, nb: int, dt: int, bn_train: bool, side_ok: bool, u8:
     """Decide the reverse pass of g on nb frames.  side_ok: a second stream may be used (no launch timing in progress).  The only place
     of the pass that reads the host switches and the DIN_GROUP_WGRAD_* options; built on every call (options change between passes)."""
     lib = L.load()
-    offsets, bn_index, pos = [], {}, 0
+    offsets, bn_index = param_layout(g)
     readers: Dict[int, set] = {}
     writers: Dict[int, list] = {}
     first_writer: Dict[int, int] = {}
     for oi, op in enumerate(g.ops):
-        if op.kind == "conv":
-            offsets.append(pos)
-            if op.bn:
-                bn_index[oi] = len(bn_index)
-            pos += 5 if op.bn else (2 if op.bias else 1)
-        else:
-            offsets.append(-1)
         readers.setdefault(op.src.tid, set()).add((op.src.coff, op.src.c))
         writers.setdefault(op.dst.tid, []).append((op.dst.coff, op.dst.c))
         first_writer.setdefault(op.dst.tid, oi)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The launch sequence of the backbone's reverse pass (nhwc.graph_backward), recorded with no GPU: profiles/backward_launch_trace.txt.
+"""The launch sequence of the backbone's reverse pass (nhwc.graph_backward), recorded with no GPU: profiles/backward_launch_trace.txt
+(and, with --forward, of its forward pass: profiles/forward_launch_trace.txt).
 
 libdin_hip.so is loaded as usual, but nhwc sees it through a proxy: the planning queries (workspace sizes, group keys, packed sizes and
 descriptors, kernel reporters, din_conv_accepts_u8, din_conv_dgrad_x_fused, din_conv_rf_eligible, din_conv_rf5_eligible, din_bn_parts, the option and error calls) reach the library,
@@ -27,6 +28,16 @@ tensor the reverse pass allocated, in the order it made them (every tensor is ke
 repeats).  Naming by allocation and not by first appearance in the trace keeps a deferred launch from renumbering everything behind it,
 so that a case differs from its base case only where its launches do.
 
+--forward records the forward pass (nhwc.graph_forward) instead, into profiles/forward_launch_trace.txt: the same lines for every C-ABI
+call of it (behind the bar also rf=<the d.rf tuple> when nhwc set one: profiling.LaunchTimer names the kernel from it), the same
+descriptor table and the same writing of a case as its difference from a base case.  Its pointers are named once the pass has returned,
+by role: img the image tensor handed in, buf<tid> the returned buffers, p<i>, aux<op>.<j> (a view of bnscale keeps that name), bnscale /
+bnshift / bnptrs / bnoffs, of the pack cache wpk<op> / wpt<op> / wfused<op> (the banks) and packtable / packlayer / packchunk (the tables
+of din_conv_pack_multi), t<k> every other tensor the pass allocated.  Its last line:
+    R bufs=<tid>,... aux=(<pointer or ->,...) ...      the entries of bufs that are not None; every aux[op] tuple, - for None
+It has the cases of the reverse trace and some of its own (FUSE_FWD_SIBLINGS off, save_for_backward=False, bn-train at 40 frames, no
+uint8 frames).
+
 Cases (all parameter gradients requested): see cases().  Notes:
   * the side stream (WGRAD_SIDE_STREAM) needs real streams and is not traced (tests/test_gpu_din_model.py runs it on the GPU);
   * `parked` runs the lone-1x1 path (the strided sibling that was to carry the 1x1's data gradient receives no gradient); the DinError
@@ -34,12 +45,14 @@ Cases (all parameter gradients requested): see cases().  Notes:
     order, so the reverse pass always visits it afterwards, and either branch it can take there consumes the parked entry.
 
     python tools/backward_trace.py > profiles/backward_launch_trace.txt
+    python tools/backward_trace.py --forward > profiles/forward_launch_trace.txt
 
 A case that differs from another by a switch, an option, the frame count or the compute type is written as its difference from that
 case: '~ <base case>', then for every run of lines that differs '@ i j' (lines [i, j) of the base's section, its '== name' line being
 line 0) and the '+ line's that stand there instead.
 
-tests/test_backward_trace_cpu.py regenerates every case and compares the file it would write with the committed one."""
+tests/test_backward_trace_cpu.py and tests/test_forward_trace_cpu.py regenerate every case and compare the file the tool would write with
+the committed one."""
 import bisect
 import contextlib
 import ctypes as C
@@ -98,20 +111,36 @@ class Recorder:
             if m[0] <= t.data_ptr() < m[1]:
                 m[2] = f"g{tid}"
 
+    def role(self, label, t):
+        """t is known by its role now that the pass has returned: the name of the allocation of the pass it lives in (unless that has one
+        already), or, when the pass did not make it, of the tensor itself"""
+        if t is None or t.numel() == 0:
+            return
+        p = t.untyped_storage().data_ptr()
+        for m in self.made:
+            if m[0] <= p < m[1]:
+                m[2] = m[2] or label
+                return
+        self.name(label, t)
+
     def finish(self):
-        """the lines with the allocations of the pass named: g<tid>, the others t<k> in the order they were made"""
+        """the lines with the allocations of the pass named: by role (g<tid>, buf<tid>, ...), the others t<k> in the order they were made;
+        a pointer that no tensor held when its call was recorded is looked up again among the tensors named since"""
         k = 0
         for m in self.made:
             if m[2] is None:
                 m[2], k = f"t{k}", k + 1
-        named = lambda text: re.sub("\0(\\d+)\0", lambda x: self.made[int(x.group(1))][2], text)      # noqa: E731
+
+        def named(text):
+            text = re.sub("\0@(\\d+)\0", lambda x: self.ptr(int(x.group(1)), final=True), text)
+            return re.sub("\0(\\d+)\0", lambda x: self.made[int(x.group(1))][2], text)
         lines = [named(line) for line in self.lines]
         if self.bn is not None:
             base, n, every = self.bn
             lines.append(f"R bn={named(base)} x{n} #{hashlib.blake2s(named(every).encode(), digest_size=4).hexdigest()}")
         return lines
 
-    def ptr(self, p):
+    def ptr(self, p, final=False):
         p = getattr(p, "value", p)
         if not p:
             return "null"
@@ -123,7 +152,7 @@ class Recorder:
         for i, m in enumerate(self.made):
             if m[0] <= p < m[1]:
                 return f"\0{i}\0" + (f"+{p - m[0]}" if p > m[0] else "")       # (named when the case ends: finish)
-        return "unknown"
+        return "unknown" if final else f"\0@{p}\0"
 
     def desc(self, d, tag):
         text = " ".join(str(getattr(d, n)) for n, _ in d._fields_ if n not in ("nb", "dtype"))
@@ -235,8 +264,9 @@ def dry_run(rec):
         nhwc._WS.clear()
 
 
-def trace(g, params, dt, nb, descs, u8=False, bn_train=False, grads_for=None, switches=(), options=()):
-    """the trace of one forward + backward run of graph g on nb frames: (lines, outcome)"""
+def trace(g, params, dt, nb, descs, u8=False, bn_train=False, grads_for=None, switches=(), options=(), forward=False, save_for_backward=True):
+    """the trace of one run of graph g on nb frames: (lines, outcome).  forward: of its forward pass (graph_forward with
+    save_for_backward as given); otherwise of the reverse pass that follows a forward pass"""
     import torch
     from din_amd import _lib
     rec = Recorder(descs, nb, (dt, _lib.storage_dtype(dt)))
@@ -249,54 +279,38 @@ def trace(g, params, dt, nb, descs, u8=False, bn_train=False, grads_for=None, sw
             ti = g.tensors[g.input_tid]
             u8 = u8 and nhwc._accepts_u8_frames(g, nb, dt)
             img = torch.empty((nb, 3, ti.h, ti.w), dtype=torch.uint8) if u8 else torch.empty((nb, ti.h, ti.w, ti.c), dtype=nhwc.torch_dtype(dt))
-            bufs, aux = nhwc.graph_forward(g, img, params, dt, True, bn_train)
-            for tid, b in enumerate(bufs):
-                rec.name(f"buf{tid}", b)
-            for i, p in enumerate(params):
-                rec.name(f"p{i}", p)
-            pc, bn = g._pack_cache, getattr(g, "_bn_tables", None)
-            rec.name("bnscale", pc.bn_scale)
-            rec.name("bnshift", pc.bn_shift)
-            for oi, t in pc.wpt.items():
-                rec.name(f"wpt{oi}", t)
-            if bn is not None:
-                rec.name("bnptrs", bn.ptrs)
-                rec.name("bnoffs", bn.offs)
-            for oi, a in enumerate(aux):
-                for j, t in enumerate(a):
-                    rec.name(f"aux{oi}.{j}", t)
-            og = {tid: torch.empty_like(bufs[tid]) for tid in (g.output_tids if grads_for is None else grads_for)}
-            for tid, t in og.items():
-                rec.name(f"og{tid}", t)
-            index = {id(p): i for i, p in enumerate(params)}
-
-            def grad_buffer(w):
-                t = torch.empty_like(w)
-                rec.name(f"dw{index[id(w)]}", t)
-                return t
 
             @contextlib.contextmanager
             def timer(kind, d, name):
                 extra = "".join(f" {a}={getattr(d, a)}" for a in ("src_couts", "flops_override") if hasattr(d, a))
+                if forward and getattr(d, "rf", None) is not None:
+                    extra += f" rf={d.rf}"
                 rec.event("")
                 rec.lines.pop()
                 rec.timed = f"{kind} {name} {d.cout}{extra}".replace("flops_override", "flops").replace(", ", ",")
                 yield
-            nhwc.GRAD_BUFFER = grad_buffer
-            nhwc.GRAD_HOOK = lambda w, dw: rec.hook(index[id(w)])
-            nhwc.GRAD_TAP = lambda tid, name, gout: (rec.gradient_of(tid, gout), rec.event(f"G {tid} {name}"))
-            nhwc.GRAD_ASSIGN = None
-            nhwc.LAUNCH_TIMER = timer
-            rec.on = True
             try:
-                grads = nhwc.graph_backward(g, bufs, aux, params, dt, og, [True] * len(params), bn_train)
-                named = [(i, rec.ptr(t.data_ptr())) for i, t in enumerate(grads) if t is not None]
-                is_bn = [".bn." in n for n in g.param_names()]
-                bn = [(i, p) for i, p in named if is_bn[i]]
-                rec.event("R " + " ".join(str(i) if p == f"dw{i}" else f"{i}={p}" for i, p in named if not is_bn[i]))
-                if bn:                                 # gamma / beta gradients: slices of one or a few buffers, as a count and a digest
-                    bases = {p.split("+")[0] for _, p in bn}
-                    rec.bn = (bases.pop() if len(bases) == 1 else "*", len(bn), " ".join(f"{i}={p}" for i, p in bn))
+                if forward:
+                    nhwc.LAUNCH_TIMER, rec.on = timer, True
+                bufs, aux = nhwc.graph_forward(g, img, params, dt, save_for_backward, bn_train)
+                rec.on = False
+                # the tensors of the forward pass by role (a view of something named earlier in this list keeps that name)
+                pc, bn = g._pack_cache, getattr(g, "_bn_tables", None)
+                roles = [("img", img)] if forward else []
+                roles += [(f"buf{tid}", b) for tid, b in enumerate(bufs)] + [(f"p{i}", p) for i, p in enumerate(params)]
+                roles += [("bnscale", pc.bn_scale), ("bnshift", pc.bn_shift)] + [(f"wpt{oi}", t) for oi, t in pc.wpt.items()]
+                if bn is not None:
+                    roles += [("bnptrs", bn.ptrs), ("bnoffs", bn.offs)]
+                roles += [(f"aux{oi}.{j}", t) for oi, a in enumerate(aux) for j, t in enumerate(a)]
+                roles += [(f"wpk{oi}", t) for oi, t in pc.wpk.items()] + [(f"wfused{oi}", t) for oi, t in pc.wfused.items()]
+                roles += [("packtable", pc.table), ("packlayer", pc.layer_of), ("packchunk", pc.chunk_index)]
+                for label, t in roles:
+                    rec.role(label, t)
+                if forward:
+                    held = ["(" + ",".join("-" if t is None else rec.ptr(t.data_ptr()) for t in a) + ")" for a in aux]
+                    rec.event("R bufs=" + ",".join(str(tid) for tid, b in enumerate(bufs) if b is not None) + " aux=" + " ".join(held))
+                else:
+                    lines_of_backward(rec, nhwc, torch, g, bufs, aux, params, dt, grads_for, bn_train, timer)
                 outcome = "ok"
             except L.DinError as e:
                 outcome = "DinError: " + str(e)
@@ -307,6 +321,33 @@ def trace(g, params, dt, nb, descs, u8=False, bn_train=False, grads_for=None, sw
             for attr in ("_pack_cache", "_bn_tables"):
                 g.__dict__.pop(attr, None)
     return [f"N nb={nb} dtype={dt}"] + rec.finish(), outcome
+
+
+def lines_of_backward(rec, nhwc, torch, g, bufs, aux, params, dt, grads_for, bn_train, timer):
+    """graph_backward under the recording hooks, and the R lines of what it returned"""
+    og = {tid: torch.empty_like(bufs[tid]) for tid in (g.output_tids if grads_for is None else grads_for)}
+    for tid, t in og.items():
+        rec.name(f"og{tid}", t)
+    index = {id(p): i for i, p in enumerate(params)}
+
+    def grad_buffer(w):
+        t = torch.empty_like(w)
+        rec.name(f"dw{index[id(w)]}", t)
+        return t
+    nhwc.GRAD_BUFFER = grad_buffer
+    nhwc.GRAD_HOOK = lambda w, dw: rec.hook(index[id(w)])
+    nhwc.GRAD_TAP = lambda tid, name, gout: (rec.gradient_of(tid, gout), rec.event(f"G {tid} {name}"))
+    nhwc.GRAD_ASSIGN = None
+    nhwc.LAUNCH_TIMER = timer
+    rec.on = True
+    grads = nhwc.graph_backward(g, bufs, aux, params, dt, og, [True] * len(params), bn_train)
+    named = [(i, rec.ptr(t.data_ptr())) for i, t in enumerate(grads) if t is not None]
+    is_bn = [".bn." in n for n in g.param_names()]
+    bn = [(i, p) for i, p in named if is_bn[i]]
+    rec.event("R " + " ".join(str(i) if p == f"dw{i}" else f"{i}={p}" for i, p in named if not is_bn[i]))
+    if bn:                                 # gamma / beta gradients: slices of one or a few buffers, as a count and a digest
+        bases = {p.split("+")[0] for _, p in bn}
+        rec.bn = (bases.pop() if len(bases) == 1 else "*", len(bn), " ".join(f"{i}={p}" for i, p in bn))
 
 
 _NETS = {}
@@ -358,8 +399,9 @@ def parked():
     return gb.g, L.DIN_BF16, _params(gb.g, shapes), [m.tid, p.tid]
 
 
-def cases():
-    """(name, the case it is written as a difference from or None, keyword arguments of trace) of every case, lazily"""
+def cases(forward=False):
+    """(name, the case it is written as a difference from or None, keyword arguments of trace) of every case, lazily; forward: and the
+    cases that only the forward trace has"""
     big = lambda nb, **kw: lambda: dict(zip(("g", "dt", "params"), backbone("inv3", "bf16", 720, 1280)), nb=nb, u8=True, **kw)       # noqa: E731
     small = lambda dtype, **kw: lambda: dict(zip(("g", "dt", "params"), backbone("inv3", dtype, 139, 203)), nb=2, **kw)               # noqa: E731
     forced = (("DIN_WGRAD_1X1_MULTI", "2"), ("DIN_WGRAD_HALO", "2"))
@@ -393,13 +435,21 @@ def cases():
     yield "vgg16 bf16 4x720x1280", None, lambda: dict(zip(("g", "dt", "params"), backbone("vgg16", "bf16", 720, 1280)), nb=4, u8=True)
     yield "partial-heads bf16 2x48x64 DIN_WGRAD_1X1_MULTI=2", None, built(partial_heads, options=(("DIN_WGRAD_1X1_MULTI", "2"),))
     yield "parked bf16 2x48x64", None, built(parked)
+    if forward:
+        yield b40 + " FUSE_FWD_SIBLINGS=off", b40, big(40, switches=("FUSE_FWD_SIBLINGS",))
+        yield b4 + " save_for_backward=False", b4, big(4, save_for_backward=False)
+        yield b40 + " bn-train", b4 + " bn-train", big(40, bn_train=True)
+        yield "inv3 bf16 4x720x1280", b4, lambda: dict(big(4)(), u8=False)
 
 
-def sections():
-    """[(case name, lines of its section)] + the descriptor table as the last section"""
+def sections(forward=False):
+    """[(case name, lines of its section)] + the descriptor table as the last section; of the reverse pass, or of the forward pass"""
     descs, out = {}, []
-    for name, _base, make in cases():
-        lines, outcome = trace(descs=descs, **make())
+    for name, _base, make in cases(forward):
+        kw = make()
+        if forward:
+            kw.pop("grads_for", None)
+        lines, outcome = trace(descs=descs, forward=forward, **kw)
         out.append((name, [f"== {name}"] + lines + [f"== end: {outcome}"]))
     from din_amd import _lib as L
     fields = ["# " + tag + ": " + " ".join(n for n, _ in ty._fields_ if n not in ("nb", "dtype")) for tag, ty in (("D", L.ConvDesc), ("P", L.PoolDesc))]
@@ -412,9 +462,12 @@ HEADER = ["# tools/backward_trace.py: the launch sequence of nhwc.graph_backward
           "graph reaches it through graph_backward (the tool's docstring says why; tests/test_backward_trace_cpu.py raises it on the pass state)"]
 
 
-def written(secs):
+HEADER_FORWARD = ["# tools/backward_trace.py --forward: the launch sequence of nhwc.graph_forward, recorded on the CPU (format and cases: the tool's docstring)"]
+
+
+def written(secs, forward=False):
     """the lines of the file: a case with a base is written as what replaces lines [i, j) of the base's section ('@ i j', then '+ line's)"""
-    full, base_of, out = dict(secs), {name: base for name, base, _ in cases()}, list(HEADER)
+    full, base_of, out = dict(secs), {name: base for name, base, _ in cases(forward)}, list(HEADER_FORWARD if forward else HEADER)
     for name, lines in secs:
         base = base_of.get(name)
         if base is None:
@@ -428,7 +481,10 @@ def written(secs):
 
 
 def main():
-    print("\n".join(written(sections())))
+    forward = sys.argv[1:] == ["--forward"]
+    if sys.argv[1:] and not forward:
+        sys.exit("usage: backward_trace.py [--forward]")
+    print("\n".join(written(sections(forward), forward)))
 
 
 if __name__ == "__main__":

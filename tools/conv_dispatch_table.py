@@ -193,19 +193,13 @@ def multi_names_table(L, lib, nhwc):
             for nb, h, w in GEOMETRIES:
                 g = net.build_graph(h, w, L.DIN_BF16 if dt == L.DIN_BF16 else L.DIN_F32)
                 head = f"{backbone} {dtn} nb{nb}"
-                for grp in g.fwd_groups:                   # graph_forward: one launch, first member into its view, the others into theirs
-                    op, rest = g.ops[grp[0]], [g.ops[i] for i in grp[1:]]
-                    ctot = op.dst.c + sum(o.dst.c for o in rest)
-                    craw = ctot - sum(o.dst.c for o in rest if o.pooled is not None)
-                    d = nhwc._conv_desc(g, op, nb, dt)
-                    d.cout = ctot
-                    v2 = nhwc.group_view(rest[0])
-                    if lib.din_conv_workspace_bytes(C.byref(d), 0) != 0:
-                        continue                           # (would run split-K: graph_forward launches the members separately)
-                    flags = L.CONV_BIAS | (L.CONV_RELU if op.relu else 0)
-                    rc = lib.din_conv_fwd2_kernel_names(C.byref(d), g.tensors[v2.tid].c, v2.coff, op.dst.c, craw if craw < ctot else 0, flags, buf, len(buf))
+                for s in nhwc.plan_forward(g, nb, dt, False, False, True).steps:      # the sibling groups the forward pass runs as one launch
+                    if s.route != "lead":
+                        continue
+                    grp, d, csplit = s.group, s.d, g.ops[s.group.members[0]].dst.c
+                    rc = lib.din_conv_fwd2_kernel_names(C.byref(d), g.tensors[grp.v2.tid].c, grp.v2.coff, csplit, grp.craw, s.flags, buf, len(buf))
                     for name in _reporter_lines(rc, buf, "din_conv_fwd2_kernel_names"):
-                        found.setdefault(("fwd2", name), f"{head} {'+'.join(g.ops[i].name for i in grp)} {d.h}x{d.w} c{d.cin}>{ctot} csplit{op.dst.c} flags={flags}")
+                        found.setdefault(("fwd2", name), f"{head} {grp.name} {d.h}x{d.w} c{d.cin}>{grp.ctot} csplit{csplit} flags={s.flags}")
                 plan = nhwc.plan_backward(g, nb, dt, False, False, False)
 
                 def source(oi):                            # the gradient operand of op oi as the reverse pass hands it on (_ConvStep)
