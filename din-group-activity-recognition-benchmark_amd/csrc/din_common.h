@@ -147,6 +147,8 @@ __device__ __forceinline__ uint32_t mix32(uint64_t x) {
 __device__ __forceinline__ uint64_t fold_seed(uint64_t seed, const uint64_t* off) {
     return off ? ((seed + *off) & 0x7FFFFFFFFFFFFFFFull) : seed;
 }
+// The contract every consumer meets (idx = the flat element index of the tensor being masked, forward and backward alike) is stated by
+// the host model tests/dropout_reference.py, which mirrors these three functions line by line.
 __device__ __forceinline__ float keep_scale(uint64_t seed, int64_t idx, float p) {
     if (p <= 0.f) return 1.f;
     float u = (float)(mix32(seed ^ ((uint64_t)idx * 0xD1342543DE82EF95ull)) >> 8) * (1.0f / 16777216.0f);

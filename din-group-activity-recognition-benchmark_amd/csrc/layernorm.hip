@@ -250,7 +250,7 @@ int din_layernorm_bwd(const float* dy, const float* x, const float* res, const f
                       const float* stats, float* dx, float* dgamma, float* dbeta, int64_t rows, int64_t len, int relu,
                       float drop_p, uint64_t seed, const uint64_t* seed_offset, void* stream) {
     DIN_REQUIRE(dy && x && gamma && y && stats && dx && dgamma && dbeta, "layernorm_bwd: null pointer");
-    DIN_REQUIRE(rows >= 0 && len > 0, "layernorm_bwd: bad argument");
+    DIN_REQUIRE(rows >= 0 && len > 0 && drop_p >= 0.f && drop_p < 1.f, "layernorm_bwd: bad argument");
     if (rows == 0) return DIN_OK;
     // few long rows (per-clip LN): per-element atomics from the row kernel are cheap (rows adds per address);
     // many short rows (nl_emb_1): dedicated column-reduction kernel

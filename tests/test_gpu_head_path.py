@@ -698,11 +698,17 @@ def test_layernorm_formula_matches_autograd(mode):
         assert torch.equal(x.grad, r.grad)                        # the res gradient is dx
 
 
-def _keep_mask(lib, L, n, p, seed, seed_off=None):
-    """the keep mask of (seed, element index, p), recovered by running din_act_dropout_fwd on ones"""
+def _keep_mask(lib, L, n, p, seed, word=None):
+    """the keep mask of (seed, element index, p), recovered by running din_act_dropout_fwd on ones; word: the device-side seed offset (a
+    one-element int64 tensor) or None.  It is the mask of the host model tests/dropout_reference.py, so every row that reads it is
+    anchored to the definition and not to this kernel"""
+    from tests import dropout_reference
     ones, out = torch.ones(n).cuda(), torch.empty(n).cuda()
-    L.check(lib.din_act_dropout_fwd(ones.data_ptr(), out.data_ptr(), n, 0, p, seed, seed_off, None))
-    return out.cpu() != 0
+    L.check(lib.din_act_dropout_fwd(ones.data_ptr(), out.data_ptr(), n, 0, p, seed, word.data_ptr() if word is not None else None, None))
+    keep = out.cpu() != 0
+    folded = dropout_reference.fold_seed(seed, None if word is None else int(word.cpu()) & 0xFFFFFFFFFFFFFFFF)
+    assert torch.equal(keep, torch.from_numpy(dropout_reference.keep(folded, np.arange(n), p))), "din_act_dropout_fwd's mask is not the model's"
+    return keep
 
 
 def _ln_launch(lib, L, o, res, relu, p, seed, seed_off, stats32, y32, bwd=True):
@@ -759,7 +765,7 @@ def test_layernorm_seed_offset_word(env):
     word = torch.tensor([977], dtype=torch.int64).cuda()
     keep = _keep_mask(lib, L, 180, p, LN_SEED + 977).view(9, 20)
     assert not torch.equal(keep, _keep_mask(lib, L, 180, p, LN_SEED).view(9, 20))
-    assert torch.equal(keep, _keep_mask(lib, L, 180, p, LN_SEED, word.data_ptr()).view(9, 20))
+    assert torch.equal(keep, _keep_mask(lib, L, 180, p, LN_SEED, word).view(9, 20))
     want = _ln_expected(row, (res, relu, p), keep)
     stats32, y32 = torch.stack([want["mean"], want["rstd"]], dim=1).float(), want["y"].float()
     a = _ln_launch(lib, L, o, res, relu, p, LN_SEED, word.data_ptr(), stats32, y32)
@@ -801,6 +807,8 @@ def test_layernorm_refusals():
     _refused(lib.din_layernorm_fwd(d, None, d, d, 1e-5, d, d, 2, 0, 0, 0.0, 0, None, None), "bad argument")
     _refused(lib.din_layernorm_fwd(d, None, d, d, 1e-5, d, d, 2, 8, 0, 1.0, 0, None, None), "bad argument")
     _refused(lib.din_layernorm_bwd(d, d, None, d, d, d, d, None, d, 2, 8, 0, 0.0, 0, None, None), "null pointer")
+    _refused(lib.din_layernorm_bwd(d, d, None, d, d, d, d, d, d, 2, 8, 0, 1.0, 0, None, None), "layernorm_bwd: bad argument")
+    _refused(lib.din_layernorm_bwd(d, d, None, d, d, d, d, d, d, 2, 8, 0, -0.5, 0, None, None), "layernorm_bwd: bad argument")
 
 
 # =====================================================================================================================================
