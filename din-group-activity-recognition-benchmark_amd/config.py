@@ -18,6 +18,11 @@ positive finite number.
 flip_prob (both trainers, training passes only; 0.0 = off): every clip of a training batch is mirrored left-right with this probability --
 all its frames inside the batch's gather launch, its boxes, and for volleyball the team side of its activity label
 (din_amd/frame_cache.py: FlipPlan); refused together with feature_cache_gb > 0.
+color_jitter (both trainers, training passes only; None = off): the amplitudes (brightness, contrast, saturation) of a per-clip colour
+jitter, each a real number in [0, 1).  Every clip of a training batch draws three factors f = 1 + a * u, u uniform in [-1, 1], and all its
+frames go through PIL.ImageEnhance.Contrast, then .Brightness, then .Color with them -- byte for byte what Pillow computes -- inside the
+batch's gather launch (din_amd/frame_cache.py: JitterPlan; include/din_hip_aug.h); boxes and labels do not change, evaluation passes never
+jitter; refused together with feature_cache_gb > 0.
 All are opt-in: at 0 / False / None the trainers behave exactly as without them."""
 from __future__ import annotations
 
@@ -43,6 +48,7 @@ _DEFAULTS = dict(
     deterministic=False,
     max_grad_norm=None,
     flip_prob=0.0,
+    color_jitter=None,
 )
 
 

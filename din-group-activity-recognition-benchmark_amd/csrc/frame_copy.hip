@@ -11,7 +11,11 @@
 //
 // din_copy_rows_u8_flip is the same gather with flagged rows mirrored left-right on their way (flip augmentation, cfg.flip_prob), and
 // din_flip_clip_labels mirrors the boxes and activity labels of those clips: see the second half of this file.
+//
+// din_rows_gray_partials and din_copy_rows_u8_jitter (include/din_hip_aug.h) are the colour augmentation (cfg.color_jitter): the gather
+// with Pillow's ImageEnhance.Contrast / Brightness / Color applied to drawn rows on their way, mirrored or not: the last part of this file.
 #include "din_common.h"
+#include "../../include/din_hip_aug.h"
 
 namespace {
 
@@ -153,6 +157,232 @@ __global__ __launch_bounds__(BLOCK) void flip_clip_labels_kernel(float* __restri
     }
 }
 
+// ---- colour jitter (din_rows_gray_partials, din_copy_rows_u8_jitter: include/din_hip_aug.h) -----------------------------------------------
+// A row is three planes of `height` lines of `width` bytes, and an item covers the SAME lines in all three planes (saturation and the
+// grey value need r, g and b of one pixel): line group `seg` of a row is its lines [seg * LPS, seg * LPS + LPS) with LPS =
+// lines_per_item(width), so an item is at most SEG pixels unless a single line is longer.  height * width < MAX_PIXELS keeps every pixel
+// index, every partial sum (<= 255 per pixel) and a row's whole sum inside 32 bits.
+constexpr int64_t MAX_PIXELS = (int64_t)1 << 24;
+
+// the one rule both launches cut a row by (ops.gray_partial_segments states it for the workspace): whole lines per item
+inline int64_t lines_per_item(int64_t width) { return width >= SEG ? 1 : SEG / width; }
+
+// the sum of v over the workgroup, in every thread (integers: exact in any order)
+__device__ __forceinline__ uint32_t block_sum(uint32_t v) {
+    __shared__ uint32_t part[BLOCK / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    __syncthreads();                                                     // (the previous item's readers of part[] are done)
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t s = 0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; ++w) s += part[w];
+    return s;
+}
+
+__device__ __forceinline__ uint32_t gray(uint32_t r, uint32_t g, uint32_t b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }
+
+__device__ __forceinline__ uint32_t gray_sum4(uint32_t r, uint32_t g, uint32_t b) {      // four pixels, one byte of each dword each
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 32; k += 8) s += gray((r >> k) & 255u, (g >> k) & 255u, (b >> k) & 255u);
+    return s;
+}
+
+__global__ __launch_bounds__(BLOCK) void rows_gray_partials_kernel(const uint64_t* __restrict__ src, uint32_t* __restrict__ partials,
+                                                                    int64_t height, int64_t width, int64_t lps, int64_t segs,
+                                                                    int64_t items) {
+    const int64_t plane = height * width;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t row = item / segs, seg = item - row * segs;
+        const uint64_t sa = src[row];
+        if (sa == 0) continue;                                           // "leave this row alone" (uniform over the workgroup)
+        const int64_t l0 = seg * lps, nl = height - l0 < lps ? height - l0 : lps;
+        const uint8_t* s = reinterpret_cast<const uint8_t*>(sa) + l0 * width;
+        const uint32_t np = (uint32_t)(nl * width);                      // pixels of this item
+        uint32_t acc = 0;
+        if (((uint64_t)width | sa) % 16 == 0) {                          // (then `plane` is a multiple of 16 too)
+            const uint4* r = reinterpret_cast<const uint4*>(s);
+            const uint4* g = reinterpret_cast<const uint4*>(s + plane);
+            const uint4* b = reinterpret_cast<const uint4*>(s + 2 * plane);
+            for (uint32_t i = threadIdx.x; i < np / 16; i += BLOCK) {
+                const uint4 x = r[i], y = g[i], z = b[i];
+                acc += gray_sum4(x.x, y.x, z.x) + gray_sum4(x.y, y.y, z.y) + gray_sum4(x.z, y.z, z.z) + gray_sum4(x.w, y.w, z.w);
+            }
+        } else {
+            for (uint32_t i = threadIdx.x; i < np; i += BLOCK) acc += gray(s[i], s[plane + i], s[2 * plane + i]);
+        }
+        acc = block_sum(acc);
+        if (threadIdx.x == 0) partials[item] = acc;                      // item = row * segs + seg: one plain store
+    }
+}
+
+// Pixel values travel through the stages as floats holding integers 0..255, so a stage costs no conversion.
+struct Jitter { float c, b, s, mean; };
+
+// Image.blend's store: t <= 0 -> 0, t >= 255 -> 255, otherwise truncated towards zero
+__device__ __forceinline__ float to_byte(float t) { return truncf(fminf(fmaxf(t, 0.f), 255.f)); }
+// multiply and add rounded separately, whatever -ffp-contract says
+__device__ __forceinline__ float blend(float d, float v, float f) { return to_byte(__fadd_rn(d, __fmul_rn(f, v - d))); }
+// L of integer-valued floats: every product and partial sum is an integer below 2^24 (at most 65536 * 255 + 32768), so the fused
+// multiply-adds, the scaling by 2^-16 and the floor are all exact -- this IS the integer expression of gray()
+__device__ __forceinline__ float gray_f(float r, float g, float b) {
+    return floorf(fmaf(19595.f, r, fmaf(38470.f, g, fmaf(7471.f, b, 32768.f))) * (1.f / 65536.f));
+}
+
+template <bool DC, bool DB, bool DS>
+__device__ __forceinline__ void jitter_px(float& r, float& g, float& b, const Jitter& j) {
+    if (DC) { r = blend(j.mean, r, j.c); g = blend(j.mean, g, j.c); b = blend(j.mean, b, j.c); }
+    if (DB) { r = blend(0.f, r, j.b); g = blend(0.f, g, j.b); b = blend(0.f, b, j.b); }
+    if (DS) {
+        const float l = gray_f(r, g, b);
+        r = blend(l, r, j.s); g = blend(l, g, j.s); b = blend(l, b, j.s);
+    }
+}
+
+template <bool DC, bool DB, bool DS>
+__device__ __forceinline__ void jitter_dword(uint32_t& r4, uint32_t& g4, uint32_t& b4, const Jitter& j) {
+    uint32_t ro = 0, go = 0, bo = 0;
+#pragma unroll
+    for (int k = 0; k < 32; k += 8) {
+        float r = (float)((r4 >> k) & 255u), g = (float)((g4 >> k) & 255u), b = (float)((b4 >> k) & 255u);     // v_cvt_f32_ubyte0..3
+        jitter_px<DC, DB, DS>(r, g, b, j);
+        ro |= (uint32_t)r << k; go |= (uint32_t)g << k; bo |= (uint32_t)b << k;       // (integers already: no rounding left to do)
+    }
+    r4 = ro; g4 = go; b4 = bo;
+}
+
+template <bool DC, bool DB, bool DS>
+__device__ __forceinline__ void jitter_unit(uint4& r, uint4& g, uint4& b, const Jitter& j) {
+    jitter_dword<DC, DB, DS>(r.x, g.x, b.x, j);
+    jitter_dword<DC, DB, DS>(r.y, g.y, b.y, j);
+    jitter_dword<DC, DB, DS>(r.z, g.z, b.z, j);
+    jitter_dword<DC, DB, DS>(r.w, g.w, b.w, j);
+}
+
+// 16-byte unit `i` of the item's nl lines of wv units, from the three planes; a mirrored row reads unit wv - 1 - v of the same line and
+// reverses its bytes (the stages are per pixel and `mean` belongs to the whole frame, so they commute with the mirror)
+__device__ __forceinline__ void load_unit(const uint8_t* __restrict__ s, int64_t plane, uint32_t wv, bool flip, uint32_t i, uint4& r,
+                                          uint4& g, uint4& b) {
+    uint32_t si = i;
+    if (flip) {
+        const uint32_t l = i / wv, v = i - l * wv;
+        si = l * wv + (wv - 1 - v);
+    }
+    r = reinterpret_cast<const uint4*>(s)[si];
+    g = reinterpret_cast<const uint4*>(s + plane)[si];
+    b = reinterpret_cast<const uint4*>(s + 2 * plane)[si];
+    if (flip) { r = mirrored(r); g = mirrored(g); b = mirrored(b); }
+}
+
+__device__ __forceinline__ void store_unit(uint8_t* __restrict__ d, int64_t plane, uint32_t i, uint4 r, uint4 g, uint4 b) {
+    reinterpret_cast<uint4*>(d)[i] = r;
+    reinterpret_cast<uint4*>(d + plane)[i] = g;
+    reinterpret_cast<uint4*>(d + 2 * plane)[i] = b;
+}
+
+// one item, 16-byte path: s, d and plane are multiples of 16, lines are wv units; nl * wv < 2^20
+template <bool DC, bool DB, bool DS>
+__device__ __forceinline__ void jitter_units(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, int64_t plane, uint32_t wv,
+                                             uint32_t nl, bool flip, const Jitter& j) {
+    const uint32_t nv = nl * wv;
+    uint32_t i = threadIdx.x;
+    for (; i + BLOCK < nv; i += 2 * BLOCK) {                             // two loads per plane in flight before the first store
+        uint4 r0, g0, b0, r1, g1, b1;
+        load_unit(s, plane, wv, flip, i, r0, g0, b0);
+        load_unit(s, plane, wv, flip, i + BLOCK, r1, g1, b1);
+        jitter_unit<DC, DB, DS>(r0, g0, b0, j);
+        store_unit(d, plane, i, r0, g0, b0);
+        jitter_unit<DC, DB, DS>(r1, g1, b1, j);
+        store_unit(d, plane, i + BLOCK, r1, g1, b1);
+    }
+    if (i < nv) {
+        uint4 r0, g0, b0;
+        load_unit(s, plane, wv, flip, i, r0, g0, b0);
+        jitter_unit<DC, DB, DS>(r0, g0, b0, j);
+        store_unit(d, plane, i, r0, g0, b0);
+    }
+}
+
+// one item, byte by byte: any width, any alignment; nl * width < 2^24
+template <bool DC, bool DB, bool DS>
+__device__ __forceinline__ void jitter_bytes(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, int64_t plane, uint32_t width,
+                                             uint32_t nl, bool flip, const Jitter& j) {
+    const uint32_t np = nl * width;
+    for (uint32_t i = threadIdx.x; i < np; i += BLOCK) {
+        uint32_t si = i;
+        if (flip) {
+            const uint32_t l = i / width, x = i - l * width;
+            si = l * width + (width - 1 - x);
+        }
+        float r = (float)s[si], g = (float)s[plane + si], b = (float)s[2 * plane + si];
+        jitter_px<DC, DB, DS>(r, g, b, j);
+        d[i] = (uint8_t)r;
+        d[plane + i] = (uint8_t)g;
+        d[2 * plane + i] = (uint8_t)b;
+    }
+}
+
+template <bool DC, bool DB, bool DS>
+__device__ __forceinline__ void jitter_item(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, int64_t plane, int64_t width,
+                                            int64_t nl, bool vec, bool flip, const Jitter& j) {
+    if (vec) jitter_units<DC, DB, DS>(s, d, plane, (uint32_t)(width / 16), (uint32_t)nl, flip, j);
+    else     jitter_bytes<DC, DB, DS>(s, d, plane, (uint32_t)width, (uint32_t)nl, flip, j);
+}
+
+__global__ __launch_bounds__(BLOCK) void copy_rows_u8_jitter_kernel(const uint64_t* __restrict__ src, const uint64_t* __restrict__ dst,
+                                                                     const int64_t* __restrict__ flip, const float* __restrict__ factors,
+                                                                     const uint32_t* __restrict__ partials, int64_t height, int64_t width,
+                                                                     int64_t lps, int64_t segs, int64_t items) {
+    const int64_t plane = height * width;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t row = item / segs, seg = item - row * segs;
+        const uint64_t sa = src[row];
+        if (sa == 0) continue;                                           // "leave this row alone"
+        const uint64_t da = dst[row];
+        const int64_t l0 = seg * lps, nl = height - l0 < lps ? height - l0 : lps;
+        const uint8_t* s = reinterpret_cast<const uint8_t*>(sa) + l0 * width;
+        uint8_t* d = reinterpret_cast<uint8_t*>(da) + l0 * width;
+        const bool mirror = flip != nullptr && flip[row] != 0;
+        const bool vec = ((uint64_t)width | sa | da) % 16 == 0;          // every real frame (then `plane` is a multiple of 16 too)
+        Jitter j = {1.f, 1.f, 1.f, 0.f};
+        if (factors) { j.c = factors[3 * row]; j.b = factors[3 * row + 1]; j.s = factors[3 * row + 2]; }
+        // everything below branches on the row alone: uniform over the workgroup
+        const int stages = (j.c != 1.f ? 1 : 0) | (j.b != 1.f ? 2 : 0) | (j.s != 1.f ? 4 : 0);
+        if (stages == 0) {                                               // the plain or mirrored body, plane by plane
+            for (int p = 0; p < 3; ++p) {
+                const uint8_t* sp = s + p * plane;
+                uint8_t* dp = d + p * plane;
+                if (!mirror) {
+                    const int64_t nb = nl * width;                       // (one segment unless a single line is longer than SEG)
+                    for (int64_t k = 0; k * SEG < nb; ++k) copy_segment(sp, dp, nb, k);
+                } else if (vec) {
+                    flip_lines<uint4>(sp, dp, width / 16, nl);
+                } else {
+                    flip_lines<uint8_t>(sp, dp, width, nl);
+                }
+            }
+            continue;
+        }
+        if (stages & 1) {                                                // the contrast pivot: the row's partials, in integers
+            uint32_t acc = 0;
+            for (int64_t t = threadIdx.x; t < segs; t += BLOCK) acc += partials[row * segs + t];
+            const uint64_t sum = block_sum(acc);
+            j.mean = (float)(uint32_t)((2 * sum + (uint64_t)plane) / (2 * (uint64_t)plane));
+        }
+        switch (stages) {
+            case 1: jitter_item<true, false, false>(s, d, plane, width, nl, vec, mirror, j); break;
+            case 2: jitter_item<false, true, false>(s, d, plane, width, nl, vec, mirror, j); break;
+            case 3: jitter_item<true, true, false>(s, d, plane, width, nl, vec, mirror, j); break;
+            case 4: jitter_item<false, false, true>(s, d, plane, width, nl, vec, mirror, j); break;
+            case 5: jitter_item<true, false, true>(s, d, plane, width, nl, vec, mirror, j); break;
+            case 6: jitter_item<false, true, true>(s, d, plane, width, nl, vec, mirror, j); break;
+            default: jitter_item<true, true, true>(s, d, plane, width, nl, vec, mirror, j); break;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int din_copy_rows_u8(const uint64_t* src, const uint64_t* dst, int n, int64_t bytes, void* stream) {
@@ -194,5 +424,43 @@ extern "C" int din_flip_clip_labels(float* boxes, int64_t* activities, const int
     hipLaunchKernelGGL(flip_clip_labels_kernel, dim3(grid_1d((int64_t)rows * per_row, BLOCK)), dim3(BLOCK), 0, as_stream(stream), boxes,
                        activities, flip, n_valid, label_map, rows, per_row, n, width, classes);
     DIN_CHECK_LAUNCH("flip_clip_labels");
+    return DIN_OK;
+}
+
+// the checks the two colour-jitter launches share; 1: nothing to do, 0: go on, negative: refused
+static int jitter_geometry(const char* what, int n, int64_t height, int64_t width) {
+    DIN_REQUIRE(n >= 0 && height >= 0 && width >= 0, "%s: n = %d, height = %lld, width = %lld must not be negative", what, n,
+                (long long)height, (long long)width);
+    if (n == 0 || height == 0 || width == 0) return 1;
+    DIN_REQUIRE(height <= INT64_MAX / width && height * width < MAX_PIXELS,
+                "%s: height * width = %lld * %lld must stay below 2^24 pixels (a row's grey sum is kept in 32 bits)", what,
+                (long long)height, (long long)width);
+    return 0;
+}
+
+extern "C" int din_rows_gray_partials(const uint64_t* src, uint32_t* partials, int n, int64_t height, int64_t width, void* stream) {
+    const int rc = jitter_geometry("rows_gray_partials", n, height, width);
+    if (rc != 0) return rc < 0 ? rc : DIN_OK;
+    DIN_REQUIRE(src && partials, "rows_gray_partials: null address table or partials with n = %d", n);
+    const int64_t lps = lines_per_item(width), segs = ceil_div64(height, lps), items = segs * (int64_t)n;
+    const int grid = (int)(items < GRID_CAP ? items : GRID_CAP);
+    hipLaunchKernelGGL(rows_gray_partials_kernel, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, partials, height, width, lps, segs,
+                       items);
+    DIN_CHECK_LAUNCH("rows_gray_partials");
+    return DIN_OK;
+}
+
+extern "C" int din_copy_rows_u8_jitter(const uint64_t* src, const uint64_t* dst, const int64_t* flip, const float* factors,
+                                       const uint32_t* partials, int n, int64_t height, int64_t width, void* stream) {
+    const int rc = jitter_geometry("copy_rows_u8_jitter", n, height, width);
+    if (rc != 0) return rc < 0 ? rc : DIN_OK;
+    DIN_REQUIRE(src && dst, "copy_rows_u8_jitter: null address table with n = %d", n);
+    DIN_REQUIRE((factors == nullptr) == (partials == nullptr), "copy_rows_u8_jitter: factors and partials come together (%s is null)",
+                factors ? "partials" : "factors");
+    const int64_t lps = lines_per_item(width), segs = ceil_div64(height, lps), items = segs * (int64_t)n;
+    const int grid = (int)(items < GRID_CAP ? items : GRID_CAP);
+    hipLaunchKernelGGL(copy_rows_u8_jitter_kernel, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, dst, flip, factors, partials, height,
+                       width, lps, segs, items);
+    DIN_CHECK_LAUNCH("copy_rows_u8_jitter");
     return DIN_OK;
 }

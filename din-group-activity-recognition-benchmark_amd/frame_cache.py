@@ -20,6 +20,11 @@ reshuffles clips across ranks every epoch, so a rank's hit rate grows over sever
 
 Flip augmentation (cfg.flip_prob, training passes only) lives here too, because a clip is mirrored where its batch is built: the gather
 becomes din_copy_rows_u8_flip for a batch with a drawn clip (FlipPlan, CachedFeed; FlippedFeed for loaders without a cache).
+
+Colour jitter (cfg.color_jitter, training passes only) is a per-pixel function applied on the same way from slot to batch: Pillow's
+ImageEnhance.Contrast, .Brightness and .Color with three factors drawn per clip (JitterPlan), byte for byte.  For a batch with a drawn
+clip the gather becomes din_rows_gray_partials (the grey sums the contrast stage pivots on) plus din_copy_rows_u8_jitter, which mirrors
+flagged rows as well; the slots keep the frame as decoded.
 """
 from __future__ import annotations
 
@@ -137,6 +142,42 @@ class TableUpload:
         return [dev[a:a + n] for a, n in views]
 
 
+def _f32_as_table(values: np.ndarray) -> np.ndarray:
+    """float32 values as int64 words (an odd count is padded with one zero), so that they travel in TableUpload's buffer"""
+    flat = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    if flat.size % 2:
+        flat = np.concatenate([flat, np.zeros(1, dtype=np.float32)])
+    return flat.view(np.int64)
+
+
+class GrayPartials:
+    """the uint32 workspace of din_rows_gray_partials, allocated once and reused by every batch of its owner (it only grows); launches
+    on one stream are ordered, so the next batch's partials cannot overtake this batch's gather"""
+
+    def __init__(self, device):
+        self.device, self.buf = torch.device(device), None
+
+    def of(self, rows: int, height: int, width: int) -> torch.Tensor:
+        from . import ops
+        need = rows * ops.gray_partial_segments(height, width)
+        if self.buf is None or self.buf.numel() < need:
+            self.buf = torch.empty(max(need, 1), dtype=torch.int32, device=self.device)
+        return self.buf
+
+
+def jitter_gather(partials: GrayPartials, frame_shape, d_src: torch.Tensor, d_dst: torch.Tensor, d_flags: Optional[torch.Tensor],
+                  d_factor_words: torch.Tensor) -> None:
+    """the two launches of a jittered batch on the current stream, in place of the plain or mirrored gather: the grey partials of the
+    R source rows, then din_copy_rows_u8_jitter.  d_src, d_dst, d_flags (or None): the uploaded tables; d_factor_words: the uploaded
+    `_f32_as_table` of the float32 [R, 3] factors (contrast, brightness, saturation)."""
+    from . import ops
+    height, width, rows = int(frame_shape[-2]), int(frame_shape[-1]), d_src.numel()
+    d_factors = d_factor_words.view(torch.float32)[:3 * rows]
+    work = partials.of(rows, height, width)
+    ops.rows_gray_partials(d_src, work, height, width)
+    ops.copy_rows_u8_jitter(d_src, d_dst, d_flags, d_factors, work, height, width)
+
+
 class SlotStore(TableUpload):
     """Device side of a SlotTable: the lazily allocated slabs, slot addresses and the rotating pinned buffers the address tables of a
     launch travel in.  FrameCache (uint8 frames) and feature_cache.FeatureCache (fp32 box features) are the two stores."""
@@ -178,15 +219,19 @@ class FrameCache(SlotStore):
         self.frame_bytes = int(np.prod(self.frame_shape))
         super().__init__(device, self.frame_bytes, capacity_bytes, chunk_frames)
         self.flip_flags: Optional[torch.Tensor] = None      # the device flags (int64 [R]) of the last build_batch, None when it mirrored nothing
+        self._gray = GrayPartials(device)                   # colour jitter's workspace (nothing is allocated until a batch is jittered)
 
     def build_batch(self, frame_ids, miss_pos=(), miss_rows: Optional[torch.Tensor] = None,
-                    flip_rows=None) -> Tuple[torch.Tensor, List[int]]:
+                    flip_rows=None, jitter_rows=None) -> Tuple[torch.Tensor, List[int]]:
         """frame_ids [R] (host), miss_pos [M] (host: which of the R rows the uploaded frames are), miss_rows uint8 [M, *frame_shape] on
         the device -> (uint8 [R, *frame_shape] on the device, the frame ids inserted by this call).  On the current stream: one launch
         that copies the new frames into free slots, then one launch that gathers all R rows (slot, or uploaded row where the cache has
         no room).  flip_rows [R] (host, bool; flip augmentation): the rows the gather mirrors left-right on their way out -- the slots
         always hold the frame as decoded.  Where any is set the gather is din_copy_rows_u8_flip, its flags travel with the address
-        tables and stay in `self.flip_flags` for the labels' launch; otherwise the two launches are the ones described above."""
+        tables and stay in `self.flip_flags` for the labels' launch; otherwise the two launches are the ones described above.
+        jitter_rows float32 [R, 3] (host; colour jitter): the (contrast, brightness, saturation) factors of every row.  Where any
+        differs from 1 the gather is din_rows_gray_partials + din_copy_rows_u8_jitter over all R rows, mirroring included, whether a
+        row comes from a slot or from an uploaded frame; the insert stays plain.  All ones is the same as None."""
         from . import ops
         ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
         pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
@@ -195,6 +240,15 @@ class FrameCache(SlotStore):
             raise ValueError(f"build_batch: {len(flags)} flip flags for {len(ids)} rows")
         if flags is not None and not flags.any():
             flags = None
+        factors = None if jitter_rows is None else np.asarray(jitter_rows, dtype=np.float32)
+        if factors is not None and factors.shape != (len(ids), 3):
+            raise ValueError(f"build_batch: jitter factors {factors.shape} for {len(ids)} rows (one triple per row)")
+        if factors is not None and not np.isfinite(factors).all():
+            raise ValueError("build_batch: a jitter factor is not finite")
+        if factors is not None and (factors == 1).all():
+            factors = None
+        if factors is not None and (len(self.frame_shape) != 3 or self.frame_shape[0] != 3):
+            raise ValueError(f"build_batch: colour jitter works on [3, H, W] frames, the cache holds {self.frame_shape}")
         if len(pos):
             if miss_rows is None or not miss_rows.is_cuda or miss_rows.dtype != torch.uint8 or not miss_rows.is_contiguous() \
                     or tuple(miss_rows.shape) != (len(pos),) + self.frame_shape:
@@ -226,6 +280,14 @@ class FrameCache(SlotStore):
                 raise KeyError(f"frame {fid} is neither resident nor among the uploaded frames of this batch")
         dst = [out_ptr + i * fb for i in range(len(ids))]
         self.flip_flags = None
+        if factors is not None:
+            extra = [] if flags is None else [flags.astype(np.int64)]
+            d_ins_src, d_ins_dst, d_src, d_dst, *d_extra = self._upload(ins_src, ins_dst, src, dst, *extra, _f32_as_table(factors))
+            if flags is not None:
+                self.flip_flags = d_extra[0]
+            ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)             # (the insert stays plain: a slot holds the frame as decoded)
+            jitter_gather(self._gray, self.frame_shape, d_src, d_dst, self.flip_flags, d_extra[-1])
+            return out, new_ids
         if flags is None:
             d_ins_src, d_ins_dst, d_src, d_dst = self._upload(ins_src, ins_dst, src, dst)
             ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)             # (no launch when nothing is new)
@@ -292,8 +354,10 @@ class CachedFeed:
     device.  Only the frames the workers decoded are uploaded (DeviceFeed overlaps that with the previous step); the batch is built on
     the compute stream by `cache.build_batch`, and `dataset.resident` is marked for what went in."""
 
-    def __init__(self, loader: Iterable, device, cache: FrameCache, dataset, flip: Optional["EpochFlips"] = None):
+    def __init__(self, loader: Iterable, device, cache: FrameCache, dataset, flip: Optional["EpochFlips"] = None,
+                 jitter: Optional["EpochJitter"] = None):
         self.loader, self.device, self.cache, self.dataset, self.flip = loader, torch.device(device), cache, dataset, flip
+        self.jitter = jitter
         self._kept: collections.deque = collections.deque()
         self._feed = DeviceFeed(_HostSide(loader, self._kept), self.device)
 
@@ -303,7 +367,10 @@ class CachedFeed:
             shape, ids, pos = self._kept.popleft()
             # flip augmentation: one draw per clip, repeated over its T rows; a batch without a flagged clip is built exactly as without it
             rows = None if self.flip is None else self.flip.rows(shape[0], shape[1])
-            images, new_ids = self.cache.build_batch(ids, pos, miss_rows, flip_rows=rows)
+            # colour jitter: one triple of factors per clip, repeated likewise; a batch whose factors are all 1 is built as without it
+            factors = None if self.jitter is None else self.jitter.rows(shape[0], shape[1])
+            kw = {} if factors is None else {"jitter_rows": factors}
+            images, new_ids = self.cache.build_batch(ids, pos, miss_rows, flip_rows=rows, **kw)
             if new_ids:
                 self.dataset.resident[torch.as_tensor(new_ids, dtype=torch.int64)] = 1
             if rows is not None:
@@ -321,8 +388,10 @@ class CachedLoader:
     def __init__(self, loader, cache: FrameCache, dataset):
         self.loader, self.cache, self.dataset = loader, cache, dataset
 
-    def feed(self, device, flip: Optional["EpochFlips"] = None) -> CachedFeed:
-        return CachedFeed(self.loader, device, self.cache, self.dataset, flip)
+    def feed(self, device, flip: Optional["EpochFlips"] = None, jitter: Optional["EpochJitter"] = None) -> CachedFeed:
+        if jitter is None:
+            return CachedFeed(self.loader, device, self.cache, self.dataset, flip)
+        return CachedFeed(self.loader, device, self.cache, self.dataset, flip, jitter=jitter)
 
     def __iter__(self):
         return iter(self.loader)
@@ -408,46 +477,144 @@ def flip_plan(cfg, epoch: int, rank: int) -> Optional[EpochFlips]:
 
 
 class FlippedFeed:
-    """DeviceFeed's iteration contract with flip augmentation over a plain loader (no frame cache): the batch is uploaded as it is and
-    its flagged clips are mirrored on the device, one din_copy_rows_u8_flip launch into a new tensor plus the labels' launch.  A batch
-    without a flagged clip is handed on untouched."""
+    """DeviceFeed's iteration contract with flip augmentation and colour jitter over a plain loader (no frame cache): the batch is
+    uploaded as it is and its drawn clips are mirrored and jittered on the device, into a new tensor: one din_copy_rows_u8_flip launch
+    for a batch that is only mirrored, din_rows_gray_partials + one din_copy_rows_u8_jitter launch for a batch with a jittered clip
+    (mirroring included), plus the labels' launch where a clip is mirrored.  A batch without a drawn clip is handed on untouched.
+    flip or jitter may be None; the partials workspace is allocated once and reused."""
 
-    def __init__(self, loader: Iterable, device, flip: EpochFlips):
-        self.loader, self.device, self.flip = loader, torch.device(device), flip
+    def __init__(self, loader: Iterable, device, flip: Optional[EpochFlips], jitter: Optional["EpochJitter"] = None):
+        self.loader, self.device, self.flip, self.jitter = loader, torch.device(device), flip, jitter
         self._feed = DeviceFeed(loader, self.device)
         self._tables = TableUpload(self.device)
+        self._gray = GrayPartials(self.device)
 
     def __iter__(self) -> Iterator:
         from . import ops
         for batch in self._feed:
             images, *labels = batch
             if images.dtype != torch.uint8 or images.dim() < 3 or not images.is_contiguous():
-                raise ValueError(f"flip_prob mirrors contiguous uint8 [B, T, ..., W] frames on the device; the loader gave {images.dtype} "
-                                 f"{tuple(images.shape)}")
+                raise ValueError(f"flip_prob and color_jitter work on contiguous uint8 [B, T, ..., W] frames on the device; the loader "
+                                 f"gave {images.dtype} {tuple(images.shape)}")
             num_clips, num_frames = images.shape[0], images.shape[1]
-            rows = self.flip.rows(num_clips, num_frames)
-            if rows is None:
+            rows = None if self.flip is None else self.flip.rows(num_clips, num_frames)
+            factors = None if self.jitter is None else self.jitter.rows(num_clips, num_frames)
+            if rows is None and factors is None:
                 yield batch
                 continue
             out = torch.empty_like(images)
             width, fb = images.shape[-1], images[0, 0].numel()
-            src = [images.data_ptr() + i * fb for i in range(len(rows))]
-            dst = [out.data_ptr() + i * fb for i in range(len(rows))]
-            d_src, d_dst, d_flags = self._tables._upload(src, dst, rows.astype(np.int64))
-            ops.copy_rows_u8_flip(d_src, d_dst, d_flags, fb // width, width)
-            self.flip.mirror_labels(labels, d_flags)
+            src = [images.data_ptr() + i * fb for i in range(num_clips * num_frames)]
+            dst = [out.data_ptr() + i * fb for i in range(num_clips * num_frames)]
+            if factors is None:
+                d_src, d_dst, d_flags = self._tables._upload(src, dst, rows.astype(np.int64))
+                ops.copy_rows_u8_flip(d_src, d_dst, d_flags, fb // width, width)
+            else:
+                if images.dim() != 5 or images.shape[2] != 3:
+                    raise ValueError(f"color_jitter works on [B, T, 3, H, W] frames; the loader gave {tuple(images.shape)}")
+                extra = [] if rows is None else [rows.astype(np.int64)]
+                d_src, d_dst, *d_extra = self._tables._upload(src, dst, *extra, _f32_as_table(factors))
+                d_flags = None if rows is None else d_extra[0]
+                jitter_gather(self._gray, images.shape[2:], d_src, d_dst, d_flags, d_extra[-1])
+            if rows is not None:
+                self.flip.mirror_labels(labels, d_flags)
             yield [out, *labels]
 
     def __len__(self):
         return len(self.loader)
 
 
-def feed_for(loader, device, flip: Optional[EpochFlips] = None):
+# ---- colour jitter (cfg.color_jitter) -----------------------------------------------------------------------------------------------------
+# In a training pass every clip draws three fp32 factors f = 1 + a * u, u uniform in [-1, 1], with the amplitudes a of
+# cfg.color_jitter = (brightness, contrast, saturation); all T frames of the clip go through PIL.ImageEnhance.Contrast, .Brightness and
+# .Color with them, in that order, byte for byte as Pillow computes them (include/din_hip_aug.h states the arithmetic), inside the launch
+# that builds the batch.  Boxes and labels do not change.  Evaluation passes never jitter.
+KERNEL_ORDER = (1, 0, 2)        # cfg.color_jitter and JitterPlan's draws are (brightness, contrast, saturation); the launch takes
+#                                 (contrast, brightness, saturation), the order the stages are applied in
+
+
+class EpochJitter:
+    """the factors of one training pass of one rank: `draw` is called once per batch, in batch order"""
+
+    def __init__(self, plan: "JitterPlan", epoch: int):
+        self.amplitudes = plan.amplitudes
+        self._rng = np.random.default_rng([plan.seed, plan.rank, int(epoch), 1])      # (the flips' stream is [seed, rank, epoch])
+        self.jittered = 0                               # clips with a factor other than 1 so far (the info's `jittered_clips`)
+
+    def draw(self, num_clips: int) -> np.ndarray:
+        """float32 [num_clips, 3]: the (brightness, contrast, saturation) factors of the clips of the next batch; an amplitude of 0
+        gives exactly 1.0"""
+        u = self._rng.uniform(-1.0, 1.0, (int(num_clips), 3))
+        f = (1.0 + self.amplitudes[None, :] * u).astype(np.float32)
+        self.jittered += int((f != 1).any(axis=1).sum())
+        return f
+
+    def rows(self, num_clips: int, num_frames: int) -> Optional[np.ndarray]:
+        """the next batch's draw as the launch takes it: float32 [B * T, 3] (contrast, brightness, saturation), every clip's triple
+        repeated over its T rows; None when every factor is 1"""
+        f = self.draw(num_clips)
+        if (f == 1).all():
+            return None
+        return np.ascontiguousarray(np.repeat(f[:, KERNEL_ORDER], int(num_frames), axis=0))
+
+
+class JitterPlan:
+    """the colour factors a run draws.  amplitudes: (brightness, contrast, saturation), each in [0, 1).  The draws of epoch e come from
+    np.random.default_rng([seed, rank, e, 1]) -- a stream of its own, so turning the jitter on never changes which clips are mirrored; a
+    resumed run repeats the draws of an epoch, ranks differ from each other, and a deterministic run stays reproducible."""
+
+    def __init__(self, amplitudes: Sequence[float], seed: int, rank: int):
+        self.amplitudes = np.asarray([float(a) for a in amplitudes], dtype=np.float64)
+        if self.amplitudes.shape != (3,):
+            raise ValueError(f"JitterPlan: three amplitudes (brightness, contrast, saturation), got {amplitudes!r}")
+        self.seed, self.rank = int(seed) & (2 ** 63 - 1), int(rank)
+
+    def epoch(self, e: int) -> EpochJitter:
+        return EpochJitter(self, e)
+
+
+def jitter_refusal(cfg) -> Optional[str]:
+    """why cfg.color_jitter cannot be honoured, or None (both trainers' train_net raise ValueError with it)"""
+    j = getattr(cfg, "color_jitter", None)
+    if j is None:
+        return None
+
+    def real(a):
+        return not isinstance(a, (bool, np.bool_)) and isinstance(a, (int, float, np.integer, np.floating)) and 0.0 <= float(a) < 1.0
+
+    if isinstance(j, (str, bytes)) or not isinstance(j, (tuple, list, np.ndarray)) or len(j) != 3 or not all(real(a) for a in j):
+        return (f"color_jitter = {j!r}: None, or the three amplitudes (brightness, contrast, saturation) of the colour jitter, each a real "
+                f"number in [0, 1)")
+    if wants_features(cfg):
+        return (f"color_jitter = {tuple(j)!r}: feature_cache_gb = {cfg.feature_cache_gb} caches the box features of the frame as decoded; "
+                f"they cannot serve a jittered one")
+    return None
+
+
+def jitter_plan(cfg, epoch: int, rank: int) -> Optional[EpochJitter]:
+    """the colour factors of training epoch `epoch` on rank `rank`, or None with cfg.color_jitter = None (nothing changes then)"""
+    j = getattr(cfg, "color_jitter", None)
+    if j is None:
+        return None
+    return JitterPlan(j, cfg.train_random_seed, rank).epoch(epoch)
+
+
+def feed_for(loader, device, flip: Optional[EpochFlips] = None, jitter: Optional[EpochJitter] = None):
     """the device feed of a pass: CachedFeed for a CachedLoader, input_feed.DeviceFeed for anything else; with the flips of a training
-    pass (`flip_plan`), the CachedFeed mirrors inside its gather and a plain loader goes through FlippedFeed"""
+    pass (`flip_plan`), the CachedFeed mirrors inside its gather and a plain loader goes through FlippedFeed; with its colour factors
+    (`jitter_plan`) likewise, mirrored or not"""
+    if jitter is not None:
+        return loader.feed(device, flip, jitter=jitter) if isinstance(loader, CachedLoader) else FlippedFeed(loader, device, flip, jitter=jitter)
     if flip is None:
         return loader.feed(device) if isinstance(loader, CachedLoader) else DeviceFeed(loader, device)
     return loader.feed(device, flip) if isinstance(loader, CachedLoader) else FlippedFeed(loader, device, flip)
+
+
+def augmentations(cfg, epoch: int, rank: int) -> Tuple[Optional[EpochFlips], Optional[EpochJitter], dict]:
+    """what a trainer's training pass hands to `feed_for`: (flips, jitter, the keyword arguments that carry the jitter -- none when
+    cfg.color_jitter is None, so that a run without it calls feed_for exactly as before)"""
+    flip, jitter = flip_plan(cfg, epoch, rank), jitter_plan(cfg, epoch, rank)
+    return flip, jitter, ({} if jitter is None else {"jitter": jitter})
 
 
 def end_pass(feed) -> None:

@@ -1048,6 +1048,68 @@ def flip_clip_labels(boxes: Optional[torch.Tensor], activities: Optional[torch.T
                                      classes, _stream()), "flip_clip_labels")
 
 
+GRAY_SEGMENT = 8192             # bytes of one plane per (row, line group) item of the colour-jitter launches (include/din_hip_aug.h)
+GRAY_MAX_PIXELS = 1 << 24       # height * width of a row stays below this: its grey sum is kept in 32 bits
+
+
+def gray_partial_segments(height: int, width: int) -> int:
+    """line groups per row of din_rows_gray_partials / din_copy_rows_u8_jitter: whole image lines, max(1, 8192 // width) to a group --
+    the workspace of n rows is n * gray_partial_segments(height, width) uint32 (SEGS of include/din_hip_aug.h, stated here once)"""
+    height, width = int(height), int(width)
+    if height <= 0 or width <= 0:
+        return 0
+    return -(-height // max(1, GRAY_SEGMENT // width))
+
+
+def _jitter_tables(what: str, tables, n: Optional[int]) -> int:
+    require_gpu(*tables)
+    if any(t.dtype != torch.int64 or not t.is_contiguous() for t in tables):
+        raise L.DinError(f"{what}: address tables and flags are contiguous int64 device tensors")
+    held = min(t.numel() for t in tables)
+    n = held if n is None else int(n)
+    if n > held:
+        raise L.DinError(f"{what}: n = {n} rows but the tables hold {[t.numel() for t in tables]} entries")
+    return n
+
+
+def _check_partials(what: str, partials: torch.Tensor, n: int, height: int, width: int) -> None:
+    require_gpu(partials)
+    need = n * gray_partial_segments(height, width)
+    if partials.dtype != torch.int32 or not partials.is_contiguous() or partials.numel() < need:
+        raise L.DinError(f"{what}: partials must be a contiguous int32 device tensor (the uint32 sums' bits) of at least {need} entries "
+                         f"({n} rows x gray_partial_segments({height}, {width})), got {partials.dtype} x {partials.numel()}")
+
+
+def rows_gray_partials(src: torch.Tensor, partials: torch.Tensor, height: int, width: int, n: Optional[int] = None) -> None:
+    """partials[i * segs + g] = the sum of L = (19595 r + 38470 g + 7471 b + 32768) >> 16 over line group g of the uint8 [3, height,
+    width] row at device address src[i], segs = gray_partial_segments(height, width); src[i] == 0 leaves row i's partials alone.  One
+    launch on the current stream, no atomics (din_rows_gray_partials: the mean of PIL.ImageEnhance.Contrast)."""
+    lib = L.load()
+    n = _jitter_tables("rows_gray_partials", (src,), n)
+    _check_partials("rows_gray_partials", partials, n, height, width)
+    L.check(lib.din_rows_gray_partials(_ptr(src), _ptr(partials), n, height, width, _stream()), "rows_gray_partials")
+
+
+def copy_rows_u8_jitter(src: torch.Tensor, dst: torch.Tensor, flip: Optional[torch.Tensor], factors: Optional[torch.Tensor],
+                        partials: Optional[torch.Tensor], height: int, width: int, n: Optional[int] = None) -> None:
+    """copy_rows_u8_flip over uint8 [3, height, width] rows with row i put through PIL.ImageEnhance.Contrast, .Brightness and .Color
+    with factors[i] = (contrast, brightness, saturation) on its way (fp32 device tensor [n, 3]); partials: what rows_gray_partials
+    wrote for the same src, height and width earlier on this stream.  A row whose factors are all 1 is copied or mirrored as
+    copy_rows_u8_flip does it; factors = partials = None means that for every row (din_copy_rows_u8_jitter, include/din_hip_aug.h)."""
+    lib = L.load()
+    n = _jitter_tables("copy_rows_u8_jitter", (src, dst) + (() if flip is None else (flip,)), n)
+    if (factors is None) != (partials is None):
+        raise L.DinError("copy_rows_u8_jitter: factors and partials come together")
+    if factors is not None:
+        require_gpu(factors)
+        if factors.dtype != torch.float32 or not factors.is_contiguous() or factors.numel() < 3 * n:
+            raise L.DinError(f"copy_rows_u8_jitter: factors must be a contiguous fp32 device tensor of {n} triples, got {factors.dtype} x "
+                             f"{factors.numel()}")
+        _check_partials("copy_rows_u8_jitter", partials, n, height, width)
+    L.check(lib.din_copy_rows_u8_jitter(_ptr(src), _ptr(dst), _ptr(flip), _ptr(factors), _ptr(partials), n, height, width, _stream()),
+            "copy_rows_u8_jitter")
+
+
 FEAT_ROWS_SEGMENT = 16384       # DIN_FEAT_ROWS_SEGMENT (include/din_hip.h): bytes of one row per work item of din_feat_rows
 
 

@@ -104,8 +104,9 @@ def _losses(actions_scores, activities_scores, actions_in, activities_in, batch_
 
 def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets, collective, max_batches=None):
     meters = _Meters(cfg, device)
-    flip = frame_cache.flip_plan(cfg, epoch, parallel.current_rank())      # None unless cfg.flip_prob > 0
-    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device, flip)):
+    # flip: None unless cfg.flip_prob > 0; jitter: None (and no keyword) unless cfg.color_jitter is set
+    flip, jitter, jitter_kw = frame_cache.augmentations(cfg, epoch, parallel.current_rank())
+    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device, flip, **jitter_kw)):
         if max_batches is not None and bi >= max_batches:
             break
         model.train()
@@ -122,7 +123,7 @@ def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets,
         else:
             optimizer.step()
         meters.add(actions_scores.detach(), actions_in, activities_scores.detach(), activities_in, total_loss, batch_size)
-    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), flip)
+    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), flip, jitter)
 
 
 def _test_pass(data_loader, model, device, epoch, cfg, collective):
@@ -170,7 +171,7 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     why_not = grad_norm_refusal(getattr(cfg, "max_grad_norm", None))       # (before anything else: it needs no device and no loader)
     if why_not:
         raise ValueError(why_not)
-    why_not = frame_cache.flip_refusal(cfg)                            # (cfg.flip_prob: no device and no loader either)
+    why_not = frame_cache.flip_refusal(cfg) or frame_cache.jitter_refusal(cfg)     # (cfg.flip_prob, cfg.color_jitter: no device and no loader either)
     if why_not:
         raise ValueError(why_not)
     model = build_model(cfg)                                           # (refuses stage 2 before touching the device)

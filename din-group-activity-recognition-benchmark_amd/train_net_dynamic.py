@@ -124,8 +124,9 @@ class _Epoch:
 
 def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets, collective, max_batches=None):
     meters = _Epoch(cfg, device)
-    flip = frame_cache.flip_plan(cfg, epoch, parallel.current_rank())      # None unless cfg.flip_prob > 0
-    feed = frame_cache.feed_for(data_loader, device, flip)
+    # flip: None unless cfg.flip_prob > 0; jitter: None (and no keyword) unless cfg.color_jitter is set
+    flip, jitter, jitter_kw = frame_cache.augmentations(cfg, epoch, parallel.current_rank())
+    feed = frame_cache.feed_for(data_loader, device, flip, **jitter_kw)
     for bi, batch_data in enumerate(feed):                             # batch k+1 crosses PCIe on the copy stream during step k
         if max_batches is not None and bi >= max_batches:
             break
@@ -147,13 +148,16 @@ def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets,
             optimizer.step()
         meters.add(activities_scores.detach(), activities_in, total_loss)
     frame_cache.end_pass(feed)                                         # (the feature cache's box check; nothing for the other feeds)
-    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), flip)
+    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), flip, jitter)
 
 
-def add_flip_stats(info, flip):
-    """with cfg.flip_prob > 0: the number of clips the pass mirrored joins its info (a host count)"""
+def add_flip_stats(info, flip, jitter=None):
+    """with cfg.flip_prob > 0: the number of clips the pass mirrored joins its info (a host count); with cfg.color_jitter set: the
+    number of clips it drew a colour factor other than 1 for (a host count too: nothing is read back)"""
     if flip is not None:
         info["flipped_clips"] = flip.flipped
+    if jitter is not None:
+        info["jittered_clips"] = jitter.jittered
     return info
 
 
@@ -226,9 +230,9 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
         raise ValueError(why_not)
     # cfg.deterministic where a sum's order is not ours (first: its answer is the same whatever the caches and workers are set to), then
     # cfg.feature_cache_gb > 0 where cached features would be wrong -- both before any process group or loader exists
-    # -- then cfg.flip_prob where a mirrored clip cannot be fed
+    # -- then cfg.flip_prob where a mirrored clip cannot be fed, and cfg.color_jitter likewise
     why_not = (ops.deterministic_refusal(cfg, int(os.environ.get("WORLD_SIZE", "1"))) or feature_cache.refusal(cfg)
-               or frame_cache.flip_refusal(cfg))
+               or frame_cache.flip_refusal(cfg) or frame_cache.jitter_refusal(cfg))
     if why_not:
         raise ValueError(why_not)
     if getattr(cfg, "deterministic", False):
