@@ -1,4 +1,4 @@
-"""ctypes binding of libdin_hip.so (C ABI declared in include/din_hip.h, and in include/din_hip_aug.h for the colour-jitter launches).
+"""ctypes binding of libdin_hip.so (C ABI declared in include/din_hip.h).
 
 The product path has NO fallback: if the shared library is missing or was built for another
 target this module raises, and every op raises on non-GPU tensors.  The library travels in-tree
@@ -16,7 +16,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DIN_LIB_PATH") or os.path.join(_HERE, "libdin_hip.so")     # (DIN_LIB_PATH: experiment builds, tools/ only)
 CSRC_DIR = os.path.join(_HERE, "csrc")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "din_hip.h")
-AUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "din_hip_aug.h")
 
 DIN_F32, DIN_BF16 = 0, 1
 DIN_F32_BF16X3 = 2          # fp32 storage, three-part bf16 MFMA compute: a value of the CONTRACTION entry points' dtype only (din_hip.h)
@@ -185,34 +184,21 @@ SIGNATURES: Dict[str, tuple] = {
     "din_adam_step_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P]),
     "din_copy_rows_u8":(_I, [_P, _P, _I, _L, _P]),
     "din_copy_rows_u8_flip": (_I, [_P, _P, _P, _I, _L, _L, _P]),
+    "din_rows_gray_partials": (_I, [_P, _P, _I, _L, _L, _P]),
+    "din_copy_rows_u8_jitter": (_I, [_P, _P, _P, _P, _P, _I, _L, _L, _P]),
     "din_flip_clip_labels": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P]),
     "din_feat_rows": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
     "din_feat_rows_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
 }
 
-# the second header, include/din_hip_aug.h (colour jitter): bound after SIGNATURES, additive, the ABI version unchanged
-SIGNATURES_AUG: Dict[str, tuple] = {
-    "din_rows_gray_partials": (_I, [_P, _P, _I, _L, _L, _P]),
-    "din_copy_rows_u8_jitter": (_I, [_P, _P, _P, _P, _P, _I, _L, _L, _P]),
-}
-
 _lib = None
-
-
-def _declared(path: str) -> List[str]:
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(din_[a-z0-9_]+)\s*\(", text)))
 
 
 def header_symbols() -> List[str]:
     """Every function name include/din_hip.h declares (used by the CPU symbol test)."""
-    return _declared(HEADER_PATH)
-
-
-def aug_header_symbols() -> List[str]:
-    """Every function name include/din_hip_aug.h declares"""
-    return _declared(AUG_HEADER_PATH)
+    text = open(HEADER_PATH).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(din_[a-z0-9_]+)\s*\(", text)))
 
 
 def build(verbose: bool = False) -> str:
@@ -239,7 +225,7 @@ def load():
     # process would hold two HIP runtimes and the second one finds no device ("no ROCm-capable device is detected")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_AUG.items()):
+    for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -21,7 +21,7 @@ all its frames inside the batch's gather launch, its boxes, and for volleyball t
 color_jitter (both trainers, training passes only; None = off): the amplitudes (brightness, contrast, saturation) of a per-clip colour
 jitter, each a real number in [0, 1).  Every clip of a training batch draws three factors f = 1 + a * u, u uniform in [-1, 1], and all its
 frames go through PIL.ImageEnhance.Contrast, then .Brightness, then .Color with them -- byte for byte what Pillow computes -- inside the
-batch's gather launch (din_amd/frame_cache.py: JitterPlan; include/din_hip_aug.h); boxes and labels do not change, evaluation passes never
+batch's gather launch (din_amd/frame_cache.py: JitterPlan; include/din_hip.h); boxes and labels do not change, evaluation passes never
 jitter; refused together with feature_cache_gb > 0.
 All are opt-in: at 0 / False / None the trainers behave exactly as without them."""
 from __future__ import annotations

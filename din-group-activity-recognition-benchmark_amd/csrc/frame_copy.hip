@@ -12,16 +12,20 @@
 // din_copy_rows_u8_flip is the same gather with flagged rows mirrored left-right on their way (flip augmentation, cfg.flip_prob), and
 // din_flip_clip_labels mirrors the boxes and activity labels of those clips: see the second half of this file.
 //
-// din_rows_gray_partials and din_copy_rows_u8_jitter (include/din_hip_aug.h) are the colour augmentation (cfg.color_jitter): the gather
+// din_rows_gray_partials and din_copy_rows_u8_jitter are the colour augmentation (cfg.color_jitter): the gather
 // with Pillow's ImageEnhance.Contrast / Brightness / Color applied to drawn rows on their way, mirrored or not: the last part of this file.
 #include "din_common.h"
-#include "../../include/din_hip_aug.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
 constexpr int64_t SEG = 8192;             // bytes of one row per work item: a multiple of 16, so a segment keeps the body's alignment
 constexpr int GRID_CAP = 256 * 16;        // workgroups: 256 CUs x 16, the rest of the items block-stride
+
+inline int capped_grid(int64_t items) { return (int)(items < GRID_CAP ? items : GRID_CAP); }
+
+// the one rule the flip, grey-partials and jitter launches cut a row by (ops.gray_partial_segments states it for the workspace)
+inline int64_t lines_per_item(int64_t width) { return width >= SEG ? 1 : SEG / width; }
 
 // nbytes is a multiple of sizeof(V); s and d are sizeof(V)-aligned
 template <typename V>
@@ -77,8 +81,30 @@ __global__ __launch_bounds__(BLOCK) void copy_rows_u8_kernel(const uint64_t* __r
 
 // ---- mirrored rows (din_copy_rows_u8_flip) -------------------------------------------------------------------------------------------------
 // A row is `lines` lines of `width` bytes; a flagged row has every line written in reverse byte order.  The (row, segment) items are cut
-// at whole lines: LPS = max(1, SEG / width) lines each, so a wave still covers contiguous memory on both sides (the source runs backwards
-// vector by vector).  An unflagged row's segment goes through copy_segment as a copy of its own.
+// at whole lines: LPS = lines_per_item(width) lines each, so a wave still covers contiguous memory on both sides (the source runs
+// backwards vector by vector).  An unflagged row's segment goes through copy_segment as a copy of its own.
+
+// item `item` of a walk over (row, line group) items: lines [seg * lps, seg * lps + nl) of row `row`, s and d at the first of them (d:
+// null where the launch has no dst table); vec: width and the row's addresses are multiples of 16 (every real frame), 16-byte vectors
+// serve it.  All of it follows from `item` and the kernel's arguments: uniform over the workgroup.
+struct Item { int64_t row, seg, nl; const uint8_t* s; uint8_t* d; bool vec; };
+
+// false: src[row] == 0, "leave this row alone"
+__device__ __forceinline__ bool decode_item(int64_t item, int64_t segs, int64_t lps, int64_t lines, int64_t width,
+                                            const uint64_t* __restrict__ src, const uint64_t* __restrict__ dst, Item& it) {
+    it.row = item / segs;
+    it.seg = item - it.row * segs;
+    const uint64_t sa = src[it.row];
+    if (sa == 0) return false;
+    const uint64_t da = dst ? dst[it.row] : 0;
+    const int64_t l0 = it.seg * lps;
+    it.nl = lines - l0 < lps ? lines - l0 : lps;
+    it.s = reinterpret_cast<const uint8_t*>(sa) + l0 * width;
+    it.d = reinterpret_cast<uint8_t*>(da + (uint64_t)(l0 * width));      // (in integers: da may be 0)
+    it.vec = ((uint64_t)width | sa | da) % 16 == 0;
+    return true;
+}
+
 __device__ __forceinline__ uint4 mirrored(uint4 a) {                 // the 16 bytes in reverse order: one v_perm_b32 per dword
     return make_uint4(__builtin_bswap32(a.w), __builtin_bswap32(a.z), __builtin_bswap32(a.y), __builtin_bswap32(a.x));
 }
@@ -113,25 +139,26 @@ __device__ __forceinline__ void flip_lines(const uint8_t* __restrict__ s, uint8_
     if (i < nv) dv[i] = mirrored(sv[l * wv + (wv - 1 - v)]);
 }
 
+// nl lines of `width` bytes from s to d, as they are or mirrored; the branches are the caller's row-uniform ones
+__device__ __forceinline__ void copy_or_mirror_lines(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, int64_t width, int64_t nl,
+                                                     bool mirror, bool vec) {
+    if (!mirror) {
+        const int64_t nb = nl * width;                                   // (one segment unless a single line is longer than SEG)
+        for (int64_t k = 0; k * SEG < nb; ++k) copy_segment(s, d, nb, k);
+    } else if (vec) {
+        flip_lines<uint4>(s, d, width / 16, nl);                         // every real frame: 16-byte loads and stores
+    } else {
+        flip_lines<uint8_t>(s, d, width, nl);
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void copy_rows_u8_flip_kernel(const uint64_t* __restrict__ src, const uint64_t* __restrict__ dst,
                                                                    const int64_t* __restrict__ flip, int64_t lines, int64_t width,
                                                                    int64_t lps, int64_t segs, int64_t items) {
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int64_t row = item / segs, seg = item - row * segs;
-        const uint64_t sa = src[row];
-        if (sa == 0) continue;                                           // "leave this row alone"
-        const uint64_t da = dst[row];
-        const int64_t l0 = seg * lps, nl = lines - l0 < lps ? lines - l0 : lps;
-        const uint8_t* s = reinterpret_cast<const uint8_t*>(sa) + l0 * width;
-        uint8_t* d = reinterpret_cast<uint8_t*>(da) + l0 * width;
-        if (flip == nullptr || flip[row] == 0) {
-            const int64_t nb = nl * width;                               // (one segment unless a single line is longer than SEG)
-            for (int64_t k = 0; k * SEG < nb; ++k) copy_segment(s, d, nb, k);
-        } else if (((uint64_t)width | sa | da) % 16 == 0) {
-            flip_lines<uint4>(s, d, width / 16, nl);                     // every real frame: 16-byte loads and stores
-        } else {
-            flip_lines<uint8_t>(s, d, width, nl);
-        }
+        Item it;
+        if (!decode_item(item, segs, lps, lines, width, src, dst, it)) continue;
+        copy_or_mirror_lines(it.s, it.d, width, it.nl, flip != nullptr && flip[it.row] != 0, it.vec);
     }
 }
 
@@ -157,15 +184,12 @@ __global__ __launch_bounds__(BLOCK) void flip_clip_labels_kernel(float* __restri
     }
 }
 
-// ---- colour jitter (din_rows_gray_partials, din_copy_rows_u8_jitter: include/din_hip_aug.h) -----------------------------------------------
+// ---- colour jitter (din_rows_gray_partials, din_copy_rows_u8_jitter) ----------------------------------------------------------------------
 // A row is three planes of `height` lines of `width` bytes, and an item covers the SAME lines in all three planes (saturation and the
 // grey value need r, g and b of one pixel): line group `seg` of a row is its lines [seg * LPS, seg * LPS + LPS) with LPS =
 // lines_per_item(width), so an item is at most SEG pixels unless a single line is longer.  height * width < MAX_PIXELS keeps every pixel
 // index, every partial sum (<= 255 per pixel) and a row's whole sum inside 32 bits.
 constexpr int64_t MAX_PIXELS = (int64_t)1 << 24;
-
-// the one rule both launches cut a row by (ops.gray_partial_segments states it for the workspace): whole lines per item
-inline int64_t lines_per_item(int64_t width) { return width >= SEG ? 1 : SEG / width; }
 
 // the sum of v over the workgroup, in every thread (integers: exact in any order)
 __device__ __forceinline__ uint32_t block_sum(uint32_t v) {
@@ -195,23 +219,20 @@ __global__ __launch_bounds__(BLOCK) void rows_gray_partials_kernel(const uint64_
                                                                     int64_t items) {
     const int64_t plane = height * width;
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int64_t row = item / segs, seg = item - row * segs;
-        const uint64_t sa = src[row];
-        if (sa == 0) continue;                                           // "leave this row alone" (uniform over the workgroup)
-        const int64_t l0 = seg * lps, nl = height - l0 < lps ? height - l0 : lps;
-        const uint8_t* s = reinterpret_cast<const uint8_t*>(sa) + l0 * width;
-        const uint32_t np = (uint32_t)(nl * width);                      // pixels of this item
+        Item it;
+        if (!decode_item(item, segs, lps, height, width, src, nullptr, it)) continue;
+        const uint32_t np = (uint32_t)(it.nl * width);                   // pixels of this item
         uint32_t acc = 0;
-        if (((uint64_t)width | sa) % 16 == 0) {                          // (then `plane` is a multiple of 16 too)
-            const uint4* r = reinterpret_cast<const uint4*>(s);
-            const uint4* g = reinterpret_cast<const uint4*>(s + plane);
-            const uint4* b = reinterpret_cast<const uint4*>(s + 2 * plane);
+        if (it.vec) {                                                    // (then `plane` is a multiple of 16 too)
+            const uint4* r = reinterpret_cast<const uint4*>(it.s);
+            const uint4* g = reinterpret_cast<const uint4*>(it.s + plane);
+            const uint4* b = reinterpret_cast<const uint4*>(it.s + 2 * plane);
             for (uint32_t i = threadIdx.x; i < np / 16; i += BLOCK) {
                 const uint4 x = r[i], y = g[i], z = b[i];
                 acc += gray_sum4(x.x, y.x, z.x) + gray_sum4(x.y, y.y, z.y) + gray_sum4(x.z, y.z, z.z) + gray_sum4(x.w, y.w, z.w);
             }
         } else {
-            for (uint32_t i = threadIdx.x; i < np; i += BLOCK) acc += gray(s[i], s[plane + i], s[2 * plane + i]);
+            for (uint32_t i = threadIdx.x; i < np; i += BLOCK) acc += gray(it.s[i], it.s[plane + i], it.s[2 * plane + i]);
         }
         acc = block_sum(acc);
         if (threadIdx.x == 0) partials[item] = acc;                      // item = row * segs + seg: one plain store
@@ -337,48 +358,31 @@ __global__ __launch_bounds__(BLOCK) void copy_rows_u8_jitter_kernel(const uint64
                                                                      int64_t lps, int64_t segs, int64_t items) {
     const int64_t plane = height * width;
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int64_t row = item / segs, seg = item - row * segs;
-        const uint64_t sa = src[row];
-        if (sa == 0) continue;                                           // "leave this row alone"
-        const uint64_t da = dst[row];
-        const int64_t l0 = seg * lps, nl = height - l0 < lps ? height - l0 : lps;
-        const uint8_t* s = reinterpret_cast<const uint8_t*>(sa) + l0 * width;
-        uint8_t* d = reinterpret_cast<uint8_t*>(da) + l0 * width;
-        const bool mirror = flip != nullptr && flip[row] != 0;
-        const bool vec = ((uint64_t)width | sa | da) % 16 == 0;          // every real frame (then `plane` is a multiple of 16 too)
+        Item it;
+        if (!decode_item(item, segs, lps, height, width, src, dst, it)) continue;
+        const bool mirror = flip != nullptr && flip[it.row] != 0;          // (it.vec: then `plane` is a multiple of 16 too)
         Jitter j = {1.f, 1.f, 1.f, 0.f};
-        if (factors) { j.c = factors[3 * row]; j.b = factors[3 * row + 1]; j.s = factors[3 * row + 2]; }
+        if (factors) { j.c = factors[3 * it.row]; j.b = factors[3 * it.row + 1]; j.s = factors[3 * it.row + 2]; }
         // everything below branches on the row alone: uniform over the workgroup
         const int stages = (j.c != 1.f ? 1 : 0) | (j.b != 1.f ? 2 : 0) | (j.s != 1.f ? 4 : 0);
         if (stages == 0) {                                               // the plain or mirrored body, plane by plane
-            for (int p = 0; p < 3; ++p) {
-                const uint8_t* sp = s + p * plane;
-                uint8_t* dp = d + p * plane;
-                if (!mirror) {
-                    const int64_t nb = nl * width;                       // (one segment unless a single line is longer than SEG)
-                    for (int64_t k = 0; k * SEG < nb; ++k) copy_segment(sp, dp, nb, k);
-                } else if (vec) {
-                    flip_lines<uint4>(sp, dp, width / 16, nl);
-                } else {
-                    flip_lines<uint8_t>(sp, dp, width, nl);
-                }
-            }
+            for (int p = 0; p < 3; ++p) copy_or_mirror_lines(it.s + p * plane, it.d + p * plane, width, it.nl, mirror, it.vec);
             continue;
         }
         if (stages & 1) {                                                // the contrast pivot: the row's partials, in integers
             uint32_t acc = 0;
-            for (int64_t t = threadIdx.x; t < segs; t += BLOCK) acc += partials[row * segs + t];
+            for (int64_t t = threadIdx.x; t < segs; t += BLOCK) acc += partials[it.row * segs + t];
             const uint64_t sum = block_sum(acc);
             j.mean = (float)(uint32_t)((2 * sum + (uint64_t)plane) / (2 * (uint64_t)plane));
         }
         switch (stages) {
-            case 1: jitter_item<true, false, false>(s, d, plane, width, nl, vec, mirror, j); break;
-            case 2: jitter_item<false, true, false>(s, d, plane, width, nl, vec, mirror, j); break;
-            case 3: jitter_item<true, true, false>(s, d, plane, width, nl, vec, mirror, j); break;
-            case 4: jitter_item<false, false, true>(s, d, plane, width, nl, vec, mirror, j); break;
-            case 5: jitter_item<true, false, true>(s, d, plane, width, nl, vec, mirror, j); break;
-            case 6: jitter_item<false, true, true>(s, d, plane, width, nl, vec, mirror, j); break;
-            default: jitter_item<true, true, true>(s, d, plane, width, nl, vec, mirror, j); break;
+            case 1: jitter_item<true, false, false>(it.s, it.d, plane, width, it.nl, it.vec, mirror, j); break;
+            case 2: jitter_item<false, true, false>(it.s, it.d, plane, width, it.nl, it.vec, mirror, j); break;
+            case 3: jitter_item<true, true, false>(it.s, it.d, plane, width, it.nl, it.vec, mirror, j); break;
+            case 4: jitter_item<false, false, true>(it.s, it.d, plane, width, it.nl, it.vec, mirror, j); break;
+            case 5: jitter_item<true, false, true>(it.s, it.d, plane, width, it.nl, it.vec, mirror, j); break;
+            case 6: jitter_item<false, true, true>(it.s, it.d, plane, width, it.nl, it.vec, mirror, j); break;
+            default: jitter_item<true, true, true>(it.s, it.d, plane, width, it.nl, it.vec, mirror, j); break;
         }
     }
 }
@@ -390,8 +394,7 @@ extern "C" int din_copy_rows_u8(const uint64_t* src, const uint64_t* dst, int n,
     if (n == 0 || bytes == 0) return DIN_OK;
     DIN_REQUIRE(src && dst, "copy_rows_u8: null address table with n = %d", n);
     const int64_t segs = ceil_div64(bytes, SEG), items = segs * (int64_t)n;
-    const int grid = (int)(items < GRID_CAP ? items : GRID_CAP);
-    hipLaunchKernelGGL(copy_rows_u8_kernel, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, dst, bytes, segs, items);
+    hipLaunchKernelGGL(copy_rows_u8_kernel, dim3(capped_grid(items)), dim3(BLOCK), 0, as_stream(stream), src, dst, bytes, segs, items);
     DIN_CHECK_LAUNCH("copy_rows_u8");
     return DIN_OK;
 }
@@ -403,11 +406,9 @@ extern "C" int din_copy_rows_u8_flip(const uint64_t* src, const uint64_t* dst, c
     if (n == 0 || lines == 0 || width == 0) return DIN_OK;
     DIN_REQUIRE(lines <= INT64_MAX / width, "copy_rows_u8_flip: lines * width = %lld * %lld overflows", (long long)lines, (long long)width);
     DIN_REQUIRE(src && dst, "copy_rows_u8_flip: null address table with n = %d", n);
-    const int64_t lps = width >= SEG ? 1 : SEG / width;                  // whole lines per work item
-    const int64_t segs = ceil_div64(lines, lps), items = segs * (int64_t)n;
-    const int grid = (int)(items < GRID_CAP ? items : GRID_CAP);
-    hipLaunchKernelGGL(copy_rows_u8_flip_kernel, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, dst, flip, lines, width, lps, segs,
-                       items);
+    const int64_t lps = lines_per_item(width), segs = ceil_div64(lines, lps), items = segs * (int64_t)n;
+    hipLaunchKernelGGL(copy_rows_u8_flip_kernel, dim3(capped_grid(items)), dim3(BLOCK), 0, as_stream(stream), src, dst, flip, lines, width,
+                       lps, segs, items);
     DIN_CHECK_LAUNCH("copy_rows_u8_flip");
     return DIN_OK;
 }
@@ -443,9 +444,8 @@ extern "C" int din_rows_gray_partials(const uint64_t* src, uint32_t* partials, i
     if (rc != 0) return rc < 0 ? rc : DIN_OK;
     DIN_REQUIRE(src && partials, "rows_gray_partials: null address table or partials with n = %d", n);
     const int64_t lps = lines_per_item(width), segs = ceil_div64(height, lps), items = segs * (int64_t)n;
-    const int grid = (int)(items < GRID_CAP ? items : GRID_CAP);
-    hipLaunchKernelGGL(rows_gray_partials_kernel, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, partials, height, width, lps, segs,
-                       items);
+    hipLaunchKernelGGL(rows_gray_partials_kernel, dim3(capped_grid(items)), dim3(BLOCK), 0, as_stream(stream), src, partials, height, width,
+                       lps, segs, items);
     DIN_CHECK_LAUNCH("rows_gray_partials");
     return DIN_OK;
 }
@@ -458,9 +458,8 @@ extern "C" int din_copy_rows_u8_jitter(const uint64_t* src, const uint64_t* dst,
     DIN_REQUIRE((factors == nullptr) == (partials == nullptr), "copy_rows_u8_jitter: factors and partials come together (%s is null)",
                 factors ? "partials" : "factors");
     const int64_t lps = lines_per_item(width), segs = ceil_div64(height, lps), items = segs * (int64_t)n;
-    const int grid = (int)(items < GRID_CAP ? items : GRID_CAP);
-    hipLaunchKernelGGL(copy_rows_u8_jitter_kernel, dim3(grid), dim3(BLOCK), 0, as_stream(stream), src, dst, flip, factors, partials, height,
-                       width, lps, segs, items);
+    hipLaunchKernelGGL(copy_rows_u8_jitter_kernel, dim3(capped_grid(items)), dim3(BLOCK), 0, as_stream(stream), src, dst, flip, factors,
+                       partials, height, width, lps, segs, items);
     DIN_CHECK_LAUNCH("copy_rows_u8_jitter");
     return DIN_OK;
 }

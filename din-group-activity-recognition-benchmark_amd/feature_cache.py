@@ -217,10 +217,10 @@ class FeatureLoader(CachedLoader):
     """a DataLoader of a `frame_ids=True` dataset together with the feature cache of that dataset: what the stage-2 trainer's passes
     receive in place of the loader when cfg.feature_cache_gb > 0"""
 
-    def feed(self, device, flip=None, jitter=None) -> FeatureFeed:
-        if flip is not None:                         # (train_net refuses the combination first: frame_cache.flip_refusal)
+    def feed(self, device, augment=None) -> FeatureFeed:
+        if augment is not None and augment.flip is not None:       # (train_net refuses the combination first: frame_cache.flip_refusal)
             raise ValueError("flip augmentation cannot be fed from the feature cache: its rows belong to the unmirrored frames")
-        if jitter is not None:                       # (likewise: frame_cache.jitter_refusal)
+        if augment is not None and augment.jitter is not None:     # (likewise: frame_cache.jitter_refusal)
             raise ValueError("colour jitter cannot be fed from the feature cache: its rows belong to the frames as decoded")
         return FeatureFeed(self.loader, device, self.cache, self.dataset)
 

@@ -109,39 +109,6 @@ class SlotTable:
         return {"hits": self.hits, "misses": self.misses, "inserted": self.inserted, "bytes": self.bytes}
 
 
-class TableUpload:
-    """the rotating pinned buffers the int64 tables of a launch (addresses, flip flags) travel in"""
-
-    TABLE_SLOTS = 4                                  # pinned address-table buffers in rotation (one batch uses one)
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self._pinned: List[Optional[torch.Tensor]] = [None] * self.TABLE_SLOTS
-        self._sent: List[Optional[torch.cuda.Event]] = [None] * self.TABLE_SLOTS
-        self._turn = 0
-
-    def _upload(self, *tables: Sequence[int]) -> List[torch.Tensor]:
-        """int64 address tables -> device, in ONE asynchronous copy on the current stream out of a pinned buffer that is reused only after
-        the copy it last fed has finished"""
-        total = sum(len(t) for t in tables)
-        k = self._turn = (self._turn + 1) % self.TABLE_SLOTS
-        if self._sent[k] is not None:
-            self._sent[k].synchronize()
-        buf = self._pinned[k]
-        if buf is None or buf.numel() < total:
-            buf = self._pinned[k] = torch.empty(max(total, 1024), dtype=torch.int64).pin_memory()
-        host = buf.numpy()
-        at, views = 0, []
-        for t in tables:
-            host[at:at + len(t)] = t
-            views.append((at, len(t)))
-            at += len(t)
-        dev = buf[:total].to(self.device, non_blocking=True)
-        self._sent[k] = torch.cuda.Event()
-        self._sent[k].record(torch.cuda.current_stream(self.device))
-        return [dev[a:a + n] for a, n in views]
-
-
 def _f32_as_table(values: np.ndarray) -> np.ndarray:
     """float32 values as int64 words (an odd count is padded with one zero), so that they travel in TableUpload's buffer"""
     flat = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
@@ -165,17 +132,85 @@ class GrayPartials:
         return self.buf
 
 
-def jitter_gather(partials: GrayPartials, frame_shape, d_src: torch.Tensor, d_dst: torch.Tensor, d_flags: Optional[torch.Tensor],
-                  d_factor_words: torch.Tensor) -> None:
-    """the two launches of a jittered batch on the current stream, in place of the plain or mirrored gather: the grey partials of the
-    R source rows, then din_copy_rows_u8_jitter.  d_src, d_dst, d_flags (or None): the uploaded tables; d_factor_words: the uploaded
-    `_f32_as_table` of the float32 [R, 3] factors (contrast, brightness, saturation)."""
-    from . import ops
-    height, width, rows = int(frame_shape[-2]), int(frame_shape[-1]), d_src.numel()
-    d_factors = d_factor_words.view(torch.float32)[:3 * rows]
-    work = partials.of(rows, height, width)
-    ops.rows_gray_partials(d_src, work, height, width)
-    ops.copy_rows_u8_jitter(d_src, d_dst, d_flags, d_factors, work, height, width)
+def drawn_rows(rows: int, frame_shape, flip_rows, jitter_rows) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+    """what a batch of `rows` frames drew, as the gather takes it: (bool [rows] or None, float32 [rows, 3] or None).  No flag set is
+    the same as no flags, all factors 1 the same as no factors; ValueError for what cannot be launched."""
+    flags = None if flip_rows is None else np.asarray(flip_rows).reshape(-1) != 0
+    if flags is not None and len(flags) != rows:
+        raise ValueError(f"frame gather: {len(flags)} flip flags for {rows} rows")
+    factors = None if jitter_rows is None else np.asarray(jitter_rows, dtype=np.float32)
+    if factors is not None and factors.shape != (rows, 3):
+        raise ValueError(f"frame gather: jitter factors {factors.shape} for {rows} rows (one triple per row)")
+    if factors is not None and not np.isfinite(factors).all():
+        raise ValueError("frame gather: a jitter factor is not finite")
+    if factors is not None and (factors == 1).all():
+        factors = None
+    if factors is not None and (len(frame_shape) != 3 or frame_shape[0] != 3):
+        raise ValueError(f"frame gather: colour jitter works on [3, H, W] frames, these are {tuple(frame_shape)}")
+    return (flags if flags is not None and flags.any() else None), factors
+
+
+class TableUpload:
+    """the rotating pinned buffers the int64 tables of a launch (addresses, flip flags, colour factors) travel in, and the one place
+    that chooses the gather launch of a batch (`gather_rows`)"""
+
+    TABLE_SLOTS = 4                                  # pinned address-table buffers in rotation (one batch uses one)
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._pinned: List[Optional[torch.Tensor]] = [None] * self.TABLE_SLOTS
+        self._sent: List[Optional[torch.cuda.Event]] = [None] * self.TABLE_SLOTS
+        self._turn = 0
+        self._gray = GrayPartials(device)            # colour jitter's workspace (nothing is allocated until a batch is jittered)
+
+    def _upload(self, *tables: Sequence[int]) -> List[torch.Tensor]:
+        """int64 address tables -> device, in ONE asynchronous copy on the current stream out of a pinned buffer that is reused only after
+        the copy it last fed has finished"""
+        total = sum(len(t) for t in tables)
+        k = self._turn = (self._turn + 1) % self.TABLE_SLOTS
+        if self._sent[k] is not None:
+            self._sent[k].synchronize()
+        buf = self._pinned[k]
+        if buf is None or buf.numel() < total:
+            buf = self._pinned[k] = torch.empty(max(total, 1024), dtype=torch.int64).pin_memory()
+        host = buf.numpy()
+        at, views = 0, []
+        for t in tables:
+            host[at:at + len(t)] = t
+            views.append((at, len(t)))
+            at += len(t)
+        dev = buf[:total].to(self.device, non_blocking=True)
+        self._sent[k] = torch.cuda.Event()
+        self._sent[k].record(torch.cuda.current_stream(self.device))
+        return [dev[a:a + n] for a, n in views]
+
+    def gather_rows(self, src: Sequence[int], dst: Sequence[int], frame_shape, flip_rows=None, jitter_rows=None,
+                    insert: Optional[Tuple[Sequence[int], Sequence[int]]] = None) -> Optional[torch.Tensor]:
+        """the gather of a batch on the current stream: row i goes from address src[i] to dst[i], mirrored where flip_rows[i] is set and
+        jittered with jitter_rows[i] = (contrast, brightness, saturation) (`drawn_rows`).  All tables cross in ONE upload; the address
+        lists `insert` = (src, dst) ride in it and are copied first, by the plain din_copy_rows_u8.  Then din_copy_rows_u8, or
+        din_copy_rows_u8_flip where a row is mirrored, or din_rows_gray_partials + din_copy_rows_u8_jitter (mirroring included) where
+        one is jittered.  Returns the device flags (int64 [R], for the labels' launch), None when nothing is mirrored."""
+        from . import ops
+        flags, factors = drawn_rows(len(src), frame_shape, flip_rows, jitter_rows)
+        fb, width = int(np.prod(frame_shape)), int(frame_shape[-1])
+        tables = [src, dst] + ([] if flags is None else [flags.astype(np.int64)]) + ([] if factors is None else [_f32_as_table(factors)])
+        if insert is not None:
+            d_ins_src, d_ins_dst, *d = self._upload(*insert, *tables)
+            ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)                  # (plain: a slot holds the frame as decoded, never mirrored)
+        else:
+            d = self._upload(*tables)
+        d_src, d_dst, d_flags = d[0], d[1], (None if flags is None else d[2])
+        if factors is not None:
+            height = int(frame_shape[-2])
+            work = self._gray.of(len(src), height, width)
+            ops.rows_gray_partials(d_src, work, height, width)
+            ops.copy_rows_u8_jitter(d_src, d_dst, d_flags, d[-1].view(torch.float32)[:3 * len(src)], work, height, width)
+        elif flags is not None:
+            ops.copy_rows_u8_flip(d_src, d_dst, d_flags, fb // width, width)
+        else:
+            ops.copy_rows_u8(d_src, d_dst, fb)
+        return d_flags
 
 
 class SlotStore(TableUpload):
@@ -219,36 +254,18 @@ class FrameCache(SlotStore):
         self.frame_bytes = int(np.prod(self.frame_shape))
         super().__init__(device, self.frame_bytes, capacity_bytes, chunk_frames)
         self.flip_flags: Optional[torch.Tensor] = None      # the device flags (int64 [R]) of the last build_batch, None when it mirrored nothing
-        self._gray = GrayPartials(device)                   # colour jitter's workspace (nothing is allocated until a batch is jittered)
 
     def build_batch(self, frame_ids, miss_pos=(), miss_rows: Optional[torch.Tensor] = None,
                     flip_rows=None, jitter_rows=None) -> Tuple[torch.Tensor, List[int]]:
         """frame_ids [R] (host), miss_pos [M] (host: which of the R rows the uploaded frames are), miss_rows uint8 [M, *frame_shape] on
         the device -> (uint8 [R, *frame_shape] on the device, the frame ids inserted by this call).  On the current stream: one launch
-        that copies the new frames into free slots, then one launch that gathers all R rows (slot, or uploaded row where the cache has
-        no room).  flip_rows [R] (host, bool; flip augmentation): the rows the gather mirrors left-right on their way out -- the slots
-        always hold the frame as decoded.  Where any is set the gather is din_copy_rows_u8_flip, its flags travel with the address
-        tables and stay in `self.flip_flags` for the labels' launch; otherwise the two launches are the ones described above.
-        jitter_rows float32 [R, 3] (host; colour jitter): the (contrast, brightness, saturation) factors of every row.  Where any
-        differs from 1 the gather is din_rows_gray_partials + din_copy_rows_u8_jitter over all R rows, mirroring included, whether a
-        row comes from a slot or from an uploaded frame; the insert stays plain.  All ones is the same as None."""
-        from . import ops
+        that copies the new frames into free slots, then the gather of all R rows (slot, or uploaded row where the cache has no room)
+        as `gather_rows` chooses it from flip_rows (host, bool [R]) and jitter_rows (host, float32 [R, 3]): plain, mirrored or jittered
+        on the way out -- the slots always hold the frame as decoded.  The device flags of a mirrored batch stay in `self.flip_flags`
+        for the labels' launch."""
         ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
         pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
-        flags = None if flip_rows is None else np.asarray(flip_rows).reshape(-1) != 0
-        if flags is not None and len(flags) != len(ids):
-            raise ValueError(f"build_batch: {len(flags)} flip flags for {len(ids)} rows")
-        if flags is not None and not flags.any():
-            flags = None
-        factors = None if jitter_rows is None else np.asarray(jitter_rows, dtype=np.float32)
-        if factors is not None and factors.shape != (len(ids), 3):
-            raise ValueError(f"build_batch: jitter factors {factors.shape} for {len(ids)} rows (one triple per row)")
-        if factors is not None and not np.isfinite(factors).all():
-            raise ValueError("build_batch: a jitter factor is not finite")
-        if factors is not None and (factors == 1).all():
-            factors = None
-        if factors is not None and (len(self.frame_shape) != 3 or self.frame_shape[0] != 3):
-            raise ValueError(f"build_batch: colour jitter works on [3, H, W] frames, the cache holds {self.frame_shape}")
+        drawn = drawn_rows(len(ids), self.frame_shape, flip_rows, jitter_rows)    # (refused here, before the table takes a frame in)
         if len(pos):
             if miss_rows is None or not miss_rows.is_cuda or miss_rows.dtype != torch.uint8 or not miss_rows.is_contiguous() \
                     or tuple(miss_rows.shape) != (len(pos),) + self.frame_shape:
@@ -279,24 +296,7 @@ class FrameCache(SlotStore):
             else:
                 raise KeyError(f"frame {fid} is neither resident nor among the uploaded frames of this batch")
         dst = [out_ptr + i * fb for i in range(len(ids))]
-        self.flip_flags = None
-        if factors is not None:
-            extra = [] if flags is None else [flags.astype(np.int64)]
-            d_ins_src, d_ins_dst, d_src, d_dst, *d_extra = self._upload(ins_src, ins_dst, src, dst, *extra, _f32_as_table(factors))
-            if flags is not None:
-                self.flip_flags = d_extra[0]
-            ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)             # (the insert stays plain: a slot holds the frame as decoded)
-            jitter_gather(self._gray, self.frame_shape, d_src, d_dst, self.flip_flags, d_extra[-1])
-            return out, new_ids
-        if flags is None:
-            d_ins_src, d_ins_dst, d_src, d_dst = self._upload(ins_src, ins_dst, src, dst)
-            ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)             # (no launch when nothing is new)
-            ops.copy_rows_u8(d_src, d_dst, fb)
-            return out, new_ids
-        d_ins_src, d_ins_dst, d_src, d_dst, self.flip_flags = self._upload(ins_src, ins_dst, src, dst, flags.astype(np.int64))
-        ops.copy_rows_u8(d_ins_src, d_ins_dst, fb)                 # (the insert stays plain: a slot is never mirrored)
-        width = self.frame_shape[-1]
-        ops.copy_rows_u8_flip(d_src, d_dst, self.flip_flags, fb // width, width)
+        self.flip_flags = self.gather_rows(src, dst, self.frame_shape, *drawn, insert=(ins_src, ins_dst))
         return out, new_ids
 
     def insert(self, frame_ids, rows: torch.Tensor) -> List[int]:
@@ -354,10 +354,8 @@ class CachedFeed:
     device.  Only the frames the workers decoded are uploaded (DeviceFeed overlaps that with the previous step); the batch is built on
     the compute stream by `cache.build_batch`, and `dataset.resident` is marked for what went in."""
 
-    def __init__(self, loader: Iterable, device, cache: FrameCache, dataset, flip: Optional["EpochFlips"] = None,
-                 jitter: Optional["EpochJitter"] = None):
-        self.loader, self.device, self.cache, self.dataset, self.flip = loader, torch.device(device), cache, dataset, flip
-        self.jitter = jitter
+    def __init__(self, loader: Iterable, device, cache: FrameCache, dataset, augment: Optional["PassAugment"] = None):
+        self.loader, self.device, self.cache, self.dataset, self.augment = loader, torch.device(device), cache, dataset, augment
         self._kept: collections.deque = collections.deque()
         self._feed = DeviceFeed(_HostSide(loader, self._kept), self.device)
 
@@ -365,16 +363,13 @@ class CachedFeed:
         self._kept.clear()
         for miss_rows, *labels in self._feed:
             shape, ids, pos = self._kept.popleft()
-            # flip augmentation: one draw per clip, repeated over its T rows; a batch without a flagged clip is built exactly as without it
-            rows = None if self.flip is None else self.flip.rows(shape[0], shape[1])
-            # colour jitter: one triple of factors per clip, repeated likewise; a batch whose factors are all 1 is built as without it
-            factors = None if self.jitter is None else self.jitter.rows(shape[0], shape[1])
-            kw = {} if factors is None else {"jitter_rows": factors}
-            images, new_ids = self.cache.build_batch(ids, pos, miss_rows, flip_rows=rows, **kw)
+            # one draw per clip, repeated over its T rows; a batch without a drawn clip is built exactly as without augmentation
+            rows, factors = (None, None) if self.augment is None else self.augment.rows(shape[0], shape[1])
+            images, new_ids = self.cache.build_batch(ids, pos, miss_rows, flip_rows=rows, jitter_rows=factors)
             if new_ids:
                 self.dataset.resident[torch.as_tensor(new_ids, dtype=torch.int64)] = 1
             if rows is not None:
-                self.flip.mirror_labels(labels, self.cache.flip_flags)
+                self.augment.mirror_labels(labels, self.cache.flip_flags)
             yield (images.view(shape + self.cache.frame_shape), *labels)
 
     def __len__(self):
@@ -388,10 +383,8 @@ class CachedLoader:
     def __init__(self, loader, cache: FrameCache, dataset):
         self.loader, self.cache, self.dataset = loader, cache, dataset
 
-    def feed(self, device, flip: Optional["EpochFlips"] = None, jitter: Optional["EpochJitter"] = None) -> CachedFeed:
-        if jitter is None:
-            return CachedFeed(self.loader, device, self.cache, self.dataset, flip)
-        return CachedFeed(self.loader, device, self.cache, self.dataset, flip, jitter=jitter)
+    def feed(self, device, augment: Optional["PassAugment"] = None) -> CachedFeed:
+        return CachedFeed(self.loader, device, self.cache, self.dataset, augment)
 
     def __iter__(self):
         return iter(self.loader)
@@ -477,47 +470,33 @@ def flip_plan(cfg, epoch: int, rank: int) -> Optional[EpochFlips]:
 
 
 class FlippedFeed:
-    """DeviceFeed's iteration contract with flip augmentation and colour jitter over a plain loader (no frame cache): the batch is
-    uploaded as it is and its drawn clips are mirrored and jittered on the device, into a new tensor: one din_copy_rows_u8_flip launch
-    for a batch that is only mirrored, din_rows_gray_partials + one din_copy_rows_u8_jitter launch for a batch with a jittered clip
-    (mirroring included), plus the labels' launch where a clip is mirrored.  A batch without a drawn clip is handed on untouched.
-    flip or jitter may be None; the partials workspace is allocated once and reused."""
+    """DeviceFeed's iteration contract with the augmentations of a training pass (PassAugment) over a plain loader (no frame cache):
+    the batch is uploaded as it is and its drawn clips are mirrored and jittered on the device, into a new tensor, by the launches of
+    `TableUpload.gather_rows`, plus the labels' launch where a clip is mirrored.  A batch without a drawn clip is handed on untouched.
+    The partials workspace is allocated once and reused."""
 
-    def __init__(self, loader: Iterable, device, flip: Optional[EpochFlips], jitter: Optional["EpochJitter"] = None):
-        self.loader, self.device, self.flip, self.jitter = loader, torch.device(device), flip, jitter
+    def __init__(self, loader: Iterable, device, augment: "PassAugment"):
+        self.loader, self.device, self.augment = loader, torch.device(device), augment
         self._feed = DeviceFeed(loader, self.device)
         self._tables = TableUpload(self.device)
-        self._gray = GrayPartials(self.device)
 
     def __iter__(self) -> Iterator:
-        from . import ops
         for batch in self._feed:
             images, *labels = batch
             if images.dtype != torch.uint8 or images.dim() < 3 or not images.is_contiguous():
                 raise ValueError(f"flip_prob and color_jitter work on contiguous uint8 [B, T, ..., W] frames on the device; the loader "
                                  f"gave {images.dtype} {tuple(images.shape)}")
-            num_clips, num_frames = images.shape[0], images.shape[1]
-            rows = None if self.flip is None else self.flip.rows(num_clips, num_frames)
-            factors = None if self.jitter is None else self.jitter.rows(num_clips, num_frames)
+            rows, factors = self.augment.rows(images.shape[0], images.shape[1])
             if rows is None and factors is None:
                 yield batch
                 continue
             out = torch.empty_like(images)
-            width, fb = images.shape[-1], images[0, 0].numel()
-            src = [images.data_ptr() + i * fb for i in range(num_clips * num_frames)]
-            dst = [out.data_ptr() + i * fb for i in range(num_clips * num_frames)]
-            if factors is None:
-                d_src, d_dst, d_flags = self._tables._upload(src, dst, rows.astype(np.int64))
-                ops.copy_rows_u8_flip(d_src, d_dst, d_flags, fb // width, width)
-            else:
-                if images.dim() != 5 or images.shape[2] != 3:
-                    raise ValueError(f"color_jitter works on [B, T, 3, H, W] frames; the loader gave {tuple(images.shape)}")
-                extra = [] if rows is None else [rows.astype(np.int64)]
-                d_src, d_dst, *d_extra = self._tables._upload(src, dst, *extra, _f32_as_table(factors))
-                d_flags = None if rows is None else d_extra[0]
-                jitter_gather(self._gray, images.shape[2:], d_src, d_dst, d_flags, d_extra[-1])
+            fb = images[0, 0].numel()
+            src = [images.data_ptr() + i * fb for i in range(images.shape[0] * images.shape[1])]
+            dst = [out.data_ptr() + i * fb for i in range(images.shape[0] * images.shape[1])]
+            d_flags = self._tables.gather_rows(src, dst, images.shape[2:], rows, factors)
             if rows is not None:
-                self.flip.mirror_labels(labels, d_flags)
+                self.augment.mirror_labels(labels, d_flags)
             yield [out, *labels]
 
     def __len__(self):
@@ -527,7 +506,7 @@ class FlippedFeed:
 # ---- colour jitter (cfg.color_jitter) -----------------------------------------------------------------------------------------------------
 # In a training pass every clip draws three fp32 factors f = 1 + a * u, u uniform in [-1, 1], with the amplitudes a of
 # cfg.color_jitter = (brightness, contrast, saturation); all T frames of the clip go through PIL.ImageEnhance.Contrast, .Brightness and
-# .Color with them, in that order, byte for byte as Pillow computes them (include/din_hip_aug.h states the arithmetic), inside the launch
+# .Color with them, in that order, byte for byte as Pillow computes them (include/din_hip.h states the arithmetic), inside the launch
 # that builds the batch.  Boxes and labels do not change.  Evaluation passes never jitter.
 KERNEL_ORDER = (1, 0, 2)        # cfg.color_jitter and JitterPlan's draws are (brightness, contrast, saturation); the launch takes
 #                                 (contrast, brightness, saturation), the order the stages are applied in
@@ -599,22 +578,40 @@ def jitter_plan(cfg, epoch: int, rank: int) -> Optional[EpochJitter]:
     return JitterPlan(j, cfg.train_random_seed, rank).epoch(epoch)
 
 
-def feed_for(loader, device, flip: Optional[EpochFlips] = None, jitter: Optional[EpochJitter] = None):
-    """the device feed of a pass: CachedFeed for a CachedLoader, input_feed.DeviceFeed for anything else; with the flips of a training
-    pass (`flip_plan`), the CachedFeed mirrors inside its gather and a plain loader goes through FlippedFeed; with its colour factors
-    (`jitter_plan`) likewise, mirrored or not"""
-    if jitter is not None:
-        return loader.feed(device, flip, jitter=jitter) if isinstance(loader, CachedLoader) else FlippedFeed(loader, device, flip, jitter=jitter)
-    if flip is None:
-        return loader.feed(device) if isinstance(loader, CachedLoader) else DeviceFeed(loader, device)
-    return loader.feed(device, flip) if isinstance(loader, CachedLoader) else FlippedFeed(loader, device, flip)
+class PassAugment:
+    """the augmentations of one training pass of one rank: its flips and its colour factors, either may be None"""
+
+    def __init__(self, flip: Optional[EpochFlips] = None, jitter: Optional[EpochJitter] = None):
+        self.flip, self.jitter = flip, jitter
+
+    def rows(self, num_clips: int, num_frames: int) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """the next batch's draws as the gather takes them: (EpochFlips.rows or None, EpochJitter.rows or None) -- the flips' stream
+        first, then the jitter's, each drawn exactly once per batch whether or not the other is on"""
+        rows = None if self.flip is None else self.flip.rows(num_clips, num_frames)
+        return rows, (None if self.jitter is None else self.jitter.rows(num_clips, num_frames))
+
+    def mirror_labels(self, labels, flags: torch.Tensor) -> None:
+        self.flip.mirror_labels(labels, flags)
+
+    def stats(self) -> dict:
+        """host counts for the pass's info: clips mirrored (with cfg.flip_prob > 0), clips that drew a colour factor other than 1"""
+        return {**({} if self.flip is None else {"flipped_clips": self.flip.flipped}),
+                **({} if self.jitter is None else {"jittered_clips": self.jitter.jittered})}
 
 
-def augmentations(cfg, epoch: int, rank: int) -> Tuple[Optional[EpochFlips], Optional[EpochJitter], dict]:
-    """what a trainer's training pass hands to `feed_for`: (flips, jitter, the keyword arguments that carry the jitter -- none when
-    cfg.color_jitter is None, so that a run without it calls feed_for exactly as before)"""
+def feed_for(loader, device, augment: Optional[PassAugment] = None):
+    """the device feed of a pass: CachedFeed for a CachedLoader, input_feed.DeviceFeed for anything else; with the augmentations of a
+    training pass (`augmentations`) the CachedFeed mirrors and jitters inside its gather and a plain loader goes through FlippedFeed"""
+    if isinstance(loader, CachedLoader):
+        return loader.feed(device, augment)
+    return DeviceFeed(loader, device) if augment is None else FlippedFeed(loader, device, augment)
+
+
+def augmentations(cfg, epoch: int, rank: int) -> Optional[PassAugment]:
+    """what a trainer's training pass hands to `feed_for`: the flips and colour factors of epoch `epoch` on rank `rank`, or None with
+    cfg.flip_prob == 0 and cfg.color_jitter = None (the pass is fed exactly as an evaluation pass then)"""
     flip, jitter = flip_plan(cfg, epoch, rank), jitter_plan(cfg, epoch, rank)
-    return flip, jitter, ({} if jitter is None else {"jitter": jitter})
+    return None if flip is None and jitter is None else PassAugment(flip, jitter)
 
 
 def end_pass(feed) -> None:

@@ -1048,13 +1048,13 @@ def flip_clip_labels(boxes: Optional[torch.Tensor], activities: Optional[torch.T
                                      classes, _stream()), "flip_clip_labels")
 
 
-GRAY_SEGMENT = 8192             # bytes of one plane per (row, line group) item of the colour-jitter launches (include/din_hip_aug.h)
+GRAY_SEGMENT = 8192             # bytes of one plane per (row, line group) item of the colour-jitter launches (include/din_hip.h)
 GRAY_MAX_PIXELS = 1 << 24       # height * width of a row stays below this: its grey sum is kept in 32 bits
 
 
 def gray_partial_segments(height: int, width: int) -> int:
     """line groups per row of din_rows_gray_partials / din_copy_rows_u8_jitter: whole image lines, max(1, 8192 // width) to a group --
-    the workspace of n rows is n * gray_partial_segments(height, width) uint32 (SEGS of include/din_hip_aug.h, stated here once)"""
+    the workspace of n rows is n * gray_partial_segments(height, width) uint32 (SEGS of include/din_hip.h, stated here once)"""
     height, width = int(height), int(width)
     if height <= 0 or width <= 0:
         return 0
@@ -1095,7 +1095,7 @@ def copy_rows_u8_jitter(src: torch.Tensor, dst: torch.Tensor, flip: Optional[tor
     """copy_rows_u8_flip over uint8 [3, height, width] rows with row i put through PIL.ImageEnhance.Contrast, .Brightness and .Color
     with factors[i] = (contrast, brightness, saturation) on its way (fp32 device tensor [n, 3]); partials: what rows_gray_partials
     wrote for the same src, height and width earlier on this stream.  A row whose factors are all 1 is copied or mirrored as
-    copy_rows_u8_flip does it; factors = partials = None means that for every row (din_copy_rows_u8_jitter, include/din_hip_aug.h)."""
+    copy_rows_u8_flip does it; factors = partials = None means that for every row (din_copy_rows_u8_jitter, include/din_hip.h)."""
     lib = L.load()
     n = _jitter_tables("copy_rows_u8_jitter", (src, dst) + (() if flip is None else (flip,)), n)
     if (factors is None) != (partials is None):

@@ -104,9 +104,8 @@ def _losses(actions_scores, activities_scores, actions_in, activities_in, batch_
 
 def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets, collective, max_batches=None):
     meters = _Meters(cfg, device)
-    # flip: None unless cfg.flip_prob > 0; jitter: None (and no keyword) unless cfg.color_jitter is set
-    flip, jitter, jitter_kw = frame_cache.augmentations(cfg, epoch, parallel.current_rank())
-    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device, flip, **jitter_kw)):
+    augment = frame_cache.augmentations(cfg, epoch, parallel.current_rank())      # None unless cfg.flip_prob > 0 or cfg.color_jitter is set
+    for bi, batch_data in enumerate(frame_cache.feed_for(data_loader, device, augment)):
         if max_batches is not None and bi >= max_batches:
             break
         model.train()
@@ -123,7 +122,7 @@ def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets,
         else:
             optimizer.step()
         meters.add(actions_scores.detach(), actions_in, activities_scores.detach(), activities_in, total_loss, batch_size)
-    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), flip, jitter)
+    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), augment)
 
 
 def _test_pass(data_loader, model, device, epoch, cfg, collective):

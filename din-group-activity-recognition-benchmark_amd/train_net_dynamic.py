@@ -124,9 +124,8 @@ class _Epoch:
 
 def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets, collective, max_batches=None):
     meters = _Epoch(cfg, device)
-    # flip: None unless cfg.flip_prob > 0; jitter: None (and no keyword) unless cfg.color_jitter is set
-    flip, jitter, jitter_kw = frame_cache.augmentations(cfg, epoch, parallel.current_rank())
-    feed = frame_cache.feed_for(data_loader, device, flip, **jitter_kw)
+    augment = frame_cache.augmentations(cfg, epoch, parallel.current_rank())      # None unless cfg.flip_prob > 0 or cfg.color_jitter is set
+    feed = frame_cache.feed_for(data_loader, device, augment)
     for bi, batch_data in enumerate(feed):                             # batch k+1 crosses PCIe on the copy stream during step k
         if max_batches is not None and bi >= max_batches:
             break
@@ -148,16 +147,13 @@ def _train_pass(data_loader, model, device, optimizer, epoch, cfg, grad_buckets,
             optimizer.step()
         meters.add(activities_scores.detach(), activities_in, total_loss)
     frame_cache.end_pass(feed)                                         # (the feature cache's box check; nothing for the other feeds)
-    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), flip, jitter)
+    return add_flip_stats(add_grad_stats(meters.info(epoch), optimizer), augment)
 
 
-def add_flip_stats(info, flip, jitter=None):
-    """with cfg.flip_prob > 0: the number of clips the pass mirrored joins its info (a host count); with cfg.color_jitter set: the
-    number of clips it drew a colour factor other than 1 for (a host count too: nothing is read back)"""
-    if flip is not None:
-        info["flipped_clips"] = flip.flipped
-    if jitter is not None:
-        info["jittered_clips"] = jitter.jittered
+def add_flip_stats(info, augment):
+    """the host counts of the pass's augmentations join its info (frame_cache.PassAugment.stats: `flipped_clips`, `jittered_clips`)"""
+    if augment is not None:
+        info.update(augment.stats())
     return info
 
 

@@ -1,4 +1,4 @@
-"""Host model of the colour jitter (include/din_hip_aug.h), in numpy: PIL.ImageEnhance.Contrast, then .Brightness, then .Color on a uint8
+"""Host model of the colour jitter (include/din_hip.h), in numpy: PIL.ImageEnhance.Contrast, then .Brightness, then .Color on a uint8
 [3, H, W] frame, restated as integer and separately rounded float32 arithmetic.  tests/test_jitter_cpu.py holds this model to Pillow
 itself, byte for byte; tests/test_gpu_jitter.py holds the kernels to this model."""
 import numpy as np

@@ -111,18 +111,38 @@ def test_flip_activities_swaps_the_team_side():
         assert {a[0], b[0]} == {"r", "l"} and a[1:].replace("-", "_") == b[1:].replace("-", "_"), (a, b)
 
 
-def test_feed_for_picks_the_feed_and_refuses_the_feature_cache(monkeypatch):
+def test_feed_for_builds_the_feed_of_every_loader_kind_with_the_very_augmentation_given(monkeypatch):
+    """the wiring of flip and colour jitter together: none, flip, jitter and both, over a plain loader, a CachedLoader and a
+    FeatureLoader.  Each feed receives the very objects given; without an augmentation a training pass is fed exactly as an evaluation
+    pass is; the feature cache refuses every augmentation."""
     from din_amd import feature_cache as FE, frame_cache as FC
-    made = []
-    monkeypatch.setattr(FC, "DeviceFeed", lambda loader, device: made.append(("plain", loader)) or made[-1])
-    monkeypatch.setattr(FC, "FlippedFeed", lambda loader, device, flip: made.append(("flipped", loader, flip)) or made[-1])
-    flip = FC.FlipPlan(0.5, 0, 0).epoch(1)
-    assert FC.feed_for("L", "cpu") == ("plain", "L") and FC.feed_for("L", "cpu", flip) == ("flipped", "L", flip)
-    cached = FC.CachedLoader("L", "C", "D")
-    monkeypatch.setattr(FC, "CachedFeed", lambda *a: a)
-    assert cached.feed("cpu") == ("L", "cpu", "C", "D", None) and FC.feed_for(cached, "cpu", flip) == ("L", "cpu", "C", "D", flip)
-    with pytest.raises(ValueError):
-        FC.feed_for(FE.FeatureLoader("L", "C", "D"), "cpu", flip)
+    monkeypatch.setattr(FC, "DeviceFeed", lambda *a: ("plain",) + a)
+    monkeypatch.setattr(FC, "FlippedFeed", lambda *a: ("flipped",) + a)
+    monkeypatch.setattr(FC, "CachedFeed", lambda *a: ("cached",) + a)
+    monkeypatch.setattr(FE, "FeatureFeed", lambda *a: ("features",) + a)
+    flip, jitter = FC.FlipPlan(0.5, 0, 0).epoch(1), FC.JitterPlan((0.4, 0.4, 0.4), 0, 0).epoch(1)
+    cached, features = FC.CachedLoader("L", "C", "D"), FE.FeatureLoader("L", "C", "D")
+    # none: what an evaluation pass builds (feed_for(loader, device)), and `augmentations` gives None when both settings are off
+    assert FC.augmentations(_cfg(), 1, 0) is None and FC.augmentations(_cfg("collective"), 3, 1) is None
+    assert FC.feed_for("L", "cpu") == FC.feed_for("L", "cpu", None) == ("plain", "L", "cpu")
+    assert FC.feed_for(cached, "cpu") == FC.feed_for(cached, "cpu", None) == cached.feed("cpu") == ("cached", "L", "cpu", "C", "D", None)
+    assert FC.feed_for(features, "cpu") == FC.feed_for(features, "cpu", None) == ("features", "L", "cpu", "C", "D")
+    for f, j in ((flip, None), (None, jitter), (flip, jitter)):
+        augment = FC.PassAugment(f, j)
+        assert augment.flip is f and augment.jitter is j
+        made = FC.feed_for("L", "cpu", augment)
+        assert made == ("flipped", "L", "cpu", augment) and made[-1] is augment
+        made = FC.feed_for(cached, "cpu", augment)
+        assert made == ("cached", "L", "cpu", "C", "D", augment) and made[-1] is augment
+        with pytest.raises(ValueError) as e:
+            FC.feed_for(features, "cpu", augment)
+        assert ("flip augmentation" if f is not None else "colour jitter") in str(e.value) and "feature cache" in str(e.value)
+    # what the trainers hand over: the object `augmentations` makes holds the plans of the two settings
+    both = FC.augmentations(_cfg(flip_prob=0.5, color_jitter=(0.4, 0.4, 0.4)), 1, 0)
+    assert isinstance(both.flip, FC.EpochFlips) and isinstance(both.jitter, FC.EpochJitter)
+    only_flip, only_jitter = FC.augmentations(_cfg(flip_prob=0.5), 1, 0), FC.augmentations(_cfg(color_jitter=(0.4, 0.4, 0.4)), 1, 0)
+    assert isinstance(only_flip.flip, FC.EpochFlips) and only_flip.jitter is None
+    assert only_jitter.flip is None and isinstance(only_jitter.jitter, FC.EpochJitter)
 
 
 def test_header_binding_and_readme_agree_on_the_two_entry_points():
@@ -146,5 +166,5 @@ def test_header_binding_and_readme_agree_on_the_two_entry_points():
         lib = C.CDLL(_lib.LIB_PATH)
         assert all(hasattr(lib, n) for n in want)
     readme = open(os.path.join(ROOT, "README.md")).read()
-    assert f"({len(_lib.header_symbols())} entry points" in readme and len(_lib.header_symbols()) == 120
+    assert f"({len(_lib.header_symbols())} entry points" in readme and len(_lib.header_symbols()) == 122
     assert "## Flip augmentation" in readme

@@ -1,5 +1,5 @@
 """Colour jitter without a GPU: the numpy model (tests/jitter_reference.py) against Pillow's ImageEnhance byte for byte, the integer mean
-rule, the setting and its refusals, the seeded draws, the wiring of the feeds, the second header and its binding."""
+rule, the setting and its refusals, the seeded draws, the pass's augmentation object, the two declarations and their binding."""
 import ctypes as C
 import importlib
 import os
@@ -124,8 +124,7 @@ def test_the_setting_is_off_by_default():
         cfg = _cfg(dataset)
         assert cfg.color_jitter is None
         assert FC.jitter_refusal(cfg) is None and FC.jitter_plan(cfg, 1, 0) is None
-        flip, jitter, kw = FC.augmentations(cfg, 1, 0)
-        assert flip is None and jitter is None and kw == {}
+        assert FC.augmentations(cfg, 1, 0) is None
 
 
 REFUSED = [(dict(color_jitter=0.4), ("color_jitter", "[0, 1)")), (dict(color_jitter=(0.4, 0.4)), ("color_jitter", "[0, 1)")),
@@ -214,47 +213,44 @@ def test_flip_draws_do_not_change_when_the_jitter_is_turned_on():
     for epoch in (1, 2, 7):
         off = FC.flip_plan(_cfg(flip_prob=0.5, train_random_seed=11), epoch, 1)
         cfg = _cfg(flip_prob=0.5, train_random_seed=11, color_jitter=(0.4, 0.4, 0.4))
-        flip, jitter, kw = FC.augmentations(cfg, epoch, 1)
-        assert kw == {"jitter": jitter} and jitter is not None
+        augment = FC.augmentations(cfg, epoch, 1)
+        flip, jitter = augment.flip, augment.jitter
+        assert flip is not None and jitter is not None
         for n in (7, 7, 3):
             assert np.array_equal(jitter.draw(n), jitter.draw(n)) is False               # the jitter's own stream advances ...
             assert np.array_equal(off.draw(n), flip.draw(n))                             # ... and the flips are those of the run without
+        # the same through the one method a feed calls: each stream drawn once per batch, the flips those of the run without jitter
+        off, alone = FC.flip_plan(_cfg(flip_prob=0.5, train_random_seed=11), epoch, 1), FC.jitter_plan(cfg, epoch, 1)
+        augment = FC.augmentations(cfg, epoch, 1)
+        for n in (7, 7, 3):
+            rows, factors = augment.rows(n, 3)
+            want_rows, want_factors = off.rows(n, 3), alone.rows(n, 3)
+            assert (rows is None and want_rows is None) or np.array_equal(rows, want_rows)
+            assert factors.shape == (3 * n, 3) and np.array_equal(factors, want_factors)
+        assert augment.flip.flipped == off.flipped and augment.jitter.jittered == alone.jittered == 17
     e = FC.jitter_plan(_cfg(color_jitter=(0.4, 0.3, 0.2), train_random_seed=11), 2, 1)
     assert np.array_equal(e.draw(64), FC.JitterPlan((0.4, 0.3, 0.2), 11, 1).epoch(2).draw(64))
 
 
-# ---- wiring ----------------------------------------------------------------------------------------------------------------------------
-def test_feed_for_passes_the_jitter_only_when_it_is_on(monkeypatch):
-    from din_amd import feature_cache as FE, frame_cache as FC
-    made = []
-    monkeypatch.setattr(FC, "DeviceFeed", lambda loader, device: made.append(("plain", loader)) or made[-1])
-    monkeypatch.setattr(FC, "FlippedFeed", lambda loader, device, flip, **kw: made.append(("flipped", loader, flip, kw)) or made[-1])
-    flip, jitter = FC.FlipPlan(0.5, 0, 0).epoch(1), FC.JitterPlan((0.4, 0.4, 0.4), 0, 0).epoch(1)
-    assert FC.feed_for("L", "cpu") == ("plain", "L") and FC.feed_for("L", "cpu", flip) == ("flipped", "L", flip, {})
-    assert FC.feed_for("L", "cpu", None, jitter=jitter) == ("flipped", "L", None, {"jitter": jitter})
-    assert FC.feed_for("L", "cpu", flip, jitter=jitter) == ("flipped", "L", flip, {"jitter": jitter})
-    cached = FC.CachedLoader("L", "C", "D")
-    monkeypatch.setattr(FC, "CachedFeed", lambda *a, **kw: a + ((kw,) if kw else ()))
-    assert cached.feed("cpu") == ("L", "cpu", "C", "D", None) and FC.feed_for(cached, "cpu", flip) == ("L", "cpu", "C", "D", flip)
-    assert FC.feed_for(cached, "cpu", flip, jitter=jitter) == ("L", "cpu", "C", "D", flip, {"jitter": jitter})
-    assert FC.feed_for(cached, "cpu", None, jitter=jitter) == ("L", "cpu", "C", "D", None, {"jitter": jitter})
-    with pytest.raises(ValueError):
-        FC.feed_for(FE.FeatureLoader("L", "C", "D"), "cpu", None, jitter=jitter)
-
-
+# ---- wiring (the feeds: tests/test_flip_cpu.py, with the flip) ---------------------------------------------------------------------------
 def test_train_pass_info_counts_jittered_clips_on_the_host():
     from din_amd import frame_cache as FC
     from din_amd.train_net_dynamic import add_flip_stats
-    jitter = FC.JitterPlan((0.4, 0, 0), 0, 0).epoch(1)
+    jitter, flip = FC.JitterPlan((0.4, 0, 0), 0, 0).epoch(1), FC.FlipPlan(1.0, 0, 0).epoch(1)
     jitter.draw(5)
-    assert add_flip_stats({}, None) == {} and add_flip_stats({}, None, None) == {}
-    assert add_flip_stats({}, None, jitter) == {"jittered_clips": 5}
+    flip.draw(3)
+    assert add_flip_stats({}, None) == {} and add_flip_stats({}, FC.PassAugment(None, None)) == {}
+    assert add_flip_stats({}, FC.PassAugment(None, jitter)) == {"jittered_clips": 5}
+    # a key is there only when its part is on
+    assert add_flip_stats({"loss": 1.0}, FC.PassAugment(flip, None)) == {"loss": 1.0, "flipped_clips": 3}
+    assert add_flip_stats({}, FC.PassAugment(flip, jitter)) == {"flipped_clips": 3, "jittered_clips": 5}
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------
 def test_second_header_binding_and_readme_agree():
+    """the jitter half of the one-header check: the two entry points are declared in include/din_hip.h and bound through SIGNATURES"""
     from din_amd import _lib
-    text = open(_lib.AUG_HEADER_PATH).read()
+    text = open(_lib.HEADER_PATH).read()
     want = {"din_rows_gray_partials": "int din_rows_gray_partials(const uint64_t* src, uint32_t* partials, int n, int64_t height, "
                                       "int64_t width, void* stream",
             "din_copy_rows_u8_jitter": "int din_copy_rows_u8_jitter(const uint64_t* src, const uint64_t* dst, const int64_t* flip, "
@@ -262,29 +258,28 @@ def test_second_header_binding_and_readme_agree():
     for name, words in want.items():
         decl = text[text.index(f"int {name}("):]
         assert re.sub(r"\s+", " ", decl[:decl.index(");")]) == words
-    assert set(_lib.aug_header_symbols()) == set(_lib.SIGNATURES_AUG) == set(want)
+    assert set(want) <= set(_lib.header_symbols())
     P, I, L = C.c_void_p, C.c_int, C.c_int64
-    assert _lib.SIGNATURES_AUG["din_rows_gray_partials"] == (I, [P, P, I, L, L, P])
-    assert _lib.SIGNATURES_AUG["din_copy_rows_u8_jitter"] == (I, [P, P, P, P, P, I, L, L, P])
-    assert "PIL.ImageEnhance" in text and "din_hip.h" in text and "#include \"din_hip.h\"" not in text
-    # the first header is what it was: 120 functions, none of them the new ones, ABI version 9, and it does not include the second
-    first = open(_lib.HEADER_PATH).read()
-    assert len(_lib.header_symbols()) == 120 and not set(_lib.header_symbols()) & set(want)
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES) and "din_hip_aug.h" not in first
-    assert "#define DIN_ABI_VERSION 9 " in first and _lib.ABI_VERSION == 9
+    assert _lib.SIGNATURES["din_rows_gray_partials"] == (I, [P, P, I, L, L, P])
+    assert _lib.SIGNATURES["din_copy_rows_u8_jitter"] == (I, [P, P, P, P, P, I, L, L, P])
+    assert "PIL.ImageEnhance" in text
+    # one header: 122 functions, each bound, ABI version 9; the second header and its binding are gone
+    assert len(_lib.header_symbols()) == 122 and set(_lib.header_symbols()) == set(_lib.SIGNATURES)
+    assert "#define DIN_ABI_VERSION 9 " in text and _lib.ABI_VERSION == 9
+    assert not os.path.exists(os.path.join(ROOT, "include", "din_hip_aug.h")) and not hasattr(_lib, "SIGNATURES_AUG")
     if os.path.exists(_lib.LIB_PATH):
         lib = C.CDLL(_lib.LIB_PATH)
         assert all(hasattr(lib, n) for n in want)
     readme = open(os.path.join(ROOT, "README.md")).read()
-    assert "## Colour jitter" in readme and "include/din_hip_aug.h" in readme and "(120 entry points" in readme
+    assert "## Colour jitter" in readme and "(122 entry points" in readme
 
 
 def test_a_library_without_an_aug_symbol_fails_loudly(monkeypatch):
-    """load() binds SIGNATURES_AUG after SIGNATURES with the same error: a library built before the entry points existed is refused"""
+    """load() refuses a library that lacks a bound entry point: one built before the entry points existed, for instance"""
     from din_amd import _lib
     assert os.path.exists(_lib.LIB_PATH), "libdin_hip.so missing: run __graft_entry__.build()"
     monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "SIGNATURES_AUG", dict(_lib.SIGNATURES_AUG, din_rows_gray_partials_of_a_later_build=(C.c_int, [])))
+    monkeypatch.setattr(_lib, "SIGNATURES", dict(_lib.SIGNATURES, din_rows_gray_partials_of_a_later_build=(C.c_int, [])))
     with pytest.raises(_lib.DinError) as e:
         _lib.load()
     assert "din_rows_gray_partials_of_a_later_build" in str(e.value) and "stale build?" in str(e.value)
