@@ -23,6 +23,12 @@ jitter, each a real number in [0, 1).  Every clip of a training batch draws thre
 frames go through PIL.ImageEnhance.Contrast, then .Brightness, then .Color with them -- byte for byte what Pillow computes -- inside the
 batch's gather launch (din_amd/frame_cache.py: JitterPlan; include/din_hip.h); boxes and labels do not change, evaluation passes never
 jitter; refused together with feature_cache_gb > 0.
+feature_cache_path (stage-2 trainer, read only with feature_cache_gb > 0 and refused without it; None = off): a directory in which the
+box-feature caches are kept between runs, one data file per cache (train.dinfc, val.dinfc; train.rank{r}of{w}.dinfc ... with several
+ranks).  A run that finds a file written for the same frames, boxes geometry and backbone weights (din_amd/feature_cache_file.py:
+fingerprint -- the head, the learning rate and the seed are not part of it) starts with those rows resident: it decodes nothing and
+launches no backbone kernel from its first step; a cache that took frames in during an epoch is written after it.  A file of another
+fingerprint is a ValueError naming the field, never overwritten.
 All are opt-in: at 0 / False / None the trainers behave exactly as without them."""
 from __future__ import annotations
 
@@ -49,6 +55,7 @@ _DEFAULTS = dict(
     max_grad_norm=None,
     flip_prob=0.0,
     color_jitter=None,
+    feature_cache_path=None,
 )
 
 

@@ -23,10 +23,17 @@ keep being decoded and computed.  Refusals and the cache's lifetime: train_net_d
 cfg.feature_cache_dtype = 'bf16' (with backbone_dtype = 'bf16' only): the slots hold the row already rounded to bf16, which is what
 fc_emb_1's GEMM multiplies in that mode.  Half the bytes per frame, ONE din_feat_rows_bf16 launch that rounds the computed rows on their
 way to feats and to the slots, and feats arrives as the GEMM's bf16 operand: no cast pass, the same numbers.
+
+cfg.feature_cache_path (a directory; None = off): the rows outlive the call.  `FeatureCache.save` / `load` move the slots between the
+slabs and one data file per cache (feature_cache_file.py: the layout, and the fingerprint that says which runs compute the same rows --
+the head, the learning rate and the seed are not part of it); `CacheFile` is a loader's file, loaded before the first pass and written
+after every pass in which the cache took frames in.  No kernel of its own: copy_ between pinned buffers and slabs on the current stream.
 """
 from __future__ import annotations
 
 import collections
+import os
+import time
 from typing import Iterable, Iterator, List, Optional, Tuple
 
 import numpy as np
@@ -56,6 +63,7 @@ class FeatureCache(SlotStore):
         self.flags: Optional[torch.Tensor] = None    # one uint8 per row gathered since the last check(); din_feat_rows only ever writes 1
         self._flagged: List[np.ndarray] = []         # the frame ids of those rows, in order
         self._used = 0
+        self._file_bufs: Optional[List[torch.Tensor]] = None        # save / load: two pinned buffers of one slab each
 
     def _flag_rows(self, ids: np.ndarray) -> torch.Tensor:
         if self.flags is None:
@@ -138,6 +146,107 @@ class FeatureCache(SlotStore):
         if bad.size:
             raise RuntimeError(f"feature cache: {bad.size} rows were served for other boxes than the ones stored with their features "
                                f"(row, frame id): {[(int(r), int(ids[r])) for r in bad[:16]]}{' ...' if bad.size > 16 else ''}")
+
+    # ---- the cache on disk (feature_cache_file.py: the layout and the fingerprint; train_net_dynamic: when) -------------------------------
+    # Bytes move between a file, two pinned host buffers and the slabs with copy_ on the current stream -- the stream whose launches wrote
+    # the slots and will read them -- so the copies are ordered with those launches, and the host waits only on the event recorded behind
+    # each copy.  No kernel is launched.
+    def _staging(self, k: int) -> torch.Tensor:
+        """pinned buffer k of the two a slab's worth of records travels through"""
+        if self._file_bufs is None:
+            n = self.table.chunk_frames * self.table.stride
+            self._file_bufs = [torch.empty(n, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        return self._file_bufs[k % 2]
+
+    def file_meta(self, fingerprint: dict) -> dict:
+        """what a file of this cache says about itself besides its count: the fingerprint and the slots' geometry"""
+        return {"fingerprint": fingerprint, "row_bytes": self.row_bytes, "box_bytes": self.box_bytes,
+                "dtype": "fp32" if self.dtype == torch.float32 else "bf16"}
+
+    def _slab_blocks(self, count: int) -> Iterator[np.ndarray]:
+        """the first `count` slots as host byte blocks, slab by slab (the slots of a slab are contiguous in device memory): the copy of
+        slab k+1 is in flight while the consumer works on slab k"""
+        stream = torch.cuda.current_stream(self.device)
+        cf, stride = self.table.chunk_frames, self.table.stride
+        used = [min(cf, count - k * cf) * stride for k in range((count + cf - 1) // cf)]
+        events: List[torch.cuda.Event] = []
+
+        def start(k):
+            self._staging(k)[:used[k]].copy_(self.slabs[k][:used[k]], non_blocking=True)
+            events.append(torch.cuda.Event())
+            events[-1].record(stream)
+
+        if used:
+            start(0)
+        for k in range(len(used)):
+            if k + 1 < len(used):                    # (into the other buffer: the consumer has finished with it, it asked for this block)
+                start(k + 1)
+            events[k].synchronize()
+            yield self._staging(k).numpy()[:used[k]]
+
+    def save(self, path: str, meta: dict) -> int:
+        """write every resident row, with its boxes, to `path` (meta: the run's fingerprint, feature_cache_file.fingerprint); returns the
+        number of frames written.  Slot order, slab by slab, device to host through two pinned buffers in rotation; the file appears
+        under its name only when it is complete (feature_cache_file.write)."""
+        from . import feature_cache_file as FF
+        ids = np.fromiter(self.table.slot_of.keys(), dtype=np.int64, count=len(self.table.slot_of))
+        assert list(self.table.slot_of.values()) == list(range(len(ids)))       # (slots are handed out in order and never given back)
+        FF.write(path, self.file_meta(meta), ids, self._slab_blocks(len(ids)))
+        return int(len(ids))
+
+    def load(self, path: str, meta: dict) -> List[int]:
+        """take in the rows of the file at `path`, written by `save` of a run with the same fingerprint; returns the frame ids that are
+        resident afterwards, in file order.  ValueError naming the first field of the fingerprint that differs from `meta`, or the
+        geometry that differs from this cache's -- before anything is inserted.  Ids go in in file order (table.insert: slabs grow as for
+        computed rows); a file with more frames than the capacity admits gives its prefix, and the rest is logged and left to be
+        computed.  The boxes travel inside the records, so din_feat_rows checks a loaded row exactly as a computed one."""
+        from . import feature_cache_file as FF
+        from .frame_cache import log
+        header, ids, records = FF.read(path)
+        field = FF.first_difference(meta, header["fingerprint"])
+        if field is not None:
+            raise ValueError(f"feature cache file {path} was written for another {field} ({header['fingerprint'].get(field)!r}, this run "
+                             f"has {meta.get(field)!r}): its rows are not the ones this run would compute.  It is neither used nor "
+                             f"overwritten: delete it, or point feature_cache_path elsewhere")
+        mine = self.file_meta(meta)
+        for k in ("row_bytes", "box_bytes", "dtype"):
+            if header[k] != mine[k]:
+                raise ValueError(f"feature cache file {path} holds {k} = {header[k]!r}, this cache {mine[k]!r}")
+        stream = torch.cuda.current_stream(self.device)
+        stride, cf = self.table.stride, self.table.chunk_frames
+        runs: List[List[int]] = []                   # [first file index, first slot, length]: contiguous in the file and inside one slab
+        resident: List[int] = []
+        for i, fid in enumerate(ids):
+            fid = int(fid)
+            if fid in self.table.slot_of:            # (already there, with the same fingerprint: the same bytes)
+                resident.append(fid)
+                continue
+            slot = self.table.insert(fid, self._grow)
+            if slot < 0:
+                break
+            resident.append(fid)
+            last = runs[-1] if runs else None
+            if last and last[0] + last[2] == i and last[1] + last[2] == slot and slot % cf:
+                last[2] += 1
+            else:
+                runs.append([i, slot, 1])
+        events: List[Optional[torch.cuda.Event]] = [None, None]
+        for k, (i, slot, n) in enumerate(runs):
+            if events[k % 2] is not None:
+                events[k % 2].synchronize()          # the copy this buffer last fed has finished
+            host = self._staging(k)
+            host.numpy()[:n * stride] = records[i:i + n].reshape(-1)      # (the file read: page faults of the memmap)
+            slab, off = self.table.locate(slot)
+            self.slabs[slab][off:off + n * stride].copy_(host[:n * stride], non_blocking=True)
+            events[k % 2] = torch.cuda.Event()
+            events[k % 2].record(stream)
+        for e in events:
+            if e is not None:
+                e.synchronize()
+        if len(resident) < len(ids):
+            log.warning("%s: %d of the %d %s of %s are resident; the capacity admits no more, the other %d will be computed", self.WHAT,
+                        len(resident), len(ids), self.UNIT, path, len(ids) - len(resident))
+        return resident
 
 
 class FrameRefs:
@@ -223,6 +332,69 @@ class FeatureLoader(CachedLoader):
         if augment is not None and augment.jitter is not None:     # (likewise: frame_cache.jitter_refusal)
             raise ValueError("colour jitter cannot be fed from the feature cache: its rows belong to the frames as decoded")
         return FeatureFeed(self.loader, device, self.cache, self.dataset)
+
+
+class CacheFile:
+    """the file one FeatureLoader's cache is kept in between runs (cfg.feature_cache_path): `load` before the first pass, `save_if_grown`
+    after every pass.  `loaded` / `saved` count frames; `say` takes the one log line of every load and save."""
+
+    def __init__(self, loader: FeatureLoader, path: str, meta: dict, say=print):
+        self.loader, self.path, self.meta, self.say = loader, path, meta, say
+        self.loaded = self.saved = 0
+
+    @property
+    def inserted(self) -> int:
+        return self.loader.cache.table.inserted
+
+    def _line(self, verb: str, frames: int, seconds: float) -> None:
+        gb = frames * self.loader.cache.table.stride / 1e9
+        self.say(f"feature cache {verb} {self.path}: {frames} frames, {gb:.3f} GB, {seconds:.2f} s")
+
+    def load(self) -> int:
+        """take the file in if there is one, and mark its frames resident so that the loader's workers stop decoding them -- what the
+        in-memory cache does from its second epoch.  A file of another fingerprint is a ValueError (FeatureCache.load)."""
+        if not os.path.exists(self.path):
+            return 0
+        t0 = time.perf_counter()
+        ids = self.loader.cache.load(self.path, self.meta)
+        flags = self.loader.dataset.resident
+        if ids and (min(ids) < 0 or max(ids) >= flags.numel()):
+            raise ValueError(f"feature cache file {self.path} names frames outside the dataset's table of {flags.numel()} frames")
+        if ids:
+            flags[torch.as_tensor(ids, dtype=torch.int64)] = 1
+        self.loaded = len(ids)
+        self._line("loaded from", self.loaded, time.perf_counter() - t0)
+        return self.loaded
+
+    def save_if_grown(self, inserted_before: int) -> int:
+        """after a pass: write the whole cache if it took frames in during the pass (`inserted_before`: `inserted` read before it);
+        returns the frames written, 0 for a pass that only read"""
+        if self.inserted == inserted_before:
+            return 0
+        t0 = time.perf_counter()
+        os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
+        self.saved = self.loader.cache.save(self.path, self.meta)
+        self._line("saved to", self.saved, time.perf_counter() - t0)
+        return self.saved
+
+
+def cache_files(cfg, model, training_loader, validation_loader, rank: int = 0, world: int = 1, say=print) -> dict:
+    """{"train": CacheFile, "val": CacheFile} for cfg.feature_cache_path, {} without the setting or without feature caches behind the
+    loaders (no real dataset tree).  The fingerprints are taken here: call it when the backbone has its stage-1 weights."""
+    from . import feature_cache_file as FF
+    folder = getattr(cfg, "feature_cache_path", None)
+    if folder is None or not (isinstance(training_loader, FeatureLoader) and isinstance(validation_loader, FeatureLoader)):
+        return {}
+    return {split: CacheFile(ld, os.path.join(str(folder), FF.file_name(split, rank, world)), FF.fingerprint(cfg, model, ld.dataset), say)
+            for split, ld in (("train", training_loader), ("val", validation_loader))}
+
+
+def path_refusal(cfg) -> Optional[str]:
+    """why cfg.feature_cache_path cannot be honoured, or None (train_net_dynamic.train_net raises ValueError with it)"""
+    if getattr(cfg, "feature_cache_path", None) is None or float(getattr(cfg, "feature_cache_gb", 0) or 0) > 0:
+        return None
+    return (f"feature_cache_path = {cfg.feature_cache_path!r}: the files there hold the rows of the box-feature cache, and feature_cache_gb "
+            f"is {getattr(cfg, 'feature_cache_gb', 0)}: there is no cache to load them into or to save")
 
 
 DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}      # cfg.feature_cache_dtype -> what the slots hold

@@ -227,8 +227,9 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     # cfg.deterministic where a sum's order is not ours (first: its answer is the same whatever the caches and workers are set to), then
     # cfg.feature_cache_gb > 0 where cached features would be wrong -- both before any process group or loader exists
     # -- then cfg.flip_prob where a mirrored clip cannot be fed, and cfg.color_jitter likewise
+    # -- and cfg.feature_cache_path without a feature cache to keep there
     why_not = (ops.deterministic_refusal(cfg, int(os.environ.get("WORLD_SIZE", "1"))) or feature_cache.refusal(cfg)
-               or frame_cache.flip_refusal(cfg) or frame_cache.jitter_refusal(cfg))
+               or frame_cache.flip_refusal(cfg) or frame_cache.jitter_refusal(cfg) or feature_cache.path_refusal(cfg))
     if why_not:
         raise ValueError(why_not)
     if getattr(cfg, "deterministic", False):
@@ -267,7 +268,8 @@ def _train_net(cfg, training_set, validation_set, max_steps):
     sampler = data.distributed.DistributedSampler(training_set, world, rank, shuffle=True) if world > 1 else None
     # cfg.num_workers / cfg.frame_cache_gb (both 0 by default: the loaders below are then the plain num_workers=0 DataLoaders) apply to
     # the real dataset tree only: worker processes decode, and decoded frames stay in HBM from their first use on (frame_cache.py); with
-    # cfg.feature_cache_gb > 0 the frozen trunk's box features stay there instead (feature_cache.py).  The caches live for this call.
+    # cfg.feature_cache_gb > 0 the frozen trunk's box features stay there instead (feature_cache.py).  The caches live for this call;
+    # with cfg.feature_cache_path the feature caches start from their files and are written back when they grew (`files` below).
     training_loader, validation_loader = frame_cache.build_loaders(cfg, training_set, validation_set, per_rank, sampler, device, real_tree)
     log_path = getattr(cfg, "log_path", None)
     if cfg.training_stage != 2:
@@ -303,8 +305,23 @@ def _train_net(cfg, training_set, validation_set, max_steps):
     buckets = parallel.GradBuckets(params) if world > 1 else None
     train = train_collective if collective else train_volleyball
     test = test_collective if collective else test_volleyball
+    # cfg.feature_cache_path (None: `files` is empty and nothing below differs): the model has its stage-1 weights, so the fingerprints
+    # can be taken; each cache takes its file in before the first pass, and is written after every pass in which it took frames in
+    files = feature_cache.cache_files(cfg, model, training_loader, validation_loader, rank, world, lambda line: print_log(log_path, line))
+    for f in files.values():
+        f.load()
+
+    def with_file(split, run_pass):
+        f = files.get(split)
+        if f is None:
+            return run_pass()
+        before = f.inserted
+        info = run_pass()
+        info.update(feature_cache_loaded=f.loaded, feature_cache_saved=f.save_if_grown(before))
+        return info
+
     if cfg.test_before_train:
-        print(test(validation_loader, model, device, 0, cfg))
+        print(with_file("val", lambda: test(validation_loader, model, device, 0, cfg)))
     infos = []
     best_result = {"epoch": 0, "activities_acc": 0}
     for epoch in range(start_epoch, start_epoch + cfg.max_epoch):
@@ -312,13 +329,13 @@ def _train_net(cfg, training_set, validation_set, max_steps):
             adjust_lr(optimizer, cfg.lr_plan[epoch])
         if sampler is not None:
             sampler.set_epoch(epoch)
-        info = train(training_loader, model, device, optimizer, epoch, cfg, buckets)
+        info = with_file("train", lambda: train(training_loader, model, device, optimizer, epoch, cfg, buckets))
         if rank == 0:
             print_log(log_path, "Train epoch %d: loss %.5f acc %.2f%%" % (epoch, info["loss"], info["activities_acc"]))
             if "grad_norm_mean" in info:
                 print_log(log_path, grad_stats_line(epoch, info))
         if epoch % cfg.test_interval_epoch == 0:
-            tinfo = test(validation_loader, model, device, epoch, cfg)
+            tinfo = with_file("val", lambda: test(validation_loader, model, device, epoch, cfg))
             if tinfo["activities_acc"] > best_result["activities_acc"]:
                 best_result = tinfo
             if rank == 0:
