@@ -17,7 +17,7 @@ whose norm is not finite is skipped (din_amd/optim.py); float('inf') measures an
 positive finite number.
 flip_prob (both trainers, training passes only; 0.0 = off): every clip of a training batch is mirrored left-right with this probability --
 all its frames inside the batch's gather launch, its boxes, and for volleyball the team side of its activity label
-(din_amd/frame_cache.py: FlipPlan); refused together with feature_cache_gb > 0.
+(din_amd/frame_cache.py: FlipPlan); refused together with feature_cache_gb > 0 unless feature_cache_flip is set.
 color_jitter (both trainers, training passes only; None = off): the amplitudes (brightness, contrast, saturation) of a per-clip colour
 jitter, each a real number in [0, 1).  Every clip of a training batch draws three factors f = 1 + a * u, u uniform in [-1, 1], and all its
 frames go through PIL.ImageEnhance.Contrast, then .Brightness, then .Color with them -- byte for byte what Pillow computes -- inside the
@@ -29,6 +29,15 @@ ranks).  A run that finds a file written for the same frames, boxes geometry and
 fingerprint -- the head, the learning rate and the seed are not part of it) starts with those rows resident: it decodes nothing and
 launches no backbone kernel from its first step; a cache that took frames in during an epoch is written after it.  A file of another
 fingerprint is a ValueError naming the field, never overwritten.
+feature_cache_flip (stage-2 trainer, with feature_cache_gb > 0 only and refused without it; False = off): a dataset's feature cache may be
+accompanied by a mirror cache of the same geometry, dtype and capacity, whose row for a frame is the RoIAlign output of the mirrored frame
+for the mirrored boxes -- the training set gets one iff flip_prob > 0, the validation set iff test_flip.  flip_prob is then served from the
+cache: a decoded frame is computed in both orientations in the step that decodes it, a batch of resident frames is one gather launch over
+both caches for any mix of orientations, and the mirror cache's file stands next to the plain one (train.flip.dinfc) under
+feature_cache_path.  Twice the memory: 61 GB per orientation for the 48300 volleyball frames as fp32 Inception-v3 rows.
+test_flip (stage-2 trainer, evaluation passes; False = off; refused by the stage-1 trainer): every clip is scored as decoded and mirrored
+and the scores are averaged, 0.5 * (s + s_m[:, volleyball.FLIP_ACTIVITIES]) in fp32 (the identity map for collective); with
+feature_cache_gb > 0 the mirrored clips come from the mirror cache, so feature_cache_flip must be set.
 All are opt-in: at 0 / False / None the trainers behave exactly as without them."""
 from __future__ import annotations
 
@@ -56,6 +65,7 @@ _DEFAULTS = dict(
     flip_prob=0.0,
     color_jitter=None,
     feature_cache_path=None,
+    feature_cache_flip=False, test_flip=False,
 )
 
 

@@ -28,6 +28,21 @@ cfg.feature_cache_path (a directory; None = off): the rows outlive the call.  `F
 slabs and one data file per cache (feature_cache_file.py: the layout, and the fingerprint that says which runs compute the same rows --
 the head, the learning rate and the seed are not part of it); `CacheFile` is a loader's file, loaded before the first pass and written
 after every pass in which the cache took frames in.  No kernel of its own: copy_ between pinned buffers and slabs on the current stream.
+
+cfg.feature_cache_flip (with cfg.flip_prob > 0 for the training set, cfg.test_flip for the validation set): the dataset's cache is
+accompanied by a MIRROR cache of the same geometry, dtype and capacity, whose row for a frame is the RoIAlign output of the mirrored
+frame for the mirrored boxes, and whose trailer holds those boxes -- the bits din_flip_clip_labels produces.  A left-right flip has
+exactly two variants, so both can be resident:
+  * a decoded frame is computed in both orientations in the step that decodes it (infer_model._cached_crops: one din_copy_rows_u8_flip
+    launch over the M decoded frames, one din_flip_clip_labels launch over their boxes, the trunk once per orientation over M frames
+    each) and goes into both caches or into neither (`insert_pair`); `dataset.resident` is marked only for frames both caches hold;
+  * `FeatureFeed` draws the clips of a training pass as the frame path does (frame_cache.EpochFlips: the same stream) and mirrors the
+    batch's labels BEFORE the gather, so the box check compares mirrored boxes with mirrored trailers; `FrameRefs.flipped` tells the
+    model call which rows are mirrored;
+  * `FeatureCache.rows_both` builds ONE address table over both caches' slabs: a batch of resident frames is one din_feat_rows (or
+    din_feat_rows_bf16) launch for any mix of orientations;
+  * the mirror cache's file stands next to the plain one (`flip_file_name`: train.flip.dinfc); its header says "orientation":
+    "mirrored", a plain file's header has no such key, and either offered as the other is refused at load.
 """
 from __future__ import annotations
 
@@ -43,6 +58,21 @@ from .frame_cache import CachedLoader, SlotStore
 from .input_feed import DeviceFeed
 
 
+ORIENTATIONS = ("plain", "mirrored")
+
+
+def insert_pair(tables, fid: int, grows=None) -> dict:
+    """the pair rule: frame `fid` goes into every one of `tables` (frame_cache.SlotTable) that lacks it, or into none of them.
+    Returns {index of the table: the new slot} -- empty when a table that lacks the frame has no room (full, frozen, or its slab is
+    refused by grows[k]); the tables that already hold the frame keep it.  After a non-empty answer every table holds the frame."""
+    fid = int(fid)
+    grows = grows or [lambda n: True] * len(tables)
+    lacking = [k for k, t in enumerate(tables) if fid not in t.slot_of]
+    if not all(tables[k].reserve(grows[k]) for k in lacking):
+        return {}
+    return {k: tables[k].insert(fid, grows[k]) for k in lacking}
+
+
 class FeatureCache(SlotStore):
     """Device-resident store of box-feature rows, fp32 or (dtype=torch.bfloat16) rounded to bf16: each slot holds `row_bytes` of
     features in that dtype followed by the `box_bytes` of the boxes they were computed for.  Filled on first use, never beyond
@@ -52,7 +82,10 @@ class FeatureCache(SlotStore):
     FLAG_ROWS = 1 << 20                              # rows between two check() calls the flags buffer holds without an extra check
 
     def __init__(self, device, row_bytes: int, box_bytes: int, capacity_bytes: int, chunk_frames: int = 64,
-                 dtype: torch.dtype = torch.float32):
+                 dtype: torch.dtype = torch.float32, orientation: str = "plain"):
+        if orientation not in ORIENTATIONS:
+            raise ValueError(f"FeatureCache: orientation is one of {ORIENTATIONS}, not {orientation!r}")
+        self.orientation = orientation               # "mirrored": the rows of the mirrored frames for the mirrored boxes
         if row_bytes <= 0 or box_bytes <= 0 or row_bytes % 16 or box_bytes % 16:
             raise ValueError(f"FeatureCache: row_bytes {row_bytes} and box_bytes {box_bytes} must be positive multiples of 16")
         if dtype not in (torch.float32, torch.bfloat16):
@@ -77,6 +110,14 @@ class FeatureCache(SlotStore):
         self._used += len(ids)
         return view
 
+    def _step_boxes(self, who: str, rows: int, boxes: torch.Tensor) -> torch.Tensor:
+        """the step's boxes as the launch reads them: fp32 on the device, `box_bytes` a row, contiguous, 16-byte aligned (a row at a
+        misaligned address would be left alone by din_feat_rows: no trailer, no box check, no error)"""
+        if not boxes.is_cuda or boxes.dtype != torch.float32 or boxes.numel() * 4 != rows * self.box_bytes:
+            raise ValueError(f"{who}: {rows} rows need fp32 device boxes of {self.box_bytes} bytes each, got {tuple(boxes.shape)} {boxes.dtype}")
+        boxes = boxes.contiguous()
+        return boxes.clone() if boxes.data_ptr() % 16 else boxes
+
     def rows(self, frame_ids, boxes: torch.Tensor, miss_pos=(), miss_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[int]]:
         """frame_ids [R] (host), boxes fp32 [R, box_bytes / 4] on the device (this step's boxes of every row), miss_pos [M] (host: which
         of the R rows the computed rows are), miss_rows fp32 [M, row_elems] on the device -> (`dtype` [R, row_elems] on the device,
@@ -84,15 +125,10 @@ class FeatureCache(SlotStore):
         with the slot's) or from the computed row, which also goes into a free slot with its boxes while the cache has room.  A frame
         that occurs twice is served both times from the computed row, never from the slot written by this launch.  With bf16 storage
         the computed rows still arrive as fp32 and the launch rounds them (din_feat_rows_bf16)."""
-        from . import ops
         ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
         pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
         rb, bb, ne = self.row_bytes, self.box_bytes, self.row_elems
-        if not boxes.is_cuda or boxes.dtype != torch.float32 or boxes.numel() * 4 != len(ids) * bb:
-            raise ValueError(f"rows: {len(ids)} rows need fp32 device boxes of {bb} bytes each, got {tuple(boxes.shape)} {boxes.dtype}")
-        boxes = boxes.contiguous()
-        if boxes.data_ptr() % 16:
-            boxes = boxes.clone()
+        boxes = self._step_boxes("rows", len(ids), boxes)
         if len(pos):
             if miss_rows is None or not miss_rows.is_cuda or miss_rows.dtype != torch.float32 or not miss_rows.is_contiguous() \
                     or tuple(miss_rows.shape) != (len(pos), ne) or miss_rows.data_ptr() % 16:
@@ -124,14 +160,92 @@ class FeatureCache(SlotStore):
             keep.append(self.slot_address(slot) if slot >= 0 else 0)
             ref.append(0)
         dst = [out_ptr + i * rb for i in range(len(ids))]
-        flags = self._flag_rows(ids)
+        self._launch(src, dst, keep, ref, boxes, self._flag_rows(ids))
+        return out, new_ids
+
+    def _launch(self, src, dst, keep, ref, boxes: torch.Tensor, flags: torch.Tensor) -> None:
+        """the one launch of a gather: din_feat_rows, or din_feat_rows_bf16 for bf16 slots"""
+        from . import ops
         if self.dtype == torch.float32:
             d_src, d_dst, d_keep, d_ref = self._upload(src, dst, keep, ref)
-            ops.feat_rows(d_src, d_dst, rb, d_keep, d_ref, boxes, flags, bb)
+            ops.feat_rows(d_src, d_dst, self.row_bytes, d_keep, d_ref, boxes, flags, self.box_bytes)
         else:                                        # a row without a stored-boxes address is a computed one: fp32, to be rounded
             d_src, d_dst, d_keep, d_ref, d_f32 = self._upload(src, dst, keep, ref, [int(r == 0) for r in ref])
-            ops.feat_rows_bf16(d_src, d_dst, ne, d_keep, d_ref, boxes, flags, bb, d_f32)
-        return out, new_ids
+            ops.feat_rows_bf16(d_src, d_dst, self.row_elems, d_keep, d_ref, boxes, flags, self.box_bytes, d_f32)
+
+    def rows_both(self, mirror: "FeatureCache", frame_ids, flipped, boxes: torch.Tensor, miss_pos=(), miss_rows=None,
+                  miss_boxes=None) -> Tuple[torch.Tensor, List[int]]:
+        """`rows` over this cache and its mirror cache with ONE address table and ONE launch: row i is frame frame_ids[i] as decoded,
+        or mirrored where flipped[i] (host, bool [R]; None: no row), and comes from the slot of the cache of its orientation or from
+        the computed row of that orientation.  boxes: this step's boxes of every row, mirrored where the row is.  The M decoded
+        frames (miss_pos [M]: one row of the batch each) arrive computed in BOTH orientations: miss_rows = (fp32 [M, row_elems] of the
+        frames as decoded, the same of the mirrored frames), miss_boxes = (fp32 [M, box_bytes / 4] unmirrored, mirrored).  A decoded
+        frame goes into both caches or into neither (`insert_pair`); an orientation that no row of the batch asks for is stored by an
+        extra row of the same launch, with its own boxes.  Returns (`dtype` [R, row_elems], the frame ids that BOTH caches hold
+        since this call).  The flags of all rows are this cache's: `check()` on it reports a mismatch in either orientation."""
+        if not isinstance(mirror, FeatureCache) or (mirror.row_bytes, mirror.box_bytes, mirror.dtype) != (self.row_bytes, self.box_bytes, self.dtype):
+            raise ValueError("rows_both: the mirror cache is a FeatureCache of the same row_bytes, box_bytes and dtype")
+        caches = (self, mirror)
+        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
+        orient = np.zeros(len(ids), dtype=np.int64) if flipped is None else (np.asarray(flipped).reshape(-1) != 0).astype(np.int64)
+        if len(orient) != len(ids):
+            raise ValueError(f"rows_both: {len(orient)} orientation flags for {len(ids)} rows")
+        rb, bb, ne = self.row_bytes, self.box_bytes, self.row_elems
+        boxes = self._step_boxes("rows_both", len(ids), boxes).reshape(len(ids), bb // 4)
+        if len(pos):
+            for what, pair, shape in (("computed rows", miss_rows, (len(pos), ne)), ("boxes of the computed rows", miss_boxes, (len(pos), bb // 4))):
+                if pair is None or len(pair) != 2 or any(t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
+                                                         or tuple(t.shape) != shape or t.data_ptr() % 16 for t in pair):
+                    raise ValueError(f"rows_both: the {what} are two contiguous, 16-byte aligned fp32 device tensors {shape}, one per orientation")
+            if pos.min() < 0 or pos.max() >= len(ids):
+                raise ValueError("rows_both: miss_pos outside the batch")
+        first, row_of = {}, ({}, {})                 # frame id -> index of its first decoded copy; per orientation: -> address of its row
+        for j, p in enumerate(pos):
+            fid = int(ids[p])
+            if fid not in first:
+                first[fid] = j
+                for o in (0, 1):
+                    row_of[o][fid] = miss_rows[o].data_ptr() + j * ne * 4
+        took, fresh, new_ids = {}, (set(), set()), []
+        for fid in first:                            # the pair rule, once per decoded frame, in batch order
+            got = insert_pair([c.table for c in caches], fid, [c._grow for c in caches])
+            for k, slot in got.items():
+                took[(fid, k)] = slot
+                fresh[k].add(fid)
+            if got:
+                new_ids.append(fid)
+        src, keep, ref = [], [], []
+        for fid, o in zip(ids, orient):
+            fid, o, c = int(fid), int(o), caches[int(o)]
+            slot = -1 if fid in fresh[o] else c.table.lookup(fid)
+            if slot >= 0:                            # resident before this launch: served from the slot, boxes compared
+                src.append(c.slot_address(slot))
+                keep.append(0)
+                ref.append(src[-1] + rb)
+                continue
+            if fid not in row_of[o]:
+                raise KeyError(f"frame {fid} ({ORIENTATIONS[o]}) is neither resident nor among the computed rows of this batch")
+            slot = took.pop((fid, o), -1)            # (its first row of this orientation stores it)
+            c.table.misses += int(slot >= 0)         # (counted as `rows` counts it: the lookup that would have missed)
+            src.append(row_of[o][fid])
+            keep.append(c.slot_address(slot) if slot >= 0 else 0)
+            ref.append(0)
+        extra = sorted(took.items(), key=lambda kv: (kv[0][1], first[kv[0][0]]))     # inserts no row of the batch carries: plain first
+        if extra:
+            picks = [miss_boxes[k].index_select(0, torch.tensor([first[f] for (f, kk), _ in extra if kk == k], dtype=torch.int64, device=boxes.device))
+                     for k in (0, 1) if any(kk == k for (_, kk), _ in extra)]
+            boxes = torch.cat([boxes] + picks)
+            for (fid, k), slot in extra:
+                src.append(row_of[k][fid])
+                keep.append(caches[k].slot_address(slot))
+                ref.append(0)
+            ids = np.concatenate([ids, np.asarray([f for (f, _), _ in extra], dtype=np.int64)])
+        out = torch.empty((len(ids), ne), dtype=self.dtype, device=self.device)     # (the extra rows' copies land behind the batch's)
+        out_ptr = out.data_ptr()
+        dst = [out_ptr + i * rb for i in range(len(ids))]
+        self._launch(src, dst, keep, ref, boxes, self._flag_rows(ids))
+        return out[:len(orient)], new_ids
 
     def check(self) -> None:
         """end of a pass: synchronise once, read the flags of every row gathered since the last check, clear them; RuntimeError naming
@@ -160,8 +274,11 @@ class FeatureCache(SlotStore):
 
     def file_meta(self, fingerprint: dict) -> dict:
         """what a file of this cache says about itself besides its count: the fingerprint and the slots' geometry"""
-        return {"fingerprint": fingerprint, "row_bytes": self.row_bytes, "box_bytes": self.box_bytes,
+        meta = {"fingerprint": fingerprint, "row_bytes": self.row_bytes, "box_bytes": self.box_bytes,
                 "dtype": "fp32" if self.dtype == torch.float32 else "bf16"}
+        if self.orientation != "plain":              # (a plain cache's header is what it always was)
+            meta["orientation"] = self.orientation
+        return meta
 
     def _slab_blocks(self, count: int) -> Iterator[np.ndarray]:
         """the first `count` slots as host byte blocks, slab by slab (the slots of a slab are contiguous in device memory): the copy of
@@ -203,6 +320,11 @@ class FeatureCache(SlotStore):
         from . import feature_cache_file as FF
         from .frame_cache import log
         header, ids, records = FF.read(path)
+        theirs = header.get("orientation", "plain")
+        if theirs != self.orientation:
+            raise ValueError(f"feature cache file {path} holds the rows of the {theirs} frames and is offered to the cache of the "
+                             f"{self.orientation} ones (a renamed file?): a mirror cache's file is `flip_file_name`'s, next to the plain "
+                             f"one.  It is neither used nor overwritten")
         field = FF.first_difference(meta, header["fingerprint"])
         if field is not None:
             raise ValueError(f"feature cache file {path} was written for another {field} ({header['fingerprint'].get(field)!r}, this run "
@@ -253,9 +375,15 @@ class FrameRefs:
     """what a model receives in place of the images tensor when box features are cached: the frame ids of the batch [B, T] (host), the
     frames that were decoded (uint8 [M, 3, H, W] on the device), which of the B*T rows they are (`miss_pos`, host; `miss_pos_dev` the
     same on the device when the feed uploaded it), and the cache.  `shape` and `reshape` of the two leading dimensions are all the
-    models and trainers use of an images tensor besides handing it to infer_model.embed_boxes, which sets `inserted`."""
+    models and trainers use of an images tensor besides handing it to infer_model.embed_boxes, which sets `inserted`.
 
-    def __init__(self, frame_ids, miss_images: torch.Tensor, miss_pos, cache: FeatureCache, miss_pos_dev: Optional[torch.Tensor] = None):
+    With a mirror cache (`mirror`, cfg.feature_cache_flip) every row has an orientation: `flipped` (host, bool [B, T]; None: no row is
+    mirrored) says which rows are the mirrored frame, and the boxes the model receives are mirrored in those rows.  `plain_boxes` (the
+    batch's boxes before any was mirrored, on the device) is needed only when a decoded frame sits in a mirrored row: its unmirrored
+    boxes cannot be had back from the mirrored ones bit for bit.  `inserted` then lists the frames BOTH caches hold since the call."""
+
+    def __init__(self, frame_ids, miss_images: torch.Tensor, miss_pos, cache: FeatureCache, miss_pos_dev: Optional[torch.Tensor] = None,
+                 mirror: Optional[FeatureCache] = None, flipped=None, plain_boxes: Optional[torch.Tensor] = None):
         self.frame_ids = np.asarray(frame_ids, dtype=np.int64)
         if self.frame_ids.ndim != 2:
             raise ValueError(f"FrameRefs: frame_ids is [B, T], got shape {self.frame_ids.shape}")
@@ -267,6 +395,12 @@ class FrameRefs:
             raise ValueError(f"FrameRefs: {miss_images.shape[0]} decoded frames but {len(self.miss_pos)} positions")
         self.miss_pos_dev = miss_pos_dev
         self.inserted: List[int] = []
+        self.mirror, self.plain_boxes = mirror, plain_boxes
+        self.flipped = None if flipped is None else np.asarray(flipped).astype(bool)
+        if self.flipped is not None and self.flipped.shape != self.frame_ids.shape:
+            raise ValueError(f"FrameRefs: flipped is bool {self.frame_ids.shape} like frame_ids, got shape {self.flipped.shape}")
+        if self.flipped is not None and mirror is None:
+            raise ValueError("FrameRefs: mirrored rows need the mirror cache they are served from")
 
     @property
     def shape(self) -> Tuple[int, ...]:
@@ -276,8 +410,17 @@ class FrameRefs:
         shape = tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list)) else tuple(shape)
         if len(shape) != 5 or tuple(shape[2:]) != self.shape[2:] or shape[0] * shape[1] != self.frame_ids.size:
             raise ValueError(f"FrameRefs.reshape: only the two leading dimensions of {self.shape} can be reshaped, got {shape}")
-        out = FrameRefs(self.frame_ids.reshape(shape[0], shape[1]), self.miss_images, self.miss_pos, self.cache, self.miss_pos_dev)
+        out = FrameRefs(self.frame_ids.reshape(shape[0], shape[1]), self.miss_images, self.miss_pos, self.cache, self.miss_pos_dev,
+                        self.mirror, None if self.flipped is None else self.flipped.reshape(shape[0], shape[1]), self.plain_boxes)
         out.inserted = self.inserted                 # (shared: the feed reads it off the object it yielded)
+        return out
+
+    def mirrored(self, plain_boxes: torch.Tensor) -> "FrameRefs":
+        """the same frames in the other orientation, every row (test-time flipping: the caller mirrors the boxes it hands to the model
+        and passes the ones it mirrored them from)"""
+        flipped = np.ones(self.frame_ids.shape, dtype=bool) if self.flipped is None else ~self.flipped
+        out = FrameRefs(self.frame_ids, self.miss_images, self.miss_pos, self.cache, self.miss_pos_dev, self.mirror, flipped, plain_boxes)
+        out.inserted = self.inserted
         return out
 
 
@@ -299,10 +442,16 @@ class _HostSide:
 class FeatureFeed:
     """frame_cache.CachedFeed's contract over the same `collate`d batches: yields (FrameRefs, *labels) with the labels on the device.
     Only the frames the workers decoded are uploaded; after the model call `dataset.resident` is marked for the frames whose features
-    went into the cache, so the loader stops decoding them."""
+    went into the cache, so the loader stops decoding them.
 
-    def __init__(self, loader: Iterable, device, cache: FeatureCache, dataset):
+    With a mirror cache (`mirror`) the frames go into both caches, `resident` is marked for those both hold, and `augment` (the pass's
+    frame_cache.PassAugment, its flips only) mirrors clips: one draw per batch from the stream the frame path draws from, the labels
+    mirrored by the one din_flip_clip_labels launch BEFORE the model call, the rows' orientations in `FrameRefs.flipped`.  A batch in
+    which nothing is drawn is fed exactly as without `augment`."""
+
+    def __init__(self, loader: Iterable, device, cache: FeatureCache, dataset, augment=None, mirror: Optional[FeatureCache] = None):
         self.loader, self.device, self.cache, self.dataset = loader, torch.device(device), cache, dataset
+        self.augment, self.mirror = augment, mirror
         self._kept: collections.deque = collections.deque()
         self._feed = DeviceFeed(_HostSide(loader, self._kept), self.device)
 
@@ -310,7 +459,14 @@ class FeatureFeed:
         self._kept.clear()
         for miss_images, miss_pos_dev, *labels in self._feed:
             ids, pos = self._kept.popleft()
-            refs = FrameRefs(ids, miss_images, pos, self.cache, miss_pos_dev)
+            rows = None if self.augment is None else self.augment.rows(ids.shape[0], ids.shape[1])[0]
+            if rows is None:
+                refs = FrameRefs(ids, miss_images, pos, self.cache, miss_pos_dev, self.mirror)
+            else:
+                plain_boxes = labels[0].clone() if len(pos) else None        # (only a decoded frame's unmirrored boxes are ever needed)
+                d_flags, = self.cache._upload(rows.astype(np.int64))
+                self.augment.mirror_labels(labels, d_flags)
+                refs = FrameRefs(ids, miss_images, pos, self.cache, miss_pos_dev, self.mirror, rows.reshape(ids.shape), plain_boxes)
             yield (refs, *labels)
             if refs.inserted:                        # (filled by embed_boxes during the model call)
                 self.dataset.resident[torch.as_tensor(refs.inserted, dtype=torch.int64)] = 1
@@ -324,35 +480,52 @@ class FeatureFeed:
 
 class FeatureLoader(CachedLoader):
     """a DataLoader of a `frame_ids=True` dataset together with the feature cache of that dataset: what the stage-2 trainer's passes
-    receive in place of the loader when cfg.feature_cache_gb > 0"""
+    receive in place of the loader when cfg.feature_cache_gb > 0.  `mirror`: the mirror cache of the dataset (cfg.feature_cache_flip),
+    None without one"""
+
+    def __init__(self, loader, cache, dataset, mirror: Optional[FeatureCache] = None):
+        super().__init__(loader, cache, dataset)
+        self.mirror = mirror
 
     def feed(self, device, augment=None) -> FeatureFeed:
-        if augment is not None and augment.flip is not None:       # (train_net refuses the combination first: frame_cache.flip_refusal)
-            raise ValueError("flip augmentation cannot be fed from the feature cache: its rows belong to the unmirrored frames")
+        if augment is not None and augment.flip is not None and self.mirror is None:   # (train_net refuses first: frame_cache.flip_refusal)
+            raise ValueError("flip augmentation cannot be fed from the feature cache: its rows belong to the unmirrored frames "
+                             "(cfg.feature_cache_flip gives the loader a mirror cache)")
         if augment is not None and augment.jitter is not None:     # (likewise: frame_cache.jitter_refusal)
             raise ValueError("colour jitter cannot be fed from the feature cache: its rows belong to the frames as decoded")
-        return FeatureFeed(self.loader, device, self.cache, self.dataset)
+        if self.mirror is None:
+            return FeatureFeed(self.loader, device, self.cache, self.dataset)
+        return FeatureFeed(self.loader, device, self.cache, self.dataset, augment, self.mirror)
 
 
 class CacheFile:
     """the file one FeatureLoader's cache is kept in between runs (cfg.feature_cache_path): `load` before the first pass, `save_if_grown`
-    after every pass.  `loaded` / `saved` count frames; `say` takes the one log line of every load and save."""
+    after every pass.  `loaded` / `saved` count frames; `say` takes the one log line of every load and save.  A loader with a mirror
+    cache keeps that one in `flip_path`, by the same rules (`flip_loaded` / `flip_saved`); only frames that both files gave are marked
+    resident."""
 
-    def __init__(self, loader: FeatureLoader, path: str, meta: dict, say=print):
+    def __init__(self, loader: FeatureLoader, path: str, meta: dict, say=print, flip_path: Optional[str] = None):
         self.loader, self.path, self.meta, self.say = loader, path, meta, say
         self.loaded = self.saved = 0
+        self.flip_path = flip_path if getattr(loader, "mirror", None) is not None else None
+        self.flip_loaded = self.flip_saved = self.flip_written = 0  # (flip_written: by the last save_if_grown call, 0 if it wrote none)
+        self._on_file = [0, 0]                       # (with a mirror cache) each table's `inserted` when its file was last read or written
 
     @property
     def inserted(self) -> int:
+        if self.flip_path is not None:
+            return self.loader.cache.table.inserted + self.loader.mirror.table.inserted
         return self.loader.cache.table.inserted
 
-    def _line(self, verb: str, frames: int, seconds: float) -> None:
+    def _line(self, verb: str, frames: int, seconds: float, path: Optional[str] = None) -> None:
         gb = frames * self.loader.cache.table.stride / 1e9
-        self.say(f"feature cache {verb} {self.path}: {frames} frames, {gb:.3f} GB, {seconds:.2f} s")
+        self.say(f"feature cache {verb} {path or self.path}: {frames} frames, {gb:.3f} GB, {seconds:.2f} s")
 
     def load(self) -> int:
         """take the file in if there is one, and mark its frames resident so that the loader's workers stop decoding them -- what the
         in-memory cache does from its second epoch.  A file of another fingerprint is a ValueError (FeatureCache.load)."""
+        if self.flip_path is not None:
+            return self._load_both()
         if not os.path.exists(self.path):
             return 0
         t0 = time.perf_counter()
@@ -366,11 +539,50 @@ class CacheFile:
         self._line("loaded from", self.loaded, time.perf_counter() - t0)
         return self.loaded
 
+    def _load_both(self) -> int:
+        """`load` for a loader with a mirror cache: each file that exists goes into its cache; resident are the frames both hold"""
+        got = []
+        for cache, path, name in ((self.loader.cache, self.path, "loaded"), (self.loader.mirror, self.flip_path, "flip_loaded")):
+            ids = []
+            if os.path.exists(path):
+                t0 = time.perf_counter()
+                ids = cache.load(path, self.meta)
+                self._line("loaded from", len(ids), time.perf_counter() - t0, path)
+            setattr(self, name, len(ids))
+            got.append(ids)
+        self._on_file = [self.loader.cache.table.inserted, self.loader.mirror.table.inserted]
+        both = sorted(set(got[0]) & set(got[1]))
+        flags = self.loader.dataset.resident
+        if both and (both[0] < 0 or both[-1] >= flags.numel()):
+            raise ValueError(f"feature cache files {self.path} and {self.flip_path} name frames outside the dataset's table of "
+                             f"{flags.numel()} frames")
+        if both:
+            flags[torch.as_tensor(both, dtype=torch.int64)] = 1
+        return self.loaded
+
+    def _save_both(self) -> int:
+        """`save_if_grown` for a loader with a mirror cache: each cache that took frames in since its file was last read or written"""
+        wrote = [0, 0]
+        for k, (cache, path, name) in enumerate(((self.loader.cache, self.path, "saved"), (self.loader.mirror, self.flip_path, "flip_saved"))):
+            if cache.table.inserted == self._on_file[k]:
+                continue
+            t0 = time.perf_counter()
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            wrote[k] = cache.save(path, self.meta)
+            self._on_file[k] = cache.table.inserted
+            setattr(self, name, wrote[k])
+            self.flip_written = wrote[1]
+            self._line("saved to", wrote[k], time.perf_counter() - t0, path)
+        return wrote[0]
+
     def save_if_grown(self, inserted_before: int) -> int:
         """after a pass: write the whole cache if it took frames in during the pass (`inserted_before`: `inserted` read before it);
-        returns the frames written, 0 for a pass that only read"""
+        returns the frames written, 0 for a pass that only read.  The mirror cache's file likewise (`flip_written`)."""
+        self.flip_written = 0
         if self.inserted == inserted_before:
             return 0
+        if self.flip_path is not None:
+            return self._save_both()
         t0 = time.perf_counter()
         os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
         self.saved = self.loader.cache.save(self.path, self.meta)
@@ -385,7 +597,8 @@ def cache_files(cfg, model, training_loader, validation_loader, rank: int = 0, w
     folder = getattr(cfg, "feature_cache_path", None)
     if folder is None or not (isinstance(training_loader, FeatureLoader) and isinstance(validation_loader, FeatureLoader)):
         return {}
-    return {split: CacheFile(ld, os.path.join(str(folder), FF.file_name(split, rank, world)), FF.fingerprint(cfg, model, ld.dataset), say)
+    return {split: CacheFile(ld, os.path.join(str(folder), FF.file_name(split, rank, world)), FF.fingerprint(cfg, model, ld.dataset), say,
+                             os.path.join(str(folder), FF.flip_file_name(split, rank, world)))
             for split, ld in (("train", training_loader), ("val", validation_loader))}
 
 
@@ -411,8 +624,39 @@ def feature_loaders(cfg, training_loader, validation_loader, training_set, valid
     capacity = int(float(cfg.feature_cache_gb) * 1e9)
     dtype = DTYPES[getattr(cfg, "feature_cache_dtype", "fp32")]
     rb, bb = row_and_box_bytes(cfg, dtype)
+    if getattr(cfg, "feature_cache_flip", False):
+        # a mirror cache where mirrored clips are asked for: the training set's with flip_prob > 0, the validation set's with test_flip
+        def pair(loader, dataset, wanted):
+            cache = FeatureCache(device, rb, bb, capacity, dtype=dtype)
+            return FeatureLoader(loader, cache, dataset, FeatureCache(device, rb, bb, capacity, dtype=dtype, orientation="mirrored") if wanted else None)
+
+        return (pair(training_loader, training_set, bool(getattr(cfg, "flip_prob", 0.0))),
+                pair(validation_loader, validation_set, bool(getattr(cfg, "test_flip", False))))
     return (FeatureLoader(training_loader, FeatureCache(device, rb, bb, capacity, dtype=dtype), training_set),
             FeatureLoader(validation_loader, FeatureCache(device, rb, bb, capacity, dtype=dtype), validation_set))
+
+
+def flip_cache_refusal(cfg) -> Optional[str]:
+    """why cfg.feature_cache_flip or cfg.test_flip cannot be honoured, or None (train_net_dynamic.train_net raises ValueError with it)"""
+    for name in ("feature_cache_flip", "test_flip"):
+        v = getattr(cfg, name, False)
+        if not isinstance(v, bool):
+            return f"{name} = {v!r}: the setting is True or False"
+    gb = float(getattr(cfg, "feature_cache_gb", 0) or 0)
+    if getattr(cfg, "feature_cache_flip", False) and gb <= 0:
+        return (f"feature_cache_flip = True: the mirror cache accompanies the box-feature cache, and feature_cache_gb is "
+                f"{getattr(cfg, 'feature_cache_gb', 0)}: there is no cache to mirror")
+    if not getattr(cfg, "test_flip", False):
+        return None
+    if gb > 0 and not cfg.feature_cache_flip:
+        return (f"test_flip = True: feature_cache_gb = {cfg.feature_cache_gb} caches the box features of the unmirrored frame; the mirrored "
+                f"clips of an evaluation pass come from the mirror cache, which feature_cache_flip = True adds")
+    if cfg.dataset_name == "volleyball":
+        from .volleyball import ACTIVITIES
+        if cfg.num_activities != len(ACTIVITIES):
+            return (f"test_flip = True: a mirrored volleyball clip's scores are read through the team-side swap of the {len(ACTIVITIES)} "
+                    f"activities of volleyball.ACTIVITIES; num_activities is {cfg.num_activities}")
+    return None
 
 
 def refusal(cfg) -> Optional[str]:

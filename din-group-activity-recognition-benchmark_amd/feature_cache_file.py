@@ -11,6 +11,7 @@ Layout (little endian, data only -- nothing in it is unpickled or executed):
     bytes 8..11     uint32 format VERSION
     bytes 12..19    uint64 L, the length of the header
     bytes 20..20+L  the header, UTF-8 JSON: {"fingerprint": {field: value, ..., "digest": sha256}, "row_bytes", "box_bytes", "dtype", "count"}
+                    (a mirror cache's file, cfg.feature_cache_flip, adds "orientation": "mirrored"; a plain file has no such key)
     then            ids, int64 [count]: the frame ids in slot order
     zero padding up to the next multiple of ALIGN
     then            count records of row_bytes + box_bytes bytes: a slot's bytes exactly as FeatureCache holds them, the row, then its boxes
@@ -64,6 +65,8 @@ def write(path: str, meta: dict, ids, blocks: Iterable) -> int:
     -- the previous file is intact and the temporary file is removed.  Returns the bytes written."""
     ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
     header = {k: meta.get(k) for k in ("fingerprint", "row_bytes", "box_bytes", "dtype")}
+    if meta.get("orientation", "plain") != "plain":              # a mirror cache's file says so; a plain file has no such key
+        header["orientation"] = str(meta["orientation"])
     header["count"] = int(ids.size)
     why = _geometry_defect(header)
     if why:
@@ -211,3 +214,9 @@ def file_name(split: str, rank: int = 0, world: int = 1) -> str:
     """the file of the `split` ("train" | "val") cache of rank `rank` of `world`: every rank's cache holds what its sampler showed it, so
     several ranks keep a file each"""
     return f"{split}.dinfc" if world <= 1 else f"{split}.rank{rank}of{world}.dinfc"
+
+
+def flip_file_name(split: str, rank: int = 0, world: int = 1) -> str:
+    """the file of the mirror cache of that split (cfg.feature_cache_flip), next to the plain one: train.flip.dinfc,
+    train.flip.rank0of2.dinfc"""
+    return file_name(split + ".flip", rank, world)

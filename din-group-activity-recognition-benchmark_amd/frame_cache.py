@@ -87,19 +87,26 @@ class SlotTable:
         if slot >= 0:
             self.hits += 1
             return slot
-        if self.full:
+        if not self.reserve(grow):
             return -1
-        if len(self.slot_of) == self.allocated:
-            n = min(self.chunk_frames, self.max_slots - self.allocated)
-            if not grow(n):
-                self.max_slots, self.frozen = self.allocated, True
-                return -1
-            self.slab_slots.append(n)
-            self.allocated += n
         slot = len(self.slot_of)
         self.slot_of[fid] = slot
         self.inserted += 1
         return slot
+
+    def reserve(self, grow: Callable[[int], bool] = lambda n: True) -> bool:
+        """whether the next `insert` of a new frame will succeed: allocates the slab it would need now (a refused slab freezes the
+        table, as in `insert`), so that several tables can be asked before any of them takes the frame in"""
+        if self.full:
+            return False
+        if len(self.slot_of) == self.allocated:
+            n = min(self.chunk_frames, self.max_slots - self.allocated)
+            if not grow(n):
+                self.max_slots, self.frozen = self.allocated, True
+                return False
+            self.slab_slots.append(n)
+            self.allocated += n
+        return True
 
     def locate(self, slot: int) -> Tuple[int, int]:
         """(slab index, byte offset inside the slab): every slab but the last holds chunk_frames slots"""
@@ -448,7 +455,7 @@ def flip_refusal(cfg) -> Optional[str]:
     if p == 0:
         return None
     pre = f"flip_prob = {p}: "
-    if wants_features(cfg):
+    if wants_features(cfg) and getattr(cfg, "feature_cache_flip", False) is not True:        # (with it: feature_cache.py's mirror cache)
         return pre + f"feature_cache_gb = {cfg.feature_cache_gb} caches the box features of the unmirrored frame; they cannot serve a mirrored one"
     if cfg.dataset_name == "volleyball":
         from .volleyball import ACTIVITIES

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import collections
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -110,6 +111,8 @@ def _cached_crops(model, refs, boxes_in, N):
     boxes = boxes_in.reshape(B * T, N * 4)
     if boxes.dtype != torch.float32:
         boxes = boxes.float()
+    if getattr(refs, "mirror", None) is not None:
+        return _paired_crops(model, refs, boxes, N)
     M = refs.miss_images.shape[0]
     rows = None
     if M:
@@ -118,6 +121,48 @@ def _cached_crops(model, refs, boxes_in, N):
             crops = _crops(model, refs.miss_images.reshape(M, 3, H, W), boxes.index_select(0, pos).reshape(M * N, 4), N)[0]
         rows = crops.reshape(M, N * D * K * K).contiguous()
     feats, new_ids = refs.cache.rows(refs.frame_ids, boxes, refs.miss_pos, rows)
+    refs.inserted.extend(new_ids)
+    return feats
+
+
+def _paired_crops(model, refs, boxes, N):
+    """_cached_crops behind a cache with a mirror cache (cfg.feature_cache_flip): boxes fp32 [B*T, N*4] are the step's, mirrored in the
+    rows `refs.flipped` names.  The M decoded frames are computed in BOTH orientations (all of them, as without a mirror cache, unless
+    both caches hold every one already -- the second call of a test-time pair, a batch decoded ahead of the step that stored it): one
+    din_copy_rows_u8_flip launch mirrors their pixels, one din_flip_clip_labels launch their unmirrored boxes, and the trunk runs once
+    per orientation over M frames each (never once over 2M: a frame's features are then what a batch of M frames gives in either
+    orientation).  One din_feat_rows launch over both caches' slabs builds feats (FeatureCache.rows_both); no launch but that one when
+    every frame is resident, whatever the mix of orientations."""
+    cfg = model.cfg
+    B, T = refs.shape[0], refs.shape[1]
+    H, W = cfg.image_size
+    D, K = cfg.emb_features, cfg.crop_size[0]
+    flipped = None if refs.flipped is None else refs.flipped.reshape(-1)
+    ids = refs.frame_ids.reshape(-1)
+    pos_h, images, pos = refs.miss_pos, refs.miss_images, refs.miss_pos_dev
+    M = len(pos_h)
+    if all(refs.cache.resident(ids[p]) and refs.mirror.resident(ids[p]) for p in pos_h):      # (true for M == 0)
+        feats, new_ids = refs.cache.rows_both(refs.mirror, ids, flipped, boxes)
+        refs.inserted.extend(new_ids)
+        return feats
+    if pos is None:
+        pos = torch.from_numpy(np.ascontiguousarray(pos_h)).to(boxes.device)
+    if flipped is not None and flipped[pos_h].any():
+        if refs.plain_boxes is None:
+            raise ValueError("a decoded frame sits in a mirrored row: FrameRefs.plain_boxes (the batch's boxes before mirroring) is needed")
+        plain = refs.plain_boxes.reshape(B * T, N * 4).float().index_select(0, pos).contiguous()
+    else:
+        plain = boxes.index_select(0, pos).contiguous()
+    images = images.reshape(M, 3, H, W).contiguous()
+    images_m, boxes_m = torch.empty_like(images), plain.clone()
+    fb = 3 * H * W
+    d_flags = refs.cache.gather_rows([images.data_ptr() + j * fb for j in range(M)], [images_m.data_ptr() + j * fb for j in range(M)],
+                                     (3, H, W), flip_rows=np.ones(M, dtype=bool))
+    ops.flip_clip_labels(boxes_m.view(M, N, 4), None, d_flags, None, None, float(cfg.out_size[1]))
+    with torch.no_grad():
+        rows = [_crops(model, im, bx.reshape(M * N, 4), N)[0].reshape(M, N * D * K * K).contiguous()
+                for im, bx in ((images, plain), (images_m, boxes_m))]
+    feats, new_ids = refs.cache.rows_both(refs.mirror, ids, flipped, boxes, pos_h, rows, (plain, boxes_m))
     refs.inserted.extend(new_ids)
     return feats
 

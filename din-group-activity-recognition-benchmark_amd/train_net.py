@@ -173,6 +173,9 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     why_not = frame_cache.flip_refusal(cfg) or frame_cache.jitter_refusal(cfg)     # (cfg.flip_prob, cfg.color_jitter: no device and no loader either)
     if why_not:
         raise ValueError(why_not)
+    if getattr(cfg, "test_flip", False):
+        raise ValueError(f"test_flip = {cfg.test_flip!r}: test-time flipping is the stage-2 trainer's (train_net_dynamic.train_net); stage 1 "
+                         f"evaluates every clip as decoded")
     model = build_model(cfg)                                           # (refuses stage 2 before touching the device)
     if getattr(cfg, "result_path", None) is None:
         cfg.init_config()

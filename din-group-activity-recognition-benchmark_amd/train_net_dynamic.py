@@ -170,16 +170,62 @@ def grad_stats_line(epoch, info):
             % (epoch, info["grad_norm_mean"], info["grad_norm_max"], info["clipped_steps"], info["skipped_steps"]))
 
 
+def combine_flip_scores(scores, mirrored_scores, label_map=None):
+    """test-time flipping (cfg.test_flip): 0.5 * (s + s_m[:, map]) in fp32.  scores [B, A] of the clips as decoded, mirrored_scores
+    [B, A] of their mirror images; label_map (volleyball.FLIP_ACTIVITIES; None: the identity, labels without a side): a mirrored
+    l_spike looks like r_spike, so the mirrored clip's column map[a] is the evidence for class a."""
+    s, m = scores.float(), mirrored_scores.float()
+    if label_map is not None:
+        m = m[:, label_map if isinstance(label_map, torch.Tensor) else torch.tensor(list(label_map), dtype=torch.int64, device=m.device)]
+    return 0.5 * (s + m)
+
+
+class _Mirror:
+    """the mirror images of an evaluation batch (cfg.test_flip), no random draw: a FrameRefs of a loader with a mirror cache turns
+    every row over (feature_cache.FrameRefs.mirrored); an images tensor goes through one din_copy_rows_u8_flip launch; the boxes
+    through one din_flip_clip_labels launch either way (the labels stay: the scores are read through the label map instead)"""
+
+    def __init__(self, cfg, device):
+        self.width, self.tables, self.flags = float(cfg.out_size[1]), frame_cache.TableUpload(device), None
+        self.label_map = None
+        if cfg.dataset_name == "volleyball":
+            from .volleyball import FLIP_ACTIVITIES
+            self.label_map = torch.tensor(FLIP_ACTIVITIES, dtype=torch.int64, device=device)
+
+    def inputs(self, images, boxes, bboxes_num=None):
+        rows = images.shape[0] * images.shape[1]
+        if isinstance(images, feature_cache.FrameRefs):
+            if images.mirror is None:
+                raise ValueError("test_flip: the loader's feature cache has no mirror cache (cfg.feature_cache_flip)")
+            if self.flags is None or self.flags.numel() != rows:
+                self.flags = torch.ones(rows, dtype=torch.int64, device=boxes.device)
+            mirrored, flags = images.mirrored(boxes), self.flags
+        else:
+            if images.dtype != torch.uint8 or not images.is_contiguous():
+                raise ValueError(f"test_flip works on contiguous uint8 [B, T, 3, H, W] frames on the device; the loader gave {images.dtype} "
+                                 f"{tuple(images.shape)}")
+            mirrored = torch.empty_like(images)
+            fb = images[0, 0].numel()
+            flags = self.tables.gather_rows([images.data_ptr() + i * fb for i in range(rows)], [mirrored.data_ptr() + i * fb for i in range(rows)],
+                                            images.shape[2:], np.ones(rows, dtype=bool))
+        boxes_m = boxes.clone()
+        ops.flip_clip_labels(boxes_m, None, flags, None if bboxes_num is None else bboxes_num.contiguous(), None, self.width)
+        return (mirrored, boxes_m) if bboxes_num is None else (mirrored, boxes_m, bboxes_num)
+
+
 def _test_pass(data_loader, model, device, epoch, cfg, collective):
     model.eval()
     meters = _Epoch(cfg, device)
     feed = frame_cache.feed_for(data_loader, device)
+    mirror = _Mirror(cfg, device) if getattr(cfg, "test_flip", False) else None      # (off: the pass below is what it always was)
     with torch.no_grad():
         for batch_data in feed:
             batch_size, num_frames = batch_data[0].shape[0], batch_data[0].shape[1]
             activities_in = batch_data[3].reshape((batch_size, num_frames))[:, 0].reshape((batch_size,))
             inputs = (batch_data[0], batch_data[1], batch_data[4]) if collective else (batch_data[0], batch_data[1])
             scores = model(inputs)["activities"]
+            if mirror is not None:                                     # both orientations, averaged; the labels are the unmirrored ones
+                scores = combine_flip_scores(scores, model(mirror.inputs(*inputs))["activities"], mirror.label_map)
             meters.add(scores, activities_in, F.cross_entropy(scores, activities_in))
     frame_cache.end_pass(feed)
     return meters.info(epoch)
@@ -229,7 +275,8 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     # -- then cfg.flip_prob where a mirrored clip cannot be fed, and cfg.color_jitter likewise
     # -- and cfg.feature_cache_path without a feature cache to keep there
     why_not = (ops.deterministic_refusal(cfg, int(os.environ.get("WORLD_SIZE", "1"))) or feature_cache.refusal(cfg)
-               or frame_cache.flip_refusal(cfg) or frame_cache.jitter_refusal(cfg) or feature_cache.path_refusal(cfg))
+               or frame_cache.flip_refusal(cfg) or frame_cache.jitter_refusal(cfg) or feature_cache.path_refusal(cfg)
+               or feature_cache.flip_cache_refusal(cfg))                     # (cfg.feature_cache_flip, cfg.test_flip)
     if why_not:
         raise ValueError(why_not)
     if getattr(cfg, "deterministic", False):
@@ -318,6 +365,8 @@ def _train_net(cfg, training_set, validation_set, max_steps):
         before = f.inserted
         info = run_pass()
         info.update(feature_cache_loaded=f.loaded, feature_cache_saved=f.save_if_grown(before))
+        if f.flip_path is not None:                                    # (a loader with a mirror cache: its file's counts as well)
+            info.update(feature_cache_flip_loaded=f.flip_loaded, feature_cache_flip_saved=f.flip_written)
         return info
 
     if cfg.test_before_train:

@@ -14,7 +14,11 @@ ARG run refuses these files by naming `frames` instead of misreading them.
 
   python tools/build_feature_cache.py --out DIR --stage1 result/stage1.pth [--data-path data/volleyball] [--backbone vgg16|inv3]
          [--backbone-dtype fp32|bf16] [--cache-dtype fp32|bf16] [--cache-gb 64] [--image-size 720 1280] [--out-size 22 40]
-         [--emb-features 512] [--set-bn-eval 0|1] [--batch 8] [--workers 4]
+         [--emb-features 512] [--set-bn-eval 0|1] [--batch 8] [--workers 4] [--flip]
+
+--flip (cfg.feature_cache_flip): every frame is computed in both orientations in the same pass and train.flip.dinfc / val.flip.dinfc are
+written next to the plain files, so that runs with flip_prob > 0 or test_flip start with both caches resident.  --cache-gb is per cache:
+the pass holds twice as much.
 """
 import argparse
 import copy
@@ -48,7 +52,7 @@ def build(cfg, device=None, say=print) -> dict:
     {split: frames in the file}.  Files that exist and match are taken in first, so only what they lack is computed."""
     from din_amd import feature_cache as FE, frame_cache as FC, infer_model as IM
     from din_amd.dataset import return_dataset
-    why_not = FE.refusal(cfg) or FE.path_refusal(cfg)
+    why_not = FE.refusal(cfg) or FE.path_refusal(cfg) or FE.flip_cache_refusal(cfg)
     if why_not:
         raise ValueError(why_not)
     if getattr(cfg, "feature_cache_path", None) is None:
@@ -56,6 +60,8 @@ def build(cfg, device=None, say=print) -> dict:
     device = torch.device(device or "cuda:0")
     dcfg = copy.copy(cfg)
     dcfg.inference_module_name, dcfg.training_stage = "dynamic_volleyball", 2       # the whole window of every clip, in both splits
+    if getattr(cfg, "feature_cache_flip", False):                  # a mirror cache behind both loaders, whatever the run will ask for
+        dcfg.flip_prob, dcfg.test_flip = (getattr(cfg, "flip_prob", 0.0) or 1.0), True
     training_set, validation_set = return_dataset(dcfg, frame_ids=True)
     loaders = FC.build_loaders(dcfg, training_set, validation_set, cfg.batch_size, None, device, True)
     trunk = Trunk(cfg)
@@ -68,14 +74,16 @@ def build(cfg, device=None, say=print) -> dict:
     for split, f in FE.cache_files(cfg, trunk, *loaders, 0, 1, say).items():
         f.load()
         before, t0 = f.inserted, time.perf_counter()
+        table = f.loader.cache.table                               # (frames are counted in the plain cache: the pair rule keeps the mirror cache level with it)
+        held = table.inserted
         feed = f.loader.feed(device)
         with torch.no_grad():
             for refs, boxes, *_ in feed:                           # (the feed marks `resident` for what this call stores)
                 IM._cached_crops(trunk, refs, boxes, cfg.num_boxes)
         feed.check()
-        say(f"{split}: {f.inserted - before} frames computed in {time.perf_counter() - t0:.1f} s, {f.inserted} resident")
+        say(f"{split}: {table.inserted - held} frames computed in {time.perf_counter() - t0:.1f} s, {table.inserted} resident")
         f.save_if_grown(before)
-        done[split] = f.inserted
+        done[split] = table.inserted
     return done
 
 
@@ -95,6 +103,7 @@ def main():
     ap.add_argument("--set-bn-eval", type=int, choices=(0, 1), default=None, help="cfg.set_bn_eval (default: 1 for inv3, 0 for vgg16)")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--flip", action="store_true", help="cfg.feature_cache_flip: write the mirror caches' files (*.flip.dinfc) as well")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("build_feature_cache.py runs the backbone on the MI355X: no GPU here, nothing written")
@@ -105,7 +114,7 @@ def main():
     cfg.out_size = tuple(a.out_size) if a.out_size else ((22, 40) if a.backbone == "vgg16" else (87, 157))
     cfg.emb_features = a.emb_features or (512 if a.backbone == "vgg16" else 1056)
     cfg.feature_cache_gb, cfg.feature_cache_dtype, cfg.feature_cache_path = a.cache_gb, a.cache_dtype, a.out
-    cfg.batch_size, cfg.num_workers = a.batch, a.workers
+    cfg.batch_size, cfg.num_workers, cfg.feature_cache_flip = a.batch, a.workers, bool(a.flip)
     if a.data_path:
         cfg.data_path = a.data_path
     if a.stage1:
