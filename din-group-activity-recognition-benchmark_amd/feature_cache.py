@@ -17,6 +17,11 @@ fc_emb_1, the head -- nothing decoded, nothing uploaded, no backbone launch.
   * the feed then marks `dataset.resident` for what went in, and the pass ends with `check()`: one synchronisation, RuntimeError if a
     served row was computed for other boxes than the step's.
 
+One cache or a cache with its mirror cache (below) is one code path throughout, the single cache being the case "every row has
+orientation 0": `gather_tables` walks the batch and builds the launch's address tables from SlotTables and plain addresses (host
+arithmetic, tested without a device), `FeatureCache.rows` / `rows_both` check their arguments and launch what it built,
+infer_model._cached_crops runs the trunk once per orientation, and `CacheFile` loops over one or two (cache, file) entries.
+
 Same store as the frame cache (frame_cache.SlotStore): lazy slabs, no eviction, a full cache stops inserting and the remaining frames
 keep being decoded and computed.  Refusals and the cache's lifetime: train_net_dynamic.train_net.
 
@@ -39,8 +44,8 @@ exactly two variants, so both can be resident:
   * `FeatureFeed` draws the clips of a training pass as the frame path does (frame_cache.EpochFlips: the same stream) and mirrors the
     batch's labels BEFORE the gather, so the box check compares mirrored boxes with mirrored trailers; `FrameRefs.flipped` tells the
     model call which rows are mirrored;
-  * `FeatureCache.rows_both` builds ONE address table over both caches' slabs: a batch of resident frames is one din_feat_rows (or
-    din_feat_rows_bf16) launch for any mix of orientations;
+  * `FeatureCache.rows_both` is `rows` over both caches' slabs: ONE address table, so a batch of resident frames is one din_feat_rows
+    (or din_feat_rows_bf16) launch for any mix of orientations;
   * the mirror cache's file stands next to the plain one (`flip_file_name`: train.flip.dinfc); its header says "orientation":
     "mirrored", a plain file's header has no such key, and either offered as the other is refused at load.
 """
@@ -71,6 +76,58 @@ def insert_pair(tables, fid: int, grows=None) -> dict:
     if not all(tables[k].reserve(grows[k]) for k in lacking):
         return {}
     return {k: tables[k].insert(fid, grows[k]) for k in lacking}
+
+
+def gather_tables(tables, slot_address, grows, frame_ids, orient, miss_pos, computed, row_bytes: int):
+    """the address tables of ONE din_feat_rows launch over one cache, or over a cache and its mirror cache -- host arithmetic only, no
+    tensor and no device; ids, orientations and positions are Python ints.  tables: one SlotTable per orientation; slot_address[k](slot) -> address and grows[k] belong to tables[k];
+    row i of the batch is frame frame_ids[i] in orientation orient[i] (all 0 with one table); miss_pos: which rows of the batch the
+    decoded frames are, each computed in every orientation, copy j of orientation o at computed[o] = (base address, row stride) -- the
+    first copy of a frame serves all its rows.  Returns (src, keep, ref, extra, reported):
+      * a row whose frame was resident before the call comes from its slot: keep 0, ref = the slot's stored boxes (they are compared);
+      * any other row comes from the computed row, ref 0; the first such row of a frame that went in carries keep = its new slot;
+      * a decoded frame goes into every table that lacks it or into none (`insert_pair`), the frames taken in the order of their first
+        row in the batch; `reported` are the frames for which that took place: every table holds them since this call;
+      * `extra`: the inserts of an orientation no row of the batch asks for, as (orientation, frame id, index of the decoded copy),
+        plain first, then by copy.  Their entries follow the batch's rows in src / keep / ref; the caller appends their boxes.
+    The counters move as if every row were looked up and then stored: one lookup per row of a frame this call did not insert, one miss
+    for the row that carries an insert, nothing for the later rows of that frame."""
+    ids = list(frame_ids)
+    first = {}                                       # frame id -> index of its first decoded copy
+    for j, p in enumerate(miss_pos):
+        first.setdefault(ids[p], j)
+    took, fresh, reported = {}, [set() for _ in tables], []
+    for fid in dict.fromkeys(f for f in ids if f in first) if first else ():     # the pair rule, once per decoded frame
+        got = insert_pair(tables, fid, grows)
+        for k, slot in got.items():
+            took[(fid, k)] = slot
+            fresh[k].add(fid)
+        if got:
+            reported.append(fid)
+    src, keep, ref = [], [], []
+    for fid, o in zip(ids, orient):
+        slot = -1 if fid in fresh[o] else tables[o].lookup(fid)
+        if slot >= 0:                                # resident before this launch: served from the slot, boxes compared
+            src.append(slot_address[o](slot))
+            keep.append(0)
+            ref.append(src[-1] + row_bytes)
+            continue
+        if fid not in first:
+            which = f" ({ORIENTATIONS[o]})" if len(tables) > 1 else ""
+            raise KeyError(f"frame {fid}{which} is neither resident nor among the computed rows of this batch")
+        slot = took.pop((fid, o), -1)                # (its first row of this orientation stores it ...
+        tables[o].misses += int(slot >= 0)           # ... and is the lookup that missed; the later ones are not looked up)
+        base, stride = computed[o]
+        src.append(base + first[fid] * stride)
+        keep.append(slot_address[o](slot) if slot >= 0 else 0)
+        ref.append(0)
+    extra = sorted(((k, fid, first[fid]) for fid, k in took), key=lambda e: (e[0], e[2]))
+    for k, fid, j in extra:
+        base, stride = computed[k]
+        src.append(base + j * stride)
+        keep.append(slot_address[k](took[(fid, k)]))
+        ref.append(0)
+    return src, keep, ref, extra, reported
 
 
 class FeatureCache(SlotStore):
@@ -118,6 +175,12 @@ class FeatureCache(SlotStore):
         boxes = boxes.contiguous()
         return boxes.clone() if boxes.data_ptr() % 16 else boxes
 
+    @staticmethod
+    def _computed(t, shape) -> bool:
+        """whether `t` can be a launch's computed rows, or their boxes: a contiguous, 16-byte aligned fp32 device tensor of this shape"""
+        return t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape) \
+            and t.data_ptr() % 16 == 0
+
     def rows(self, frame_ids, boxes: torch.Tensor, miss_pos=(), miss_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[int]]:
         """frame_ids [R] (host), boxes fp32 [R, box_bytes / 4] on the device (this step's boxes of every row), miss_pos [M] (host: which
         of the R rows the computed rows are), miss_rows fp32 [M, row_elems] on the device -> (`dtype` [R, row_elems] on the device,
@@ -125,53 +188,12 @@ class FeatureCache(SlotStore):
         with the slot's) or from the computed row, which also goes into a free slot with its boxes while the cache has room.  A frame
         that occurs twice is served both times from the computed row, never from the slot written by this launch.  With bf16 storage
         the computed rows still arrive as fp32 and the launch rounds them (din_feat_rows_bf16)."""
-        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
         pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
-        rb, bb, ne = self.row_bytes, self.box_bytes, self.row_elems
-        boxes = self._step_boxes("rows", len(ids), boxes)
-        if len(pos):
-            if miss_rows is None or not miss_rows.is_cuda or miss_rows.dtype != torch.float32 or not miss_rows.is_contiguous() \
-                    or tuple(miss_rows.shape) != (len(pos), ne) or miss_rows.data_ptr() % 16:
-                raise ValueError(f"rows: {len(pos)} computed rows need a contiguous, 16-byte aligned fp32 device tensor "
-                                 f"{(len(pos), ne)}, got {None if miss_rows is None else tuple(miss_rows.shape)}")
-            if pos.min() < 0 or pos.max() >= len(ids):
-                raise ValueError("rows: miss_pos outside the batch")
-        row_of = {}                                  # frame id -> address of its computed row (the first one serves all)
-        for j, p in enumerate(pos):
-            row_of.setdefault(int(ids[p]), miss_rows.data_ptr() + j * ne * 4)
-        out = torch.empty((len(ids), ne), dtype=self.dtype, device=self.device)
-        out_ptr = out.data_ptr()
-        src, keep, ref, new_ids, fresh = [], [], [], [], set()
-        for fid in ids:
-            fid = int(fid)
-            slot = -1 if fid in fresh else self.table.lookup(fid)
-            if slot >= 0:                            # resident before this launch: served from the slot, boxes compared
-                src.append(self.slot_address(slot))
-                keep.append(0)
-                ref.append(src[-1] + rb)
-                continue
-            if fid not in row_of:
-                raise KeyError(f"frame {fid} is neither resident nor among the computed rows of this batch")
-            slot = -1 if fid in fresh else self.table.insert(fid, self._grow)
-            if slot >= 0:
-                fresh.add(fid)
-                new_ids.append(fid)
-            src.append(row_of[fid])
-            keep.append(self.slot_address(slot) if slot >= 0 else 0)
-            ref.append(0)
-        dst = [out_ptr + i * rb for i in range(len(ids))]
-        self._launch(src, dst, keep, ref, boxes, self._flag_rows(ids))
-        return out, new_ids
-
-    def _launch(self, src, dst, keep, ref, boxes: torch.Tensor, flags: torch.Tensor) -> None:
-        """the one launch of a gather: din_feat_rows, or din_feat_rows_bf16 for bf16 slots"""
-        from . import ops
-        if self.dtype == torch.float32:
-            d_src, d_dst, d_keep, d_ref = self._upload(src, dst, keep, ref)
-            ops.feat_rows(d_src, d_dst, self.row_bytes, d_keep, d_ref, boxes, flags, self.box_bytes)
-        else:                                        # a row without a stored-boxes address is a computed one: fp32, to be rounded
-            d_src, d_dst, d_keep, d_ref, d_f32 = self._upload(src, dst, keep, ref, [int(r == 0) for r in ref])
-            ops.feat_rows_bf16(d_src, d_dst, self.row_elems, d_keep, d_ref, boxes, flags, self.box_bytes, d_f32)
+        M = len(pos)
+        if M and not self._computed(miss_rows, (M, self.row_elems)):
+            raise ValueError(f"rows: {M} computed rows need a contiguous, 16-byte aligned fp32 device tensor "
+                             f"{(M, self.row_elems)}, got {None if miss_rows is None else tuple(miss_rows.shape)}")
+        return self._gather("rows", (self,), frame_ids, None, boxes, pos, (miss_rows,), None)
 
     def rows_both(self, mirror: "FeatureCache", frame_ids, flipped, boxes: torch.Tensor, miss_pos=(), miss_rows=None,
                   miss_boxes=None) -> Tuple[torch.Tensor, List[int]]:
@@ -185,67 +207,45 @@ class FeatureCache(SlotStore):
         since this call).  The flags of all rows are this cache's: `check()` on it reports a mismatch in either orientation."""
         if not isinstance(mirror, FeatureCache) or (mirror.row_bytes, mirror.box_bytes, mirror.dtype) != (self.row_bytes, self.box_bytes, self.dtype):
             raise ValueError("rows_both: the mirror cache is a FeatureCache of the same row_bytes, box_bytes and dtype")
-        caches = (self, mirror)
-        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
         pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
-        orient = np.zeros(len(ids), dtype=np.int64) if flipped is None else (np.asarray(flipped).reshape(-1) != 0).astype(np.int64)
+        M = len(pos)
+        for what, pair, shape in (("computed rows", miss_rows, (M, self.row_elems)), ("boxes of the computed rows", miss_boxes, (M, self.box_bytes // 4))):
+            if M and (pair is None or len(pair) != 2 or not all(self._computed(t, shape) for t in pair)):
+                raise ValueError(f"rows_both: the {what} are two contiguous, 16-byte aligned fp32 device tensors {shape}, one per orientation")
+        return self._gather("rows_both", (self, mirror), frame_ids, flipped, boxes, pos, miss_rows, miss_boxes)
+
+    def _gather(self, who: str, caches, frame_ids, flipped, boxes: torch.Tensor, pos: np.ndarray, miss_rows, miss_boxes):
+        """`rows` / `rows_both` behind the checks of their computed rows: the address tables (`gather_tables`), `out`, the flags, the launch"""
+        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        orient = [0] * len(ids) if flipped is None else (np.asarray(flipped).reshape(-1) != 0).astype(np.int64).tolist()
         if len(orient) != len(ids):
-            raise ValueError(f"rows_both: {len(orient)} orientation flags for {len(ids)} rows")
-        rb, bb, ne = self.row_bytes, self.box_bytes, self.row_elems
-        boxes = self._step_boxes("rows_both", len(ids), boxes).reshape(len(ids), bb // 4)
-        if len(pos):
-            for what, pair, shape in (("computed rows", miss_rows, (len(pos), ne)), ("boxes of the computed rows", miss_boxes, (len(pos), bb // 4))):
-                if pair is None or len(pair) != 2 or any(t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
-                                                         or tuple(t.shape) != shape or t.data_ptr() % 16 for t in pair):
-                    raise ValueError(f"rows_both: the {what} are two contiguous, 16-byte aligned fp32 device tensors {shape}, one per orientation")
-            if pos.min() < 0 or pos.max() >= len(ids):
-                raise ValueError("rows_both: miss_pos outside the batch")
-        first, row_of = {}, ({}, {})                 # frame id -> index of its first decoded copy; per orientation: -> address of its row
-        for j, p in enumerate(pos):
-            fid = int(ids[p])
-            if fid not in first:
-                first[fid] = j
-                for o in (0, 1):
-                    row_of[o][fid] = miss_rows[o].data_ptr() + j * ne * 4
-        took, fresh, new_ids = {}, (set(), set()), []
-        for fid in first:                            # the pair rule, once per decoded frame, in batch order
-            got = insert_pair([c.table for c in caches], fid, [c._grow for c in caches])
-            for k, slot in got.items():
-                took[(fid, k)] = slot
-                fresh[k].add(fid)
-            if got:
-                new_ids.append(fid)
-        src, keep, ref = [], [], []
-        for fid, o in zip(ids, orient):
-            fid, o, c = int(fid), int(o), caches[int(o)]
-            slot = -1 if fid in fresh[o] else c.table.lookup(fid)
-            if slot >= 0:                            # resident before this launch: served from the slot, boxes compared
-                src.append(c.slot_address(slot))
-                keep.append(0)
-                ref.append(src[-1] + rb)
-                continue
-            if fid not in row_of[o]:
-                raise KeyError(f"frame {fid} ({ORIENTATIONS[o]}) is neither resident nor among the computed rows of this batch")
-            slot = took.pop((fid, o), -1)            # (its first row of this orientation stores it)
-            c.table.misses += int(slot >= 0)         # (counted as `rows` counts it: the lookup that would have missed)
-            src.append(row_of[o][fid])
-            keep.append(c.slot_address(slot) if slot >= 0 else 0)
-            ref.append(0)
-        extra = sorted(took.items(), key=lambda kv: (kv[0][1], first[kv[0][0]]))     # inserts no row of the batch carries: plain first
-        if extra:
-            picks = [miss_boxes[k].index_select(0, torch.tensor([first[f] for (f, kk), _ in extra if kk == k], dtype=torch.int64, device=boxes.device))
-                     for k in (0, 1) if any(kk == k for (_, kk), _ in extra)]
-            boxes = torch.cat([boxes] + picks)
-            for (fid, k), slot in extra:
-                src.append(row_of[k][fid])
-                keep.append(caches[k].slot_address(slot))
-                ref.append(0)
-            ids = np.concatenate([ids, np.asarray([f for (f, _), _ in extra], dtype=np.int64)])
-        out = torch.empty((len(ids), ne), dtype=self.dtype, device=self.device)     # (the extra rows' copies land behind the batch's)
+            raise ValueError(f"{who}: {len(orient)} orientation flags for {len(ids)} rows")
+        rb, ne = self.row_bytes, self.row_elems
+        boxes = self._step_boxes(who, len(ids), boxes)
+        if len(pos) and (pos.min() < 0 or pos.max() >= len(ids)):
+            raise ValueError(f"{who}: miss_pos outside the batch")
+        computed = [(t.data_ptr(), ne * 4) for t in miss_rows] if len(pos) else []
+        src, keep, ref, extra, reported = gather_tables([c.table for c in caches], [c.slot_address for c in caches], [c._grow for c in caches],
+                                                        ids.tolist(), orient, pos.tolist(), computed, rb)
+        if extra:                                    # (their boxes are the decoded copies' of that orientation; their copies land behind the batch's)
+            picks = [miss_boxes[k].index_select(0, torch.tensor([j for kk, _, j in extra if kk == k], dtype=torch.int64, device=boxes.device))
+                     for k in sorted({k for k, _, _ in extra})]
+            boxes = torch.cat([boxes.reshape(len(ids), -1)] + picks)
+            ids = np.concatenate([ids, np.asarray([f for _, f, _ in extra], dtype=np.int64)])
+        out = torch.empty((len(ids), ne), dtype=self.dtype, device=self.device)
         out_ptr = out.data_ptr()
-        dst = [out_ptr + i * rb for i in range(len(ids))]
-        self._launch(src, dst, keep, ref, boxes, self._flag_rows(ids))
-        return out[:len(orient)], new_ids
+        self._launch(src, [out_ptr + i * rb for i in range(len(ids))], keep, ref, boxes, self._flag_rows(ids))
+        return out[:len(orient)], reported
+
+    def _launch(self, src, dst, keep, ref, boxes: torch.Tensor, flags: torch.Tensor) -> None:
+        """the one launch of a gather: din_feat_rows, or din_feat_rows_bf16 for bf16 slots"""
+        from . import ops
+        if self.dtype == torch.float32:
+            d_src, d_dst, d_keep, d_ref = self._upload(src, dst, keep, ref)
+            ops.feat_rows(d_src, d_dst, self.row_bytes, d_keep, d_ref, boxes, flags, self.box_bytes)
+        else:                                        # a row without a stored-boxes address is a computed one: fp32, to be rounded
+            d_src, d_dst, d_keep, d_ref, d_f32 = self._upload(src, dst, keep, ref, [int(r == 0) for r in ref])
+            ops.feat_rows_bf16(d_src, d_dst, self.row_elems, d_keep, d_ref, boxes, flags, self.box_bytes, d_f32)
 
     def check(self) -> None:
         """end of a pass: synchronise once, read the flags of every row gathered since the last check, clear them; RuntimeError naming
@@ -410,16 +410,18 @@ class FrameRefs:
         shape = tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list)) else tuple(shape)
         if len(shape) != 5 or tuple(shape[2:]) != self.shape[2:] or shape[0] * shape[1] != self.frame_ids.size:
             raise ValueError(f"FrameRefs.reshape: only the two leading dimensions of {self.shape} can be reshaped, got {shape}")
-        out = FrameRefs(self.frame_ids.reshape(shape[0], shape[1]), self.miss_images, self.miss_pos, self.cache, self.miss_pos_dev,
-                        self.mirror, None if self.flipped is None else self.flipped.reshape(shape[0], shape[1]), self.plain_boxes)
-        out.inserted = self.inserted                 # (shared: the feed reads it off the object it yielded)
-        return out
+        return self._but(frame_ids=self.frame_ids.reshape(shape[0], shape[1]),
+                         flipped=None if self.flipped is None else self.flipped.reshape(shape[0], shape[1]))
 
     def mirrored(self, plain_boxes: torch.Tensor) -> "FrameRefs":
         """the same frames in the other orientation, every row (test-time flipping: the caller mirrors the boxes it hands to the model
         and passes the ones it mirrored them from)"""
-        flipped = np.ones(self.frame_ids.shape, dtype=bool) if self.flipped is None else ~self.flipped
-        out = FrameRefs(self.frame_ids, self.miss_images, self.miss_pos, self.cache, self.miss_pos_dev, self.mirror, flipped, plain_boxes)
+        return self._but(flipped=np.ones(self.frame_ids.shape, dtype=bool) if self.flipped is None else ~self.flipped, plain_boxes=plain_boxes)
+
+    def _but(self, **changed) -> "FrameRefs":
+        """these refs with `changed` constructor arguments; `inserted` is shared: the feed reads it off the object it yielded"""
+        out = FrameRefs(**{**dict(frame_ids=self.frame_ids, miss_images=self.miss_images, miss_pos=self.miss_pos, cache=self.cache,
+                                  miss_pos_dev=self.miss_pos_dev, mirror=self.mirror, flipped=self.flipped, plain_boxes=self.plain_boxes), **changed})
         out.inserted = self.inserted
         return out
 
@@ -507,87 +509,63 @@ class CacheFile:
     def __init__(self, loader: FeatureLoader, path: str, meta: dict, say=print, flip_path: Optional[str] = None):
         self.loader, self.path, self.meta, self.say = loader, path, meta, say
         self.loaded = self.saved = 0
-        self.flip_path = flip_path if getattr(loader, "mirror", None) is not None else None
+        mirror = getattr(loader, "mirror", None)
+        self.flip_path = flip_path if mirror is not None else None
         self.flip_loaded = self.flip_saved = self.flip_written = 0  # (flip_written: by the last save_if_grown call, 0 if it wrote none)
-        self._on_file = [0, 0]                       # (with a mirror cache) each table's `inserted` when its file was last read or written
+        # (cache, its file, what its counters are called before "loaded" / "saved" / "written"), the plain one first
+        self._files = [(loader.cache, path, "")] + ([(mirror, flip_path, "flip_")] if mirror is not None else [])
+        self._on_file = [0] * len(self._files)       # each table's `inserted` when its file was last read or written
 
     @property
     def inserted(self) -> int:
-        if self.flip_path is not None:
-            return self.loader.cache.table.inserted + self.loader.mirror.table.inserted
-        return self.loader.cache.table.inserted
+        return sum(cache.table.inserted for cache, _, _ in self._files)
 
-    def _line(self, verb: str, frames: int, seconds: float, path: Optional[str] = None) -> None:
+    def _line(self, verb: str, frames: int, seconds: float, path: str) -> None:
         gb = frames * self.loader.cache.table.stride / 1e9
-        self.say(f"feature cache {verb} {path or self.path}: {frames} frames, {gb:.3f} GB, {seconds:.2f} s")
+        self.say(f"feature cache {verb} {path}: {frames} frames, {gb:.3f} GB, {seconds:.2f} s")
 
     def load(self) -> int:
-        """take the file in if there is one, and mark its frames resident so that the loader's workers stop decoding them -- what the
-        in-memory cache does from its second epoch.  A file of another fingerprint is a ValueError (FeatureCache.load)."""
-        if self.flip_path is not None:
-            return self._load_both()
-        if not os.path.exists(self.path):
-            return 0
-        t0 = time.perf_counter()
-        ids = self.loader.cache.load(self.path, self.meta)
-        flags = self.loader.dataset.resident
-        if ids and (min(ids) < 0 or max(ids) >= flags.numel()):
-            raise ValueError(f"feature cache file {self.path} names frames outside the dataset's table of {flags.numel()} frames")
-        if ids:
-            flags[torch.as_tensor(ids, dtype=torch.int64)] = 1
-        self.loaded = len(ids)
-        self._line("loaded from", self.loaded, time.perf_counter() - t0)
-        return self.loaded
-
-    def _load_both(self) -> int:
-        """`load` for a loader with a mirror cache: each file that exists goes into its cache; resident are the frames both hold"""
+        """take in each file there is, and mark the frames every cache of the loader got from its file resident, so that the loader's
+        workers stop decoding them -- what the in-memory cache does from its second epoch.  A file of another fingerprint is a
+        ValueError (FeatureCache.load)."""
         got = []
-        for cache, path, name in ((self.loader.cache, self.path, "loaded"), (self.loader.mirror, self.flip_path, "flip_loaded")):
+        for k, (cache, path, name) in enumerate(self._files):
             ids = []
             if os.path.exists(path):
                 t0 = time.perf_counter()
                 ids = cache.load(path, self.meta)
                 self._line("loaded from", len(ids), time.perf_counter() - t0, path)
-            setattr(self, name, len(ids))
+            setattr(self, name + "loaded", len(ids))
+            self._on_file[k] = cache.table.inserted
             got.append(ids)
-        self._on_file = [self.loader.cache.table.inserted, self.loader.mirror.table.inserted]
-        both = sorted(set(got[0]) & set(got[1]))
+        held = sorted(set(got[0]).intersection(*got[1:]))
         flags = self.loader.dataset.resident
-        if both and (both[0] < 0 or both[-1] >= flags.numel()):
-            raise ValueError(f"feature cache files {self.path} and {self.flip_path} name frames outside the dataset's table of "
-                             f"{flags.numel()} frames")
-        if both:
-            flags[torch.as_tensor(both, dtype=torch.int64)] = 1
+        if held and (held[0] < 0 or held[-1] >= flags.numel()):
+            which = f"file {self.path} names" if self.flip_path is None else f"files {self.path} and {self.flip_path} name"
+            raise ValueError(f"feature cache {which} frames outside the dataset's table of {flags.numel()} frames")
+        if held:
+            flags[torch.as_tensor(held, dtype=torch.int64)] = 1
         return self.loaded
 
-    def _save_both(self) -> int:
-        """`save_if_grown` for a loader with a mirror cache: each cache that took frames in since its file was last read or written"""
-        wrote = [0, 0]
-        for k, (cache, path, name) in enumerate(((self.loader.cache, self.path, "saved"), (self.loader.mirror, self.flip_path, "flip_saved"))):
+    def save_if_grown(self, inserted_before: int) -> int:
+        """after a pass: if a cache took frames in during the pass (`inserted_before`: `inserted` read before it), write each cache that
+        took frames in since its file was last read or written, whole; returns the frames written to the plain cache's file, 0 for a
+        pass that only read (`flip_written`: the same of the mirror cache's file)."""
+        self.flip_written = 0
+        if self.inserted == inserted_before:
+            return 0
+        wrote = {}
+        for k, (cache, path, name) in enumerate(self._files):
             if cache.table.inserted == self._on_file[k]:
                 continue
             t0 = time.perf_counter()
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-            wrote[k] = cache.save(path, self.meta)
+            wrote[name] = cache.save(path, self.meta)
             self._on_file[k] = cache.table.inserted
-            setattr(self, name, wrote[k])
-            self.flip_written = wrote[1]
-            self._line("saved to", wrote[k], time.perf_counter() - t0, path)
-        return wrote[0]
-
-    def save_if_grown(self, inserted_before: int) -> int:
-        """after a pass: write the whole cache if it took frames in during the pass (`inserted_before`: `inserted` read before it);
-        returns the frames written, 0 for a pass that only read.  The mirror cache's file likewise (`flip_written`)."""
-        self.flip_written = 0
-        if self.inserted == inserted_before:
-            return 0
-        if self.flip_path is not None:
-            return self._save_both()
-        t0 = time.perf_counter()
-        os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
-        self.saved = self.loader.cache.save(self.path, self.meta)
-        self._line("saved to", self.saved, time.perf_counter() - t0)
-        return self.saved
+            setattr(self, name + "saved", wrote[name])
+            self._line("saved to", wrote[name], time.perf_counter() - t0, path)
+        self.flip_written = wrote.get("flip_", 0)
+        return wrote.get("", 0)
 
 
 def cache_files(cfg, model, training_loader, validation_loader, rank: int = 0, world: int = 1, say=print) -> dict:
@@ -620,20 +598,17 @@ def row_and_box_bytes(cfg, dtype: torch.dtype = torch.float32) -> Tuple[int, int
 
 
 def feature_loaders(cfg, training_loader, validation_loader, training_set, validation_set, device):
-    """frame_cache.build_loaders with cfg.feature_cache_gb > 0: one FeatureCache of that many GB per dataset"""
+    """frame_cache.build_loaders with cfg.feature_cache_gb > 0: one FeatureCache of that many GB per dataset, and with
+    cfg.feature_cache_flip a mirror cache beside it where mirrored clips are asked for: the training set's with flip_prob > 0, the
+    validation set's with test_flip"""
     capacity = int(float(cfg.feature_cache_gb) * 1e9)
     dtype = DTYPES[getattr(cfg, "feature_cache_dtype", "fp32")]
     rb, bb = row_and_box_bytes(cfg, dtype)
-    if getattr(cfg, "feature_cache_flip", False):
-        # a mirror cache where mirrored clips are asked for: the training set's with flip_prob > 0, the validation set's with test_flip
-        def pair(loader, dataset, wanted):
-            cache = FeatureCache(device, rb, bb, capacity, dtype=dtype)
-            return FeatureLoader(loader, cache, dataset, FeatureCache(device, rb, bb, capacity, dtype=dtype, orientation="mirrored") if wanted else None)
-
-        return (pair(training_loader, training_set, bool(getattr(cfg, "flip_prob", 0.0))),
-                pair(validation_loader, validation_set, bool(getattr(cfg, "test_flip", False))))
-    return (FeatureLoader(training_loader, FeatureCache(device, rb, bb, capacity, dtype=dtype), training_set),
-            FeatureLoader(validation_loader, FeatureCache(device, rb, bb, capacity, dtype=dtype), validation_set))
+    flip = getattr(cfg, "feature_cache_flip", False)
+    mirrored = (flip and bool(getattr(cfg, "flip_prob", 0.0)), flip and bool(getattr(cfg, "test_flip", False)))
+    return tuple(FeatureLoader(loader, FeatureCache(device, rb, bb, capacity, dtype=dtype), dataset,
+                               FeatureCache(device, rb, bb, capacity, dtype=dtype, orientation="mirrored") if wanted else None)
+                 for loader, dataset, wanted in zip((training_loader, validation_loader), (training_set, validation_set), mirrored))
 
 
 def flip_cache_refusal(cfg) -> Optional[str]:

@@ -98,10 +98,15 @@ def _crops(model, images_flat, boxes_flat, N):
 
 
 def _cached_crops(model, refs, boxes_in, N):
-    """the trunk behind the box-feature cache (feature_cache.py): the backbone and RoIAlign run, without autograd, on the M frames of
-    `refs` that were decoded -- no launch when M == 0 -- and one din_feat_rows launch builds fp32 [B*T, N*D*K*K] from those rows and the
-    cache's slots, stores the new rows with their boxes and checks the boxes of the rows served from slots.  A cache of bf16 rows
-    (cfg.feature_cache_dtype = 'bf16') returns feats as bf16, ops.linear's lowp operand: one din_feat_rows_bf16 launch, no cast pass"""
+    """the trunk behind the box-feature cache (feature_cache.py), or behind the cache and its mirror cache (`refs.mirror`,
+    cfg.feature_cache_flip; the boxes are then mirrored in the rows `refs.flipped` names): the backbone and RoIAlign run, without
+    autograd, on the M frames of `refs` that were decoded, once per orientation over M frames each (never once over 2M: a frame's
+    features are then what a batch of M frames gives in either orientation) -- no launch when M == 0, nor with a mirror cache when both
+    caches hold every decoded frame already (the second call of a test-time pair, a batch decoded ahead of the step that stored it).
+    For the second orientation one din_copy_rows_u8_flip launch mirrors the pixels and one din_flip_clip_labels launch the unmirrored
+    boxes.  One din_feat_rows launch builds fp32 [B*T, N*D*K*K] from those rows and the slots of either cache, stores the new rows
+    with their boxes and checks the boxes of the rows served from slots (FeatureCache.rows / rows_both).  Caches of bf16 rows
+    (cfg.feature_cache_dtype = 'bf16') return feats as bf16, ops.linear's lowp operand: one din_feat_rows_bf16 launch, no cast pass"""
     cfg = model.cfg
     if cfg.train_backbone:
         raise ValueError("cached box features (cfg.feature_cache_gb) are the output of a frozen backbone; this model trains its backbone")
@@ -111,58 +116,36 @@ def _cached_crops(model, refs, boxes_in, N):
     boxes = boxes_in.reshape(B * T, N * 4)
     if boxes.dtype != torch.float32:
         boxes = boxes.float()
-    if getattr(refs, "mirror", None) is not None:
-        return _paired_crops(model, refs, boxes, N)
-    M = refs.miss_images.shape[0]
-    rows = None
-    if M:
-        pos = refs.miss_pos_dev if refs.miss_pos_dev is not None else torch.from_numpy(refs.miss_pos).to(boxes.device)
-        with torch.no_grad():
-            crops = _crops(model, refs.miss_images.reshape(M, 3, H, W), boxes.index_select(0, pos).reshape(M * N, 4), N)[0]
-        rows = crops.reshape(M, N * D * K * K).contiguous()
-    feats, new_ids = refs.cache.rows(refs.frame_ids, boxes, refs.miss_pos, rows)
-    refs.inserted.extend(new_ids)
-    return feats
-
-
-def _paired_crops(model, refs, boxes, N):
-    """_cached_crops behind a cache with a mirror cache (cfg.feature_cache_flip): boxes fp32 [B*T, N*4] are the step's, mirrored in the
-    rows `refs.flipped` names.  The M decoded frames are computed in BOTH orientations (all of them, as without a mirror cache, unless
-    both caches hold every one already -- the second call of a test-time pair, a batch decoded ahead of the step that stored it): one
-    din_copy_rows_u8_flip launch mirrors their pixels, one din_flip_clip_labels launch their unmirrored boxes, and the trunk runs once
-    per orientation over M frames each (never once over 2M: a frame's features are then what a batch of M frames gives in either
-    orientation).  One din_feat_rows launch over both caches' slabs builds feats (FeatureCache.rows_both); no launch but that one when
-    every frame is resident, whatever the mix of orientations."""
-    cfg = model.cfg
-    B, T = refs.shape[0], refs.shape[1]
-    H, W = cfg.image_size
-    D, K = cfg.emb_features, cfg.crop_size[0]
-    flipped = None if refs.flipped is None else refs.flipped.reshape(-1)
-    ids = refs.frame_ids.reshape(-1)
-    pos_h, images, pos = refs.miss_pos, refs.miss_images, refs.miss_pos_dev
+    mirror = getattr(refs, "mirror", None)
+    ids, pos_h = refs.frame_ids.reshape(-1), refs.miss_pos
+    flipped = None if mirror is None or refs.flipped is None else refs.flipped.reshape(-1)
+    if mirror is not None and all(refs.cache.resident(ids[p]) and mirror.resident(ids[p]) for p in pos_h):
+        pos_h = pos_h[:0]                            # nothing to compute (a cache without a mirror cache computes its M frames regardless)
     M = len(pos_h)
-    if all(refs.cache.resident(ids[p]) and refs.mirror.resident(ids[p]) for p in pos_h):      # (true for M == 0)
-        feats, new_ids = refs.cache.rows_both(refs.mirror, ids, flipped, boxes)
-        refs.inserted.extend(new_ids)
-        return feats
-    if pos is None:
-        pos = torch.from_numpy(np.ascontiguousarray(pos_h)).to(boxes.device)
-    if flipped is not None and flipped[pos_h].any():
-        if refs.plain_boxes is None:
-            raise ValueError("a decoded frame sits in a mirrored row: FrameRefs.plain_boxes (the batch's boxes before mirroring) is needed")
-        plain = refs.plain_boxes.reshape(B * T, N * 4).float().index_select(0, pos).contiguous()
+    computed = []                                  # per orientation: (its rows of the M decoded frames, the boxes they were computed for)
+    if M:
+        pos = refs.miss_pos_dev if refs.miss_pos_dev is not None else torch.from_numpy(np.ascontiguousarray(pos_h)).to(boxes.device)
+        if flipped is not None and flipped[pos_h].any():
+            if refs.plain_boxes is None:
+                raise ValueError("a decoded frame sits in a mirrored row: FrameRefs.plain_boxes (the batch's boxes before mirroring) is needed")
+            plain = refs.plain_boxes.reshape(B * T, N * 4).float().index_select(0, pos).contiguous()
+        else:
+            plain = boxes.index_select(0, pos).contiguous()
+        oriented = [(refs.miss_images.reshape(M, 3, H, W).contiguous(), plain)]
+        if mirror is not None:
+            images = oriented[0][0]
+            images_m, boxes_m = torch.empty_like(images), plain.clone()
+            fb = 3 * H * W
+            d_flags = refs.cache.gather_rows([images.data_ptr() + j * fb for j in range(M)], [images_m.data_ptr() + j * fb for j in range(M)],
+                                             (3, H, W), flip_rows=np.ones(M, dtype=bool))
+            ops.flip_clip_labels(boxes_m.view(M, N, 4), None, d_flags, None, None, float(cfg.out_size[1]))
+            oriented.append((images_m, boxes_m))
+        with torch.no_grad():
+            computed = [(_crops(model, im, bx.reshape(M * N, 4), N)[0].reshape(M, N * D * K * K).contiguous(), bx) for im, bx in oriented]
+    if mirror is None:
+        feats, new_ids = refs.cache.rows(ids, boxes, pos_h, computed[0][0] if M else None)
     else:
-        plain = boxes.index_select(0, pos).contiguous()
-    images = images.reshape(M, 3, H, W).contiguous()
-    images_m, boxes_m = torch.empty_like(images), plain.clone()
-    fb = 3 * H * W
-    d_flags = refs.cache.gather_rows([images.data_ptr() + j * fb for j in range(M)], [images_m.data_ptr() + j * fb for j in range(M)],
-                                     (3, H, W), flip_rows=np.ones(M, dtype=bool))
-    ops.flip_clip_labels(boxes_m.view(M, N, 4), None, d_flags, None, None, float(cfg.out_size[1]))
-    with torch.no_grad():
-        rows = [_crops(model, im, bx.reshape(M * N, 4), N)[0].reshape(M, N * D * K * K).contiguous()
-                for im, bx in ((images, plain), (images_m, boxes_m))]
-    feats, new_ids = refs.cache.rows_both(refs.mirror, ids, flipped, boxes, pos_h, rows, (plain, boxes_m))
+        feats, new_ids = refs.cache.rows_both(mirror, ids, flipped, boxes, pos_h, [r for r, _ in computed], [bx for _, bx in computed])
     refs.inserted.extend(new_ids)
     return feats
 
