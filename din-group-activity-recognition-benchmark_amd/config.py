@@ -38,6 +38,14 @@ feature_cache_path.  Twice the memory: 61 GB per orientation for the 48300 volle
 test_flip (stage-2 trainer, evaluation passes; False = off; refused by the stage-1 trainer): every clip is scored as decoded and mirrored
 and the scores are averaged, 0.5 * (s + s_m[:, volleyball.FLIP_ACTIVITIES]) in fp32 (the identity map for collective); with
 feature_cache_gb > 0 the mirrored clips come from the mirror cache, so feature_cache_flip must be set.
+map_cache_gb (stage-2 trainer, frozen VGG16 backbone, either dataset, every stage-2 model; 0 = off; ignored by the stage-1 trainer): the
+frozen backbone's output map of every frame stays in HBM, up to that many GB per dataset, in the dtype the backbone emits (22 x 40 x 512
+fp32 = 1 802 240 bytes a volleyball frame, 87 GB for the 48300 frames, half as bf16; 675 840 bytes a collective frame).  A step runs the
+trunk over its decoded frames only, gathers the maps of the others from their slots in the same one launch, and runs RoIAlign on the
+step's own boxes -- so it serves what feature_cache_gb refuses: dynamic_tce_volleyball, which reads the map itself, and collective's
+per-clip actor counts.  For the other models the feature cache is the smaller choice.  Refused with train_backbone, with another cache
+(frame_cache_gb, feature_cache_gb), with backbone 'inv3' (two maps, 13 MB a frame), and with flip_prob, color_jitter or test_flip
+(din_amd/feature_cache.py: MapCache, map_refusal).
 All are opt-in: at 0 / False / None the trainers behave exactly as without them."""
 from __future__ import annotations
 
@@ -66,6 +74,7 @@ _DEFAULTS = dict(
     color_jitter=None,
     feature_cache_path=None,
     feature_cache_flip=False, test_flip=False,
+    map_cache_gb=0,
 )
 
 

@@ -48,6 +48,13 @@ exactly two variants, so both can be resident:
     (or din_feat_rows_bf16) launch for any mix of orientations;
   * the mirror cache's file stands next to the plain one (`flip_file_name`: train.flip.dinfc); its header says "orientation":
     "mirrored", a plain file's header has no such key, and either offered as the other is refused at load.
+
+cfg.map_cache_gb (`MapCache`, `map_loaders`, `map_refusal`): a second, coarser cache for what the rows above cannot serve --
+Dynamic_TCE_volleyball, which reads the backbone's map of every frame, and the collective dataset, whose actor count varies per clip.
+A slot keeps the frozen VGG16's output map of a frame (22 x 40 x 512 fp32 = 1 802 240 bytes at the volleyball launchers' sizes, 87 GB for
+the 48 300 frames, half of that as bf16; 675 840 bytes for collective at 15 x 22), not the crops cut from it.  Same store, same feed, same
+refs and the same one launch (the map is the launch's "row", a 16-byte trailer naming frame and geometry its "boxes"); RoIAlign runs every
+step on the gathered maps with the step's own boxes.  No file, no mirror cache, no bf16 slots under an fp32 backbone.
 """
 from __future__ import annotations
 
@@ -59,7 +66,7 @@ from typing import Iterable, Iterator, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .frame_cache import CachedLoader, SlotStore
+from .frame_cache import CachedLoader, SlotStore, _f32_as_table
 from .input_feed import DeviceFeed
 
 
@@ -136,6 +143,7 @@ class FeatureCache(SlotStore):
     `capacity_bytes`, no eviction."""
 
     WHAT, UNIT = "feature cache", "frames"
+    MISMATCH = "for other boxes than the ones stored with their features"      # what check() says of a row whose trailer differs
     FLAG_ROWS = 1 << 20                              # rows between two check() calls the flags buffer holds without an extra check
 
     def __init__(self, device, row_bytes: int, box_bytes: int, capacity_bytes: int, chunk_frames: int = 64,
@@ -258,7 +266,7 @@ class FeatureCache(SlotStore):
         self._flagged, self._used = [], 0
         bad = np.flatnonzero(got)
         if bad.size:
-            raise RuntimeError(f"feature cache: {bad.size} rows were served for other boxes than the ones stored with their features "
+            raise RuntimeError(f"{self.WHAT}: {bad.size} rows were served {self.MISMATCH} "
                                f"(row, frame id): {[(int(r), int(ids[r])) for r in bad[:16]]}{' ...' if bad.size > 16 else ''}")
 
     # ---- the cache on disk (feature_cache_file.py: the layout and the fingerprint; train_net_dynamic: when) -------------------------------
@@ -371,11 +379,81 @@ class FeatureCache(SlotStore):
         return resident
 
 
+class MapCache(FeatureCache):
+    """cfg.map_cache_gb: the coarser sibling of the box-feature cache.  A slot holds the raw bytes of one frame of the frozen backbone's
+    output map as `forward_nhwc` returns it (NHWC [OH, OW, C], the backbone's dtype, padded channels included), followed by a 16-byte
+    trailer of four fp32 numbers that name it: frame id, OH, OW, C.  A map does not depend on boxes, so RoIAlign runs every step on the
+    step's own boxes, whatever their number (the collective dataset), and the map itself is the context Dynamic_TCE_volleyball reads.
+
+    The store, the address tables and the ONE din_feat_rows launch per step are FeatureCache's, unchanged: the launch is byte-agnostic,
+    so a map travels as the `row_bytes / 4` opaque 32-bit words of a "row" and the trailer as its "boxes".  The comparison the launch
+    makes on every served row becomes an integrity check: the slot holds the frame and the geometry that was asked for.
+
+    What infer_model._crops reads off the backbone's graph -- the output tensor's `relu_masked` flag and its dtype -- is not to be had in
+    a step that runs no trunk, so it is recorded here with the first insert (`map_dtype`, `relu_masked`)."""
+
+    WHAT = "map cache"
+    MISMATCH = "from slots whose trailer names another frame or map geometry than the one asked for"
+    TRAILER_BYTES = 16
+    MAX_ID = 1 << 24                                 # frame ids and sizes up to here are exact as fp32
+
+    def __init__(self, device, map_shape, itemsize: int, capacity_bytes: int, chunk_frames: int = 64):
+        self.map_shape = tuple(int(v) for v in map_shape)
+        if len(self.map_shape) != 3 or min(self.map_shape) <= 0 or max(self.map_shape) >= self.MAX_ID or itemsize not in (2, 4):
+            raise ValueError(f"MapCache: a map is [OH, OW, C] of 2- or 4-byte elements, got {map_shape!r} x {itemsize} bytes")
+        self.itemsize = int(itemsize)
+        super().__init__(device, int(np.prod(self.map_shape)) * self.itemsize, self.TRAILER_BYTES, capacity_bytes, chunk_frames)
+        self.map_dtype: Optional[torch.dtype] = None
+        self.relu_masked: Optional[bool] = None
+
+    def trailers(self, frame_ids) -> np.ndarray:
+        """float32 [R, 4]: (frame id, OH, OW, C) of every row -- what a slot's trailer holds and what a served row is compared with"""
+        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        if len(ids) and (ids.min() < 0 or ids.max() >= self.MAX_ID):
+            raise ValueError(f"map cache: frame ids lie in [0, {self.MAX_ID}) (exact as fp32), got {int(ids.min())} .. {int(ids.max())}")
+        out = np.empty((len(ids), 4), dtype=np.float32)
+        out[:, 0], out[:, 1:] = ids, self.map_shape
+        return out
+
+    def _describe(self, computed: torch.Tensor, relu_masked: bool) -> None:
+        """the first computed maps say what the slots hold; every later call must bring the same"""
+        OH, OW, C = self.map_shape
+        if not computed.is_cuda or tuple(computed.shape[1:]) != self.map_shape or computed.element_size() != self.itemsize:
+            raise ValueError(f"map cache: the slots hold [{OH}, {OW}, {C}] maps of {self.itemsize}-byte elements (cfg.out_size, "
+                             f"cfg.emb_features, cfg.backbone_dtype); the backbone returned {tuple(computed.shape[1:])} {computed.dtype}")
+        if self.map_dtype is None:
+            self.map_dtype, self.relu_masked = computed.dtype, bool(relu_masked)
+        elif (self.map_dtype, self.relu_masked) != (computed.dtype, bool(relu_masked)):
+            raise ValueError(f"map cache: the slots hold {self.map_dtype} maps with relu_masked = {self.relu_masked}; the backbone now "
+                             f"returned {computed.dtype} with relu_masked = {bool(relu_masked)}")
+
+    def maps(self, frame_ids, miss_pos=(), computed: Optional[torch.Tensor] = None, relu_masked: bool = False) -> Tuple[torch.Tensor, List[int]]:
+        """frame_ids [R] (host), miss_pos [M] (host: which of the R rows the computed maps are), computed [M, OH, OW, C] on the device
+        (bufs[0] of backbone.forward_nhwc over exactly those M frames; relu_masked: its output tensor's flag) -> (fm [R, OH, OW, C] in
+        the backbone's dtype, the frame ids inserted by this call).  `FeatureCache.rows` with the trailers as boxes: one launch; a frame
+        that occurs twice is served both times from the computed map, a full cache serves computed maps without keeping them."""
+        pos = np.asarray(miss_pos, dtype=np.int64).reshape(-1)
+        words = None
+        if len(pos):
+            if computed is None or computed.dim() != 4 or computed.shape[0] != len(pos):
+                raise ValueError(f"maps: {len(pos)} computed maps need a device tensor [{len(pos)}, OH, OW, C], got "
+                                 f"{None if computed is None else tuple(computed.shape)}")
+            self._describe(computed, relu_masked)
+            words = computed.contiguous().reshape(len(pos), -1).view(torch.float32)
+        t = self.trailers(frame_ids)
+        d_trailers, = self._upload(_f32_as_table(t))
+        out, new_ids = self.rows(frame_ids, d_trailers.view(torch.float32)[:t.size].reshape(len(t), 4), pos, words)
+        if self.map_dtype is None:                   # (no row at all: rows() has raised KeyError for any row it could not serve)
+            return out.reshape((0,) + self.map_shape), new_ids
+        return out.view(self.map_dtype).reshape((len(t),) + self.map_shape), new_ids
+
+
 class FrameRefs:
     """what a model receives in place of the images tensor when box features are cached: the frame ids of the batch [B, T] (host), the
     frames that were decoded (uint8 [M, 3, H, W] on the device), which of the B*T rows they are (`miss_pos`, host; `miss_pos_dev` the
     same on the device when the feed uploaded it), and the cache.  `shape` and `reshape` of the two leading dimensions are all the
-    models and trainers use of an images tensor besides handing it to infer_model.embed_boxes, which sets `inserted`.
+    models and trainers use of an images tensor besides handing it to infer_model.embed_boxes, which sets `inserted`.  `cache` may be
+    a MapCache (cfg.map_cache_gb): the same refs, fed by the same FeatureFeed; embed_boxes then also leaves the gathered maps in `context`.
 
     With a mirror cache (`mirror`, cfg.feature_cache_flip) every row has an orientation: `flipped` (host, bool [B, T]; None: no row is
     mirrored) says which rows are the mirrored frame, and the boxes the model receives are mirrored in those rows.  `plain_boxes` (the
@@ -395,6 +473,7 @@ class FrameRefs:
             raise ValueError(f"FrameRefs: {miss_images.shape[0]} decoded frames but {len(self.miss_pos)} positions")
         self.miss_pos_dev = miss_pos_dev
         self.inserted: List[int] = []
+        self.context = None                          # with a MapCache: (fm [B*T, OH, OW, C], its relu_masked flag), set by the model call
         self.mirror, self.plain_boxes = mirror, plain_boxes
         self.flipped = None if flipped is None else np.asarray(flipped).astype(bool)
         if self.flipped is not None and self.flipped.shape != self.frame_ids.shape:
@@ -664,4 +743,48 @@ def refusal(cfg) -> Optional[str]:
     if cfg.emb_features * K * K % 8 or cfg.num_features_boxes % 8:
         return pre + (f"the embedding GEMM multiplies bf16 operands only when emb_features * K * K = {cfg.emb_features * K * K} and "
                       f"num_features_boxes = {cfg.num_features_boxes} are multiples of 8")
+    return None
+
+
+# ---- the map cache (cfg.map_cache_gb; MapCache above) --------------------------------------------------------------------------------------
+def map_shape_and_itemsize(cfg) -> Tuple[Tuple[int, int, int], int]:
+    """([OH, OW, C], bytes per element) of the one map a frozen VGG16 ends in: cfg.out_size, all cfg.emb_features channels, bf16 under
+    backbone_dtype = 'bf16' and fp32 otherwise ('fp32_bf16x3' stores fp32).  22 x 40 x 512 x 4 = 1 802 240 bytes at the volleyball
+    launchers' sizes, 15 x 22 x 512 x 4 = 675 840 for collective; MapCache refuses a backbone that returns anything else."""
+    return (int(cfg.out_size[0]), int(cfg.out_size[1]), int(cfg.emb_features)), (2 if getattr(cfg, "backbone_dtype", "fp32") == "bf16" else 4)
+
+
+def map_loaders(cfg, training_loader, validation_loader, training_set, validation_set, device):
+    """frame_cache.build_loaders with cfg.map_cache_gb > 0: one MapCache of that many GB per dataset behind a FeatureLoader -- the
+    feed, the refs and the `resident` marking are the box-feature cache's"""
+    capacity = int(float(cfg.map_cache_gb) * 1e9)
+    shape, itemsize = map_shape_and_itemsize(cfg)
+    return tuple(FeatureLoader(loader, MapCache(device, shape, itemsize, capacity), dataset)
+                 for loader, dataset in ((training_loader, training_set), (validation_loader, validation_set)))
+
+
+def map_refusal(cfg) -> Optional[str]:
+    """why cfg.map_cache_gb cannot be honoured, or None (train_net_dynamic.train_net raises ValueError with it, after every other
+    refusal)"""
+    gb = getattr(cfg, "map_cache_gb", 0)
+    if isinstance(gb, (bool, np.bool_)) or not isinstance(gb, (int, float, np.integer, np.floating)) or not 0.0 <= float(gb) < float("inf"):
+        return f"map_cache_gb = {gb!r}: the size of the map cache in GB is a real number >= 0 (0 = off)"
+    if gb == 0:
+        return None
+    pre = f"map_cache_gb = {gb}: "
+    if cfg.train_backbone:
+        return pre + "cached maps are the output of a FROZEN backbone; train_backbone is set"
+    for other in ("frame_cache_gb", "feature_cache_gb"):
+        if float(getattr(cfg, other, 0) or 0) > 0:
+            return pre + f"{other} = {getattr(cfg, other)} is set as well; a step is fed from one cache: choose one of the three"
+    if cfg.backbone == "inv3":
+        return pre + ("backbone 'inv3' does not end in one map that holds all emb_features channels: its two maps (288 channels at 87 x "
+                      "157 and 768 at 43 x 78) are 13 MB a frame even as bf16, 630 GB for the 48300 volleyball frames; the box-feature "
+                      "cache (feature_cache_gb) keeps 1.3 MB a frame for it")
+    if getattr(cfg, "flip_prob", 0.0):
+        return pre + f"flip_prob = {cfg.flip_prob}: a cached map belongs to the frame as decoded; it cannot serve a mirrored one"
+    if getattr(cfg, "color_jitter", None) is not None:
+        return pre + f"color_jitter = {tuple(cfg.color_jitter)!r}: a cached map belongs to the frame as decoded; it cannot serve a jittered one"
+    if getattr(cfg, "test_flip", False):
+        return pre + "test_flip = True: a cached map belongs to the frame as decoded; there is no mirror map cache"
     return None

@@ -633,8 +633,12 @@ def wants_features(cfg) -> bool:
     return float(getattr(cfg, "feature_cache_gb", 0) or 0) > 0
 
 
+def wants_maps(cfg) -> bool:
+    return float(getattr(cfg, "map_cache_gb", 0) or 0) > 0
+
+
 def wants_frame_ids(cfg) -> bool:
-    return float(getattr(cfg, "frame_cache_gb", 0) or 0) > 0 or wants_features(cfg)
+    return float(getattr(cfg, "frame_cache_gb", 0) or 0) > 0 or wants_features(cfg) or wants_maps(cfg)
 
 
 def build_loaders(cfg, training_set, validation_set, per_rank: int, sampler, device, real_tree: bool):
@@ -655,6 +659,9 @@ def build_loaders(cfg, training_set, validation_set, per_rank: int, sampler, dev
     if wants_features(cfg):
         from .feature_cache import feature_loaders
         return feature_loaders(cfg, training_loader, validation_loader, training_set, validation_set, device)
+    if wants_maps(cfg):                              # (cfg.map_cache_gb: the frozen backbone's maps instead, feature_cache.MapCache)
+        from .feature_cache import map_loaders
+        return map_loaders(cfg, training_loader, validation_loader, training_set, validation_set, device)
     capacity = int(float(cfg.frame_cache_gb) * 1e9)
     frame_shape = (3,) + tuple(cfg.image_size)
     return (CachedLoader(training_loader, FrameCache(device, frame_shape, capacity), training_set),

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import ops
 from .backbone.backbone import MyInception_v3, MyVGG16
-from .feature_cache import FrameRefs
+from .feature_cache import FrameRefs, MapCache
 from .infer_module.ARG_infer_module import GCN_Module
 from .infer_module.AT_infer_module import Actor_Transformer, Embfeature_PositionEmbedding
 from .infer_module.dynamic_infer_module import (Dynamic_Person_Inference, Hierarchical_Dynamic_Inference,
@@ -106,7 +106,8 @@ def _cached_crops(model, refs, boxes_in, N):
     For the second orientation one din_copy_rows_u8_flip launch mirrors the pixels and one din_flip_clip_labels launch the unmirrored
     boxes.  One din_feat_rows launch builds fp32 [B*T, N*D*K*K] from those rows and the slots of either cache, stores the new rows
     with their boxes and checks the boxes of the rows served from slots (FeatureCache.rows / rows_both).  Caches of bf16 rows
-    (cfg.feature_cache_dtype = 'bf16') return feats as bf16, ops.linear's lowp operand: one din_feat_rows_bf16 launch, no cast pass"""
+    (cfg.feature_cache_dtype = 'bf16') return feats as bf16, ops.linear's lowp operand: one din_feat_rows_bf16 launch, no cast pass.
+    A `refs.cache` that is a feature_cache.MapCache (cfg.map_cache_gb) keeps maps instead of crops: the branch below."""
     cfg = model.cfg
     if cfg.train_backbone:
         raise ValueError("cached box features (cfg.feature_cache_gb) are the output of a frozen backbone; this model trains its backbone")
@@ -118,6 +119,24 @@ def _cached_crops(model, refs, boxes_in, N):
         boxes = boxes.float()
     mirror = getattr(refs, "mirror", None)
     ids, pos_h = refs.frame_ids.reshape(-1), refs.miss_pos
+    if isinstance(refs.cache, MapCache):
+        # cfg.map_cache_gb: the slots hold the backbone's map, not the crops.  The trunk runs once over exactly the M decoded frames, one
+        # din_feat_rows launch builds fm [B*T, OH, OW, C] from those maps and the slots, and RoIAlign cuts this step's boxes out of it:
+        # any number of boxes (Dynamic_collective), and fm is the context Dynamic_TCE_volleyball reads (`refs.context`).  No autograd
+        # edge leads into fm.  What _crops reads off the graph comes from the cache, which recorded it with its first insert.
+        computed, masked = None, False
+        if len(pos_h):
+            with torch.no_grad():
+                bufs, graph = model.backbone.forward_nhwc(refs.miss_images.reshape(len(pos_h), 3, H, W).contiguous())
+            if len(bufs) != 1 or bufs[0].shape[3] < D:
+                raise ValueError(f"cached maps (cfg.map_cache_gb) need a backbone that ends in one map holding all {D} channels; this one "
+                                 f"returned {[tuple(b.shape) for b in bufs]}")
+            computed, masked = bufs[0], graph.tensors[graph.output_tids[0]].relu_masked
+        fm, new_ids = refs.cache.maps(ids, pos_h, computed, masked)
+        refs.inserted.extend(new_ids)
+        refs.context = (fm, refs.cache.relu_masked)
+        return model.roi_align(fm, boxes_in.reshape(B * T * N, 4), ops.boxes_frame_index(B * T, N, boxes_in.device), nhwc=True,
+                               channels=D, relu_masked=refs.cache.relu_masked)
     flipped = None if mirror is None or refs.flipped is None else refs.flipped.reshape(-1)
     if mirror is not None and all(refs.cache.resident(ids[p]) and mirror.resident(ids[p]) for p in pos_h):
         pos_h = pos_h[:0]                            # nothing to compute (a cache without a mirror cache computes its M frames regardless)
@@ -193,6 +212,11 @@ class _DynamicBase(nn.Module):
     def _embed(self, images_in, boxes_in, N, return_context: bool = False):
         x, bufs, views, graph = embed_boxes(self, images_in, boxes_in, N, self.fc_emb_1)
         x = ops.layer_norm(x, self.nl_emb_1.weight, self.nl_emb_1.bias, relu=True)   # :185-186
+        if return_context and bufs is None:                                          # a FrameRefs: the gathered maps of a map cache
+            if images_in.context is None:
+                raise ValueError("this model reads the backbone's map of every frame, which the box-feature cache does not keep "
+                                 "(cfg.map_cache_gb does)")
+            return (x, *images_in.context)
         if return_context:                                                           # the LAST backbone output, pixel-major (:404)
             tid_last, coff, c = views[-1]
             assert coff == 0 and bufs[-1].shape[3] == c

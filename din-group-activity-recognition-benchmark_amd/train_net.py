@@ -190,6 +190,7 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     real_tree = False
     lcfg = copy.copy(cfg)
     lcfg.feature_cache_gb = 0                                          # stage 1 trains the backbone: the box-feature cache is stage 2's
+    lcfg.map_cache_gb = 0                                              # ... and so is the map cache
     if training_set is None and validation_set is None and getattr(cfg, "data_path", None) and os.path.isdir(cfg.data_path):
         from .dataset import return_dataset                           # stage-1 frame sampling (is_finetune) follows cfg.training_stage
         training_set, validation_set = return_dataset(cfg, frame_ids=frame_cache.wants_frame_ids(lcfg))

@@ -276,7 +276,8 @@ def train_net(cfg, training_set=None, validation_set=None, max_steps=None):
     # -- and cfg.feature_cache_path without a feature cache to keep there
     why_not = (ops.deterministic_refusal(cfg, int(os.environ.get("WORLD_SIZE", "1"))) or feature_cache.refusal(cfg)
                or frame_cache.flip_refusal(cfg) or frame_cache.jitter_refusal(cfg) or feature_cache.path_refusal(cfg)
-               or feature_cache.flip_cache_refusal(cfg))                     # (cfg.feature_cache_flip, cfg.test_flip)
+               or feature_cache.flip_cache_refusal(cfg)                      # (cfg.feature_cache_flip, cfg.test_flip)
+               or feature_cache.map_refusal(cfg))                            # (cfg.map_cache_gb: after every other refusal)
     if why_not:
         raise ValueError(why_not)
     if getattr(cfg, "deterministic", False):
@@ -315,7 +316,8 @@ def _train_net(cfg, training_set, validation_set, max_steps):
     sampler = data.distributed.DistributedSampler(training_set, world, rank, shuffle=True) if world > 1 else None
     # cfg.num_workers / cfg.frame_cache_gb (both 0 by default: the loaders below are then the plain num_workers=0 DataLoaders) apply to
     # the real dataset tree only: worker processes decode, and decoded frames stay in HBM from their first use on (frame_cache.py); with
-    # cfg.feature_cache_gb > 0 the frozen trunk's box features stay there instead (feature_cache.py).  The caches live for this call;
+    # cfg.feature_cache_gb > 0 the frozen trunk's box features stay there instead (feature_cache.py), with cfg.map_cache_gb > 0 its
+    # output maps (feature_cache.MapCache: Dynamic_TCE_volleyball and the collective dataset too).  The caches live for this call;
     # with cfg.feature_cache_path the feature caches start from their files and are written back when they grew (`files` below).
     training_loader, validation_loader = frame_cache.build_loaders(cfg, training_set, validation_set, per_rank, sampler, device, real_tree)
     log_path = getattr(cfg, "log_path", None)
@@ -358,10 +360,26 @@ def _train_net(cfg, training_set, validation_set, max_steps):
     for f in files.values():
         f.load()
 
+    # cfg.map_cache_gb (0: `map_caches` is empty and nothing below differs): a pass's info gains the rows its cache served from slots
+    # and the frames it took in, and the log one line per pass
+    map_caches = {split: ld.cache for split, ld in (("train", training_loader), ("val", validation_loader))
+                  if isinstance(getattr(ld, "cache", None), feature_cache.MapCache)}
+
+    def with_map_stats(split, run_pass):
+        cache = map_caches.get(split)
+        if cache is None:
+            return run_pass()
+        hits, inserted = cache.hits, cache.inserted
+        info = run_pass()
+        info.update(map_cache_hits=cache.hits - hits, map_cache_inserted=cache.inserted - inserted)
+        print_log(log_path, f"map cache {split} epoch {info['epoch']}: {info['map_cache_hits']} rows from slots, {info['map_cache_inserted']} "
+                            f"frames inserted; {cache.inserted} frames, {cache.bytes / 1e9:.3f} GB resident")
+        return info
+
     def with_file(split, run_pass):
         f = files.get(split)
         if f is None:
-            return run_pass()
+            return with_map_stats(split, run_pass)
         before = f.inserted
         info = run_pass()
         info.update(feature_cache_loaded=f.loaded, feature_cache_saved=f.save_if_grown(before))
